@@ -15,10 +15,16 @@ Launch modes (`config.launch` says which one was timed):
 Either way the timed region is hipGraph replays only, bracketed by barrier + synchronize and by one HIP event pair on the
 launch stream (`roofline.kernel_ms` = event time / launches, so it can never exceed the wall-clock figure).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--lanes 65536] [--opponent minimax] ...
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--lanes 65536] [--opponent minimax] [--full] [--dump-outputs DIR] ...
 `--gpus N` (N > 1) outside torchrun starts the N ranks itself (torch.distributed.run, one process per GPU, RCCL).
 Rank 0 prints ONE JSON line.  Inputs (boards, dice, RNG state) are resident in HBM before the timed region; no
 host<->device traffic happens inside it.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds the measurements that take runs of
+their own: the CPU-oracle baseline (`cpu_baseline`) and the other launch modes / agents (`extras`).
+`--dump-outputs DIR` writes, after the timed region, what the timed path's caller holds after its last step as DIR/<name>.npy
+(float32, float64 where the engine's array is float64; see timed_outputs): the inputs are seeded, so two builds run with the
+same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -31,9 +37,10 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 ALGO_BYTES_PER_LANE_STEP = {5: 64, 7: 112}  # read board+dice+action, write board+dice+reward+flags
+DUMP_LIMIT_BYTES = 60 * 10 ** 6  # --dump-outputs: all arrays together (the .npy headers stay well inside 64 MB)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
@@ -82,7 +89,13 @@ def parse():
     ap.add_argument("--collective-barrier", action="store_true",
                     help="N > 1: bracket the timed region with dist.barrier() (an RCCL all-reduce) instead of the node-local shared-memory barrier")
     ap.add_argument("--no-extras", action="store_true", help="skip the extra measurements (single-step launch, no-trajectory rollout, uniform6 agent)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU-oracle baseline (unless --no-cpu-baseline) and the extra "
+                         "measurements (unless --no-extras)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the timed path's caller holds after its last step as DIR/<name>.npy "
+                         "(rank 0's lanes; a fixed seeded sample of lanes, listed in lane_index.npy, past %d MB in all)" % (DUMP_LIMIT_BYTES // 10 ** 6))
+    return ap.parse_args(argv)
 
 
 def _cpu_worker(job):
@@ -156,6 +169,43 @@ def pmc_key(mode, opponent, max_depth, rng, board_size, lanes, steps_per_launch,
         if trajectory and layout != "record":
             key += "_" + layout
     return key
+
+
+def timed_outputs(runner, steps):
+    """What the caller of the timed path holds after its last timed step, as host arrays with the lane as first axis.
+    board / dice: the environment state (what rollout() and step() return first).  Rollout mode with a trajectory: the last step's
+    trajectory row (traj_board ... traj_info).  Step mode: ewn_step's outputs (reward ... info, and the fused agent's next action)."""
+    env = runner.env
+    out = {"board": env.board, "dice": env.dice}
+    if runner.mode == "rollout":
+        if runner.traj is not None:
+            k = (runner.plan(steps)[-1][0] - 1) % runner.K       # the last launch wrote rows 0 .. k
+            for name in ("board", "dice", "action", "reward", "terminated", "truncated", "info"):
+                out["traj_" + name] = runner.traj[name][k]
+    else:
+        out.update(reward=env.reward, terminated=env.terminated, truncated=env.truncated, info=env.info)
+        if runner.fused_agent:
+            out["random_action"] = env.random_action
+    return {name: t.cpu().numpy() for name, t in out.items()}
+
+
+def write_outputs(path, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """arrays: name -> array with the lane as first axis, saved as path/<name>.npy in float32 (float64 where the array is float64).
+    Past `limit` bytes in all, every array keeps the same seeded sample of lanes, whose indices go to lane_index.npy."""
+    import numpy as np
+    arrays = {name: np.asarray(a) for name, a in arrays.items()}
+    arrays = {name: a.astype(np.float64 if a.dtype == np.float64 else np.float32) for name, a in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    per_lane = sum(a.nbytes for a in arrays.values()) // max(1, n)
+    if per_lane * n > limit:
+        keep = max(1, limit // (per_lane + 8))                   # + the float64 lane index
+        idx = np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        arrays["lane_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(arrays)
 
 
 class ShmBarrier:
@@ -410,9 +460,9 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     # The host-core baseline runs FIRST, before anything touches the GPU: it starts worker processes, and a process
-    # that has initialised HIP must not be the one that forks/execs them.  Rank 0 at N=1 only.
+    # that has initialised HIP must not be the one that forks/execs them.  Rank 0 at N=1 only, --full only.
     cpub = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         cpub = cpu_baseline(args, args.cpu_baseline_seconds)
     dist_on = world > 1 or args.force_collectives
     if dist_on:
@@ -505,6 +555,9 @@ def main():
     dt, ev_ms = runner.run(args.steps, barrier, use_graph=not args.no_graph, spin=spin)   # exactly K timed steps
     if rank == 0:
         print("host side of the timed region (us): " + ", ".join("%s %.1f" % kv for kv in runner.host_us.items()) + "; events %.1f" % (ev_ms * 1e3), file=sys.stderr)
+        if args.dump_outputs:
+            names = write_outputs(args.dump_outputs, timed_outputs(runner, args.steps))
+            print("outputs of the last timed step: %s in %s" % (", ".join(names), args.dump_outputs), file=sys.stderr)
     tmax = torch.tensor([dt], dtype=torch.float64, device="cuda" if (dist_on and args.backend == "nccl") else "cpu")
     ranks_seen = None
     if dist_on:
@@ -520,9 +573,9 @@ def main():
         dist.all_reduce(dg, op=dist.ReduceOp.SUM)
         digest = int(dg.item())
 
-    # ---- extras (N=1 only; clearly labelled, never `value`)
+    # ---- extras (N=1 and --full only; clearly labelled, never `value`)
     extras = {}
-    if world == 1 and not args.no_extras and not args.no_graph:
+    if args.full and world == 1 and not args.no_extras and not args.no_graph:
         def extra(name, mode_, **kw):
             try:
                 r = Runner(torch, make_env(), args, mode_, **kw)

@@ -62,8 +62,21 @@ def pytest_sessionstart(session):
         # the RCCL branch at world_size 1: bench.py's N>1 code path under backend nccl, and the trainers' gradient all-reduce
         PRELAUNCH["bench_nccl_w1"] = _run([sys.executable, "bench.py", "--gpus", "1", "--force-collectives", "--backend", "nccl", "--lanes", "16384"] + common)
         PRELAUNCH["nccl_selftest"] = _run([sys.executable, "tools/nccl_selftest.py"])
+        # plain runs with --dump-outputs (twice with the same arguments, and once in step mode), and one --full run
+        import tempfile
+        PRELAUNCH["dump_root"] = tempfile.mkdtemp(prefix="ewn_bench_dump_")
+        plain = ["--lanes", "16384", "--steps", "20", "--warmup", "6", "--steps-per-launch", "8"]
+        for key, extra in (("bench_dump_a", []), ("bench_dump_b", []), ("bench_dump_step", ["--mode", "step"])):
+            PRELAUNCH[key] = _run([sys.executable, "bench.py"] + plain + extra + ["--dump-outputs", os.path.join(PRELAUNCH["dump_root"], key)])
+        PRELAUNCH["bench_full"] = _run([sys.executable, "bench.py", "--full", "--steps", "20", "--warmup", "5", "--cpu-baseline-seconds", "1"])
     except Exception as exc:   # reported by the tests that need the output
         PRELAUNCH["error"] = repr(exc)
+
+
+def pytest_sessionfinish(session, exitstatus):
+    if "dump_root" in PRELAUNCH:
+        import shutil
+        shutil.rmtree(PRELAUNCH["dump_root"], ignore_errors=True)
 
 
 @pytest.fixture(scope="session")

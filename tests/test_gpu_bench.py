@@ -59,3 +59,66 @@ def test_rccl_branch_runs_at_world_size_one(prelaunched):
     t = _line(prelaunched, "nccl_selftest")
     assert t["backend"] == "nccl" and t["world"] == 1 and t["rccl_ranks"] == 1
     assert t["bucket_ok"] and t["fused_updated"] and t["grad_norm"] > 0
+
+
+def _dump(prelaunched, key):
+    import os
+
+    import numpy as np
+    d = os.path.join(prelaunched["dump_root"], key)
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d)) if f.endswith(".npy")}
+
+
+def _digest(board):
+    """bench.py's state_digest, from a dumped board"""
+    import numpy as np
+    n = board.shape[0]
+    return int((board.astype(np.int64).reshape(n, -1) * np.arange(1, board[0].size + 1)).sum())
+
+
+def test_plain_run_dumps_the_last_timed_step(prelaunched):
+    """--dump-outputs: the last timed step of a plain run (26 env steps = 6 warm-up + 20 timed in launches of 8, so the last launch
+    is a short one), float32 / float64, the state the line's digest was taken from, bit-exact against the oracle on a slice of lanes,
+    and the same arrays from a second run with the same arguments.  A plain run has neither the CPU baseline nor the extras."""
+    import numpy as np
+    from oracle import pyoracle as po
+    b, b2 = _line(prelaunched, "bench_dump_a"), _line(prelaunched, "bench_dump_b")
+    assert b["steps"] == 20 and b["ms_per_step"] > 0 and b["config"]["mode"] == "rollout"
+    assert b["cpu_baseline"] is None and b["extras"] is None
+    out, out2 = _dump(prelaunched, "bench_dump_a"), _dump(prelaunched, "bench_dump_b")
+    names = ["board", "dice"] + ["traj_" + n for n in ("board", "dice", "action", "reward", "terminated", "truncated", "info")]
+    assert sorted(out) == sorted(out2) == sorted(names)
+    for name, a in out.items():
+        assert a.dtype == (np.float64 if name == "traj_reward" else np.float32) and a.shape[0] == 16384, name
+        assert np.array_equal(a, out2[name]), name
+    assert _digest(out["board"]) == b["state_digest"] == b2["state_digest"]
+    N, lo, hi = 16384, 9000, 9256
+    seeds = (np.arange(N, dtype=np.uint64) + 9487).astype(np.uint32)
+    orc = po.OracleVecEnv(hi - lo, opponent="minimax", max_depth=3, rng="philox", philox_key=2024, autoreset=True, seed_stride=N, lane_offset=lo)
+    orc.reset(seeds=seeds[lo:hi])
+    for _ in range(26):
+        a = orc.random_actions()
+        ob, od, r, te, tr, info = orc.step(a)
+    want = {"board": ob, "dice": od, "traj_board": ob, "traj_dice": od, "traj_action": a, "traj_reward": r,
+            "traj_terminated": te, "traj_truncated": tr, "traj_info": info}
+    for name, o in want.items():
+        assert np.array_equal(out[name][lo:hi], o.astype(out[name].dtype)), name
+
+
+def test_plain_step_mode_run_dumps_the_step_outputs(prelaunched):
+    import numpy as np
+    b = _line(prelaunched, "bench_dump_step")
+    assert b["config"]["mode"] == "step" and b["extras"] is None
+    out = _dump(prelaunched, "bench_dump_step")
+    assert sorted(out) == ["board", "dice", "info", "random_action", "reward", "terminated", "truncated"]
+    assert out["reward"].dtype == np.float64 and out["board"].dtype == np.float32 and out["random_action"].shape == (16384, 2)
+    assert _digest(out["board"]) == b["state_digest"]
+
+
+def test_full_run_has_the_cpu_baseline_and_the_extras(prelaunched):
+    b = _line(prelaunched, "bench_full")
+    assert b["cpu_baseline"]["value"] > 0 and b["cpu_baseline"]["single_thread_value"] > 0
+    assert sorted(b["extras"]) == sorted(["single_step_launch", "rollout_without_trajectory", "agent_uniform_over_all_6_actions",
+                                          "agent_uniform_over_all_6_actions_torch_policy"])
+    for name, e in b["extras"].items():
+        assert "error" not in e and e["value"] > 0 and e["steps"] == 20, (name, e)

@@ -20,8 +20,8 @@ if [[ $P == *A* ]]; then
   timeout -k 10 200 $R/tools/profile_cfg.sh $O d5_k50 --max-depth 5 --steps 150 --warmup 50 | tail -1
   timeout -k 10 200 $R/tools/profile_cfg.sh $O mcts7 --opponent mcts --board-size 7 --lanes 32768 --num-simulations 40 --num-env-copies 10 --steps 20 --warmup 4 --mode step | tail -1
   cd $R
-  timeout -k 10 200 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
-  timeout -k 10 120 python3 bench.py --steps 20 --warmup 5 > $O/bench_driver_shape.json 2>/dev/null
+  timeout -k 10 200 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+  timeout -k 10 120 python3 bench.py --full --steps 20 --warmup 5 > $O/bench_driver_shape.json 2>/dev/null
   # the MT19937-compat one-step path, the MCTS opponent both ways
   for o in minimax random; do timeout -k 10 120 python3 bench.py --rng mt19937 --mode step --opponent $o --steps 1000 --warmup 100 --no-cpu-baseline --no-extras > $O/bench_mt19937_step_$o.json 2>/dev/null; done
   for m in rollout step; do
