@@ -29,6 +29,19 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _describe(t):
+    if not isinstance(t, torch.Tensor):
+        return type(t).__name__
+    return "%s %s on %s%s" % (t.dtype, list(t.shape), t.device, "" if t.is_contiguous() else " (not contiguous)")
+
+
+def _no_initial_obs(traj):
+    if "obs_board" in traj:
+        raise ValueError("this trajectory was allocated with initial_obs=True (K + 1 record rows, the step views start at row 1): that "
+                         "layout belongs to rollout_policy; ewn_step_k writes rows 0 .. K - 1, so rollout() would read every column one "
+                         "step late.  Allocate it with alloc_rollout(K, layout='record') instead")
+
+
 _TABLES = {}
 
 
@@ -201,6 +214,7 @@ class VecEWN:
         ("minimax") or env.action_space.sample() ("sample": all six actions, illegal ones included).
         traj: dict from alloc_rollout (first dimension >= K) or None; totals: dict from alloc_totals or None."""
         traj, totals = traj or {}, totals or {}
+        _no_initial_obs(traj)
         for v in traj.values():
             assert v.shape[0] >= K and v.shape[1] == self.N
         col = (lambda k: None) if "record" in traj else traj.get   # record layout: the column entries are views, not buffers
@@ -217,6 +231,7 @@ class VecEWN:
         repeat the same call: one C-ABI call per invocation, a few microseconds of host time instead of the ~20 of building the structs).
         The buffers of traj / totals must stay alive as long as the callable is used."""
         traj, totals = traj or {}, totals or {}
+        _no_initial_obs(traj)
         for v in traj.values():
             assert v.shape[0] >= K and v.shape[1] == self.N
         col = (lambda k: None) if "record" in traj else traj.get
@@ -245,13 +260,26 @@ class VecEWN:
     def rollout_policy(self, K, params, traj=None, totals=None, deterministic=False, noise_key=0, logits=None, value=None, noise=None):
         """Play K steps of every lane in one launch, actions sampled from the actor-critic whose flat fp32 parameter vector is
         `params` (a2c.ActorCritic.flat order).  traj: dict from alloc_rollout (a record layout allocated with initial_obs=True gets
-        K + 1 rows); logits [K, N, 5] / value [K, N] / noise [K, N, 5] float32: optional per-step outputs of the policy."""
+        K + 1 rows); logits [K, N, 5] / value [K, N] / noise [K, N, 5] float32: optional per-step outputs of the policy.  Buffers of the
+        wrong shape, dtype or layout raise ValueError before anything is launched."""
         traj, totals = traj or {}, totals or {}
         assert params.dtype == torch.float32 and params.is_contiguous() and params.numel() == self.policy_param_count()
+        N = self.N
+        for name, t, shape in (("logits", logits, (N, 5)), ("value", value, (N,)), ("noise", noise, (N, 5))):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_cuda and t.is_contiguous()
+                                      and t.dim() == 1 + len(shape) and t.shape[0] >= K and tuple(t.shape[1:]) == shape):
+                raise ValueError("rollout_policy: %s must be a contiguous float32 device tensor of shape [>= %d, %s], got %s" % (
+                    name, K, ", ".join(map(str, shape)), _describe(t)))
         rec0 = 0
         if "record" in traj:
             rec0 = 1 if "obs_board" in traj else 0
             assert traj["record"].shape[0] >= K + rec0
+        for name, t in traj.items():
+            if name == "record" or name.startswith("obs_"):
+                continue
+            if t.shape[0] < K or t.shape[1] != N or ("record" not in traj and not t.is_contiguous()):
+                raise ValueError("rollout_policy: traj[%r] must have shape [>= %d, %d, ...]%s, got %s" % (
+                    name, K, N, "" if "record" in traj else " and be contiguous", _describe(t)))
         col = (lambda k: None) if "record" in traj else traj.get
         out = EwnRolloutOut(_ptr(col("board")), _ptr(col("dice")), _ptr(col("action")), _ptr(traj.get("reward")),
                             _ptr(col("terminated")), _ptr(col("truncated")), _ptr(col("info")),

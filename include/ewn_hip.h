@@ -114,9 +114,9 @@ typedef struct ewn_state {
     double *prev_score;  /* [N]  shaped env only (training_ewn.py:35), may be NULL otherwise */
     int32_t *tolerance;  /* [N]  shaped env only (training_ewn.py:38), may be NULL otherwise */
     const void *tables;  /* device copy of ewn_build_tables() output, or NULL.  When present and the config is
-                            (cube_layer 3, un-shaped; RandomAgent opponent, or minimax with max_depth 1..6 and
-                            'hybrid') ewn_step runs the specialised table-driven kernel; results are identical
-                            either way. */
+                            (cube_layer 3, boards 5..8, plain or shaped; RandomAgent opponent, or minimax with max_depth
+                            1..6 and 'hybrid', 'min_dist', 'attk' or 'two_min_dist') ewn_step runs the specialised
+                            table-driven kernel; results are identical either way. */
 } ewn_state;
 
 /* Outputs of one step, device pointers, caller-owned.  The post-step observation is
@@ -179,8 +179,11 @@ int ewn_step(const ewn_config *cfg, const ewn_state *st, const int8_t *actions, 
  *     while not done: action, _ = agent.predict(obs); obs, reward, done, trunc, info = env.step(action)
  * (and a rollout collector's inner loop) when `agent` is one of the classical policies: the state is read once, stays in
  * registers for K steps and is written once; results are identical, step for step, to K ewn_step calls with the agent's
- * action fed back.  Available for the table-driven configurations (cube_layer 3, board sizes 5..8, ewn_state.tables set,
- * un-shaped, opponent RandomAgent or 'hybrid' minimax); MT19937-compat dice only without auto-reset. */
+ * action fed back.  Always un-shaped, and MT19937-compat dice only without auto-reset.  Served for (ewn_step_k_supported() says which):
+ * the table-driven configurations (cube_layer 3, board sizes 5..8, ewn_state.tables set; opponent RandomAgent or minimax with
+ * 'hybrid', 'min_dist', 'attk' -- every agent -- or 'two_min_dist' -- RandomAgent / sample agents); the MCTS opponent (cube_layer <= 3,
+ * boards <= 8x8, RandomAgent / sample agents); and the geometries without a table image (the generic kernel, see
+ * ewn_step_k_supported). */
 #define EWN_AGENT_RANDOM 0  /* RandomAgent.predict (classical_policies/random_policy.py:11-15): the hash-driven uniform legal pick
                                of ewn_step_out.random_action, same stream */
 #define EWN_AGENT_MINIMAX 1 /* ExpectiMinimaxAgent(agent_max_depth, 'hybrid').predict (classical_policies/minimax.py:89-93) */
@@ -276,11 +279,14 @@ typedef struct ewn_a2c_hyper {
     int32_t world_size;     /* ewn_a2c_apply divides the (all-reduced, summed) gradient by it */
 } ewn_a2c_hyper;
 
-/* bytes of device scratch ewn_a2c_grad needs (advantages [K][N] + per-block partial gradients); < 0: configuration not served */
+/* bytes of device scratch ewn_a2c_grad needs (advantages [K][N], per-block partial gradients and loss sums, then 64 floats that only
+ * a timing build writes); < 0: configuration not served */
 int64_t ewn_a2c_scratch_bytes(const ewn_config *cfg, int K);
 /* record: [K + 1][N][EWN_TRAJ_RECORD_STRIDE(S)] written by ewn_step_k_policy with record_initial_obs = 1; reward [K][N].
- * grad [ewn_policy_param_count() + 8]: the gradient of THIS rank's mean loss in the layout of ewn_policy.params, then the loss sums
- * {policy, value, entropy, 0} of the policy pass and of the value pass (divide by K * N for means).  Three launches. */
+ * grad [ewn_policy_param_count() + 8]: the gradient of THIS rank's mean loss in the layout of ewn_policy.params, then eight loss sums
+ * over the K * N samples (divide by K * N for means), {policy, value, entropy, 0} of the policy pass and then of the value pass.  Each
+ * pass counts only its own: [P + 0] policy loss -(adv log pi(a)), [P + 2] entropy, [P + 5] squared error (R - V)^2; [P + 1], [P + 3],
+ * [P + 4], [P + 6] and [P + 7] are exactly 0.  Three launches. */
 int ewn_a2c_grad(const ewn_config *cfg, int K, const uint8_t *record, const double *reward, const float *params, const ewn_a2c_hyper *hp,
                  float *grad, void *scratch, void *stream);
 /* clip by the global norm, then one RMSprop step on params / sq_avg (both [param count], in place); grad_norm_out (may be NULL)

@@ -633,25 +633,14 @@ def test_g13_cube_layers_4_and_5(ea, golden):
         _run_group(ea, grp["traj"], "minimax", max_depth=2, heuristic="hybrid")
 
 
-def test_no_kernel_writes_outside_its_buffers(ea, monkeypatch):
-    """Every tensor VecEWN hands to the C ABI is carved out of a larger allocation with 4 KB of 0xA5 on either side; after stepping
-    (auto-reset, both RNG kinds, every opponent, every lanes-per-game choice of the lean kernel) the guards must be intact.
+def test_no_kernel_writes_outside_its_buffers(ea):
+    """Every tensor VecEWN hands to the C ABI is carved out of a larger allocation with 4 KB of 0xA5 directly in front of its first
+    byte and directly behind its last one (tests/guarded_alloc.py: no round-up slack); after stepping (auto-reset, both RNG kinds,
+    every opponent, every lanes-per-game choice of the lean kernel) the guards must be intact.
     (Added after a refill queue sized for 4 lanes per game let a one-lane-per-game launch write 8 KB past it.)"""
     from ewn_gym_amd import vec_env
-    G = 4096
-    guarded = []
-    real_zeros = torch.zeros
-
-    def guarded_zeros(shape, dtype=torch.float32, device=None):
-        if device is None or torch.device(device).type != "cuda":
-            return real_zeros(shape, dtype=dtype, device=device)
-        shape = (shape,) if isinstance(shape, int) else tuple(shape)
-        nbytes = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-        pad = (nbytes + 511) // 512 * 512
-        buf = torch.full((G + pad + G,), 0xA5, dtype=torch.uint8, device=device)
-        buf[G:G + pad] = 0
-        guarded.append((buf, pad))
-        return buf[G:G + nbytes].view(dtype).view(shape)
+    from tests.guarded_alloc import GuardedAllocator
+    alloc = GuardedAllocator()
 
     cases = [dict(n=64, opponent_policy="minimax", max_depth=5, rng="mt19937"), dict(n=64, opponent_policy="random", rng="mt19937"),
              dict(n=300, opponent_policy="minimax", max_depth=3, rng="mt19937"), dict(n=3000, opponent_policy="random", rng="mt19937"),
@@ -662,78 +651,61 @@ def test_no_kernel_writes_outside_its_buffers(ea, monkeypatch):
     # through the guarded allocator; their guards are checked after every case below and the cache is dropped at the end
     saved_tables = dict(vec_env._TABLES)
     vec_env._TABLES.clear()
-    monkeypatch.setattr(vec_env.torch, "zeros", guarded_zeros)
     try:
-        for (S, L) in ((5, 3), (7, 3), (6, 3), (8, 3)):
-            assert vec_env.search_tables(S, L, torch.device("cuda")) is not None
+        tables = GuardedAllocator()
+        with tables.patch(tag="tables"):
+            for (S, L) in ((5, 3), (7, 3), (6, 3), (8, 3)):
+                assert vec_env.search_tables(S, L, torch.device("cuda")) is not None
+        assert len(tables.buffers) == 4
+
+        for kw in cases:
+            kw = dict(kw)
+            n = kw.pop("n")
+            with alloc.patch(tag="env %s" % kw):
+                env = ea.VecEWN(n, autoreset=True, want_terminal_obs=True, want_random_action=True, **kw)
+            env.reset(seeds=np.arange(n) + 3)
+            for t in range(25):
+                env.step(env.sample_legal_actions(t))
+            torch.cuda.synchronize()
+            alloc.check(str(kw))
+            tables.check(str(kw))
+            alloc.clear()
+        # ewn_step_k: state, trajectory ([K][N] columns) and per-lane totals, every lanes-per-game choice, partial last blocks
+        for kw in (dict(n=1000, opponent_policy="minimax", max_depth=3, rng="philox"), dict(n=257, opponent_policy="random", rng="philox"),
+                   dict(n=40000, opponent_policy="minimax", max_depth=3, rng="philox"), dict(n=140000, opponent_policy="minimax", max_depth=2, rng="philox"),
+                   dict(n=300, opponent_policy="minimax", max_depth=5, rng="mt19937", autoreset=False, agent="minimax"),
+                   dict(n=513, opponent_policy="minimax", max_depth=4, rng="philox", board_size=8, agent="minimax")):
+            kw = dict(kw)
+            n, agent, autoreset = kw.pop("n"), kw.pop("agent", "random"), kw.pop("autoreset", True)
+            with alloc.patch(tag="rollout %s" % kw):
+                env = ea.VecEWN(n, autoreset=autoreset, **kw)
+                traj, tot = env.alloc_rollout(7), env.alloc_totals()
+            env.reset(seeds=np.arange(n) + 3)
+            for _ in range(3):
+                env.rollout(7, agent=agent, agent_max_depth=3, traj=traj, totals=tot)
+                env.rollout(5, agent=agent, agent_max_depth=3)
+            torch.cuda.synchronize()
+            alloc.check(str(kw))
+            tables.check(str(kw))
+            alloc.clear()
+        # the stateless queries allocate their outputs with torch.zeros too
+        for (S, L, M) in ((5, 3, 1), (5, 3, 63), (7, 3, 1000), (8, 5, 77), (6, 4, 130)):
+            b, d = _random_positions(S, L, M, 900 + M, max_steps=20)
+            d = np.minimum(d, 6).astype(np.int8)
+            with alloc.patch(tag="queries S=%d L=%d M=%d" % (S, L, M)):
+                ea.predict_minimax(b, d, 3, "hybrid", cube_layer=L)
+                ea.predict_minimax(b, d, 2, "attk", cube_layer=L)
+                ea.predict_mcts(b, d, num_simulations=7, num_env_copies=3, key=M, cube_layer=L)
+                ea.playout_wins(b, first_player=2, n_sims=37, key=M, cube_layer=L)
+                ea.evaluate(b, "hybrid", cube_layer=L)
+                ea.predict_random(b, d, key=M, step=3, cube_layer=L) if hasattr(ea, "predict_random") else None
+            torch.cuda.synchronize()
+            alloc.check(str((S, L, M)))
+            tables.check(str((S, L, M)))
+            alloc.clear()
     finally:
-        monkeypatch.setattr(vec_env.torch, "zeros", real_zeros)
-    table_guards = list(guarded)
-    guarded.clear()
-    assert len(table_guards) == 4
-
-    def tables_intact():
-        return all(bool((buf[:G] == 0xA5).all()) and bool((buf[G + pad:] == 0xA5).all()) for buf, pad in table_guards)
-
-    for kw in cases:
-        kw = dict(kw)
-        n = kw.pop("n")
-        monkeypatch.setattr(vec_env.torch, "zeros", guarded_zeros)
-        try:
-            env = ea.VecEWN(n, autoreset=True, want_terminal_obs=True, want_random_action=True, **kw)
-        finally:
-            monkeypatch.setattr(vec_env.torch, "zeros", real_zeros)
-        env.reset(seeds=np.arange(n) + 3)
-        for t in range(25):
-            env.step(env.sample_legal_actions(t))
-        torch.cuda.synchronize()
-        for buf, pad in guarded:
-            assert bool((buf[:G] == 0xA5).all()) and bool((buf[G + pad:] == 0xA5).all()), kw
-        assert tables_intact(), kw
-        guarded.clear()
-    # ewn_step_k: state, trajectory ([K][N] columns) and per-lane totals, every lanes-per-game choice, partial last blocks
-    for kw in (dict(n=1000, opponent_policy="minimax", max_depth=3, rng="philox"), dict(n=257, opponent_policy="random", rng="philox"),
-               dict(n=40000, opponent_policy="minimax", max_depth=3, rng="philox"), dict(n=140000, opponent_policy="minimax", max_depth=2, rng="philox"),
-               dict(n=300, opponent_policy="minimax", max_depth=5, rng="mt19937", autoreset=False, agent="minimax"),
-               dict(n=513, opponent_policy="minimax", max_depth=4, rng="philox", board_size=8, agent="minimax")):
-        kw = dict(kw)
-        n, agent, autoreset = kw.pop("n"), kw.pop("agent", "random"), kw.pop("autoreset", True)
-        monkeypatch.setattr(vec_env.torch, "zeros", guarded_zeros)
-        try:
-            env = ea.VecEWN(n, autoreset=autoreset, **kw)
-            traj, tot = env.alloc_rollout(7), env.alloc_totals()
-        finally:
-            monkeypatch.setattr(vec_env.torch, "zeros", real_zeros)
-        env.reset(seeds=np.arange(n) + 3)
-        for _ in range(3):
-            env.rollout(7, agent=agent, agent_max_depth=3, traj=traj, totals=tot)
-            env.rollout(5, agent=agent, agent_max_depth=3)
-        torch.cuda.synchronize()
-        for buf, pad in guarded:
-            assert bool((buf[:G] == 0xA5).all()) and bool((buf[G + pad:] == 0xA5).all()), kw
-        assert tables_intact(), kw
-        guarded.clear()
-    # the stateless queries allocate their outputs with torch.zeros too
-    for (S, L, M) in ((5, 3, 1), (5, 3, 63), (7, 3, 1000), (8, 5, 77), (6, 4, 130)):
-        b, d = _random_positions(S, L, M, 900 + M, max_steps=20)
-        d = np.minimum(d, 6).astype(np.int8)
-        monkeypatch.setattr(vec_env.torch, "zeros", guarded_zeros)
-        try:
-            ea.predict_minimax(b, d, 3, "hybrid", cube_layer=L)
-            ea.predict_minimax(b, d, 2, "attk", cube_layer=L)
-            ea.predict_mcts(b, d, num_simulations=7, num_env_copies=3, key=M, cube_layer=L)
-            ea.playout_wins(b, first_player=2, n_sims=37, key=M, cube_layer=L)
-            ea.evaluate(b, "hybrid", cube_layer=L)
-            ea.predict_random(b, d, key=M, step=3, cube_layer=L) if hasattr(ea, "predict_random") else None
-        finally:
-            monkeypatch.setattr(vec_env.torch, "zeros", real_zeros)
-        torch.cuda.synchronize()
-        for buf, pad in guarded:
-            assert bool((buf[:G] == 0xA5).all()) and bool((buf[G + pad:] == 0xA5).all()), (S, L, M)
-        assert tables_intact(), (S, L, M)
-        guarded.clear()
-    vec_env._TABLES.clear()
-    vec_env._TABLES.update(saved_tables)
+        vec_env._TABLES.clear()
+        vec_env._TABLES.update(saved_tables)
 
 
 @pytest.mark.parametrize("heur", ["min_dist", "attk", "two_min_dist"])

@@ -162,6 +162,145 @@ def test_policy_rollout_at_config4_shape(ea):
     _policy_vs_torch_and_oracle(ea, 65536, 65236, 65536, 5, 2, **kw)
 
 
+def _f64_bits_equal(a, b):
+    return torch.equal(a.contiguous().view(torch.int64), b.contiguous().view(torch.int64))
+
+
+@pytest.mark.parametrize("N", [3000, 65536])
+def test_trainer_instance_matches_the_generic_instance(ea, N):
+    """FusedA2CTrainer's call (records from the initial observation on + the reward column, nothing else, sampled actions) runs its own
+    kernel instance, k_rollout_mlp<S, 0, NT, 1>, which the tests above never reach (they ask for logits and noise).  From the same saved
+    state and with the same noise key it must play exactly what the generic instance plays: records, rewards, end state, prev_score and
+    tolerance bit-identical (no flip budget needed: both instances run the same arithmetic).  Its actions against the Gumbel-max of the
+    generic run's logits and noise (torch's log against the device's: the near-tie budget of _policy_vs_torch_and_oracle), and a 96-lane
+    slice of it replayed on the oracle, whose policy noise must equal the generic run's."""
+    K, lo, hi, key = 5, N - 96, N, 99
+    kw = dict(max_depth=3, shaped=True, reward=10.0, illegal_move_reward=-1.0, illegal_move_tolerance=10, shaped_refresh_on_reset=True,
+              philox_key=9487)
+    env = ea.VecEWN(N, opponent_policy="minimax", rng="philox", autoreset=True, seed_stride=N, **kw)
+    seeds = (np.arange(N, dtype=np.uint64) * 3 + 41).astype(np.uint32)
+    env.reset(seeds=seeds)
+    orc = po.OracleVecEnv(hi - lo, opponent="minimax", rng="philox", autoreset=True, seed_stride=N, lane_offset=lo, **kw)
+    orc.reset(seeds=seeds[lo:hi])
+    params = make_model(5, 17).flat_parameters()
+    # a few launches first (mid-game state: finished episodes, tolerance counters), their actions fed to the oracle slice
+    pre = env.alloc_rollout(6, layout="record")
+    for _ in range(3):
+        env.rollout_policy(6, params, traj=pre, noise_key=3)
+        for k in range(6):
+            orc.step(cpu(pre["action"][k, lo:hi]))
+    assert np.array_equal(cpu(env.board[lo:hi]), orc.obs()[0])
+    sd = env.state_dict()
+    gen = env.alloc_rollout(K, layout="record", initial_obs=True)
+    logits = torch.zeros((K, N, 5), dtype=torch.float32, device="cuda")
+    noise = torch.zeros((K, N, 5), dtype=torch.float32, device="cuda")
+    env.rollout_policy(K, params, traj=gen, noise_key=key, logits=logits, noise=noise)        # the generic instance (TRJ = 0)
+    end_gen = env.state_dict()
+    env.load_state_dict(sd)
+    trn = env.alloc_rollout(K, layout="record", initial_obs=True)
+    env.rollout_policy(K, params, traj=trn, noise_key=key)                                     # the trainer's instance (TRJ = 1)
+    end_trn = env.state_dict()
+    torch.cuda.synchronize()
+    assert torch.equal(gen["record"], trn["record"])
+    assert _f64_bits_equal(gen["reward"], trn["reward"])
+    for name in ("board", "dice", "done", "rng_state", "tolerance"):
+        assert torch.equal(end_gen[name], end_trn[name]), name
+    assert _f64_bits_equal(end_gen["prev_score"], end_trn["prev_score"])
+    # the trainer's actions are the Gumbel-max of the generic run's logits and noise
+    exp = gumbel_actions(logits, noise)
+    flips = int((trn["action"] != exp).any(-1).sum())
+    assert flips <= max(2, K * N // 20000), (flips, K * N)
+    # the oracle slice: the same noise stream, the same transitions
+    for k in range(K):
+        assert np.array_equal(cpu(noise[k, lo:hi]), orc.policy_noise(key)), k
+        ob, od, r, te, tr, info = orc.step(cpu(trn["action"][k, lo:hi]))
+        assert np.array_equal(cpu(trn["board"][k, lo:hi]), ob) and np.array_equal(cpu(trn["dice"][k, lo:hi]), od), k
+        assert np.array_equal(bits(cpu(trn["reward"][k, lo:hi])), bits(r)), k
+        assert np.array_equal(cpu(trn["terminated"][k, lo:hi]), te) and np.array_equal(cpu(trn["truncated"][k, lo:hi]), tr), k
+        assert np.array_equal(cpu(trn["info"][k, lo:hi]), info), k
+    ps, tol, _ = orc.aux()
+    assert np.array_equal(bits(cpu(env.prev_score[lo:hi])), bits(ps)) and np.array_equal(cpu(env.tolerance[lo:hi]), tol)
+
+
+def test_rollout_policy_rejects_malformed_buffers(ea):
+    """logits / noise must be contiguous float32 [>= K, N, 5], value [>= K, N], column trajectories [>= K, N, ...] and contiguous: each
+    violation raises ValueError before anything is launched (the state is untouched)"""
+    N, K = 300, 4
+    env = ea.VecEWN(N, opponent_policy="minimax", max_depth=3, rng="philox", autoreset=True, philox_key=4)
+    env.reset(seeds=np.arange(N) + 1)
+    params = make_model(5, 3).flat_parameters()
+    f32 = dict(dtype=torch.float32, device="cuda")
+    good = dict(logits=torch.zeros((K, N, 5), **f32), value=torch.zeros((K, N), **f32), noise=torch.zeros((K, N, 5), **f32))
+    bad = {
+        "logits": [torch.zeros((K - 1, N, 5), **f32), torch.zeros((K, N - 1, 5), **f32), torch.zeros((K, N, 4), **f32),
+                   torch.zeros((K, N * 5), **f32), torch.zeros((K, N, 5), dtype=torch.float64, device="cuda"),
+                   torch.zeros((K, 5, N), **f32).transpose(1, 2), torch.zeros((K, N, 5))],
+        "value": [torch.zeros((K - 1, N), **f32), torch.zeros((K, N + 1), **f32), torch.zeros((K, N, 1), **f32),
+                  torch.zeros((K, N), dtype=torch.float16, device="cuda"), torch.zeros((N, K), **f32).t()],
+        "noise": [torch.zeros((K - 1, N, 5), **f32), torch.zeros((K, N, 6), **f32), torch.zeros((K, N, 5), dtype=torch.int32, device="cuda")],
+    }
+    before = env.state_dict()
+    for name, cases in bad.items():
+        for t in cases:
+            kw = dict(good)
+            kw[name] = t
+            with pytest.raises(ValueError, match=name):
+                env.rollout_policy(K, params, **kw)
+    cols = env.alloc_rollout(K)
+    for name in ("board", "dice", "action", "reward", "terminated", "truncated", "info"):
+        short = dict(cols)
+        short[name] = cols[name][:K - 1]
+        with pytest.raises(ValueError, match=name):
+            env.rollout_policy(K, params, traj=short)
+        narrow = dict(cols)
+        narrow[name] = cols[name][:, :N - 1]
+        with pytest.raises(ValueError, match=name):
+            env.rollout_policy(K, params, traj=narrow)
+    strided = dict(cols)
+    strided["dice"] = torch.zeros((N, K), dtype=torch.int8, device="cuda").t()
+    with pytest.raises(ValueError, match="dice"):
+        env.rollout_policy(K, params, traj=strided)
+    rec = env.alloc_rollout(K, layout="record", initial_obs=True)
+    rec["reward"] = rec["reward"][:K - 1]
+    with pytest.raises(ValueError, match="reward"):
+        env.rollout_policy(K, params, traj=rec)
+    torch.cuda.synchronize()
+    after = env.state_dict()
+    assert all(torch.equal(before[k], after[k]) for k in before)
+    # the well-formed call still runs, and over-long buffers (first dimension > K) stay allowed
+    env.rollout_policy(K, params, traj=env.alloc_rollout(K + 2), logits=torch.zeros((K + 1, N, 5), **f32), noise_key=1)
+    torch.cuda.synchronize()
+
+
+def test_rollout_refuses_a_trajectory_allocated_for_rollout_policy(ea):
+    """ewn_step_k has no initial-observation row: a record trajectory allocated with initial_obs=True (K + 1 rows, the step views from
+    row 1 on) would read back one step late through rollout() / bind_rollout(); both refuse it.  A plain record trajectory through
+    rollout() still agrees with the columns layout."""
+    N, K = 500, 6
+    kw = dict(opponent_policy="minimax", max_depth=3, rng="philox", autoreset=True, philox_key=6, seed_stride=N)
+    env = ea.VecEWN(N, **kw)
+    env.reset(seeds=np.arange(N) + 8)
+    bad = env.alloc_rollout(K, layout="record", initial_obs=True)
+    before = env.state_dict()
+    with pytest.raises(ValueError, match="initial_obs"):
+        env.rollout(K, traj=bad)
+    with pytest.raises(ValueError, match="initial_obs"):
+        env.bind_rollout(K, traj=bad)
+    torch.cuda.synchronize()
+    assert all(torch.equal(before[k], v) for k, v in env.state_dict().items())
+    env2 = ea.VecEWN(N, **kw)
+    env2.reset(seeds=np.arange(N) + 8)
+    rec, cols = env.alloc_rollout(K, layout="record"), env2.alloc_rollout(K)
+    for _ in range(2):
+        env.rollout(K, traj=rec)
+        env2.rollout(K, traj=cols)
+        torch.cuda.synchronize()
+        for name in ("board", "dice", "action", "terminated", "truncated", "info"):
+            assert torch.equal(rec[name], cols[name]), name
+        assert _f64_bits_equal(rec["reward"], cols["reward"])
+    assert torch.equal(env.board, env2.board) and torch.equal(env.dice, env2.dice)
+
+
 def test_policy_rollout_is_unsupported_where_documented(ea):
     env = ea.VecEWN(64, opponent_policy="minimax", max_depth=5, rng="philox")
     assert not env.supports_policy_rollout()
