@@ -24,7 +24,8 @@ EXPORTS = ["ewn_abi_version", "ewn_strerror", "ewn_rng_words", "ewn_step_scratch
            "ewn_build_tables", "ewn_init_aux", "ewn_reset",
            "ewn_step", "ewn_legal_actions", "ewn_apply_action", "ewn_playout_wins", "ewn_evaluate", "ewn_predict_minimax", "ewn_predict_random",
            "ewn_predict_mcts", "ewn_step_k", "ewn_step_k_supported", "ewn_predict_minimax_sim", "ewn_lanes_per_game", "ewn_roll_dice",
-           "ewn_policy_param_count", "ewn_step_k_policy", "ewn_a2c_scratch_bytes", "ewn_a2c_grad", "ewn_a2c_apply"]
+           "ewn_policy_param_count", "ewn_step_k_policy", "ewn_a2c_scratch_bytes", "ewn_a2c_grad", "ewn_a2c_apply",
+           "ewn_ppo_scratch_bytes", "ewn_ppo_prepare", "ewn_ppo_shuffle", "ewn_ppo_grad", "ewn_ppo_apply"]
 AGENT = {"random": 0, "minimax": 1, "sample": 2, "mlp": 3}   # "mlp": the trained policy, through ewn_step_k_policy   # "sample": env.action_space.sample(), all six actions (EWN_AGENT_SAMPLE)
 
 
@@ -66,6 +67,12 @@ class EwnPolicy(C.Structure):  # struct ewn_policy
 class EwnA2cHyper(C.Structure):  # struct ewn_a2c_hyper
     _fields_ = [("gamma", C.c_float), ("vf_coef", C.c_float), ("ent_coef", C.c_float), ("max_grad_norm", C.c_float),
                 ("learning_rate", C.c_float), ("rms_alpha", C.c_float), ("rms_eps", C.c_float), ("world_size", C.c_int32)]
+
+
+class EwnPpoHyper(C.Structure):  # struct ewn_ppo_hyper
+    _fields_ = [("gamma", C.c_float), ("gae_lambda", C.c_float), ("clip_range", C.c_float), ("vf_coef", C.c_float),
+                ("ent_coef", C.c_float), ("max_grad_norm", C.c_float), ("learning_rate", C.c_float), ("adam_beta1", C.c_float),
+                ("adam_beta2", C.c_float), ("adam_eps", C.c_float), ("normalize_advantage", C.c_int32), ("world_size", C.c_int32)]
 
 
 class EwnError(RuntimeError):
@@ -122,6 +129,11 @@ def load():
         "ewn_a2c_scratch_bytes": (C.c_int64, [cfgp, i32]),
         "ewn_a2c_grad": (i32, [cfgp, i32, vp, vp, vp, C.POINTER(EwnA2cHyper), vp, vp, vp]),
         "ewn_a2c_apply": (i32, [cfgp, vp, vp, vp, C.POINTER(EwnA2cHyper), vp, vp]),
+        "ewn_ppo_scratch_bytes": (C.c_int64, [cfgp, i32, i32]),
+        "ewn_ppo_prepare": (i32, [cfgp, i32, vp, vp, vp, C.POINTER(EwnPpoHyper), vp, vp]),
+        "ewn_ppo_shuffle": (i32, [C.c_int64, i32, u64, vp, vp, vp]),
+        "ewn_ppo_grad": (i32, [cfgp, i32, vp, vp, vp, C.POINTER(EwnPpoHyper), vp, i32, vp, vp, vp]),
+        "ewn_ppo_apply": (i32, [cfgp, vp, vp, vp, vp, vp, C.POINTER(EwnPpoHyper), vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -1,11 +1,12 @@
-// ewn_policy.hip -- the policy-driven rollout (ewn_step_k_policy) and the fused A2C update (ewn_a2c_*): kernels in
-// ewn_policy.hpp / ewn_a2c.hpp, C ABI here.
+// ewn_policy.hip -- the policy-driven rollout (ewn_step_k_policy), the fused A2C update (ewn_a2c_*) and the fused PPO update
+// (ewn_ppo_*): kernels in ewn_policy.hpp / ewn_a2c.hpp / ewn_ppo.hpp, C ABI here.
 #include "ewn_host.hpp"
 #include "ewn_lds.hpp"
 #include "ewn_policy.hpp"
 #include "ewn_a2c.hpp"
 #include "ewn_a2c2.hpp"
 #include "ewn_a2c3.hpp"
+#include "ewn_ppo.hpp"
 
 // which instantiation serves the configuration: opp 0 minimax (table image, max_depth 1-4), 1 RandomAgent
 static int policy_plan(const ewn_config *cfg, const Geom &g, int &opp)
@@ -223,5 +224,120 @@ int ewn_a2c_apply(const ewn_config *cfg, float *params, float *sq_avg, const flo
     const bool vec = ac.P <= 1024 * 4 * A2C_APPLY_V && ((uintptr_t)params | (uintptr_t)sq_avg | (uintptr_t)grad) % 16 == 0;
     if (vec) k_a2c_apply_v4<<<1, 1024, 0, (hipStream_t)stream>>>(ac, params, sq_avg, grad, grad_norm_out);
     else k_a2c_apply<<<1, 1024, 0, (hipStream_t)stream>>>(ac, params, sq_avg, grad, grad_norm_out);
+    return launch_status();
+}
+
+// ---------------------------------------------------------------- the PPO update
+
+// the geometry ewn_a2c_* serves, 1 <= K, K * N samples addressable by int32, 1 <= batch_size <= K * N
+static int ppo_check(const ewn_config *cfg, int K, int batch_size, Geom &g, KCfg &k)
+{
+    int rc = a2c_geom(cfg, g, k);
+    if (rc) return rc;
+    if (K < 1 || (int64_t)K * k.N > INT32_MAX) return EWN_EINVAL;
+    if (batch_size < 1 || (int64_t)batch_size > (int64_t)K * k.N) return EWN_EINVAL;
+    return EWN_OK;
+}
+
+int64_t ewn_ppo_scratch_bytes(const ewn_config *cfg, int K, int batch_size)
+{
+    Geom g; KCfg k;
+    int rc = ppo_check(cfg, K, batch_size, g, k);
+    if (rc) return rc;
+    const int64_t P = ewn_policy_param_count(g.S, g.L);
+    return (int64_t)A2C_MAX_BLOCKS * (P + 8) * 4 + (int64_t)A2C_MAX_BLOCKS * 2 * 8;
+}
+
+static PpoCfg ppo_cfg(const KCfg &k, int K, int batch_size, const ewn_ppo_hyper *hp)
+{
+    PpoCfg c = { k.N, K, batch_size, hp->gamma, hp->gae_lambda, hp->clip_range, hp->vf_coef, hp->ent_coef, 1.0f / (float)batch_size,
+                 hp->normalize_advantage ? 1 : 0 };
+    return c;
+}
+
+int ewn_ppo_prepare(const ewn_config *cfg, int K, const uint8_t *record, const double *reward, const float *params, const ewn_ppo_hyper *hp,
+                    float *samples, void *stream)
+{
+    Geom g; KCfg k;
+    int rc = ppo_check(cfg, K, 1, g, k);
+    if (rc) return rc;
+    if (!record || !reward || !params || !hp || !samples) return EWN_ENULL;
+    PpoBuf b;
+    memset(&b, 0, sizeof(b));
+    b.rec = record; b.reward = reward; b.params = params; b.samples = (float4 *)samples;
+    const PpoCfg c = ppo_cfg(k, K, 1, hp);
+    const int blocks = (k.N + 127) / 128;            // one 32-lane tile per wave
+    hipStream_t s = (hipStream_t)stream;
+    auto launch = [&](auto kern, size_t lds) {
+        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return EWN_ELAUNCH;
+        kern<<<blocks, 256, lds, s>>>(c, b);
+        return launch_status();
+    };
+    static_assert(2 * Mlp3Geo<7>::FWD_BYTES <= 160 * 1024, "both nets' forward images must fit the CU's LDS");
+    return g.S == 5 ? launch(k_ppo_prepare<5>, 2 * (size_t)Mlp3Geo<5>::FWD_BYTES) : launch(k_ppo_prepare<7>, 2 * (size_t)Mlp3Geo<7>::FWD_BYTES);
+}
+
+int ewn_ppo_shuffle(int64_t n, int n_epochs, uint64_t key, const int32_t *counter, int32_t *perm, void *stream)
+{
+    if (n < 1 || n > INT32_MAX || n_epochs < 1 || n_epochs > 65535) return EWN_EINVAL;
+    if (!perm) return EWN_ENULL;
+    int bits = 0;
+    while ((1ll << bits) < n) bits++;
+    const int half = bits < 2 ? 1 : (bits + 1) / 2;
+    const int64_t need = (n + 255) / 256;
+    const unsigned gx = (unsigned)(need < 1024 ? need : 1024);
+    k_ppo_shuffle<<<dim3(gx, (unsigned)n_epochs), 256, 0, (hipStream_t)stream>>>((long long)n, half, (u64)key, counter, perm);
+    return launch_status();
+}
+
+template <int S>
+static int ppo_grad_launch(const PpoCfg &c, const PpoBuf &b, float *grad, hipStream_t s)
+{
+    constexpr size_t lds = Ppo3Geo<S>::lds_bytes();
+    static_assert(lds <= 160 * 1024, "weight images + the gradient image must fit the CU's LDS");
+    auto kv = k_ppo_grad3<S, 1>;
+    auto kp = k_ppo_grad3<S, 0>;
+    if (hipFuncSetAttribute((const void *)kv, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return EWN_ELAUNCH;
+    if (hipFuncSetAttribute((const void *)kp, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return EWN_ELAUNCH;
+    const int blocks = a2c_blocks(c.B, 4);
+    kv<<<blocks, 256, lds, s>>>(c, b);           // value pass first: it leaves the advantage sums for the policy pass
+    kp<<<blocks, 256, lds, s>>>(c, b);
+    A2cRedBuf rb = { b.partial, b.stats, grad, blocks, MlpGeo<S>::P };
+    a2c_reduce_launch(rb, s);
+    return launch_status();
+}
+
+int ewn_ppo_grad(const ewn_config *cfg, int K, const uint8_t *record, const float *samples, const float *params, const ewn_ppo_hyper *hp,
+                 const int32_t *idx, int batch_size, float *grad, void *scratch, void *stream)
+{
+    Geom g; KCfg k;
+    int rc = ppo_check(cfg, K, batch_size, g, k);
+    if (rc) return rc;
+    if (!record || !samples || !params || !hp || !idx || !grad || !scratch) return EWN_ENULL;
+    const int64_t P = ewn_policy_param_count(g.S, g.L);
+    PpoBuf b;
+    memset(&b, 0, sizeof(b));
+    b.rec = record; b.params = params; b.samples = (float4 *)samples; b.idx = idx;
+    b.partial = (float *)scratch;
+    b.stats = b.partial + (size_t)A2C_MAX_BLOCKS * P;
+    b.advst = (double *)(b.stats + (size_t)A2C_MAX_BLOCKS * 8);
+    const PpoCfg c = ppo_cfg(k, K, batch_size, hp);
+    hipStream_t s = (hipStream_t)stream;
+    return g.S == 5 ? ppo_grad_launch<5>(c, b, grad, s) : ppo_grad_launch<7>(c, b, grad, s);
+}
+
+int ewn_ppo_apply(const ewn_config *cfg, float *params, float *exp_avg, float *exp_avg_sq, int32_t *step, const float *grad,
+                  const ewn_ppo_hyper *hp, float *grad_norm_out, void *stream)
+{
+    Geom g; KCfg k;
+    int rc = a2c_geom(cfg, g, k);
+    if (rc) return rc;
+    if (!params || !exp_avg || !exp_avg_sq || !step || !grad || !hp) return EWN_ENULL;
+    if (hp->world_size < 1) return EWN_EINVAL;
+    PpoApplyCfg ac = { (int)ewn_policy_param_count(g.S, g.L), hp->learning_rate, hp->adam_beta1, hp->adam_beta2, hp->adam_eps, hp->max_grad_norm,
+                       1.0f / (float)hp->world_size };
+    const bool vec = ac.P <= 1024 * 4 * A2C_APPLY_V && ((uintptr_t)params | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)grad) % 16 == 0;
+    if (vec) k_ppo_apply<true><<<1, 1024, 0, (hipStream_t)stream>>>(ac, params, exp_avg, exp_avg_sq, step, grad, grad_norm_out);
+    else k_ppo_apply<false><<<1, 1024, 0, (hipStream_t)stream>>>(ac, params, exp_avg, exp_avg_sq, step, grad, grad_norm_out);
     return launch_status();
 }

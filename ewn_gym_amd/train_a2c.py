@@ -26,8 +26,9 @@ def main():
                     help="PPO: minibatch size in samples of the n_steps x lanes rollout buffer (default: a quarter of it; train.py:178-183)")
     ap.add_argument("--n_epochs", type=int, default=10, help="PPO: passes over the rollout buffer per update (SB3 default)")
     ap.add_argument("--trainer", default="auto", choices=["auto", "fused", "torch"],
-                    help="A2C only.  fused: the whole loop in the engine (ewn_step_k_policy + ewn_a2c_grad / ewn_a2c_apply, five kernel launches "
-                         "per update); torch: torch policy forward per step + ewn_step, autograd update; auto: fused where the engine has it")
+                    help="fused: the whole loop in the engine (A2C: ewn_step_k_policy + ewn_a2c_grad / ewn_a2c_apply, five kernel launches per "
+                         "update; PPO: ewn_step_k_policy + ewn_ppo_prepare / _shuffle / _grad / _apply, one hipGraph per update); torch: torch "
+                         "policy forward per step + ewn_step, autograd update; auto: A2C fused where the engine has it, PPO the torch trainer")
     ap.add_argument("--checkpoint", default=None, help="path of a checkpoint written by this trainer to resume from (train.py:137-139, 248-251)")
     ap.add_argument("--model_seed", type=int, default=None, help="seed of the policy initialisation and sampling (default: --env_seed)")
     ap.add_argument("--num_envs", "-ne", type=int, default=4096, help="lanes per GPU")
@@ -64,8 +65,9 @@ def main():
     env.reset(seeds=lane_seeds(lo, hi, a.seed).cuda())
     mseed = a.seed if a.model_seed is None else a.model_seed
     if a.algorithm == "PPO":   # train.py:39-49: SB3's PPO with batch_size and learning_rate given, the rest at its defaults (ewn_gym_amd/ppo.py)
-        from .ppo import PPOTrainer
-        trainer = PPOTrainer(env, n_steps=a.n_steps, batch_size=a.batch_size, n_epochs=a.n_epochs, learning_rate=a.learning_rate, seed=mseed)
+        from .ppo import FusedPPOTrainer, PPOTrainer
+        cls = FusedPPOTrainer if a.trainer == "fused" else PPOTrainer   # auto keeps the torch trainer for PPO
+        trainer = cls(env, n_steps=a.n_steps, batch_size=a.batch_size, n_epochs=a.n_epochs, learning_rate=a.learning_rate, seed=mseed)
     elif a.trainer == "fused" or (a.trainer == "auto" and env.supports_policy_rollout()):
         trainer = FusedA2CTrainer(env, n_steps=a.n_steps, learning_rate=a.learning_rate, seed=mseed)
     else:

@@ -35,7 +35,8 @@ extern "C" {
 #endif
 
 #define EWN_ABI_VERSION 4 /* 2: ewn_step_k, ewn_predict_minimax_sim, ewn_lanes_per_game; six table images; boards up to 11x11.  3: EWN_AGENT_SAMPLE; 32 KB table images.
-                             4: ewn_rollout_out.record, ewn_roll_dice, EWN_AGENT_MLP / ewn_policy, shaped env and MCTS opponent in ewn_step_k, ewn_a2c_* */
+                             4: ewn_rollout_out.record, ewn_roll_dice, EWN_AGENT_MLP / ewn_policy, shaped env and MCTS opponent in ewn_step_k, ewn_a2c_*;
+                                later ewn_ppo_hyper / ewn_ppo_* (purely additive: the version stays 4) */
 
 /* error codes */
 #define EWN_OK 0
@@ -293,6 +294,46 @@ int ewn_a2c_grad(const ewn_config *cfg, int K, const uint8_t *record, const doub
  * receives the norm before clipping.  A multi-GPU job all-reduces (sums) grad between the two calls -- the one collective. */
 int ewn_a2c_apply(const ewn_config *cfg, float *params, float *sq_avg, const float *grad, const ewn_a2c_hyper *hp, float *grad_norm_out,
                   void *stream);
+
+/* ---- the PPO update on the records of ewn_step_k_policy: stable_baselines3 PPO.train as train.py:39-49, 178-183 configures it, in the
+ * arithmetic of ewn_gym_amd/ppo.py's PPOTrainer (parity with SB3 unpinned, as for A2C).  Per update: ewn_ppo_prepare once (behaviour-
+ * policy log-probabilities, values, GAE(lambda) advantages and returns), ewn_ppo_shuffle once (every epoch's minibatch order), then per
+ * minibatch ewn_ppo_grad, the all-reduce of a multi-GPU job, ewn_ppo_apply.  Sample s = t * N + lane.  Served where ewn_a2c_* is
+ * (cube_layer 3, 5x5 and 7x7; anything else EWN_EUNSUPPORTED); K < 1 or batch_size outside [1, K * N]: EWN_EINVAL. */
+typedef struct ewn_ppo_hyper {
+    float gamma;               /* 0.99 */
+    float gae_lambda;          /* 0.95 */
+    float clip_range;          /* 0.2: the ratio is clamped to [1 - clip_range, 1 + clip_range] */
+    float vf_coef;             /* 0.5 */
+    float ent_coef;            /* 0.0 */
+    float max_grad_norm;       /* 0.5; <= 0: no clipping */
+    float learning_rate;       /* 3e-4 */
+    float adam_beta1;          /* 0.9 */
+    float adam_beta2;          /* 0.999 */
+    float adam_eps;            /* 1e-5 */
+    int32_t normalize_advantage; /* 1: (A - mean) / (std + 1e-8) over the minibatch (unbiased std, sums in double; minibatches of 2 or more) */
+    int32_t world_size;        /* ewn_ppo_apply divides the (all-reduced, summed) gradient by it */
+} ewn_ppo_hyper;
+
+/* bytes of device scratch ewn_ppo_grad needs (per-block partial gradients, loss sums and advantage sums; 8-byte aligned) */
+int64_t ewn_ppo_scratch_bytes(const ewn_config *cfg, int K, int batch_size);
+/* record [K + 1][N][EWN_TRAJ_RECORD_STRIDE(S)] from ewn_step_k_policy with record_initial_obs = 1, reward [K][N]; params: the parameters
+ * the rollout ran with.  samples [K * N][4] fp32 (16-byte aligned): {log pi(a_t | s_t), advantage, return = advantage + value, value}.
+ * One launch. */
+int ewn_ppo_prepare(const ewn_config *cfg, int K, const uint8_t *record, const double *reward, const float *params, const ewn_ppo_hyper *hp, float *samples, void *stream);
+/* perm [n_epochs][n] int32: row e a permutation of 0 .. n - 1 keyed by (key, *counter, e) (counter: a device int32, NULL = 0; FusedPPOTrainer
+ * passes its Adam step count, so a replayed graph shuffles differently every update).  A four-round Feistel network on the next even
+ * power of two with cycle walking; tests/test_ppo_fused_cpu.py holds a numpy mirror.  One launch. */
+int ewn_ppo_shuffle(int64_t n, int n_epochs, uint64_t key, const int32_t *counter, int32_t *perm, void *stream);
+/* One minibatch: idx [batch_size] sample indices (any, e.g. a slice of perm; an index outside [0, K * N) reads sample 0).
+ * grad [ewn_policy_param_count() + 8]: the gradient of the minibatch's mean loss in the layout of ewn_policy.params, then eight sums over
+ * the minibatch: [P + 0] -min(A r, A clamp(r)), [P + 1] entropy, [P + 2] samples with |r - 1| > clip_range, [P + 3] (r - 1) - log r,
+ * [P + 4] (R - V)^2; [P + 5 .. P + 7] are 0.  Deterministic (no atomics).  Three launches. */
+int ewn_ppo_grad(const ewn_config *cfg, int K, const uint8_t *record, const float *samples, const float *params, const ewn_ppo_hyper *hp, const int32_t *idx, int batch_size, float *grad, void *scratch, void *stream);
+/* clip by the global norm, then one Adam step (bias-corrected, torch's formula) on params / exp_avg / exp_avg_sq ([param count], in
+ * place); *step (device int32) is the number of steps taken so far and is incremented.  grad_norm_out (may be NULL): the norm before
+ * clipping.  One launch. */
+int ewn_ppo_apply(const ewn_config *cfg, float *params, float *exp_avg, float *exp_avg_sq, int32_t *step, const float *grad, const ewn_ppo_hyper *hp, float *grad_norm_out, void *stream);
 
 /* ---- stateless policy / rule queries on M given observations (canonical: TOP_LEFT to move) ---- */
 

@@ -1,7 +1,8 @@
 """Throughput of the on-device A2C loop (BASELINE config 4 on one GPU): shaped env, depth-3 minimax opponent, n_steps 5.
-   python tools/a2c_throughput.py [--trainer fused|torch|both] [--lanes 65536] [--updates 200]
+   python tools/a2c_throughput.py [--algorithm A2C|PPO] [--trainer fused|torch|both] [--lanes 65536] [--updates 200]
 fused: ewn_step_k_policy + ewn_a2c_grad + ewn_a2c_apply (five kernel launches per update, one hipGraph replay);
-torch: the round-2 loop (torch policy forward per step + ewn_step, torch autograd update)."""
+torch: the round-2 loop (torch policy forward per step + ewn_step, torch autograd update).
+--algorithm PPO: FusedPPOTrainer against PPOTrainer at their defaults (10 epochs x 4 minibatches) with the same n_steps."""
 import argparse
 import os
 import sys
@@ -11,8 +12,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import ewn_gym_amd as ea  # noqa: E402
 from ewn_gym_amd.a2c import A2CTrainer, FusedA2CTrainer  # noqa: E402
+from ewn_gym_amd.ppo import FusedPPOTrainer, PPOTrainer  # noqa: E402
 
 ap = argparse.ArgumentParser()
+ap.add_argument("--algorithm", default="A2C", choices=["A2C", "PPO"])
 ap.add_argument("--trainer", default="both", choices=["fused", "torch", "both"])
 ap.add_argument("--lanes", type=int, nargs="*", default=[4096, 65536])
 ap.add_argument("--updates", type=int, default=200)
@@ -23,9 +26,14 @@ for kind in (("fused", "torch") if a.trainer == "both" else (a.trainer,)):
         env = ea.VecEWN(N, opponent_policy="minimax", max_depth=3, rng="philox", shaped=True, reward=10.0, illegal_move_reward=-1.0,
                         illegal_move_tolerance=10, autoreset=True, shaped_refresh_on_reset=True, philox_key=1)
         env.reset(seeds=torch.arange(N, dtype=torch.int32))
-        cls = FusedA2CTrainer if kind == "fused" else A2CTrainer
+        if a.algorithm == "PPO":
+            cls = FusedPPOTrainer if kind == "fused" else PPOTrainer
+        else:
+            cls = FusedA2CTrainer if kind == "fused" else A2CTrainer
         tr = cls(env, n_steps=a.n_steps, learning_rate=3e-4, seed=0)
         n_upd = a.updates if kind == "fused" else max(10, a.updates // 5)
+        if a.algorithm == "PPO":   # forty optimiser steps per update
+            n_upd = max(5, n_upd // 10)
         for _ in range(5):
             tr.collect_and_update()
         torch.cuda.synchronize()
@@ -36,5 +44,5 @@ for kind in (("fused", "torch") if a.trainer == "both" else (a.trainer,)):
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         sd = tr.stats_dict() if kind == "fused" else tr.stats_dict(st)
-        print("A2C %s N=%d: %.3e env steps/s (%.3f ms per %d-step update), mean reward %.3f" %
-              (kind, N, (tr.num_timesteps - n0) / dt, dt / n_upd * 1e3, a.n_steps, sd["mean_reward"]), flush=True)
+        print("%s %s N=%d: %.3e env steps/s (%.3f ms per %d-step update), mean reward %.3f" %
+              (a.algorithm, kind, N, (tr.num_timesteps - n0) / dt, dt / n_upd * 1e3, a.n_steps, sd["mean_reward"]), flush=True)
