@@ -401,6 +401,35 @@ EWN_DEV void philox4x32_10(u32 c0, u32 c1, u32 c2, u32 c3, u32 k0, u32 k1, u32 (
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
+// The same block computed by a PAIR of lanes that execute together (xor-1 partners inside a quad; `sub` = 0 / 1; both lanes pass
+// the same counter and key and both get all four words).  A round maps half A = (c0, c1) and half B = (c2, c3) to
+// A' = (hi(MB * c2) ^ c1 ^ k0, lo(MB * c2)) and B' = (hi(MA * c0) ^ c3 ^ k1, lo(MA * c0)): the lane that holds one half makes
+// the OTHER half from its own two products and its partner's y ^ key.  The halves swap lanes every round, so each round costs
+// one multiply pair and one DPP exchange per lane, where philox4x32_10 spends two multiply pairs on every lane.
+EWN_DEV void philox4x32_10_pair(u32 c0, u32 c1, u32 c2, u32 c3, u32 k0, u32 k1, int sub, u32 (&out)[4])
+{
+    constexpr u32 MA = 0xD2511F53u, MB = 0xCD9E8D57u, WA = 0x9E3779B9u, WB = 0xBB67AE85u;
+    const bool b = (sub & 1) != 0;              // the half this lane holds at even rounds: A on sub 0, B on sub 1
+    u32 x = b ? c2 : c0, y = b ? c3 : c1;
+    const u32 mE = b ? MB : MA, mO = b ? MA : MB;
+    u32 kE = b ? k1 : k0, kO = b ? k0 + WA : k1 + WB; // key of the half held at the next even / odd round, at that round
+    const u32 wE = b ? 2u * WB : 2u * WA, wO = b ? 2u * WA : 2u * WB;
+    #pragma unroll
+    for (int r = 0; r < 10; r++) {
+        const u32 k = (r & 1) ? kO : kE, m = (r & 1) ? mO : mE;
+        const u32 send = y ^ k;
+        const u32 h = __umulhi(m, x), l = m * x;
+        x = h ^ (u32)__builtin_amdgcn_update_dpp(0, (int)send, 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true);
+        y = l;
+        if (r & 1) kO += wO; else kE += wE;
+    }
+    // ten rounds: sub 0 holds A again, sub 1 holds B
+    out[0] = (u32)__builtin_amdgcn_update_dpp(0, (int)x, 0xA0 /* quad_perm [0,0,2,2] */, 0xF, 0xF, true);
+    out[1] = (u32)__builtin_amdgcn_update_dpp(0, (int)y, 0xA0, 0xF, 0xF, true);
+    out[2] = (u32)__builtin_amdgcn_update_dpp(0, (int)x, 0xF5 /* quad_perm [1,1,3,3] */, 0xF, 0xF, true);
+    out[3] = (u32)__builtin_amdgcn_update_dpp(0, (int)y, 0xF5, 0xF, 0xF, true);
+}
+
 // Sequential u32 stream: word n = philox(ctr={n>>2, c1, c2, c3}, key)[n&3].
 // The cached block is four scalars, not an array: an array indexed by (n & 3) ends up in scratch memory.
 struct PhiloxStream {
@@ -413,6 +442,12 @@ struct PhiloxStream {
     {
         const u32 b = n >> 2;
         if (have != b + 1) { u32 o[4]; philox4x32_10(b, c1, c2, c3, k0, k1, o); b0 = o[0]; b1 = o[1]; b2 = o[2]; b3 = o[3]; have = b + 1; }
+    }
+    // prime() for two lanes that hold the same stream and run together (philox4x32_10_pair; `sub` = 0 / 1): the same block
+    EWN_DEV void prime_pair(int sub)
+    {
+        const u32 b = n >> 2;
+        if (have != b + 1) { u32 o[4]; philox4x32_10_pair(b, c1, c2, c3, k0, k1, sub, o); b0 = o[0]; b1 = o[1]; b2 = o[2]; b3 = o[3]; have = b + 1; }
     }
     EWN_DEV u32 next()
     {

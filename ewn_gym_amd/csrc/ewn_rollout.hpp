@@ -101,13 +101,21 @@ EWN_DEV void rec_slot_build(const FastTab<S> *Tb, const RState<S> &s, int sub, i
     __builtin_amdgcn_wave_barrier();
 }
 
-// setup_game into the slot (auto-reset): every lane of the game stores the same constants
-template <int S>
-EWN_DEV void rec_slot_init(int8_t *slot)
+// setup_game into the slot (auto-reset): lane `sub` of the game's T lanes stores the 16-byte pieces sub, sub + T, ...
+template <int S, int T = 1>
+EWN_DEV void rec_slot_init(int8_t *slot, int sub = 0)
 {
     constexpr InitRec<S> I{};
     #pragma unroll
-    for (int c = 0; c < RecGeo<S>::NCH; c++) ((uint4 *)slot)[c] = make_uint4(I.w[4 * c], I.w[4 * c + 1], I.w[4 * c + 2], I.w[4 * c + 3]);
+    for (int c0 = 0; c0 < RecGeo<S>::NCH; c0 += T) {
+        const int c = c0 + sub;
+        u32 w[4] = { I.w[4 * c0], I.w[4 * c0 + 1], I.w[4 * c0 + 2], I.w[4 * c0 + 3] };
+        #pragma unroll
+        for (int cc = c0 + 1; cc < c0 + T && cc < RecGeo<S>::NCH; cc++) // the compile-time candidates for c
+            #pragma unroll
+            for (int i = 0; i < 4; i++) w[i] = c == cc ? I.w[4 * cc + i] : w[i];
+        if (c < RecGeo<S>::NCH) ((uint4 *)slot)[c] = make_uint4(w[0], w[1], w[2], w[3]);
+    }
 }
 
 // one record out: lane `sub` of the game's T lanes takes the 16-byte pieces sub, sub + T, ...; the six meta bytes are OR-ed into
@@ -148,10 +156,11 @@ EWN_DEV void rec_store(const int8_t *slot, int sub, int dice, int aflag, int adi
 // The stand-in agent's action for the current observation (the agent is the canonical BOTTOM_RIGHT side): RandomAgent.predict -- the
 // same draw ewn_step_out.random_action makes at the end of the previous step -- or, with c.agent_sample, env.action_space.sample():
 // one of the six (flag, direction) pairs, legal or not.  Hash-driven: the dice stream is not touched.
+// e: pk_sel(s.posN, dice), which the agent half reads too
 template <int S>
-EWN_DEV void roll_stand_in_action(const FastTab<S> *Tb, const RState<S> &s, int dice, LaneRng &r, const RollCfg &c, int game, int &aflag, int &adir)
+EWN_DEV void roll_stand_in_action(const FastTab<S> *Tb, const RState<S> &s, u32 e, LaneRng &r, const RollCfg &c, int game, int &aflag, int &adir)
 {
-    const u32 e = pk_sel<S>(Tb, s.posN, dice), pp = pk_pair(s.posN, e);
+    const u32 pp = pk_pair(s.posN, e);
     const u32 okm = (u32)Tb->lgn[pp & 0xFFu] | ((u32)Tb->lgn[pp >> 8] << 3);
     const int n = __popc(okm);
     const u32 w = agent_hash(r.seed_mix(), r.draws(), (u32)(c.lane_offset + game), c.key);
@@ -166,27 +175,49 @@ EWN_DEV void roll_stand_in_action(const FastTab<S> *Tb, const RState<S> &s, int 
     }
 }
 
-// agent half of step() (envs/ewn.py:438-458): true if the opponent has to reply (then `dice` is the opponent's roll)
-// slot: the game's board bytes in LDS, kept current (NULL: the caller encodes the board itself)
-template <int S>
-EWN_DEV bool roll_agent_half(const FastTab<S> *Tb, RState<S> &s, int aflag, int adir, int &dice, LaneRng &r, double R,
-                             double &reward, int &term, int &trunc, int &info, int8_t *slot = nullptr)
+// A move's two byte stores into the game's LDS slot: the source cell cleared, the destination set to `v`.  With T = 1 one lane stores
+// both, source first (LDS stores of one wave land in program order); with T > 1 lane 0 of the game clears the source and lane 1
+// sets the destination: one table read and one store per lane (the cells differ, so the order does not matter).
+template <int S, int T>
+EWN_DEV void slot_move(const FastTab<S> *Tb, int8_t *slot, int sub, int pb, int q, int v)
 {
-    const int k = pk_cube(pk_sel<S>(Tb, s.posN, dice), aflag == 1);
+    if constexpr (T == 1) { const int cp = Tb->real_of_ring[pb & 63], cq = Tb->real_of_ring[q & 63]; slot[cp] = 0; slot[cq] = (int8_t)v; }
+    else {
+        const bool dst = sub == 1;
+        if (sub < 2) slot[Tb->real_of_ring[(dst ? q : pb) & 63]] = (int8_t)(dst ? v : 0);
+    }
+}
+
+// agent half of step() (envs/ewn.py:438-458): true if the opponent has to reply (then `dice` is the opponent's roll)
+// e: pk_sel(s.posN, dice); slot: the game's board bytes in LDS, kept current (NULL: the caller encodes the board itself),
+// by the game's T lanes (`sub`: this lane's index among them)
+template <int S, int T = 1>
+EWN_DEV bool roll_agent_half(const FastTab<S> *Tb, RState<S> &s, u32 e, int aflag, int adir, int &dice, LaneRng &r, double R,
+                             double &reward, int &term, int &trunc, int &info, int8_t *slot = nullptr, int sub = 0)
+{
+    const int k = pk_cube(e, aflag == 1);
     const int pb = pk_get(s.posN, k);
     const int q = Tb->nbn[adir][pb]; // no cube at all: byte 6 -> 255
     if (q == 255) { reward = -R; term = 1; trunc = 1; info = EWN_INFO_INVALID_PLAYER; return false; }
-    if (slot) { // the agent's cube k is the real +(k + 1); source first: LDS stores of one wave land in program order
-        const int cp = Tb->real_of_ring[pb & 63], cq = Tb->real_of_ring[q];
-        slot[cp] = 0; slot[cq] = (int8_t)(k + 1);
-    }
+    if (slot) slot_move<S, T>(Tb, slot, sub, pb, q, k + 1); // the agent's cube k is the real +(k + 1)
     rs_move<S, false>(s, k, q);
     if (q == Tb->ri_origin || s.P == 0) { reward = R; term = 1; info = EWN_INFO_WON; return false; }
     dice = r.randint(1, 7);
     return true;
 }
 
-// opponent half (envs/ewn.py:464-486) once its action (oflag, odir) is known
+// opponent half (envs/ewn.py:464-486) once its move is known: cube k from ring cell pb (its position byte) to ring cell q
+template <int S, int T = 1>
+EWN_DEV void roll_opponent_move(const FastTab<S> *Tb, RState<S> &s, int k, int pb, int q, int &dice, LaneRng &r, double R,
+                                double &reward, int &term, int &info, int8_t *slot = nullptr, int sub = 0)
+{
+    if (slot) slot_move<S, T>(Tb, slot, sub, pb, q, -(k + 1));
+    rs_move<S, true>(s, k, q);
+    if (q == FastTab<S>::CELLS - 1 || s.N == 0) { reward = -R; term = 1; info = EWN_INFO_LOST; }
+    else dice = r.randint(1, 7);
+}
+
+// ... once its action (oflag, odir) is known
 template <int S>
 EWN_DEV void roll_opponent_half(const FastTab<S> *Tb, RState<S> &s, u32 e, int oflag, int odir, int &dice, LaneRng &r, double R,
                                 double &reward, int &term, int &info, int8_t *slot = nullptr)
@@ -194,10 +225,7 @@ EWN_DEV void roll_opponent_half(const FastTab<S> *Tb, RState<S> &s, u32 e, int o
     const int k = pk_cube(e, oflag == 1);
     const int pb = pk_get(s.posP, k);
     const int q = Tb->nbp[odir][pb];
-    if (slot) { const int cp = Tb->real_of_ring[pb & 63], cq = Tb->real_of_ring[q & 63]; slot[cp] = 0; slot[cq] = (int8_t)(-(k + 1)); }
-    rs_move<S, true>(s, k, q);
-    if (q == FastTab<S>::CELLS - 1 || s.N == 0) { reward = -R; term = 1; info = EWN_INFO_LOST; }
-    else dice = r.randint(1, 7);
+    roll_opponent_move<S>(Tb, s, k, pb, q, dice, r, R, reward, term, info, slot);
 }
 
 // AGENT 0: RandomAgent (the hash-driven uniform legal pick of ewn_step_out.random_action); 1: ExpectiMinimaxAgent of
@@ -270,7 +298,7 @@ __global__ __launch_bounds__(D3_BS, ((OPP == 2 || AGENT == 2) ? 2 : 1)) void k_r
         // ---- the agent's action for the current observation (the agent is the canonical BOTTOM_RIGHT side)
         int aflag = 0, adir = 0;
         if constexpr (AGENT == 0) {
-            roll_stand_in_action<S>(Tb, s, dice, r, c, game, aflag, adir);
+            roll_stand_in_action<S>(Tb, s, pk_sel<S>(Tb, s.posN, dice), r, c, game, aflag, adir);
         } else {
             // ExpectiMinimaxAgent.predict(canonical observation): the agent's own position IS canonical for it once flipped
             const RState<S> f = rs_flip<S>(Ta, s);
@@ -284,7 +312,7 @@ __global__ __launch_bounds__(D3_BS, ((OPP == 2 || AGENT == 2) ? 2 : 1)) void k_r
         }
         RSTAMP(0); // agent's action + RNG block
         bool reply = false;
-        if (active) reply = roll_agent_half<S>(Tb, s, aflag, adir, dice, r, c.reward, reward, term, trunc, info);
+        if (active) reply = roll_agent_half<S>(Tb, s, pk_sel<S>(Tb, s.posN, dice), aflag, adir, dice, r, c.reward, reward, term, trunc, info);
         RSTAMP(1); // agent half
         // the opponent's search: run by every lane (lanes without a pending reply compute on a harmless state)
         int oflag = 0, odir = 0;
@@ -447,6 +475,7 @@ __global__ __launch_bounds__(D3_BS, (OPP == 2 ? 2 : 1)) void k_rollout_slots(Rol
     int kdone = 0, phase = 0;                       // env steps finished; 0 = next iteration starts a step, 1 = it searches the second cube
     double reward = 0.0, best = 0.0;
     int term = 0, trunc = 0, info = EWN_INFO_NONE, aflag = 0, adir = 0, oflag = 0, odir = 0;
+    u32 omove = 0;                                  // OPP 0: the opponent's move as d3_search returns it (bmove)
     bool reply = false;
 #ifdef EWN_ROLLOUT_STAMPS
     unsigned long long st_acc[6] = { 0, 0, 0, 0, 0, 0 }, st_prev;   // [4] counts the iterations
@@ -460,32 +489,41 @@ __global__ __launch_bounds__(D3_BS, (OPP == 2 ? 2 : 1)) void k_rollout_slots(Rol
         const bool active = start && !frozen;
         if (start) {
             reward = 0.0; term = frozen ? 1 : 0; trunc = 0; info = EWN_INFO_NONE; reply = false; aflag = 0; adir = 0;
-            roll_stand_in_action<S>(Tb, s, dice, r, c, game, aflag, adir);
+            const u32 esel = pk_sel<S>(Tb, s.posN, dice);
+            roll_stand_in_action<S>(Tb, s, esel, r, c, game, aflag, adir);
             if (active) { // a frozen lane's stream stays where its last step left it
                 if constexpr (RNGK == 0) r.prefetch();
                 r.begin_step();
-                if constexpr (RNGK == 1) r.ps.prime();
-                reply = roll_agent_half<S>(Tb, s, aflag, adir, dice, r, c.reward, reward, term, trunc, info, slot_m);
+                // the game's two lanes share the step's Philox block (the lanes of a game take the same branches)
+                if constexpr (RNGK == 1) { if constexpr (T == 2) r.ps.prime_pair(sub); else r.ps.prime(); }
+                reply = roll_agent_half<S, T>(Tb, s, esel, aflag, adir, dice, r, c.reward, reward, term, trunc, info, slot_m, sub);
             }
         }
         RSTAMP(0); // start of an env step: the agent's action, RNG block, agent half
         // one cube's three roots of the opponent's search, run by every lane (lanes without a pending reply compute on a harmless
         // state, so the DPP exchanges inside always see their partners)
         bool second = false;
-        if constexpr (OPP == 0) best = d3_search<S, T, H2, true>(Tb, s, dice, sub, c.depth, oflag, odir, phase, best, &second);
+        if constexpr (OPP == 0) best = d3_search<S, T, H2, true>(Tb, s, dice, sub, c.depth, oflag, odir, phase, best, &second, &omove);
         else best = d5c_search<S, TS, true>(Tb, s, dice, T > 2 ? (sub & 1) : sub, oflag, odir, phase, best, &second);
         RSTAMP(1); // search
         if (pending && phase == 0 && reply && second) phase = 1; // the same env step goes on with the second cube
         else if (pending) {
             phase = 0;
-            if (reply) roll_opponent_half<S>(Tb, s, pk_sel<S>(Tb, s.posP, dice), oflag, odir, dice, r, c.reward, reward, term, info, slot_m);
+            if (reply) {
+                if constexpr (OPP == 0) { // the search's chosen root is the move
+                    roll_opponent_move<S, T>(Tb, s, (int)(omove & 7u), (int)((omove >> 8) & 0xFFu), (int)(omove >> 16), dice, r, c.reward, reward, term, info, slot_m, sub);
+                } else {
+                    const int k = pk_cube(pk_sel<S>(Tb, s.posP, dice), oflag == 1), pb = pk_get(s.posP, k);
+                    roll_opponent_move<S, T>(Tb, s, k, pb, Tb->nbp[odir][pb], dice, r, c.reward, reward, term, info, slot_m, sub);
+                }
+            }
             if (!frozen) {
                 ret_acc += reward; n_steps++; n_eps += term; n_wins += info == EWN_INFO_WON ? 1 : 0;
                 if (term) {
                     if (c.autoreset) { // reset(seed = next_seed) + setup_game (envs/ewn.py:488-494, 94-108); Philox kind only (host check)
                         r.next_episode(B.rng, c.N, game, c.seed_stride, c.key, nullptr);
                         d3_init_state<S>(Tb, s);
-                        if (want_slot) rec_slot_init<S>(slot_b);
+                        if (want_slot) rec_slot_init<S, T>(slot_b, sub);
                         dice = r.first_dice(6);
                     } else frozen = true;
                 }

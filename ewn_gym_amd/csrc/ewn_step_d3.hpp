@@ -265,9 +265,13 @@ template <int T> EWN_DEV void publish(u32 mine, int i, u32 (&out)[6])
 // PERLANE (the slot-task rollout kernel, ewn_rollout.hpp): one call searches the three roots of ONE root cube -- slotL = 0: the
 // first cube of the legal list, 1: the second -- and carries best / bflag / bdir in and out, so that a game whose dice selects a
 // single cube (most do) is finished after one call; returns through `have_second` whether the list has a second cube.
+// bmove (PERLANE only, may be NULL): the chosen root as the move the caller makes, carried in and out like bflag / bdir:
+// cube | its position byte << 8 | destination ring cell << 16 -- what the opponent half would otherwise look up again
+// (set whenever a valid root exists, which it does for every position whose game goes on: only the corner a TOP_LEFT cube wins
+// on has no legal direction)
 template <int S, int T, bool H2 = false, bool PERLANE = false>
 __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S> &c, int dice, int sub, int depth, int &bflag, int &bdir,
-                                            int slotL = 0, double best_in = 0.0, bool *have_second = nullptr)
+                                            int slotL = 0, double best_in = 0.0, bool *have_second = nullptr, u32 *bmove = nullptr)
 {
     typedef typename MaskOf<S>::type M;
     constexpr int KPT = 6 / T + (6 % T ? 1 : 0); // replier cubes / dice values per lane: k = sub + T*i
@@ -279,11 +283,15 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
     const bool have0 = !(rb0 & PK_OFF), have1 = !(rb1 & PK_OFF);
     const int flag0 = (int)(rsel >> 15);
     const int rp0 = rb0 & 63, rp1 = rb1 & 63;
+    // (cube | position byte << 8) of the two root cubes, for bmove
+    const u32 rm0 = (rsel & 7u) | ((rpp & 0xFFu) << 8), rm1 = ((rsel >> 8) & 7u) | (rpp & 0xFF00u);
+    u32 bm = 0;
 
     double best = -__builtin_inf(); // alpha = max(alpha, best_val): the running best (root beta stays +inf)
     if constexpr (PERLANE) {
         *have_second = have1;
         if (slotL == 0) { bflag = 0; bdir = 0; } else best = best_in;
+        if (bmove && slotL != 0) bm = *bmove;
     } else { bflag = 0; bdir = 0; }
 
     if (depth < 3) {
@@ -306,9 +314,9 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
             #pragma unroll
             for (int d = 0; d < 6; d++) v = v + e6;
             v = term ? 10.0 : (depth == 1 ? e1 : v);
-            if (valid && v > best) { best = v; bflag = slot == 0 ? flag0 : 0; bdir = dir; }
+            if (valid && v > best) { best = v; bflag = slot == 0 ? flag0 : 0; bdir = dir; bm = (slot == 0 ? rm0 : rm1) | ((u32)dest << 16); }
         }
-        if constexpr (PERLANE) *have_second = false; // both cubes were searched in this one call
+        if constexpr (PERLANE) { *have_second = false; if (bmove) *bmove = bm; } // both cubes were searched in this one call
         return best;
     }
 
@@ -344,6 +352,7 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
     // kernel) do not fit the instruction cache shared by two CUs
     // (the slot-task kernel's three roots ARE unrolled: 24 KB of code still fit, the direction becomes a constant: -1.5 %, 163 -> 152 VGPRs)
     constexpr int ROOT_UNROLL = PERLANE ? 3 : 1;
+    const u32 rmL = slotL == 0 ? rm0 : rm1;
     #pragma unroll ROOT_UNROLL
     for (int r = 0; r < (PERLANE ? 3 : 6); r++) {
         const int slot = PERLANE ? slotL : (r >= 3 ? 1 : 0), dir = PERLANE ? r : r - 3 * slot;
@@ -447,9 +456,10 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
         #pragma unroll
         for (int d = 0; d < 6; d++) v = v + ft_val6<S>(Tb, wq[d]); // expected_val += val / 6 in dice order, minimax.py:72
         v = term ? 10.0 : v;
-        if (valid && v > best) { best = v; bflag = slot == 0 ? flag0 : 0; bdir = dir; }
+        if (valid && v > best) { best = v; bflag = slot == 0 ? flag0 : 0; bdir = dir; if constexpr (PERLANE) bm = rmL | ((u32)dest << 16); }
     }
     D3_PRIO_LO();
+    if constexpr (PERLANE) { if (bmove) *bmove = bm; }
     return best;
 }
 
