@@ -25,7 +25,8 @@ EXPORTS = ["ewn_abi_version", "ewn_strerror", "ewn_rng_words", "ewn_step_scratch
            "ewn_step", "ewn_legal_actions", "ewn_apply_action", "ewn_playout_wins", "ewn_evaluate", "ewn_predict_minimax", "ewn_predict_random",
            "ewn_predict_mcts", "ewn_step_k", "ewn_step_k_supported", "ewn_predict_minimax_sim", "ewn_lanes_per_game", "ewn_roll_dice",
            "ewn_policy_param_count", "ewn_step_k_policy", "ewn_a2c_scratch_bytes", "ewn_a2c_grad", "ewn_a2c_apply",
-           "ewn_ppo_scratch_bytes", "ewn_ppo_prepare", "ewn_ppo_shuffle", "ewn_ppo_grad", "ewn_ppo_apply"]
+           "ewn_ppo_scratch_bytes", "ewn_ppo_prepare", "ewn_ppo_shuffle", "ewn_ppo_grad", "ewn_ppo_apply",
+           "ewn_policy_eval_supported", "ewn_policy_eval"]
 AGENT = {"random": 0, "minimax": 1, "sample": 2, "mlp": 3}   # "mlp": the trained policy, through ewn_step_k_policy   # "sample": env.action_space.sample(), all six actions (EWN_AGENT_SAMPLE)
 
 
@@ -134,6 +135,8 @@ def load():
         "ewn_ppo_shuffle": (i32, [C.c_int64, i32, u64, vp, vp, vp]),
         "ewn_ppo_grad": (i32, [cfgp, i32, vp, vp, vp, C.POINTER(EwnPpoHyper), vp, i32, vp, vp, vp]),
         "ewn_ppo_apply": (i32, [cfgp, vp, vp, vp, vp, vp, C.POINTER(EwnPpoHyper), vp, vp]),
+        "ewn_policy_eval_supported": (i32, [cfgp]),
+        "ewn_policy_eval": (i32, [cfgp, stp, i32, vp, C.POINTER(EwnRolloutOut), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

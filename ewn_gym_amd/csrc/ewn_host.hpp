@@ -180,3 +180,8 @@ int ewn_launch_rollout_s7(const RollCfg &rc, const RollBuf &rb, int T, int opp, 
 int ewn_launch_rollout_s8(const RollCfg &rc, const RollBuf &rb, int T, int opp, int rngk, int agent, bool h2, hipStream_t s);
 // ewn_policy.hip: the policy-driven rollout (ewn_step_k_policy); EWN_OK when it serves the configuration
 int ewn_policy_supported(const ewn_config *cfg, const Geom &g);
+// ewn_policy_eval.hip: the evaluation instances of the policy-driven rollout (ewn_policy_eval); opp 0 minimax max_depth 1-4,
+// 1 RandomAgent, 2 minimax max_depth 5 / 6; rngk EWN_RNG_*
+struct PolCfg;
+struct PolBuf;
+int ewn_launch_policy_eval(const PolCfg &pc, const PolBuf &pb, int S, int opp, int rngk, hipStream_t s);

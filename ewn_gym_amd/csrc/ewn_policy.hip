@@ -1,5 +1,6 @@
-// ewn_policy.hip -- the policy-driven rollout (ewn_step_k_policy), the fused A2C update (ewn_a2c_*) and the fused PPO update
-// (ewn_ppo_*): kernels in ewn_policy.hpp / ewn_a2c.hpp / ewn_ppo.hpp, C ABI here.
+// ewn_policy.hip -- the policy-driven rollout (ewn_step_k_policy), its evaluation form (ewn_policy_eval: instances in
+// ewn_policy_eval.hip), the fused A2C update (ewn_a2c_*) and the fused PPO update (ewn_ppo_*): kernels in ewn_policy.hpp /
+// ewn_a2c.hpp / ewn_ppo.hpp, C ABI here.
 #include "ewn_host.hpp"
 #include "ewn_lds.hpp"
 #include "ewn_policy.hpp"
@@ -95,6 +96,57 @@ int ewn_step_k_policy(const ewn_config *cfg, const ewn_state *st, int K, const e
     }
     hipStream_t s = (hipStream_t)stream;
     return g.S == 5 ? pol_dispatch<5>(pc, pb, opp, s) : pol_dispatch<7>(pc, pb, opp, s);
+}
+
+// ---------------------------------------------------------------- the evaluation (ewn_policy_eval)
+
+// which evaluation instance serves the configuration: un-shaped, no auto-reset, either dice kind; opp 0 minimax max_depth 1-4,
+// 1 RandomAgent, 2 minimax max_depth 5 / 6 (the closed form: the (level, count) images only, not 'two_min_dist')
+static int policy_eval_plan(const ewn_config *cfg, const Geom &g, int &opp)
+{
+    if (fast_tables_bytes(g.S, g.L) <= 0 || (g.S != 5 && g.S != 7)) return EWN_EUNSUPPORTED;
+    if (cfg->shaped || cfg->autoreset) return EWN_EUNSUPPORTED;
+    if (cfg->opponent_kind == EWN_OPP_RANDOM) opp = 1;
+    else if (cfg->opponent_kind == EWN_OPP_MINIMAX && fast_heur_lean(cfg->heuristic)) opp = cfg->max_depth > 4 ? 2 : 0;
+    else return EWN_EUNSUPPORTED;
+    return EWN_OK;
+}
+
+int ewn_policy_eval_supported(const ewn_config *cfg)
+{
+    Geom g; KCfg k;
+    int rc = check_cfg(cfg, g, k);
+    if (rc) return rc;
+    int opp;
+    rc = policy_eval_plan(cfg, g, opp);
+    return rc == EWN_OK ? 1 : (rc == EWN_EUNSUPPORTED ? 0 : rc);
+}
+
+int ewn_policy_eval(const ewn_config *cfg, const ewn_state *st, int K, const float *params, const ewn_rollout_out *out, void *stream)
+{
+    Geom g; KCfg k;
+    int rc = check_cfg(cfg, g, k);
+    if (rc) return rc;
+    if (K < 1) return EWN_EINVAL;
+    if (!st || !st->board || !st->dice || !st->done || !st->rng || !st->tables || !params || !out) return EWN_ENULL;
+    if (!out->return_sum || !out->n_steps || !out->n_episodes || !out->n_wins) return EWN_ENULL;
+    if (out->board || out->dice || out->reward || out->terminated || out->truncated || out->info || out->record) return EWN_EINVAL;
+    int opp;
+    rc = policy_eval_plan(cfg, g, opp);
+    if (rc) return rc;
+    PolCfg pc;
+    memset(&pc, 0, sizeof(pc));
+    pc.N = k.N; pc.lane_offset = k.lane_offset; pc.depth = k.depth; pc.K = K;
+    pc.deterministic = 1;
+    pc.seed_stride = k.seed_stride; pc.W = k.W; pc.reward = k.reward; pc.illegal_reward = k.illegal_reward; pc.key = k.key;
+    PolBuf pb;
+    memset(&pb, 0, sizeof(pb));
+    pb.board = st->board; pb.dice = st->dice; pb.done = st->done; pb.rng = st->rng;
+    pb.tables = opp == 1 ? st->tables : fast_image(st->tables, g.S, g.L, cfg->max_depth, cfg->heuristic);
+    pb.params = params;
+    pb.t_action = out->action;
+    pb.ret_sum = out->return_sum; pb.n_steps = out->n_steps; pb.n_episodes = out->n_episodes; pb.n_wins = out->n_wins;
+    return ewn_launch_policy_eval(pc, pb, g.S, opp, k.rng_kind, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------- the A2C update

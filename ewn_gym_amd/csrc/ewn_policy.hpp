@@ -63,15 +63,21 @@ EWN_DEV float pol_uniform(u32 w0, int i)
 // ln x on v_log_f32 (log2, ~1 ulp) -- the Gumbel noise -ln(-ln u) ten times per game and step; the library logf is ~20 instructions each
 EWN_DEV float pol_log(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
 
-// OPP 0: minimax max_depth 1-4 on a (level, count) table image; 1: RandomAgent.  Philox dice.
+// OPP 0: minimax max_depth 1-4 on a (level, count) table image; 1: RandomAgent; 2: minimax max_depth 5 / 6 on such an image (the
+// closed form, d5_dispatch; TRJ 2 only).  RNGK: the dice, 1 Philox; 0 MT19937-compat (TRJ 2 only: one episode per lane).
 // TRJ 1: the trainer's call, known at compile time -- records (row 0 = the initial observation) and the reward column, nothing else
 // written per step, actions sampled, no value output (FusedA2CTrainer; the gradient kernels recompute the forward pass).  0: everything
 // by PolCfg / PolBuf at run time (a dozen loop-invariant tests whose masks the compiler keeps in spilled SGPRs: 126 of them).
-template <int S, int OPP, int NT, int TRJ = 0>
-__global__ __launch_bounds__(NT, NT / 256) void k_rollout_mlp(PolCfg c, PolBuf B)
+// TRJ 2: the evaluation (ewn_policy_eval), known at compile time -- argmax actions (no noise computed), un-shaped env, no auto-reset,
+// no records and no policy outputs; the per-lane totals and optionally the action column of the steps a lane plays.  Nothing is
+// written for a finished lane, so a wave whose 32 games are all finished leaves the step loop (there is no block barrier inside it);
+// the other instances write rows for finished lanes and keep stepping.  Held to 256 registers (two waves per SIMD) at every NT.
+template <int S, int OPP, int NT, int TRJ = 0, int RNGK = 1>
+__global__ __launch_bounds__(NT, TRJ == 2 ? 2 : NT / 256) void k_rollout_mlp(PolCfg c, PolBuf B)
 {
-    constexpr bool FIX = TRJ == 1;
-    const bool want_value = !FIX && c.want_value, deterministic = !FIX && c.deterministic, rec0 = FIX || c.rec0;
+    constexpr bool FIX = TRJ == 1, EV = TRJ == 2;
+    static_assert(EV || (OPP != 2 && RNGK == 1), "the depth-5 opponent and the MT19937-compat dice are evaluation-only");
+    const bool want_value = !FIX && !EV && c.want_value, deterministic = EV || (!FIX && c.deterministic), rec0 = FIX || (!EV && c.rec0);
     constexpr int T = 2, GPB = NT / T, NW = NT / 64, CELLS = S * S, STR = RecGeo<S>::STR, NCH = RecGeo<S>::NCH;
     using G = MlpGeo<S>;
     extern __shared__ __attribute__((aligned(16))) int8_t lds[];
@@ -103,11 +109,11 @@ __global__ __launch_bounds__(NT, NT / 256) void k_rollout_mlp(PolCfg c, PolBuf B
         hdr = *rng_hdr_ptr(B.rng, game);
         dice = B.dice[game];
         frozen = B.done[game] != 0;
-        if (c.shaped) { tol = B.tolerance[game]; prev = B.prev_score[game]; }
+        if (!EV && c.shaped) { tol = B.tolerance[game]; prev = B.prev_score[game]; }
     }
     const bool frozen0 = frozen;
     block_copy_in(slots, B.board + (size_t)g0 * CELLS, ng * CELLS);      // packed boards, decoded from there
-    LaneRng r; r.load(1, hdr, nullptr, c.W, c.key);
+    LaneRng r; r.load(RNGK, hdr, RNGK == 0 ? rng_win_ptr(B.rng, c.N, c.W, live ? game : 0, RNGF_CUR(hdr.w)) : nullptr, c.W, c.key);
     r.begin_kernel();
     lds_dma_wait();
     __syncthreads();
@@ -126,6 +132,7 @@ __global__ __launch_bounds__(NT, NT / 256) void k_rollout_mlp(PolCfg c, PolBuf B
 
     #pragma unroll 1
     for (int kstep = 0; kstep < c.K; kstep++) {
+        if constexpr (EV) { if (__ballot(live && !frozen) == 0) break; }   // wave-uniform: every game of this wave is over
         const bool active = live && !frozen;
         double reward = 0.0;
         int term = 0, trunc = 0, info = EWN_INFO_NONE;
@@ -168,7 +175,7 @@ __global__ __launch_bounds__(NT, NT / 256) void k_rollout_mlp(PolCfg c, PolBuf B
         const float z0 = lg.x + gn[0], z1 = lg.y + gn[1], z2 = lg.z + gn[2], z3 = lg.w + gn[3], z4 = lg4 + gn[4];
         const int aflag = z1 > z0 ? 1 : 0;
         const int adir = z3 > z2 ? (z4 > z3 ? 2 : 1) : (z4 > z2 ? 2 : 0);
-        if (!FIX && writer) {
+        if (!FIX && !EV && writer) {
             const size_t o = (size_t)kstep * c.N + game;
             if (B.t_logits) { float *p = B.t_logits + o * 5; p[0] = lg.x; p[1] = lg.y; p[2] = lg.z; p[3] = lg.w; p[4] = lg4; }
             if (B.t_value) B.t_value[o] = val;
@@ -177,13 +184,14 @@ __global__ __launch_bounds__(NT, NT / 256) void k_rollout_mlp(PolCfg c, PolBuf B
         // ---- agent half, envs/ewn.py:438-458 / envs/training_ewn.py:44-66 (the agent is the canonical BOTTOM_RIGHT side)
         bool reply = false;
         if (active) {
+            if constexpr (RNGK == 0) r.prefetch();
             r.begin_step();
-            r.ps.prime();
+            if constexpr (RNGK == 1) r.ps.prime();
             const int k = pk_cube(pk_sel<S>(Tb, s.posN, dice), aflag == 1);
             const int pb = pk_get(s.posN, k);
             const int q = Tb->nbn[adir][pb];
             if (q == 255) {
-                if (c.shaped) { // an illegal move costs tolerance; the game goes on until it is used up (training_ewn.py:48-56)
+                if (!EV && c.shaped) { // an illegal move costs tolerance; the game goes on until it is used up (training_ewn.py:48-56)
                     tol -= 1;
                     if (tol <= 0) { reward = -c.reward; term = 1; trunc = 1; info = EWN_INFO_INVALID_PLAYER; }
                     else { reward = c.illegal_reward; info = EWN_INFO_TOLERANCE; }
@@ -199,6 +207,7 @@ __global__ __launch_bounds__(NT, NT / 256) void k_rollout_mlp(PolCfg c, PolBuf B
         // ---- the opponent's search: run by every lane (lanes without a pending reply compute on a harmless state)
         int oflag = 0, odir = 0;
         if constexpr (OPP == 0) d3_search<S, T>(Tb, s, dice, sub, c.depth, oflag, odir);
+        if constexpr (OPP == 2) d5_dispatch<S, T>(Tb, s, dice, sub, oflag, odir);
         if (reply) {
             const u32 e = pk_sel<S>(Tb, s.posP, dice);
             if constexpr (OPP == 1) {
@@ -209,7 +218,7 @@ __global__ __launch_bounds__(NT, NT / 256) void k_rollout_mlp(PolCfg c, PolBuf B
                 odir = sl < 3 ? sl : sl - 3;
             }
             roll_opponent_half<S>(Tb, s, e, oflag, odir, dice, r, c.reward, reward, term, info, slot);
-            if (c.shaped && !term) { // reward = evaluate() - prev_score (training_ewn.py:94-96)
+            if (!EV && c.shaped && !term) { // reward = evaluate() - prev_score (training_ewn.py:94-96)
                 const double cur = d3_shaped_score<S>(Tb, s);
                 reward = cur - prev;
                 prev = cur;
@@ -218,18 +227,21 @@ __global__ __launch_bounds__(NT, NT / 256) void k_rollout_mlp(PolCfg c, PolBuf B
         if (active) {
             ret_acc += reward; n_steps++; n_eps += term; n_wins += info == EWN_INFO_WON ? 1 : 0;
             if (term) {
-                if (c.autoreset) {
+                if (!EV && c.autoreset) {
                     r.next_episode(B.rng, c.N, game, c.seed_stride, c.key, nullptr);
                     d3_init_state<S>(Tb, s);
                     rec_slot_init<S>(slot);
                     dice = r.first_dice(6);
-                    if (c.shaped && c.refresh) prev = d3_shaped_score<S>(Tb, s);
+                    if (!EV && c.shaped && c.refresh) prev = d3_shaped_score<S>(Tb, s);
                 } else frozen = true;
             }
         }
         // ---- this step's trajectory row
         __builtin_amdgcn_wave_barrier();
-        if (live) {
+        if constexpr (EV) {
+            if (active && sub == 0 && B.t_action)
+                ((uint16_t *)B.t_action)[(size_t)kstep * c.N + game] = (uint16_t)((uint8_t)aflag | ((uint16_t)(uint8_t)adir << 8));
+        } else if (live) {
             const size_t o = (size_t)kstep * c.N + game;
             if constexpr (FIX) {
                 if (sub == 0) B.t_reward[o] = reward;
@@ -251,7 +263,7 @@ __global__ __launch_bounds__(NT, NT / 256) void k_rollout_mlp(PolCfg c, PolBuf B
     if (writer) {
         if (!frozen0) { *rng_hdr_ptr(B.rng, game) = r.header(); B.dice[game] = (int8_t)dice; }
         B.done[game] = frozen ? 1 : 0;
-        if (c.shaped) { B.tolerance[game] = tol; B.prev_score[game] = prev; }
+        if (!EV && c.shaped) { B.tolerance[game] = tol; B.prev_score[game] = prev; }
         if (B.ret_sum) B.ret_sum[game] += ret_acc;
         if (B.n_steps) B.n_steps[game] += n_steps;
         if (B.n_episodes) B.n_episodes[game] += n_eps;

@@ -47,14 +47,30 @@ def _policy(spec, cube_layer, key):
     raise ValueError("unknown agent kind %r" % kind)
 
 
+def flat_policy_params(model):
+    """The actor-critic's parameters as ONE fp32 device vector in parameters() order (the layout ewn_policy_eval reads): a copy, the
+    module is left as it is."""
+    return torch.cat([p.detach().reshape(-1).to(torch.float32) for p in model.parameters()]).contiguous()
+
+
+def _totals_result(totals, num, engine):
+    score, length = totals["return_sum"], totals["n_steps"]   # un-shaped env: the only non-zero reward of an episode is its last
+    wins = int((score > 0).sum().item())
+    lo, hi = wilson(wins, num)
+    return {"scores": score, "lengths": length, "wins": wins, "episodes": num, "win_rate": wins / num, "engine": engine,
+            "ci95": [lo, hi], "avg_score": float(score.mean().item()), "avg_length": float(length.float().mean().item())}
+
+
 def evaluate(agent, opponent, num=1024, board_size=5, cube_layer=3, rng="mt19937", seed_offset=0, key=12345, max_steps=400,
              use_rollout=True, chunk=16):
-    """agent: a dict like the opponent's or a callable policy (board, dice, t) -> actions.
+    """agent: a dict like the opponent's, {"kind": "mlp", "model": a2c.ActorCritic} (its deterministic policy), or a callable policy
+    (board, dice, t) -> actions.
     agent / opponent: dicts {"kind": "random"|"minimax"|"mcts", max_depth=, heuristic=, num_simulations=, num_env_copies=}.
     Returns per-episode scores (float64 tensor), episode lengths and summary statistics.
     When both sides are engine policies the table-driven kernels cover (RandomAgent, 'hybrid' minimax; cube_layer 3) the whole
-    predict/step loop runs on the device, `chunk` steps per launch (ewn_step_k); otherwise one policy kernel + one ewn_step per
-    step.  Both give identical per-episode results for deterministic agents ("engine" in the result says which one ran)."""
+    predict/step loop runs on the device, `chunk` steps per launch (ewn_step_k); an "mlp" agent likewise wherever ewn_policy_eval serves
+    the opponent and geometry; otherwise one policy evaluation + one ewn_step per step.  Both give identical per-episode results for
+    deterministic agents ("engine" in the result says which one ran)."""
     env = VecEWN(num, board_size=board_size, cube_layer=cube_layer, opponent_policy=opponent["kind"],
                  max_depth=opponent.get("max_depth", 3), heuristic=opponent.get("heuristic", "hybrid"),
                  num_simulations=opponent.get("num_simulations", 10), num_env_copies=opponent.get("num_env_copies", 5),
@@ -68,12 +84,23 @@ def evaluate(agent, opponent, num=1024, board_size=5, cube_layer=3, rng="mt19937
             if bool((env.done != 0).all()):
                 break
         env.check_rng()
-        score, length = totals["return_sum"], totals["n_steps"]   # un-shaped env: the only non-zero reward of an episode is its last
-        wins = int((score > 0).sum().item())
-        lo, hi = wilson(wins, num)
-        return {"scores": score, "lengths": length, "wins": wins, "episodes": num, "win_rate": wins / num, "engine": "ewn_step_k",
-                "ci95": [lo, hi], "avg_score": float(score.mean().item()), "avg_length": float(length.float().mean().item())}
-    policy = _policy(agent, cube_layer, key)
+        return _totals_result(totals, num, "ewn_step_k")
+    if isinstance(agent, dict) and agent["kind"] == "mlp":
+        model = agent["model"]
+        if getattr(model, "S", board_size) != board_size:
+            raise ValueError("evaluate: the model plays %dx%d boards, the evaluation is on %dx%d" % (model.S, model.S, board_size, board_size))
+        params = flat_policy_params(model).to(env.device)
+        if use_rollout and env.supports_policy_eval() and params.numel() == env.policy_param_count():
+            totals = env.alloc_totals()
+            for _ in range(0, max_steps, chunk):
+                env.eval_policy(chunk, params, totals)
+                if bool((env.done != 0).all()):
+                    break
+            env.check_rng()
+            return _totals_result(totals, num, "ewn_policy_eval")
+        policy = lambda b, d, t: model.act(b, d, deterministic=True)[0]   # noqa: E731
+    else:
+        policy = _policy(agent, cube_layer, key)
     score = torch.zeros(num, dtype=torch.float64, device=env.device)
     length = torch.zeros(num, dtype=torch.int32, device=env.device)
     for t in range(max_steps):
@@ -106,9 +133,42 @@ def tournament(names=("random", "minimax", "mcts"), num=1024, max_depth=5, num_s
     return table
 
 
+def load_policy(path, board_size=5, cube_layer=3, device="cuda"):
+    """The actor-critic of a checkpoint written by any of the trainers (A2CTrainer / PPOTrainer: a "model" state dict;
+    FusedA2CTrainer / FusedPPOTrainer: the flat "params" vector), on `device`, in eval mode."""
+    from .a2c import ActorCritic
+    sd = torch.load(path, map_location=device, weights_only=True)
+    model = ActorCritic(board_size, cube_layer * (cube_layer + 1) // 2).to(device)
+    if "params" in sd:
+        flat = sd["params"].to(device=device, dtype=torch.float32).reshape(-1)
+        n = sum(p.numel() for p in model.parameters())
+        if flat.numel() != n:
+            raise ValueError("%s: %d parameters, a %dx%d actor-critic has %d (wrong --board_size / --cube_layer?)" % (
+                path, flat.numel(), board_size, board_size, n))
+        model.load_flat_parameters(flat)
+    elif "model" in sd:
+        model.load_state_dict(sd["model"])
+    else:
+        raise ValueError("%s holds neither a \"model\" state dict nor flat \"params\": not a checkpoint of these trainers" % path)
+    return model.eval()
+
+
+def evaluate_model(model, names=("random", "minimax"), num=1024, max_depth=5, num_simulations=10, num_env_copies=5, board_size=5,
+                   cube_layer=3, heuristic="hybrid", rng="mt19937"):
+    """eval_A2C.py's loop: the model's deterministic policy against every listed opponent"""
+    table = {}
+    for o in names:
+        opp = {"kind": o, "max_depth": max_depth, "heuristic": heuristic, "num_simulations": num_simulations, "num_env_copies": num_env_copies}
+        r = evaluate({"kind": "mlp", "model": model}, opp, num=num, board_size=board_size, cube_layer=cube_layer, rng=rng)
+        table["model vs %s" % o] = {k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}
+    return table
+
+
 def main():
-    ap = argparse.ArgumentParser(description="agent-vs-opponent win-rate matrix (counterpart of eval_pairs.py)")
+    ap = argparse.ArgumentParser(description="agent-vs-opponent win-rate matrix (counterpart of eval_pairs.py); with --model, a "
+                                             "trained policy against each listed opponent (counterpart of eval_A2C.py)")
     ap.add_argument("--agents", nargs="+", default=["random", "minimax", "mcts"])
+    ap.add_argument("--model", default=None, help="checkpoint (best.pt) of any of the trainers: evaluate its deterministic policy")
     ap.add_argument("--num", type=int, default=1024)
     ap.add_argument("--max_depth", type=int, default=5)
     ap.add_argument("--heuristic", default="hybrid")
@@ -118,8 +178,13 @@ def main():
     ap.add_argument("--cube_layer", type=int, default=3)
     ap.add_argument("--rng", default="mt19937")
     a = ap.parse_args()
-    t = tournament(a.agents, a.num, a.max_depth, a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer,
-                   a.heuristic, a.rng)
+    if a.model is not None:
+        model = load_policy(a.model, a.board_size, a.cube_layer)
+        t = evaluate_model(model, a.agents, a.num, a.max_depth, a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer,
+                           a.heuristic, a.rng)
+    else:
+        t = tournament(a.agents, a.num, a.max_depth, a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer,
+                       a.heuristic, a.rng)
     for k, v in t.items():
         print("%-22s win rate %.3f  (95%% CI %.3f-%.3f, %d/%d, %.1f steps/episode)"
               % (k, v["win_rate"], v["ci95"][0], v["ci95"][1], v["wins"], v["episodes"], v["avg_length"]))

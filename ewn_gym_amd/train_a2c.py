@@ -8,6 +8,7 @@ against minimax on the un-shaped env (train.py:66-117), best-model checkpointing
 import argparse
 import json
 import os
+import time
 
 import torch
 import torch.distributed as dist
@@ -82,13 +83,18 @@ def main():
     for epoch in range(a.epoch_num):
         stats = trainer.learn(a.timesteps_per_epoch // world)   # dict of the last update's statistics
         # train.py:73-81: evaluate on the UN-shaped env against minimax(depth 5), seeds 0..n-1, deterministic actions
+        # (the model's argmax in the engine, ewn_policy_eval, where it serves the configuration; else per step)
         n_eval = a.eval_episode_num // world
-        r = evaluate(trainer.policy_fn(True), {"kind": "minimax", "max_depth": a.eval_max_depth}, num=n_eval,
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = evaluate({"kind": "mlp", "model": trainer.model}, {"kind": "minimax", "max_depth": a.eval_max_depth}, num=n_eval,
                      board_size=a.board_size, cube_layer=a.cube_layer, rng="mt19937", seed_offset=rank * n_eval)
+        eval_s = time.perf_counter() - t0    # evaluate() ends on a host sync (its win count)
         c = all_reduce_counters(torch.tensor([r["wins"], r["episodes"]], dtype=torch.int64, device="cuda"))
         win_rate = c[0].item() / max(1, c[1].item())
         if rank == 0:
-            print(json.dumps({"epoch": epoch, "timesteps": trainer.num_timesteps * world, "win_rate": win_rate, **stats}), flush=True)
+            print(json.dumps({"epoch": epoch, "timesteps": trainer.num_timesteps * world, "win_rate": win_rate, **stats,
+                              "eval_engine": r["engine"], "eval_s": eval_s}), flush=True)
             if win_rate > best:          # train.py:109-112
                 best = trainer.best_score = win_rate
                 os.makedirs(a.save_dir, exist_ok=True)

@@ -290,6 +290,38 @@ class VecEWN:
               "ewn_step_k_policy")
         return self.board, self.dice
 
+    # -- K env steps per launch with the trained policy's argmax as the agent, one episode per lane (ewn_policy_eval; train.py:66-117)
+    def supports_policy_eval(self):
+        return self.tables is not None and self.lib.ewn_policy_eval_supported(C.byref(self.cfg)) == 1
+
+    def eval_policy(self, K, params, totals, action=None):
+        """Play K steps of every lane in one launch, the agent playing the argmax of the actor-critic whose flat fp32 parameter vector
+        is `params` (a2c.ActorCritic.parameters() order), on the un-shaped env without auto-reset.  totals: dict from alloc_totals
+        (required, ADDED to); action: optional int8 [>= K, N, 2] (row k of a lane is written only if the lane played step k).
+        Buffers of the wrong shape, dtype or layout raise ValueError before anything is launched."""
+        N = self.N
+        if not (isinstance(params, torch.Tensor) and params.dtype == torch.float32 and params.is_cuda and params.is_contiguous()
+                and params.dim() == 1 and params.numel() == self.policy_param_count()):
+            raise ValueError("eval_policy: params must be a contiguous float32 device vector of %d elements, got %s" % (
+                self.policy_param_count(), _describe(params)))
+        if not isinstance(totals, dict):
+            raise ValueError("eval_policy: totals must be the dict of alloc_totals(), got %s" % type(totals).__name__)
+        for name, dt in (("return_sum", torch.float64), ("n_steps", torch.int32), ("n_episodes", torch.int32), ("n_wins", torch.int32)):
+            t = totals.get(name)
+            if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (N,)):
+                raise ValueError("eval_policy: totals[%r] must be a contiguous %s device tensor of shape [%d], got %s" % (
+                    name, str(dt).replace("torch.", ""), N, _describe(t)))
+        if action is not None and not (isinstance(action, torch.Tensor) and action.dtype == torch.int8 and action.is_cuda
+                                       and action.is_contiguous() and action.dim() == 3 and action.shape[0] >= K
+                                       and tuple(action.shape[1:]) == (N, 2)):
+            raise ValueError("eval_policy: action must be a contiguous int8 device tensor of shape [>= %d, %d, 2], got %s" % (
+                K, N, _describe(action)))
+        out = EwnRolloutOut(None, None, _ptr(action), None, None, None, None, _ptr(totals["return_sum"]), _ptr(totals["n_steps"]),
+                            _ptr(totals["n_episodes"]), _ptr(totals["n_wins"]), None)
+        check(self.lib.ewn_policy_eval(C.byref(self.cfg), C.byref(self._st), int(K), _ptr(params), C.byref(out), _stream()),
+              "ewn_policy_eval")
+        return self.board, self.dice
+
     def set_obs(self, boards, dice):
         """Overwrite the observation of every lane (agent = TOP_LEFT to move); RNG state is kept."""
         self.board.copy_(torch.as_tensor(boards).reshape(self.N, self.S, self.S))

@@ -263,6 +263,22 @@ int64_t ewn_policy_param_count(int board_size, int cube_layer);
 /* K >= 1 steps of every lane, the agent's action sampled from the policy; out may be NULL.  One kernel launch, no scratch. */
 int ewn_step_k_policy(const ewn_config *cfg, const ewn_state *st, int K, const ewn_policy *pol, const ewn_rollout_out *out, void *stream);
 
+/* ---- evaluating a trained policy: train.py:66-117's per-epoch evaluation (and eval_A2C.py's loop) as K steps per launch ----------
+ * The agent plays the argmax of the actor-critic's logits (model.predict(deterministic=True)) on the UN-shaped env without auto-reset,
+ * one episode per lane, against RandomAgent or minimax max_depth 1..6 ('hybrid', 'min_dist', 'attk'; max_depth 5 / 6 through the
+ * closed-form search), on MT19937-compat or Philox dice; cube_layer 3, board sizes 5 and 7.  The same transitions as the agent's
+ * argmax fed to ewn_step step by step.  Not served ('two_min_dist', 'sim_winrate', MCTS opponents, shaped or auto-resetting envs,
+ * other geometries): ewn_policy_eval returns EWN_EUNSUPPORTED.  ewn_step_k_policy / EWN_AGENT_MLP stay as documented above. */
+/* 1 if ewn_policy_eval serves cfg, 0 if not, < 0 for an invalid cfg; decided on the host */
+int ewn_policy_eval_supported(const ewn_config *cfg);
+/* K >= 1 steps of every lane, the agent = argmax of the actor-critic `params` (ewn_policy.params layout); un-shaped, no auto-reset.
+ * out: the four per-lane totals are required (ADDED to; return_sum is the episode's score: the un-shaped env rewards only its last
+ * step); out->action is optional: row k of lane n is written only if the lane played step k of this call (a finished lane is left
+ * alone); every other pointer of out must be NULL (EWN_EINVAL).  One kernel launch, no scratch; a lane whose episode is over is not
+ * stepped, so a caller loops launches until ewn_state.done is set everywhere.  The MT19937-compat overflow flag is kept in the lane's
+ * RNG header as ewn_step keeps it. */
+int ewn_policy_eval(const ewn_config *cfg, const ewn_state *st, int K, const float *params, const ewn_rollout_out *out, void *stream);
+
 /* ---- the A2C update on the records of ewn_step_k_policy: stable_baselines3 A2C.train as train.py:35-63, 148 configures it ----
  * (n-step returns = GAE with lambda 1, no advantage normalisation; loss = policy gradient + vf_coef * MSE(returns, values) +
  * ent_coef * (-entropy), a mean over the n_steps x lanes batch; clip_grad_norm_(max_grad_norm); RMSprop(alpha, eps)).  SB3 is not
