@@ -26,8 +26,9 @@ EXPORTS = ["ewn_abi_version", "ewn_strerror", "ewn_rng_words", "ewn_step_scratch
            "ewn_predict_mcts", "ewn_step_k", "ewn_step_k_supported", "ewn_predict_minimax_sim", "ewn_lanes_per_game", "ewn_roll_dice",
            "ewn_policy_param_count", "ewn_step_k_policy", "ewn_a2c_scratch_bytes", "ewn_a2c_grad", "ewn_a2c_apply",
            "ewn_ppo_scratch_bytes", "ewn_ppo_prepare", "ewn_ppo_shuffle", "ewn_ppo_grad", "ewn_ppo_apply",
-           "ewn_policy_eval_supported", "ewn_policy_eval"]
+           "ewn_policy_eval_supported", "ewn_policy_eval", "ewn_step_k_agent_supported", "ewn_step_k_agent"]
 AGENT = {"random": 0, "minimax": 1, "sample": 2, "mlp": 3}   # "mlp": the trained policy, through ewn_step_k_policy   # "sample": env.action_space.sample(), all six actions (EWN_AGENT_SAMPLE)
+AGENT_MCTS = 4   # ewn_agent.kind of the MCTS agent (ewn_step_k_agent only; ewn_step_k does not take it)
 
 
 class EwnConfig(C.Structure):  # struct ewn_config
@@ -58,6 +59,11 @@ class EwnRolloutOut(C.Structure):  # struct ewn_rollout_out
                 ("terminated", C.c_void_p), ("truncated", C.c_void_p), ("info", C.c_void_p),
                 ("return_sum", C.c_void_p), ("n_steps", C.c_void_p), ("n_episodes", C.c_void_p), ("n_wins", C.c_void_p),
                 ("record", C.c_void_p)]
+
+
+class EwnAgent(C.Structure):  # struct ewn_agent (ewn_step_k_agent)
+    _fields_ = [("kind", C.c_int32), ("max_depth", C.c_int32), ("heuristic", C.c_int32), ("num_simulations", C.c_int32),
+                ("num_env_copies", C.c_int32), ("step_base", C.c_uint32), ("key", C.c_uint64)]
 
 
 class EwnPolicy(C.Structure):  # struct ewn_policy
@@ -137,6 +143,8 @@ def load():
         "ewn_ppo_apply": (i32, [cfgp, vp, vp, vp, vp, vp, C.POINTER(EwnPpoHyper), vp, vp]),
         "ewn_policy_eval_supported": (i32, [cfgp]),
         "ewn_policy_eval": (i32, [cfgp, stp, i32, vp, C.POINTER(EwnRolloutOut), vp]),
+        "ewn_step_k_agent_supported": (i32, [cfgp, C.POINTER(EwnAgent)]),
+        "ewn_step_k_agent": (i32, [cfgp, stp, i32, C.POINTER(EwnAgent), C.POINTER(EwnRolloutOut), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -805,6 +805,8 @@ struct MctsRoll { int K, total, gl, agent_sample, strd, gpb; };   // strd: bytes
 // balances its playouts over the whole chip, this kernel over one block's cells.
 #define MR_GPB 128        // the most games a block takes (LDS arrays); the launcher picks mr.gpb <= MR_GPB (default 64)
 
+// Its twin: rollout_mcts_body below (ewn_step_k_agent's loop, the same phases with an agent of its own, the playout phase factored
+// into mcts_playout_phase).  A fix to the state load, the trajectory rows or the write-back here belongs there too.
 __global__ __launch_bounds__(BS) void k_rollout_mcts(Geom g, KCfg c, KState st, MctsRoll mr, RollBuf B)
 {
     extern __shared__ __attribute__((aligned(16))) int8_t lds[];   // [MR_GPB][strd]: packed boards in and out, trajectory rows in between
@@ -941,6 +943,213 @@ __global__ __launch_bounds__(BS) void k_rollout_mcts(Geom g, KCfg c, KState st, 
     }
     __syncthreads();
     block_copy_out(st.board + (size_t)lane0 * g.cells, lds, nl * g.cells);
+}
+
+// the agent of k_rollout_mcts_agent (ewn_step_k_agent): minimax max_depth / heuristic, or MCTS with `total` playouts per root move in
+// groups of 2^gl lanes on the playout stream of evaluation step t = step_base + kstep: obs_word(lane_offset + lane, 'MCTS', key_t),
+// key_t = key + 0x9E3779B97F4A7C15 * (t + 1) -- what tournament.evaluate's per-step loop passes to predict_mcts
+struct AgentRoll { int depth, heur, total, gl; u32 step_base; u64 key; };
+
+// One flat Monte-Carlo decision (mcts.py:47-69) for every game of the block whose owner thread passes n_root > 0, its start position,
+// dice and playout stream already in pb0 / pdice / pword[tid]: `total` playouts per (game, root move) cell, BOTTOM_RIGHT replying
+// first, a group of 2^gl lanes per cell; a group that has finished its cell takes the next unplayed one (results do not depend on who
+// plays what).  Leaves the wins per root move in wins[tid] (-1: no such move).  Every thread of the block calls it (block barriers).
+EWN_DEV void mcts_playout_phase(const Geom &g, const PlayTab *T, const PState *pb0, const u32 *pword, const int8_t *pdice, int (*wins)[6],
+                                uint16_t *livec, int *nlive_s, int *next_slot, int *nextc, int *myslot, int tid, bool owner, int n_root,
+                                int total, int gl, int tc, int glane, int grp)
+{
+    if (owner) {
+        #pragma unroll
+        for (int i = 0; i < 6; i++) wins[tid][i] = i < n_root ? 0 : -1;
+    }
+    if (tid == 0) { *nlive_s = 0; *next_slot = BS >> gl; }
+    __syncthreads();
+    if (n_root > 0) { const int base = atomicAdd(nlive_s, n_root); for (int i = 0; i < n_root; i++) livec[base + i] = (uint16_t)(tid * 8 + i); }
+    __syncthreads();
+    const int nlive = *nlive_s;
+    int slot = grp;
+    while (slot < nlive) {
+        const int cell = livec[slot], gi = cell >> 3, i = cell & 7;
+        if (glane == 0) nextc[grp] = tc;   // same wave as the lanes that read it: LDS operations of a wave execute in order
+        PState b0 = pb0[gi];
+        int w;
+        if (playout_root_move(T, b0, g.S, pdice[gi], i)) w = glane < total ? (total - glane + tc - 1) >> gl : 0;   // TOP_LEFT has won
+        else w = run_playouts<1>(T, b0, g.S, pword[gi], (u32)(i * total), glane, total, &nextc[grp]);         // BOTTOM_RIGHT replies first
+        for (int off = tc >> 1; off > 0; off >>= 1) w += __shfl_down(w, off, tc);
+        if (glane == 0) { wins[gi][i] = w; myslot[grp] = atomicAdd(next_slot, 1); }
+        __builtin_amdgcn_wave_barrier();
+        slot = myslot[grp];
+        __builtin_amdgcn_wave_barrier();
+    }
+    __syncthreads();
+}
+
+// np.argmax over the root moves' wins (first maximum), then that entry of the legal list of the observation (mcts.py:68)
+EWN_DEV void mcts_pick(const Geom &g, const GState<1> &obs, int dice, const int *w6, int &flag, int &dir)
+{
+    int best = 0, bw = -1;
+    #pragma unroll
+    for (int i = 0; i < 6; i++) { const int w = w6[i]; if (w > bw) { bw = w; best = i; } }
+    int f = 0, d = 0, j = 0;
+    for_each_legal<0, 1>(g, obs, dice, [&](int fl, int, int dr) { if (j == best) { f = fl; d = dr; } j++; return j <= best; });
+    flag = f; dir = d;
+}
+
+// k_rollout_mcts's loop with an agent of its own.  AG: 1 minimax (ar.depth, ar.heur), 2 MCTS (a playout phase over the agent's
+// observation before the agent half).  OPP: 0 RandomAgent, 1 minimax (c.depth, c.heur), 2 MCTS (its playout phase between the two
+// halves).  The minimax searches (AG 1's agent, OPP 1's opponent: one of them per instance) are the table-driven fast_d3 of
+// k_predict_minimax_fast / ewn_step's table path, on the rules thread, from an image of the search's table in LDS (S = board size;
+// 0 = no search, no table).  k_rollout_mcts itself keeps its own text: routed through this body, its RandomAgent / sample instance
+// compiled to different register allocation (129 -> 132 VGPRs), and that instance must stay the code it is.
+template <int AG, int OPP, int S>
+EWN_DEV void rollout_mcts_body(const Geom &g, const KCfg &c, const KState &st, const MctsRoll &mr, const RollBuf &B, const AgentRoll &ar)
+{
+    extern __shared__ __attribute__((aligned(16))) int8_t lds[];   // [MR_GPB][strd]: packed boards in and out, trajectory rows in between
+    __shared__ PlayTab T;
+    __shared__ PState pb0[MR_GPB];
+    __shared__ u32 pword[MR_GPB];
+    __shared__ int8_t pdice[MR_GPB];
+    __shared__ int wins[MR_GPB][6];
+    __shared__ uint16_t livec[MR_GPB * 6];
+    __shared__ int nlive_s, next_slot;
+    __shared__ int nextc[BS / 8], myslot[BS / 8];
+    constexpr int TS = S ? S : 5;
+    [[maybe_unused]] const FastTab<TS> *ft = nullptr;
+    if constexpr (S != 0) {   // LDS-DMA behind the boards area, waited for at the first barrier
+        int8_t *tb = lds + ((mr.gpb * mr.strd + 15) & ~15);
+        tables_to_lds<FAST_TAB_BYTES(TS)>(tb, (const int8_t *)B.tables);
+        ft = (const FastTab<TS> *)tb;
+    }
+    playtab_build(&T, g.S);
+    const int tid = (int)threadIdx.x, lane0 = (int)blockIdx.x * mr.gpb, nl = min(mr.gpb, c.N - lane0), lane = lane0 + tid;
+    const bool owner = tid < mr.gpb, live = owner && lane < c.N;
+    uint4 hdr = make_uint4(0u, 0u, 0u, 0u);
+    int dice = 1;
+    bool frozen = true;
+    if (live) { hdr = *rng_hdr_ptr(st.rng, lane); dice = st.dice[lane]; frozen = st.done[lane] != 0; }
+    const bool frozen0 = frozen;
+    block_copy_in(lds, st.board + (size_t)lane0 * g.cells, nl * g.cells);
+    if constexpr (S != 0) lds_dma_wait();
+    __syncthreads();
+    GState<1> s;
+    decode_board<1>(g, lds + (live ? tid : 0) * g.cells, s);
+    LaneRng r; r.load(c.rng_kind, hdr, rng_win_ptr(st.rng, c.N, c.W, live ? lane : 0, RNGF_CUR(hdr.w)), c.W, c.key);
+    r.begin_kernel();
+    double ret_acc = 0.0;
+    int n_steps = 0, n_eps = 0, n_wins = 0;
+    const int tc = 1 << mr.gl, glane = tid & (tc - 1), grp = tid >> mr.gl;
+    const int atc = 1 << ar.gl, aglane = tid & (atc - 1), agrp = tid >> ar.gl;   // the agent's playout groups (AG 2)
+
+    for (int kstep = 0; kstep < mr.K; kstep++) {
+        const bool active = live && !frozen;
+        StepRes o; o.reward = 0.0; o.term = (live && frozen) ? 1 : 0; o.trunc = 0; o.info = EWN_INFO_NONE;
+        int aflag = 0, adir = 0, n_root = 0;
+        bool reply = false;
+        GState<1> cst = s;
+        if constexpr (AG == 2) {
+            // MctsAgent.predict(env.board, env.dice): the agent's observation as it stands, its root moves, its playout stream
+            int a_root = 0;
+            if (active) {
+                pb0[tid] = pstate_from_gstate(g, s);
+                pdice[tid] = (int8_t)dice;
+                const u64 key_t = ar.key + 0x9E3779B97F4A7C15ull * ((u64)ar.step_base + (u64)kstep + 1ull);
+                pword[tid] = PlayoutRng::obs_word((u32)(c.lane_offset + lane), 0x4D435453u, key_t);
+                a_root = for_each_legal<0, 1>(g, s, dice, [](int, int, int) { return true; });
+            }
+            mcts_playout_phase(g, &T, pb0, pword, pdice, wins, livec, &nlive_s, &next_slot, nextc, myslot, tid, owner, a_root, ar.total,
+                               ar.gl, atc, aglane, agrp);
+            if (active) mcts_pick(g, s, dice, wins[tid], aflag, adir);
+        }
+        if (active) {
+            if constexpr (AG == 1) {   // ExpectiMinimaxAgent.predict on the agent's observation (TOP_LEFT to move): k_predict_minimax_fast
+                aflag = -1; adir = -1;
+                if (ar.heur == EWN_H_TWO_MIN_DIST) fast_d3<TS, true>(ft, s, dice, ar.depth, aflag, adir);
+                else fast_d3<TS, false>(ft, s, dice, ar.depth, aflag, adir);
+            }
+            r.prefetch();
+            r.begin_step();
+            reply = step_agent<1>(g, c, s, dice, aflag, adir, r, nullptr, o);      // envs/ewn.py:438-458
+            if constexpr (OPP == 2) {
+                if (reply) { // MctsAgent.predict's input: the canonical observation (envs/ewn.py:289-296), its root moves, its playout stream
+                    cst = canonicalize<1>(g, s);
+                    pb0[tid] = pstate_from_gstate(g, cst);
+                    pdice[tid] = (int8_t)dice;
+                    pword[tid] = PlayoutRng::obs_word(r.seed_mix() * 0x9E3779B1u + r.draws(), 0x4D435453u, c.key);
+                    n_root = for_each_legal<0, 1>(g, cst, dice, [](int, int, int) { return true; });
+                }
+            } else if (reply) {
+                int oflag = 0, odir = 0;
+                if constexpr (OPP == 0) policy_random<1>(g, s, dice, r, oflag, odir);
+                else {   // the minimax opponent on its canonical observation, as ewn_step's table path searches it
+                    cst = canonicalize<1>(g, s);
+                    if (c.heur == EWN_H_TWO_MIN_DIST) fast_d3<TS, true>(ft, cst, dice, c.depth, oflag, odir);
+                    else fast_d3<TS, false>(ft, cst, dice, c.depth, oflag, odir);
+                }
+                step_opponent<1>(g, c, s, dice, oflag, odir, r, nullptr, o);              // envs/ewn.py:464-486
+            }
+        }
+        if constexpr (OPP == 2) {
+            // ---- the playouts of the block's (game, root move) cells, then the opponent's half (envs/ewn.py:464-486)
+            mcts_playout_phase(g, &T, pb0, pword, pdice, wins, livec, &nlive_s, &next_slot, nextc, myslot, tid, owner, n_root, mr.total,
+                               mr.gl, tc, glane, grp);
+            if (reply) {
+                int oflag = 0, odir = 0;
+                mcts_pick(g, cst, dice, wins[tid], oflag, odir);
+                step_opponent<1>(g, c, s, dice, oflag, odir, r, nullptr, o);
+            }
+        }
+        if (active) {
+            ret_acc += o.reward; n_steps++; n_eps += o.term; n_wins += o.info == EWN_INFO_WON ? 1 : 0;
+            if (o.term) { if (c.autoreset) lane_auto_reset<1>(g, c, st.rng, lane, s, dice, r); else frozen = true; }
+        }
+        // ---- this step's trajectory row
+        if (live) {
+            const size_t oo = (size_t)kstep * c.N + lane;
+            if (B.t_action) ((uint16_t *)B.t_action)[oo] = (uint16_t)((uint8_t)aflag | ((uint16_t)(uint8_t)adir << 8));
+            if (B.t_dice) B.t_dice[oo] = (int8_t)dice;
+            if (B.t_reward) B.t_reward[oo] = o.reward;
+            if (B.t_term) B.t_term[oo] = (uint8_t)o.term;
+            if (B.t_trunc) B.t_trunc[oo] = (uint8_t)o.trunc;
+            if (B.t_info) B.t_info[oo] = (uint8_t)o.info;
+        }
+        if (B.t_board) {
+            if (live) encode_board<1>(g, s, lds + tid * g.cells);
+            __syncthreads();
+            block_copy_out(B.t_board + ((size_t)kstep * c.N + lane0) * g.cells, lds, nl * g.cells);
+            __syncthreads();
+        }
+        if (B.t_rec) { // one aligned record per lane-step: board | dice | action | flags | padding (ewn_rollout_out.record)
+            if (live) {
+                int8_t *rec = lds + tid * mr.strd;
+                for (int i = g.cells; i < mr.strd; i++) rec[i] = 0;
+                encode_board<1>(g, s, rec);
+                rec[g.cells] = (int8_t)dice; rec[g.cells + 1] = (int8_t)aflag; rec[g.cells + 2] = (int8_t)adir;
+                rec[g.cells + 3] = (int8_t)o.term; rec[g.cells + 4] = (int8_t)o.trunc; rec[g.cells + 5] = (int8_t)o.info;
+            }
+            __syncthreads();
+            block_copy_out((int8_t *)B.t_rec + ((size_t)kstep * c.N + lane0) * mr.strd, lds, nl * mr.strd);
+            __syncthreads();
+        }
+    }
+    if (live) encode_board<1>(g, s, lds + tid * g.cells);
+    if (live) {
+        if (!frozen0) { *rng_hdr_ptr(st.rng, lane) = r.header(); st.dice[lane] = (int8_t)dice; }
+        st.done[lane] = frozen ? 1 : 0;
+        if (B.ret_sum) B.ret_sum[lane] += ret_acc;
+        if (B.n_steps) B.n_steps[lane] += n_steps;
+        if (B.n_episodes) B.n_episodes[lane] += n_eps;
+        if (B.n_wins) B.n_wins[lane] += n_wins;
+    }
+    __syncthreads();
+    block_copy_out(st.board + (size_t)lane0 * g.cells, lds, nl * g.cells);
+}
+
+// ewn_step_k_agent: the minimax agent against the MCTS opponent <1, 2, S>; the MCTS agent against RandomAgent <2, 0, 0>, minimax
+// <2, 1, S> or MCTS <2, 2, 0>
+template <int AG, int OPP, int S>
+__global__ __launch_bounds__(BS) void k_rollout_mcts_agent(Geom g, KCfg c, KState st, MctsRoll mr, RollBuf B, AgentRoll ar)
+{
+    rollout_mcts_body<AG, OPP, S>(g, c, st, mr, B, ar);
 }
 
 template <int NW>
@@ -1353,6 +1562,90 @@ int ewn_step_k(const ewn_config *cfg, const ewn_state *st, int K, int agent_kind
     case 7: return ewn_launch_rollout_s7(rcf, rb, T, opp, k.rng_kind, agent, h2, s);
     default: return ewn_launch_rollout_s8(rcf, rb, T, opp, k.rng_kind, agent, h2, s);
     }
+}
+
+// the cells of the agent-vs-opponent matrix ewn_step_k leaves out (k_rollout_mcts_agent): the minimax agent against the MCTS opponent,
+// the MCTS agent against RandomAgent, minimax (the four evaluate() heuristics) or MCTS.  Byte-per-cube playouts (cube_layer 3 -- the
+// searches need six cubes --, boards <= 8x8), un-shaped; MT19937-compat dice only without auto-reset (as every K-step kernel).
+static int agent_rollout_plan(const ewn_config *cfg, const Geom &g, const ewn_agent *a, int &ag, bool &opp_mcts)
+{
+    if (a->kind == EWN_AGENT_MINIMAX) {
+        if (a->max_depth < 1 || a->heuristic < 0 || a->heuristic > EWN_H_SIM_WINRATE) return EWN_EINVAL;
+        if (a->max_depth > EWN_MAX_DEPTH || a->heuristic == EWN_H_SIM_WINRATE) return EWN_EUNSUPPORTED;
+        if (cfg->opponent_kind != EWN_OPP_MCTS) return EWN_EUNSUPPORTED;   // ewn_step_k's cells (or the per-step path)
+        ag = 1;
+    } else if (a->kind == EWN_AGENT_MCTS) {
+        if (a->num_simulations < 1 || a->num_env_copies < 1) return EWN_EINVAL;
+        if ((long long)a->num_simulations * a->num_env_copies > 0x7fffffffll / 6) return EWN_EUNSUPPORTED;
+        if (cfg->opponent_kind == EWN_OPP_MINIMAX && cfg->heuristic == EWN_H_SIM_WINRATE) return EWN_EUNSUPPORTED;
+        ag = 2;
+    } else if (a->kind == EWN_AGENT_RANDOM || a->kind == EWN_AGENT_SAMPLE || a->kind == EWN_AGENT_MLP) return EWN_EUNSUPPORTED;
+    else return EWN_EINVAL;
+    if (cfg->shaped || g.CN != 6 || g.S > 8) return EWN_EUNSUPPORTED;
+    if (cfg->rng_kind == EWN_RNG_MT19937 && cfg->autoreset) return EWN_EUNSUPPORTED;
+    opp_mcts = cfg->opponent_kind == EWN_OPP_MCTS;
+    return EWN_OK;
+}
+
+int ewn_step_k_agent_supported(const ewn_config *cfg, const ewn_agent *agent)
+{
+    Geom g; KCfg k;
+    int rc = check_cfg(cfg, g, k);
+    if (rc) return rc;
+    if (!agent) return EWN_ENULL;
+    int ag; bool om;
+    rc = agent_rollout_plan(cfg, g, agent, ag, om);
+    return rc == EWN_OK ? 1 : (rc == EWN_EUNSUPPORTED ? 0 : rc);
+}
+
+int ewn_step_k_agent(const ewn_config *cfg, const ewn_state *st, int K, const ewn_agent *agent, const ewn_rollout_out *out, void *stream)
+{
+    Geom g; KCfg k;
+    int rc = check_cfg(cfg, g, k);
+    if (rc) return rc;
+    if (K < 1) return EWN_EINVAL;
+    if (!agent || !st || !st->board || !st->dice || !st->done || !st->rng) return EWN_ENULL;
+    int ag; bool om;
+    rc = agent_rollout_plan(cfg, g, agent, ag, om);
+    if (rc) return rc;
+    // the minimax side (the agent of AG 1, the opponent of AG 2 against minimax) searches from its table image
+    const bool tab = ag == 1 || cfg->opponent_kind == EWN_OPP_MINIMAX;
+    if (tab && !st->tables) return EWN_ENULL;
+    RollBuf rb;
+    memset(&rb, 0, sizeof(rb));
+    if (tab) rb.tables = ag == 1 ? fast_image(st->tables, g.S, g.L, agent->max_depth, agent->heuristic)
+                                 : fast_image(st->tables, g.S, g.L, cfg->max_depth, cfg->heuristic);
+    if (out) {
+        rb.t_board = out->board; rb.t_dice = out->dice; rb.t_action = out->action; rb.t_reward = out->reward;
+        rb.t_term = out->terminated; rb.t_trunc = out->truncated; rb.t_info = out->info; rb.t_rec = out->record;
+        rb.ret_sum = out->return_sum; rb.n_steps = out->n_steps; rb.n_episodes = out->n_episodes; rb.n_wins = out->n_wins;
+    }
+    // games per block: ewn_step_k's rule for the MCTS opponent (8 .. MR_GPB, about 2 048 blocks), from 4 for the instances with a search:
+    // its searching lanes diverge, fewer per wave and twice the blocks at small N measured 11-13 % faster at 1 024 lanes
+    int gpb = tab ? 4 : 8;
+    while (gpb < MR_GPB && (long long)k.N / (2 * gpb) >= 2048) gpb *= 2;
+    const int atotal = ag == 2 ? agent->num_simulations * agent->num_env_copies : 0;
+    MctsRoll mr = { K, k.nsim_total, om ? playout_group_log2(k.nsim_total) : 3, 0, (g.cells + 6 + 15) & ~15, gpb };
+    AgentRoll ar = { agent->max_depth, agent->heuristic, atotal, ag == 2 ? playout_group_log2(atotal) : 3, agent->step_base, agent->key };
+    const dim3 grid((unsigned)((k.N + gpb - 1) / gpb));
+    const size_t lds = (((size_t)gpb * mr.strd + 15) & ~(size_t)15) + (tab ? (size_t)fast_tables_bytes(g.S, g.L) : 0);
+    hipStream_t s = (hipStream_t)stream;
+    if (!tab) {
+        if (om) k_rollout_mcts_agent<2, 2, 0><<<grid, BS, lds, s>>>(g, k, kstate(st), mr, rb, ar);
+        else k_rollout_mcts_agent<2, 0, 0><<<grid, BS, lds, s>>>(g, k, kstate(st), mr, rb, ar);
+        return launch_status();
+    }
+#define AGL(SS) do { auto kern = ag == 1 ? k_rollout_mcts_agent<1, 2, SS> : k_rollout_mcts_agent<2, 1, SS>; \
+                     if (lds > 64 * 1024 && hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return EWN_ELAUNCH; \
+                     kern<<<grid, BS, lds, s>>>(g, k, kstate(st), mr, rb, ar); } while (0)
+    switch (g.S) {
+    case 5: AGL(5); break;
+    case 6: AGL(6); break;
+    case 7: AGL(7); break;
+    default: AGL(8); break;
+    }
+#undef AGL
+    return launch_status();
 }
 
 static int query_geom(int S, int L, int M, const void *boards, Geom &g)

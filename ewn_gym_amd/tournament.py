@@ -68,9 +68,11 @@ def evaluate(agent, opponent, num=1024, board_size=5, cube_layer=3, rng="mt19937
     agent / opponent: dicts {"kind": "random"|"minimax"|"mcts", max_depth=, heuristic=, num_simulations=, num_env_copies=}.
     Returns per-episode scores (float64 tensor), episode lengths and summary statistics.
     When both sides are engine policies the table-driven kernels cover (RandomAgent, 'hybrid' minimax; cube_layer 3) the whole
-    predict/step loop runs on the device, `chunk` steps per launch (ewn_step_k); an "mlp" agent likewise wherever ewn_policy_eval serves
-    the opponent and geometry; otherwise one policy evaluation + one ewn_step per step.  Both give identical per-episode results for
-    deterministic agents ("engine" in the result says which one ran)."""
+    predict/step loop runs on the device, `chunk` steps per launch (ewn_step_k); an MCTS agent, or a minimax agent against MCTS, likewise
+    through ewn_step_k_agent (cube_layer 3, boards 5..8); an "mlp" agent wherever ewn_policy_eval serves the opponent and geometry;
+    otherwise one policy evaluation + one ewn_step per step (use_rollout=False forces that loop).  The engines give the per-step loop's
+    per-episode results, the MCTS agent's included: its playouts at step t use key + 0x9E3779B97F4A7C15 * (t + 1) either way
+    ("engine" in the result says which one ran)."""
     env = VecEWN(num, board_size=board_size, cube_layer=cube_layer, opponent_policy=opponent["kind"],
                  max_depth=opponent.get("max_depth", 3), heuristic=opponent.get("heuristic", "hybrid"),
                  num_simulations=opponent.get("num_simulations", 10), num_env_copies=opponent.get("num_env_copies", 5),
@@ -85,6 +87,16 @@ def evaluate(agent, opponent, num=1024, board_size=5, cube_layer=3, rng="mt19937
                 break
         env.check_rng()
         return _totals_result(totals, num, "ewn_step_k")
+    if use_rollout and isinstance(agent, dict) and agent["kind"] in ("minimax", "mcts") and env.supports_agent_rollout(agent):
+        # the MCTS agent, or the minimax agent against MCTS: ewn_step_k_agent, whose MCTS agent draws the playouts the per-step loop's
+        # predict_mcts draws at the same step t (step_base + k)
+        totals = env.alloc_totals()
+        for t0 in range(0, max_steps, chunk):
+            env.agent_rollout(chunk, agent, step_base=t0, key=key, totals=totals)
+            if bool((env.done != 0).all()):
+                break
+        env.check_rng()
+        return _totals_result(totals, num, "ewn_step_k_agent")
     if isinstance(agent, dict) and agent["kind"] == "mlp":
         model = agent["model"]
         if getattr(model, "S", board_size) != board_size:
@@ -129,7 +141,7 @@ def tournament(names=("random", "minimax", "mcts"), num=1024, max_depth=5, num_s
     for a in names:
         for o in names:
             r = evaluate(spec(a), spec(o), num=num, board_size=board_size, cube_layer=cube_layer, rng=rng)
-            table["%s vs %s" % (a, o)] = {k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length")}
+            table["%s vs %s" % (a, o)] = {k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}
     return table
 
 
@@ -186,8 +198,8 @@ def main():
         t = tournament(a.agents, a.num, a.max_depth, a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer,
                        a.heuristic, a.rng)
     for k, v in t.items():
-        print("%-22s win rate %.3f  (95%% CI %.3f-%.3f, %d/%d, %.1f steps/episode)"
-              % (k, v["win_rate"], v["ci95"][0], v["ci95"][1], v["wins"], v["episodes"], v["avg_length"]))
+        print("%-22s win rate %.3f  (95%% CI %.3f-%.3f, %d/%d, %.1f steps/episode)  %s"
+              % (k, v["win_rate"], v["ci95"][0], v["ci95"][1], v["wins"], v["episodes"], v["avg_length"], v["engine"]))
     print(json.dumps(t))
 
 

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import AGENT, HEUR, OPP, RNG, EwnConfig, EwnPolicy, EwnRolloutOut, EwnState, EwnStepOut, check
+from ._lib import AGENT, AGENT_MCTS, HEUR, OPP, RNG, EwnAgent, EwnConfig, EwnPolicy, EwnRolloutOut, EwnState, EwnStepOut, check
 
 
 def _require_gpu(device):
@@ -320,6 +320,75 @@ class VecEWN:
                             _ptr(totals["n_episodes"]), _ptr(totals["n_wins"]), None)
         check(self.lib.ewn_policy_eval(C.byref(self.cfg), C.byref(self._st), int(K), _ptr(params), C.byref(out), _stream()),
               "ewn_policy_eval")
+        return self.board, self.dice
+
+    # -- K env steps per launch with an MCTS agent, or a minimax agent against the MCTS opponent (ewn_step_k_agent; eval_pairs.py:10-35)
+    def _agent_struct(self, agent, step_base=0, key=0):
+        """tournament-style agent spec {"kind": "mcts"|"minimax", ...} -> EwnAgent, or None for kinds this path never takes"""
+        kind = agent.get("kind") if isinstance(agent, dict) else None
+        if kind == "mcts":
+            return EwnAgent(AGENT_MCTS, 0, 0, int(agent.get("num_simulations", 10)), int(agent.get("num_env_copies", 5)),
+                            int(step_base) & 0xFFFFFFFF, int(key) & 0xFFFFFFFFFFFFFFFF)
+        if kind == "minimax":
+            heur = agent.get("heuristic", "hybrid")
+            if heur not in HEUR:
+                return None
+            return EwnAgent(AGENT["minimax"], int(agent.get("max_depth", 3)), HEUR[heur], 0, 0, 0, 0)
+        return None
+
+    def supports_agent_rollout(self, agent):
+        """True when ewn_step_k_agent serves this configuration and agent (an MCTS agent against RandomAgent, minimax or MCTS; a
+        minimax agent against MCTS); decided on the host"""
+        a = self._agent_struct(agent)
+        if a is None:
+            return False
+        if self.tables is None and (a.kind == AGENT["minimax"] or self.cfg.opponent_kind == OPP["minimax"]):
+            return False           # use_tables=False: the minimax side searches from its table image
+        return self.lib.ewn_step_k_agent_supported(C.byref(self.cfg), C.byref(a)) == 1
+
+    def agent_rollout(self, K, agent, step_base=0, key=0, traj=None, totals=None):
+        """Play K steps of every lane in one launch, the agent being the tournament spec `agent` (MctsAgent or ExpectiMinimaxAgent).
+        The MCTS agent's playouts at step k of this call are those of predict_mcts(board, dice, key=key_t, obs_id=lane_offset + lane),
+        key_t = key + 0x9E3779B97F4A7C15 * (step_base + k + 1) mod 2^64: tournament.evaluate's per-step loop at t = step_base + k.
+        traj: dict from alloc_rollout (columns or record layout, first dimension >= K) or None; totals: dict from alloc_totals or None
+        (ADDED to).  Buffers of the wrong shape, dtype or layout raise ValueError before anything is launched."""
+        a = self._agent_struct(agent, step_base, key)
+        if a is None:
+            raise ValueError("agent_rollout: agent must be {\"kind\": \"mcts\"|\"minimax\", ...} with a known heuristic, got %r" % (agent,))
+        traj, totals = traj or {}, totals or {}
+        if not isinstance(traj, dict) or not isinstance(totals, dict):
+            raise ValueError("agent_rollout: traj / totals must be the dicts of alloc_rollout() / alloc_totals()")
+        _no_initial_obs(traj)
+        N, S = self.N, self.S
+        stride = (S * S + 6 + 15) & ~15
+        cols = {"board": (torch.int8, (N, S, S)), "dice": (torch.int8, (N,)), "action": (torch.int8, (N, 2)),
+                "reward": (torch.float64, (N,)), "terminated": (torch.uint8, (N,)), "truncated": (torch.uint8, (N,)),
+                "info": (torch.uint8, (N,)), "record": (torch.uint8, (N, stride))}
+        record = "record" in traj
+        for name, t in traj.items():
+            if name not in cols:
+                raise ValueError("agent_rollout: unknown trajectory entry %r" % name)
+            if record and name not in ("record", "reward"):
+                continue            # the record layout's column entries are views into the records, not buffers of their own
+            dt, shape = cols[name]
+            if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_cuda and t.is_contiguous() and t.dim() == 1 + len(shape)
+                    and t.shape[0] >= K and tuple(t.shape[1:]) == shape):
+                raise ValueError("agent_rollout: traj[%r] must be a contiguous %s device tensor of shape [>= %d, %s], got %s" % (
+                    name, str(dt).replace("torch.", ""), K, ", ".join(str(x) for x in shape), _describe(t)))
+        for name, t in totals.items():
+            dt = {"return_sum": torch.float64, "n_steps": torch.int32, "n_episodes": torch.int32, "n_wins": torch.int32}.get(name)
+            if dt is None:
+                raise ValueError("agent_rollout: unknown totals entry %r" % name)
+            if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (N,)):
+                raise ValueError("agent_rollout: totals[%r] must be a contiguous %s device tensor of shape [%d], got %s" % (
+                    name, str(dt).replace("torch.", ""), N, _describe(t)))
+        col = (lambda k: None) if record else traj.get
+        out = EwnRolloutOut(_ptr(col("board")), _ptr(col("dice")), _ptr(col("action")), _ptr(traj.get("reward")),
+                            _ptr(col("terminated")), _ptr(col("truncated")), _ptr(col("info")),
+                            _ptr(totals.get("return_sum")), _ptr(totals.get("n_steps")), _ptr(totals.get("n_episodes")),
+                            _ptr(totals.get("n_wins")), _ptr(traj.get("record")))
+        check(self.lib.ewn_step_k_agent(C.byref(self.cfg), C.byref(self._st), int(K), C.byref(a), C.byref(out), _stream()),
+              "ewn_step_k_agent")
         return self.board, self.dice
 
     def set_obs(self, boards, dice):

@@ -184,7 +184,7 @@ int ewn_step(const ewn_config *cfg, const ewn_state *st, const int8_t *actions, 
  * the table-driven configurations (cube_layer 3, board sizes 5..8, ewn_state.tables set; opponent RandomAgent or minimax with
  * 'hybrid', 'min_dist', 'attk' -- every agent -- or 'two_min_dist' -- RandomAgent / sample agents); the MCTS opponent (cube_layer <= 3,
  * boards <= 8x8, RandomAgent / sample agents); and the geometries without a table image (the generic kernel, see
- * ewn_step_k_supported). */
+ * ewn_step_k_supported).  The MCTS agent, and the minimax agent against the MCTS opponent, are ewn_step_k_agent's (below). */
 #define EWN_AGENT_RANDOM 0  /* RandomAgent.predict (classical_policies/random_policy.py:11-15): the hash-driven uniform legal pick
                                of ewn_step_out.random_action, same stream */
 #define EWN_AGENT_MINIMAX 1 /* ExpectiMinimaxAgent(agent_max_depth, 'hybrid').predict (classical_policies/minimax.py:89-93) */
@@ -231,6 +231,30 @@ int ewn_step_k_supported(const ewn_config *cfg, int agent_kind, int agent_max_de
 /* K >= 1 steps of every lane; out may be NULL (only the state advances).  No scratch; one kernel launch. */
 int ewn_step_k(const ewn_config *cfg, const ewn_state *st, int K, int agent_kind, int agent_max_depth,
                const ewn_rollout_out *out, void *stream);
+
+/* ---- K env steps per launch with an MCTS agent, or a minimax agent against the MCTS opponent: the cells of eval_pairs.py:10-35's
+ * matrix that ewn_step_k does not serve -- MctsAgent against RandomAgent, minimax (the four evaluate() heuristics, max_depth 1..6) or
+ * MCTS, and ExpectiMinimaxAgent(max_depth 1..6; 'hybrid', 'min_dist', 'attk', 'two_min_dist') against MCTS.  cube_layer 3, boards 5..8,
+ * un-shaped; Philox dice with or without auto-reset, MT19937-compat dice without.  Results are identical, step for step, to the
+ * agent's predict_minimax / predict_mcts fed to ewn_step: the MCTS agent's observation is the board as it stands (TOP_LEFT to move),
+ * and at evaluation step t = step_base + k its playouts of lane n use the stream of ewn_predict_mcts with obs_id = lane_offset + n and
+ * key_t = key + 0x9E3779B97F4A7C15 * (t + 1) (mod 2^64).  The MCTS opponent's stream is ewn_step_k's.  The minimax side (the agent, or
+ * the opponent of the MCTS agent) runs the table-driven search of ewn_predict_minimax / ewn_step and needs ewn_state.tables. */
+#define EWN_AGENT_MCTS 4    /* MctsAgent(num_simulations, num_env_copies).predict (classical_policies/mcts.py:47-69), ewn_step_k_agent only */
+typedef struct ewn_agent {
+    int32_t kind;             /* EWN_AGENT_MCTS, or EWN_AGENT_MINIMAX (against the MCTS opponent) */
+    int32_t max_depth;        /* minimax: 1..EWN_MAX_DEPTH */
+    int32_t heuristic;        /* minimax: EWN_H_*, not EWN_H_SIM_WINRATE */
+    int32_t num_simulations;  /* mcts: MctsAgent.num_simulations */
+    int32_t num_env_copies;   /* mcts: MctsAgent.num_env_copies */
+    uint32_t step_base;       /* mcts: evaluation step index of this launch's first step */
+    uint64_t key;             /* mcts: playout key (see above) */
+} ewn_agent;
+/* 1 if ewn_step_k_agent serves (cfg, agent), 0 if not, < 0 for an invalid cfg or agent; decided on the host */
+int ewn_step_k_agent_supported(const ewn_config *cfg, const ewn_agent *agent);
+/* K >= 1 steps of every lane; out may be NULL, and takes what ewn_step_k's does (columns and/or records, totals ADDED to).  One kernel
+ * launch, no scratch.  Anything ewn_step_k_agent_supported does not answer 1 for returns EWN_EUNSUPPORTED / EWN_EINVAL unlaunched. */
+int ewn_step_k_agent(const ewn_config *cfg, const ewn_state *st, int K, const ewn_agent *agent, const ewn_rollout_out *out, void *stream);
 
 /* ---- K env steps per launch with the TRAINED policy as the agent: the rollout collector of train.py:35-63, 134, 148 -----------
  * (SB3 A2C("MultiInputPolicy", env, policy_kwargs=dict(activation_fn=Tanh)).learn -> collect_rollouts over SubprocVecEnv workers)
