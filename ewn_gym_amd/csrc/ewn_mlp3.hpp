@@ -1,6 +1,6 @@
 // ewn_mlp3.hpp -- the actor-critic's matrix products on the bf16 matrix pipe at fp32 accuracy ("bf16 x 3").
 //
-// Why not the f32-input MFMA (ewn_mlp.hpp): measured (tools/mfma_probe.hip) v_mfma_f32_32x32x2_f32 takes 64 cycles for K = 2 and
+// Why not the f32-input MFMA: measured (tools/mfma_probe.hip) v_mfma_f32_32x32x2_f32 takes 64 cycles for K = 2 and
 // overlaps with NOTHING on its SIMD (it runs on the fp32 vector ALUs), while v_mfma_f32_32x32x16_bf16 takes 32 cycles for K = 16
 // and runs on the matrix pipe beside the VALU: sixteen times the multiply-adds per cycle, and free issue slots on top.  An fp32
 // number is EXACTLY the sum of three bf16 numbers (8 significant bits each: hi = the top 16 bits of x, mid = the top 16 bits of
@@ -15,7 +15,7 @@
 // eight k-slots (h, jj), h = l >> 5, jj = 0 .. 7, as 8 bf16 in four registers; slot (h, jj) of A meets slot (h, jj) of B.  WHICH k a
 // slot stands for is ours to choose, as long as both operands agree: a "k-block" kb is sixteen k values, U(kb, h, jj) below for the
 // 64 hidden units, 16 kb + 8 h + jj for the features.  The 32 x 32 result has its column on the lane and row mlp_row(r, h) in
-// register r (as the f32 MFMA: ewn_mlp.hpp) -- so eight consecutive registers of a result ARE the eight slots of a k-block of the
+// register r (ewn_mlp.hpp) -- so eight consecutive registers of a result ARE the eight slots of a k-block of the
 // next product, after the split: layers chain through registers, no LDS round trip, no lane movement.
 #pragma once
 #include "ewn_mlp.hpp"

@@ -5,7 +5,6 @@
 #include "ewn_lds.hpp"
 #include "ewn_policy.hpp"
 #include "ewn_a2c.hpp"
-#include "ewn_a2c2.hpp"
 #include "ewn_a2c3.hpp"
 #include "ewn_ppo.hpp"
 
@@ -79,8 +78,6 @@ int ewn_step_k_policy(const ewn_config *cfg, const ewn_state *st, int K, const e
     pc.N = k.N; pc.autoreset = k.autoreset; pc.lane_offset = k.lane_offset; pc.depth = k.depth; pc.K = K;
     pc.shaped = k.shaped; pc.refresh = k.refresh; pc.deterministic = pol->deterministic ? 1 : 0; pc.want_value = pol->value ? 1 : 0;
     pc.rec0 = pol->record_initial_obs ? 1 : 0;
-    static const int stagger = [] { const char *e = getenv("EWN_POLICY_STAGGER"); return e ? atoi(e) : 0; }();   // tuning knob; measured: no effect (the f32 MFMA does not overlap with the other wave's VALU work)
-    pc.stagger = stagger;
     pc.seed_stride = k.seed_stride; pc.W = k.W; pc.reward = k.reward; pc.illegal_reward = k.illegal_reward;
     pc.key = k.key; pc.noise_key = pol->noise_key;
     PolBuf pb;
@@ -153,9 +150,6 @@ int ewn_policy_eval(const ewn_config *cfg, const ewn_state *st, int K, const flo
 
 #define A2C_MAX_BLOCKS 256   // one block per CU
 
-template <int S> struct A2cWaves { static constexpr int N = 4; };
-template <> struct A2cWaves<7> { static constexpr int N = 3; };   // the 7x7 images leave room for three waves' transpose tiles
-
 static int a2c_blocks(int N, int nwv)
 {
     const int tiles = (N + 31) / 32, need = (tiles + nwv - 1) / nwv;
@@ -187,26 +181,9 @@ static void a2c_reduce_launch(const A2cRedBuf &rb, hipStream_t s)
     else k_a2c_reduce<<<(rb.P + 8 + A2C_RED_E - 1) / A2C_RED_E, 256, 0, s>>>(rb);
 }
 
-// 5x5, f32 MFMA: two waves per tile (k_a2c_grad2)
-static int a2c_grad_launch_team(const A2cCfg &ac, A2cBuf ab, float *grad, hipStream_t s)
-{
-    constexpr size_t lds = A2c2Geo<5>::lds_bytes();
-    static_assert(lds <= 160 * 1024, "weight images + four teams' tiles must fit the CU's LDS");
-    auto kv = k_a2c_grad2<5, 1>;
-    auto kp = k_a2c_grad2<5, 0>;
-    if (hipFuncSetAttribute((const void *)kv, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return EWN_ELAUNCH;
-    if (hipFuncSetAttribute((const void *)kp, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return EWN_ELAUNCH;
-    const int blocks = a2c_blocks(ac.N, A2c2Geo<5>::TEAMS);
-    kv<<<blocks, 512, lds, s>>>(ac, ab);
-    kp<<<blocks, 512, lds, s>>>(ac, ab);
-    A2cRedBuf rb = { ab.partial, ab.stats, grad, blocks, MlpGeo<5>::P };
-    a2c_reduce_launch(rb, s);
-    return launch_status();
-}
-
 // the bf16 x 3 kernel (ewn_a2c3.hpp): one wave per tile and SIMD, everything in registers
 template <int S>
-static int a2c_grad_launch_b3(const A2cCfg &ac, A2cBuf ab, float *grad, hipStream_t s)
+static int a2c_grad_launch(const A2cCfg &ac, A2cBuf ab, float *grad, hipStream_t s)
 {
     constexpr size_t lds = A2c3Geo<S>::lds_bytes();
     static_assert(lds <= 160 * 1024, "weight images + the gradient image must fit the CU's LDS");
@@ -217,29 +194,6 @@ static int a2c_grad_launch_b3(const A2cCfg &ac, A2cBuf ab, float *grad, hipStrea
     const int blocks = a2c_blocks(ac.N, 4);
     kv<<<blocks, 256, lds, s>>>(ac, ab);         // value pass first: it leaves the advantages for the policy pass
     kp<<<blocks, 256, lds, s>>>(ac, ab);
-    A2cRedBuf rb = { ab.partial, ab.stats, grad, blocks, MlpGeo<S>::P };
-    a2c_reduce_launch(rb, s);
-    return launch_status();
-}
-
-// EWN_A2C_KERNEL: 3 (default) the bf16 x 3 register kernel; 2 the f32-MFMA team kernel (5x5); 1 the f32-MFMA one-wave kernel -- the
-// older two stay for A/B measurements and as independent implementations the tests compare
-template <int S>
-static int a2c_grad_launch(const A2cCfg &ac, A2cBuf ab, float *grad, hipStream_t s)
-{
-    static const int kind = [] { const char *e = getenv("EWN_A2C_KERNEL"); return e ? atoi(e) : 3; }();
-    if (kind >= 3 || kind <= 0) return a2c_grad_launch_b3<S>(ac, ab, grad, s);
-    if (S == 5 && kind == 2) return a2c_grad_launch_team(ac, ab, grad, s);
-    constexpr int NWV = A2cWaves<S>::N;
-    constexpr size_t lds = a2c_lds_bytes<S, NWV>();
-    static_assert(lds <= 160 * 1024, "the gradient kernel's images and transpose tiles must fit the CU's LDS");
-    auto kv = k_a2c_grad<S, 1, NWV>;
-    auto kp = k_a2c_grad<S, 0, NWV>;
-    if (hipFuncSetAttribute((const void *)kv, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return EWN_ELAUNCH;
-    if (hipFuncSetAttribute((const void *)kp, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return EWN_ELAUNCH;
-    const int blocks = a2c_blocks(ac.N, NWV);
-    kv<<<blocks, NWV * 64, lds, s>>>(ac, ab);    // value pass first: it leaves the advantages for the policy pass
-    kp<<<blocks, NWV * 64, lds, s>>>(ac, ab);
     A2cRedBuf rb = { ab.partial, ab.stats, grad, blocks, MlpGeo<S>::P };
     a2c_reduce_launch(rb, s);
     return launch_status();
@@ -274,8 +228,8 @@ int ewn_a2c_apply(const ewn_config *cfg, float *params, float *sq_avg, const flo
     if (hp->world_size < 1) return EWN_EINVAL;
     A2cApplyCfg ac = { (int)ewn_policy_param_count(g.S, g.L), hp->learning_rate, hp->rms_alpha, hp->rms_eps, hp->max_grad_norm, 1.0f / (float)hp->world_size };
     const bool vec = ac.P <= 1024 * 4 * A2C_APPLY_V && ((uintptr_t)params | (uintptr_t)sq_avg | (uintptr_t)grad) % 16 == 0;
-    if (vec) k_a2c_apply_v4<<<1, 1024, 0, (hipStream_t)stream>>>(ac, params, sq_avg, grad, grad_norm_out);
-    else k_a2c_apply<<<1, 1024, 0, (hipStream_t)stream>>>(ac, params, sq_avg, grad, grad_norm_out);
+    if (vec) k_a2c_apply<true><<<1, 1024, 0, (hipStream_t)stream>>>(ac, params, sq_avg, grad, grad_norm_out);
+    else k_a2c_apply<false><<<1, 1024, 0, (hipStream_t)stream>>>(ac, params, sq_avg, grad, grad_norm_out);
     return launch_status();
 }
 

@@ -1,7 +1,7 @@
 // ewn_policy.hpp -- K env steps per launch with the TRAINED policy as the agent (C ABI: ewn_step_k_policy, EWN_AGENT_MLP):
 // the rollout collector of the reference's trainer (train.py:35-63, 134, 148: SB3 A2C.learn -> collect_rollouts over
 // SubprocVecEnv workers of `MiniMaxHeuristicEnv`, envs/training_ewn.py:40-99) as ONE kernel.  Per env step and game:
-// observation -> features -> the policy network on the matrix cores (ewn_mlp.hpp) -> Gumbel-max sample of MultiDiscrete([2, 3])
+// observation -> features -> the policy network on the matrix cores (ewn_mlp3.hpp) -> Gumbel-max sample of MultiDiscrete([2, 3])
 // -> the env step (plain or reward-shaped, with its tolerance counter) -> the opponent's search -> reply -> auto-reset ->
 // one trajectory record.  The game never leaves its registers, the network's weights never leave LDS.
 //
@@ -15,7 +15,6 @@
 
 struct PolCfg {
     int N, autoreset, lane_offset, depth, K;
-    int stagger;                                            // start delay of every other wave, in units of 64 cycles (0: none)
     int shaped, refresh, deterministic, want_value, rec0;   // rec0: record row 0 = the observation before step 0 (then K + 1 rows)
     u32 seed_stride, W;
     double reward, illegal_reward;
@@ -78,7 +77,7 @@ __global__ __launch_bounds__(NT, TRJ == 2 ? 2 : NT / 256) void k_rollout_mlp(Pol
     constexpr bool FIX = TRJ == 1, EV = TRJ == 2;
     static_assert(EV || (OPP != 2 && RNGK == 1), "the depth-5 opponent and the MT19937-compat dice are evaluation-only");
     const bool want_value = !FIX && !EV && c.want_value, deterministic = EV || (!FIX && c.deterministic), rec0 = FIX || (!EV && c.rec0);
-    constexpr int T = 2, GPB = NT / T, NW = NT / 64, CELLS = S * S, STR = RecGeo<S>::STR, NCH = RecGeo<S>::NCH;
+    constexpr int T = 2, GPB = NT / T, CELLS = S * S, STR = RecGeo<S>::STR, NCH = RecGeo<S>::NCH;
     using G = MlpGeo<S>;
     extern __shared__ __attribute__((aligned(16))) int8_t lds[];
     using Q3 = Mlp3Geo<S>;
@@ -125,10 +124,6 @@ __global__ __launch_bounds__(NT, TRJ == 2 ? 2 : NT / 256) void k_rollout_mlp(Pol
     if ((FIX || B.t_rec) && rec0 && live) rec_store<S, T>(slot, sub, dice, 0, 0, 0, 0, 0, B.t_rec + (size_t)game * STR);
     double ret_acc = 0.0;
     int n_steps = 0, n_eps = 0, n_wins = 0;
-    // The two waves that share a SIMD run the same loop; started together they stay in phase -- both in the network (the matrix
-    // pipe contended, the VALU idle), then both in the search (the reverse).  The block's second half of waves starts c.stagger x 64 cycles late, about
-    // one network evaluation, so that one wave's MFMAs run under the other's search from then on (nothing in the loop re-aligns them).
-    if (wave >= NW / 2 && c.stagger > 0) { for (int i = 0; i < c.stagger; i += 127) __builtin_amdgcn_s_sleep(127); }   // waves w and w + NW / 2 share a SIMD
 
     #pragma unroll 1
     for (int kstep = 0; kstep < c.K; kstep++) {

@@ -3,7 +3,7 @@
 //   k_ppo_prepare     one pass over the K + 1 record rows: both nets' forward (bf16 x 3, ewn_mlp3.hpp) and the backward GAE
 //                     recursion per lane in registers -> one float4 per sample {old log pi(a), advantage, return, old value}
 //   k_ppo_shuffle     the minibatch order of every epoch: a keyed Feistel bijection of [0, n) with cycle walking (no sort, no host)
-//   k_ppo_grad3<S, NET>  forward + backward of ONE minibatch for one net (k_a2c_grad3's register layout; the t-loop becomes a loop
+//   k_ppo_grad3<S, NET>  forward + backward of ONE minibatch for one net (k_a2c_grad3's step body; the t-loop becomes a loop
 //                     over the minibatch's gathered 32-sample tiles); the value pass also leaves the minibatch's advantage sums for
 //                     the policy pass's normalisation; per-block partials, summed by k_a2c_reduce*
 //   k_ppo_apply       clip_grad_norm_ + one torch.optim.Adam step, the step count in device memory (graph replays stay right).
@@ -205,49 +205,18 @@ template <int S> struct Ppo3Geo {
 };
 
 // NET 0: policy body + action head; NET 1: value body + value head.  256 threads: four waves, one per SIMD.  The value pass runs
-// first: its blocks leave the advantage sums the policy pass normalises with (the same grid size for both).
+// first: its blocks leave the advantage sums the policy pass normalises with (the same grid size for both).  The step body and the
+// epilogue are k_a2c_grad3's (ewn_a2c3.hpp); the loop runs over the minibatch's gathered 32-sample tiles instead of the steps.
 template <int S, int NET>
 __global__ __launch_bounds__(256, 1) void k_ppo_grad3(PpoCfg c, PpoBuf B)
 {
-    using G = MlpGeo<S>;
-    using Q = Mlp3Geo<S>;
-    using A = A2c3Geo<S>;
-    constexpr int CELLS = S * S, NT = 256, NWV = 4, NOUT = NET ? 1 : MLP_NA, KB1 = Q::KB1, FT = A::FT;
+    constexpr int NWV = 4;
     extern __shared__ __attribute__((aligned(16))) int8_t lds3p[];
     int8_t *img = lds3p;
-    const u32x4 *I1 = (const u32x4 *)(img + Q::O_W1), *I2 = (const u32x4 *)(img + Q::O_W2);
-    u32x4 *IW2T = (u32x4 *)(img + A::O_W2T), *IWH = (u32x4 *)(img + A::O_WH), *IWF = (u32x4 *)(img + A::O_WF);
-    const float *Lf = (const float *)(img + Q::O_F);
-    float *GI = (float *)(img + A::O_GI);
     double *ADV = (double *)(img + Ppo3Geo<S>::O_ADV);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
 
-    mlp3_pack_fwd<S>(img, B.params, NET, threadIdx.x, NT);
-    {
-        const float *W2 = B.params + (NET ? G::O_VF : G::O_PI) + MLP_H * G::F + MLP_H;
-        const float *Wh = B.params + (NET ? G::O_VW : G::O_AW);
-        for (int e = threadIdx.x; e < A::N_W2T; e += NT) {
-            const int l = e & 63, kb = (e >> 6) & 3, nt = e >> 8;
-            float v[8];
-            #pragma unroll
-            for (int jj = 0; jj < 8; jj++) v[jj] = W2[mlp3_unit(kb, l >> 5, jj) * MLP_H + 32 * nt + (l & 31)];
-            mlp3_store(IW2T, A::N_W2T, e, v);
-        }
-        for (int e = threadIdx.x; e < A::N_WH; e += NT) {
-            const int l = e & 63, mt = e >> 6;
-            float v[8];
-            #pragma unroll
-            for (int jj = 0; jj < 8; jj++) { const int a = 8 * (l >> 5) + jj; v[jj] = a < NOUT ? Wh[a * MLP_H + 32 * mt + (l & 31)] : 0.0f; }
-            mlp3_store(IWH, A::N_WH, e, v);
-        }
-        for (int e = threadIdx.x; e < A::N_WF; e += NT) {
-            const int l = e & 63, kb = e >> 6;
-            float v[8];
-            #pragma unroll
-            for (int jj = 0; jj < 8; jj++) v[jj] = (l & 31) < NOUT ? Wh[(l & 31) * MLP_H + mlp3_unit(kb, l >> 5, jj)] : 0.0f;
-            mlp3_store(IWF, A::N_WF, e, v);
-        }
-    }
+    a2c3_pack<S, NET>(img, B.params);
     // the policy pass: the minibatch's advantage mean and unbiased std from the value pass's per-block sums (every wave sums the
     // blocks in the same fixed order: the same bits everywhere)
     float amean = 0.0f, astd = 1.0f;
@@ -262,20 +231,8 @@ __global__ __launch_bounds__(256, 1) void k_ppo_grad3(PpoCfg c, PpoBuf B)
     }
     __syncthreads();
 
-    const u32x4 idu[2] = { a2c3_identity(lane, true, 0), a2c3_identity(lane, true, 1) };
-    const u32x4 idf[2] = { a2c3_identity(lane, false, 0), a2c3_identity(lane, false, 1) };
-
-    f32x16 dW2[2][2], dW1[2][FT], dWh[2];
-    #pragma unroll
-    for (int a = 0; a < 2; a++) {
-        #pragma unroll
-        for (int b = 0; b < 2; b++) dW2[a][b] = (f32x16)(0.0f);
-        #pragma unroll
-        for (int b = 0; b < FT; b++) dW1[a][b] = (f32x16)(0.0f);
-        dWh[a] = (f32x16)(0.0f);
-    }
-    float db2a[2] = { 0.0f, 0.0f };
-    float dbh[MLP_NA] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
+    const A2c3Id id(lane);
+    A2c3Acc<S> acc;
     float st[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
     double st_sa = 0.0, st_sq = 0.0;
 
@@ -287,243 +244,18 @@ __global__ __launch_bounds__(256, 1) void k_ppo_grad3(PpoCfg c, PpoBuf B)
         const int pos = tile * 32 + j;
         const bool valid = pos < c.B;
         const Ppo3Ld<S> nxt = ppo3_load<S>(c, B, tile + stride < tiles ? (tile + stride) * 32 + j : pos, h);
-        Mlp3Op w1[2][KB1];
-        #pragma unroll
-        for (int kb = 0; kb < KB1; kb++) { w1[0][kb] = mlp3_load(I1, Q::N_W1, kb * 64 + lane); w1[1][kb] = mlp3_load(I1, Q::N_W1, (KB1 + kb) * 64 + lane); }
-        u32x4 xop[KB1];
-        a2c3_features<S>(cur.l, h, xop);
-        A2C3_FENCE();
-        // ---- from here to the end of the tile: k_a2c_grad3's step body (see there for the fenced-region schedule)
-        f32x16 h1[2], h2[2];
-        Mlp3Op wa = mlp3_load(I2, Q::N_W2, lane), wb = mlp3_load(I2, Q::N_W2, 4 * 64 + lane);
-        {
-            f32x16 a0 = mlp_bias_acc(Lf + Q::F_B1, h), a1 = mlp_bias_acc(Lf + Q::F_B1 + 32, h);
-            #pragma unroll
-            for (int kb = 0; kb < KB1; kb++) { a0 = mlp3_mac_ax(a0, w1[0][kb], xop[kb]); a1 = mlp3_mac_ax(a1, w1[1][kb], xop[kb]); }
-            h1[0] = mlp_tanh16(a0); h1[1] = mlp_tanh16(a1);
-        }
-        f32x16 h1U[2] = { (f32x16)(0.0f), (f32x16)(0.0f) };
-        Mlp3Op wf = wa;
-        {
-            f32x16 c0 = mlp_bias_acc(Lf + Q::F_B2, h), c1 = mlp_bias_acc(Lf + Q::F_B2 + 32, h);
-            Mlp3Op u = mlp3_operand(h1[0], 0);
-            A2C3_FENCE();
-            #pragma unroll
-            for (int kb = 0; kb < 4; kb++) {
-                Mlp3Op un = u, wan = wa, wbn = wb;
-                if (kb + 1 < 4) { wan = mlp3_load(I2, Q::N_W2, (kb + 1) * 64 + lane); wbn = mlp3_load(I2, Q::N_W2, (4 + kb + 1) * 64 + lane); }
-                else if (NET == 0) wf = mlp3_load(IWF, A::N_WF, lane);
-                if (kb + 1 < 4) un = mlp3_operand(h1[(kb + 1) >> 1], (kb + 1) & 1);
-                c0 = mlp3_mac(c0, wa, u);
-                c1 = mlp3_mac(c1, wb, u);
-                h1U[kb >> 1] = a2c3_transpose_add(h1U[kb >> 1], u, idu[kb & 1]);
-                A2C3_FENCE();
-                u = un; wa = wan; wb = wbn;
-            }
-            h2[0] = mlp_tanh16(c0); h2[1] = mlp_tanh16(c1);
-        }
-        float out[NOUT];
-        f32x16 h2U[2] = { (f32x16)(0.0f), (f32x16)(0.0f) };
-        if constexpr (NET == 1) {
-            mlp3_head<S, 1>(img, lane, h2, out);
-        } else {
-            f32x16 lg = (f32x16)(0.0f);
-            Mlp3Op u = mlp3_operand(h2[0], 0);
-            A2C3_FENCE();
-            #pragma unroll
-            for (int kb = 0; kb < 4; kb++) {
-                Mlp3Op un = u, wfn = wf;
-                if (kb + 1 < 4) { wfn = mlp3_load(IWF, A::N_WF, (kb + 1) * 64 + lane); un = mlp3_operand(h2[(kb + 1) >> 1], (kb + 1) & 1); }
-                lg = mlp3_mac(lg, wf, u);
-                h2U[kb >> 1] = a2c3_transpose_add(h2U[kb >> 1], u, idu[kb & 1]);
-                A2C3_FENCE();
-                u = un; wf = wfn;
-            }
-            const float o0 = mlp_other_half(lg[0], lane), o1 = mlp_other_half(lg[1], lane), o2 = mlp_other_half(lg[2], lane), o3 = mlp_other_half(lg[3], lane);
-            out[0] = (h ? o0 : lg[0]) + Lf[Q::F_BH]; out[1] = (h ? o1 : lg[1]) + Lf[Q::F_BH + 1];
-            out[2] = (h ? o2 : lg[2]) + Lf[Q::F_BH + 2]; out[3] = (h ? o3 : lg[3]) + Lf[Q::F_BH + 3];
-            out[4] = (h ? lg[0] : o0) + Lf[Q::F_BH + 4];
-        }
-        A2C3_FENCE();
-        const Mlp3Op wh0 = mlp3_load(IWH, A::N_WH, lane), wh1 = mlp3_load(IWH, A::N_WH, 64 + lane);
-        float d[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
-        ppo_loss_grad<S, NET>(c, cur, valid, h == 0, out, amean, astd, d, st, st_sa, st_sq);
-        Mlp3Op dop;
-        {
-            float v[8];
-            #pragma unroll
-            for (int jj = 0; jj < 8; jj++) v[jj] = (jj < NOUT && h == 0) ? d[jj] : 0.0f;
-            dop = mlp3_operand(v);
-        }
-        A2C3_FENCE();
-        f32x16 g2[2], dU = (f32x16)(0.0f);
-        Mlp3Op h2k[2][2];
-        {
-            g2[0] = mlp3_mac((f32x16)(0.0f), wh0, dop); g2[1] = mlp3_mac((f32x16)(0.0f), wh1, dop);
-            if constexpr (NET == 0) {
-                dU = a2c3_transpose_add(dU, dop, idf[0]);
-                #pragma unroll
-                for (int nt = 0; nt < 2; nt++) { h2k[nt][0] = mlp3_operand(h2U[nt], 0); h2k[nt][1] = mlp3_operand(h2U[nt], 1); }
-                if (h == 0) { for (int i = 0; i < 5; i++) dbh[i] += d[i]; }
-            } else {
-                #pragma unroll
-                for (int mt = 0; mt < 2; mt++) {
-                    #pragma unroll
-                    for (int r = 0; r < 16; r++) dWh[mt][r] += d[0] * h2[mt][r];
-                }
-                if (h == 0) dbh[0] += d[0];
-            }
-        }
-        A2C3_FENCE();
-        #pragma unroll
-        for (int mt = 0; mt < 2; mt++) {
-            #pragma unroll
-            for (int r = 0; r < 16; r++) g2[mt][r] *= 1.0f - h2[mt][r] * h2[mt][r];
-        }
-        Mlp3Op dk[2];
-        if constexpr (NET == 0) { dk[0] = mlp3_operand(dU, 0); dk[1] = mlp3_operand(dU, 1); }
-        Mlp3Op wt0 = mlp3_load(IW2T, A::N_W2T, lane), wt1 = mlp3_load(IW2T, A::N_W2T, 4 * 64 + lane);
-        A2C3_FENCE();
-        f32x16 g2U[2] = { (f32x16)(0.0f), (f32x16)(0.0f) }, g1U[2] = { (f32x16)(0.0f), (f32x16)(0.0f) };
-        Mlp3Op h1k[2][2];
-        {
-            Mlp3Op u = mlp3_operand(g2[0], 0);
-            A2C3_FENCE();
-            #pragma unroll
-            for (int kb = 0; kb < 4; kb++) {
-                Mlp3Op un = u, wt0n = wt0, wt1n = wt1;
-                if (kb + 1 < 4) {
-                    wt0n = mlp3_load(IW2T, A::N_W2T, (kb + 1) * 64 + lane); wt1n = mlp3_load(IW2T, A::N_W2T, (4 + kb + 1) * 64 + lane);
-                    un = mlp3_operand(g2[(kb + 1) >> 1], (kb + 1) & 1);
-                }
-                h1k[kb >> 1][kb & 1] = mlp3_operand(h1U[kb >> 1], kb & 1);
-                g2U[kb >> 1] = a2c3_transpose_add(g2U[kb >> 1], u, idu[kb & 1]);
-                g1U[0] = mlp3_mac(g1U[0], u, wt0); g1U[1] = mlp3_mac(g1U[1], u, wt1);
-                if constexpr (NET == 0) dWh[kb >> 1] = mlp3_mac(dWh[kb >> 1], dk[kb & 1], h2k[kb >> 1][kb & 1]);
-                A2C3_FENCE();
-                u = un; wt0 = wt0n; wt1 = wt1n;
-            }
-        }
-        #pragma unroll
-        for (int nt = 0; nt < 2; nt++) {
-            float sb = 0.0f;
-            #pragma unroll
-            for (int r = 0; r < 16; r++) { g1U[nt][r] *= 1.0f - h1U[nt][r] * h1U[nt][r]; sb += g2U[nt][r]; }
-            db2a[nt] += sb;
-        }
-        A2C3_FENCE();
-        {
-            Mlp3Op ka[2] = { mlp3_operand(g2U[0], 0), mlp3_operand(g2U[1], 0) };
-            Mlp3Op g1k[2][2];
-            f32x16 xU[FT];
-            A2C3_FENCE();
-            #pragma unroll
-            for (int kb = 0; kb < 2; kb++) {
-                Mlp3Op kan[2] = { ka[0], ka[1] };
-                if (kb == 0) { kan[0] = mlp3_operand(g2U[0], 1); kan[1] = mlp3_operand(g2U[1], 1); }
-                g1k[0][kb] = mlp3_operand(g1U[0], kb); g1k[1][kb] = mlp3_operand(g1U[1], kb);
-                if (kb == 0) {
-                    #pragma unroll
-                    for (int ft = 0; ft < FT; ft++) {
-                        xU[ft] = (f32x16)(0.0f);
-                        #pragma unroll
-                        for (int cc = 0; cc < 2; cc++) { if (2 * ft + cc < KB1) xU[ft] = MLP3_MFMA(xop[2 * ft + cc], idf[cc], xU[ft]); }
-                    }
-                }
-                #pragma unroll
-                for (int mt = 0; mt < 2; mt++) {
-                    #pragma unroll
-                    for (int nt = 0; nt < 2; nt++) dW2[mt][nt] = mlp3_mac(dW2[mt][nt], ka[mt], h1k[nt][kb]);
-                }
-                A2C3_FENCE();
-                ka[0] = kan[0]; ka[1] = kan[1];
-            }
-            #pragma unroll
-            for (int ft = 0; ft < FT; ft++) {
-                #pragma unroll
-                for (int kb = 0; kb < 2; kb++) {
-                    u32x4 xk;
-                    #pragma unroll
-                    for (int q = 0; q < 4; q++) xk[q] = mlp3_pack(__float_as_uint(xU[ft][8 * kb + 2 * q]), __float_as_uint(xU[ft][8 * kb + 2 * q + 1]));
-                    #pragma unroll
-                    for (int mt = 0; mt < 2; mt++) dW1[mt][ft] = mlp3_mac_ax(dW1[mt][ft], g1k[mt][kb], xk);
-                }
-            }
-            A2C3_FENCE();
-        }
+        a2c3_step<S, NET>(img, lane, cur.l, id, acc, [&](const float *out, float (&d)[6]) {
+            ppo_loss_grad<S, NET>(c, cur, valid, h == 0, out, amean, astd, d, st, st_sa, st_sq);
+        }, [](int) {});
         cur = nxt;
     }
 
-    // ---- the block's gradient image in LDS: waves add in a fixed order (bit-reproducible), then one coalesced copy out
-    constexpr int I_W1 = 0, I_B1 = I_W1 + MLP_H * G::F, I_W2 = I_B1 + MLP_H, I_B2 = I_W2 + MLP_H * MLP_H, I_WH = I_B2 + MLP_H,
-                  I_BH = I_WH + NOUT * MLP_H, I_END = I_BH + NOUT;
-    #pragma unroll
-    for (int nt = 0; nt < 2; nt++) db2a[nt] += __shfl_xor(db2a[nt], 32, 64);
-    if constexpr (NET == 1) {
-        #pragma unroll
-        for (int mt = 0; mt < 2; mt++) {
-            #pragma unroll
-            for (int r = 0; r < 16; r++) dWh[mt][r] = a2c_sum32(dWh[mt][r]);
-        }
+    if constexpr (NET == 1) {       // the wave's advantage sums, added up per block below
         #pragma unroll
         for (int m = 1; m < 32; m <<= 1) { st_sa += __shfl_xor(st_sa, m, 64); st_sq += __shfl_xor(st_sq, m, 64); }
         if (lane == 0) { ADV[2 * wave] = st_sa; ADV[2 * wave + 1] = st_sq; }
     }
-    #pragma unroll
-    for (int i = 0; i < NOUT; i++) { dbh[i] = a2c_sum32(dbh[i]); dbh[i] += __shfl_xor(dbh[i], 32, 64); }
-    #pragma unroll
-    for (int q = 0; q < 4; q++) st[q] = a2c_sum32(st[q]);
-    #pragma unroll 1
-    for (int w = 0; w < NWV; w++) {
-        if (wave == w) {
-            const bool first = w == 0;
-            #pragma unroll
-            for (int mt = 0; mt < 2; mt++) {
-                #pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int row = 32 * mt + mlp_row(r, h);
-                    #pragma unroll
-                    for (int nt = 0; nt < 2; nt++) { float *p = GI + I_W2 + row * MLP_H + 32 * nt + j; *p = (first ? 0.0f : *p) + dW2[mt][nt][r]; }
-                    #pragma unroll
-                    for (int ft = 0; ft < FT; ft++) {
-                        const int col = 32 * ft + j;
-                        if (col < G::F) { float *p = GI + I_W1 + row * G::F + col; *p = (first ? 0.0f : *p) + dW1[mt][ft][r]; }
-                    }
-                    if (NET == 1 && j == 0) { float *p = GI + I_WH + row; *p = (first ? 0.0f : *p) + dWh[mt][r]; }
-                }
-                if (h == 0) { float *p = GI + I_B2 + 32 * mt + j; *p = (first ? 0.0f : *p) + db2a[mt]; }
-            }
-            if constexpr (NET == 0) {
-                #pragma unroll
-                for (int nt = 0; nt < 2; nt++) {
-                    #pragma unroll
-                    for (int r = 0; r < 16; r++) {
-                        const int a = mlp_row(r, h);
-                        if (a < MLP_NA) { float *p = GI + I_WH + a * MLP_H + 32 * nt + j; *p = (first ? 0.0f : *p) + dWh[nt][r]; }
-                    }
-                }
-            }
-            if (lane == 0) {
-                #pragma unroll
-                for (int i = 0; i < NOUT; i++) { float *p = GI + I_BH + i; *p = (first ? 0.0f : *p) + dbh[i]; }
-                float *sp = GI + I_END;
-                #pragma unroll
-                for (int q = 0; q < 4; q++) sp[q] = (first ? 0.0f : sp[q]) + st[q];
-            }
-        }
-        __syncthreads();
-    }
-    for (int row = threadIdx.x; row < MLP_H; row += NT) {
-        float sacc = 0.0f;
-        for (int dd = 0; dd < 7; dd++) sacc += GI[I_W1 + row * G::F + CELLS + dd];
-        GI[I_B1 + row] = sacc;
-    }
-    __syncthreads();
-    float *dst = B.partial + (size_t)blockIdx.x * G::P;
-    const int o_body = NET ? G::O_VF : G::O_PI, o_hw = NET ? G::O_VW : G::O_AW;
-    for (int e = threadIdx.x; e < G::BODY; e += NT) dst[o_body + e] = GI[e];
-    for (int e = threadIdx.x; e < NOUT * MLP_H + NOUT; e += NT) dst[o_hw + e] = GI[I_WH + e];
-    if (threadIdx.x < 4) B.stats[((size_t)blockIdx.x * 2 + NET) * 4 + threadIdx.x] = GI[I_END + threadIdx.x];
+    a2c3_epilogue<S, NET>(img, acc, st, B.partial, B.stats);     // its barriers make ADV visible to the block
     if (NET == 1 && threadIdx.x < 2) {
         double s = 0.0;
         for (int w = 0; w < NWV; w++) s += ADV[2 * w + threadIdx.x];
@@ -541,36 +273,13 @@ template <bool VEC>
 __global__ __launch_bounds__(1024) void k_ppo_apply(PpoApplyCfg c, float *params, float *exp_avg, float *exp_avg_sq, int32_t *step,
                                                     const float *grad, float *norm_out)
 {
-    __shared__ float red[16];
     const int tid = (int)threadIdx.x;
     const int t = *step + 1;
-    // VEC: 16-byte aligned buffers, P <= 1024 x 4 x A2C_APPLY_V -- a thread's float4 pieces stay in registers between the norm and
-    // the step (k_a2c_apply_v4); else the plain strided loop
     const int n4 = VEC ? c.P >> 2 : 0, tail = VEC ? c.P & 3 : 0;
     float4 g[A2C_APPLY_V];
-    float ss = 0.0f, gt = 0.0f;
-    if constexpr (VEC) {
-        #pragma unroll
-        for (int v = 0; v < A2C_APPLY_V; v++) { const int i = tid + v * 1024; g[v] = i < n4 ? ((const float4 *)grad)[i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
-        gt = tid < tail ? grad[4 * n4 + tid] * c.grad_scale : 0.0f;
-        ss = gt * gt;
-        #pragma unroll
-        for (int v = 0; v < A2C_APPLY_V; v++) {
-            g[v].x *= c.grad_scale; g[v].y *= c.grad_scale; g[v].z *= c.grad_scale; g[v].w *= c.grad_scale;
-            ss += (g[v].x * g[v].x + g[v].y * g[v].y) + (g[v].z * g[v].z + g[v].w * g[v].w);
-        }
-    } else {
-        for (int i = tid; i < c.P; i += 1024) { const float gg = grad[i] * c.grad_scale; ss += gg * gg; }
-    }
-    #pragma unroll
-    for (int m = 1; m < 64; m <<= 1) ss += __shfl_xor(ss, m, 64);
-    if ((tid & 63) == 0) red[tid >> 6] = ss;
-    __syncthreads();
-    float tot = 0.0f;
-    #pragma unroll
-    for (int k = 0; k < 16; k++) tot += red[k];
-    const float norm = sqrtf(tot);
-    const float clip = c.max_norm > 0.0f ? fminf(1.0f, c.max_norm / (norm + 1e-6f)) : 1.0f;   // torch.nn.utils.clip_grad_norm_
+    float gt;
+    const ApplyClip nc = apply_clip<VEC>(grad, c.P, c.grad_scale, c.max_norm, g, gt, [] {});
+    const float clip = nc.clip;
     const double bc1 = 1.0 - pow((double)c.beta1, (double)t), bc2 = 1.0 - pow((double)c.beta2, (double)t);
     const float step_size = (float)((double)c.lr / bc1), bc2s = (float)sqrt(bc2);
     const float w1 = (float)(1.0 - (double)c.beta1), w2 = (float)(1.0 - (double)c.beta2);
@@ -610,7 +319,7 @@ __global__ __launch_bounds__(1024) void k_ppo_apply(PpoApplyCfg c, float *params
         }
     }
     if (tid == 0) {
-        if (norm_out) *norm_out = norm;
+        if (norm_out) *norm_out = nc.norm;
         *step = t;
     }
 }

@@ -17,8 +17,11 @@
  *  - `stream` is a hipStream_t passed as void* (NULL = the null stream).
  *  - Return value: 0 on success, a negative EWN_E* code otherwise (never throws,
  *    never aborts).  ewn_strerror() maps a code to text.
- *  - No hidden global state; a call is thread-safe w.r.t. other calls that do
- *    not share buffers.
+ *  - No hidden global state beyond five tuning overrides, each read once per
+ *    process from the environment and selecting only a launch shape or a kernel
+ *    instance: EWN_D3_T, EWN_ROLLOUT_T, EWN_ROLLOUT_SLOTS, EWN_MCTS_GPB and
+ *    EWN_EVAL_NT.  A call is thread-safe w.r.t. other calls that do not share
+ *    buffers.
  *  - Boards are int8, row-major [lane][row][col], value k>0 = TOP_LEFT cube k,
  *    k<0 = BOTTOM_RIGHT cube |k|, 0 = empty (envs/ewn.py:49-58, 94-107).
  *  - Actions are int8 [lane][2] = {chose_larger in {0,1}, direction in {0,1,2}}
@@ -260,7 +263,8 @@ int ewn_step_k_agent(const ewn_config *cfg, const ewn_state *st, int K, const ew
  * (SB3 A2C("MultiInputPolicy", env, policy_kwargs=dict(activation_fn=Tanh)).learn -> collect_rollouts over SubprocVecEnv workers)
  * as one kernel: observation -> features (S*S board cells as floats ++ one_hot(dice_roll - 1), width cube_num + 1 = 7,
  * envs/ewn.py:66-68) -> policy network (SB3's default net_arch: two separate hidden-64-64 tanh bodies, 5 logits for
- * MultiDiscrete([2, 3]) and a scalar value) on the matrix cores in exact fp32 -> Gumbel-max sample -> env step (plain or
+ * MultiDiscrete([2, 3]) and a scalar value) on the bf16 matrix pipe with every operand split into three bf16 parts (fp32 accuracy)
+ * -> Gumbel-max sample -> env step (plain or
  * cfg->shaped: envs/training_ewn.py:43-99) -> opponent reply -> auto-reset.  Served for cube_layer 3, board sizes 5 and 7,
  * opponent RandomAgent or minimax max_depth 1..4 with a (level, count) heuristic image, Philox dice. */
 #define EWN_AGENT_MLP 3     /* agent_kind of ewn_step_k_supported for this path (ewn_step_k itself takes no parameters: use ewn_step_k_policy) */

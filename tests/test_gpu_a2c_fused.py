@@ -113,7 +113,7 @@ def _apply_f64(params, sq, grad, P, world, max_norm, lr=7e-4, alpha=0.99, eps=1e
 
 
 def test_fused_apply_is_clip_plus_rmsprop(ea):
-    """5x5 and 7x7, each on aligned buffers (k_a2c_apply_v4) and on views one float past a 16-byte boundary (the scalar k_a2c_apply);
+    """5x5 and 7x7, each on aligned buffers (k_a2c_apply<true>) and on views one float past a 16-byte boundary (the scalar k_a2c_apply<false>);
     max_grad_norm 0 takes no clipping (the norm is still reported).  Against torch fp32 and float64."""
     for S in (5, 7):
         for offset in (0, 1):

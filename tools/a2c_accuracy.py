@@ -1,5 +1,5 @@
 """How close to exact arithmetic are the policy forward pass and the A2C gradient?  Reference: the same torch model in FLOAT64.
-   python tools/a2c_accuracy.py            (run once per EWN_A2C_KERNEL=3|2|1: the kernel kind is read once per process)
+   python tools/a2c_accuracy.py
 Prints: max |logit - logit64| of ewn_step_k_policy, the relative l2 error of ewn_a2c_grad's gradient against the float64 gradient, and
 the same two numbers for plain fp32 torch (what "fp32 accuracy" means on this problem)."""
 import copy
@@ -57,8 +57,6 @@ g32 = grad_of(model, traj, torch.float32)
 with torch.no_grad():
     l64 = torch.stack([torch.cat(m64(traj["obs_board"][t], traj["obs_dice"][t])[:2], 1) for t in range(K)])
     l32 = torch.stack([torch.cat(model(traj["obs_board"][t], traj["obs_dice"][t])[:2], 1) for t in range(K)])
-kind = os.environ.get("EWN_A2C_KERNEL", "3")
-print("EWN_A2C_KERNEL=%s  (rollout forward: bf16 x 3)" % kind)
 print("  logits   max |engine - f64| %.3e   max |torch fp32 - f64| %.3e" % (float((logits.double() - l64).abs().max()), float((l32.double() - l64).abs().max())))
 print("  gradient |engine - f64| / |f64| %.3e   |torch fp32 - f64| / |f64| %.3e" %
       (float((grad[:-8].double() - g64).norm() / g64.norm()), float((g32.double() - g64).norm() / g64.norm())))
