@@ -26,7 +26,8 @@ EXPORTS = ["ewn_abi_version", "ewn_strerror", "ewn_rng_words", "ewn_step_scratch
            "ewn_predict_mcts", "ewn_step_k", "ewn_step_k_supported", "ewn_predict_minimax_sim", "ewn_lanes_per_game", "ewn_roll_dice",
            "ewn_policy_param_count", "ewn_step_k_policy", "ewn_a2c_scratch_bytes", "ewn_a2c_grad", "ewn_a2c_apply",
            "ewn_ppo_scratch_bytes", "ewn_ppo_prepare", "ewn_ppo_shuffle", "ewn_ppo_grad", "ewn_ppo_apply",
-           "ewn_policy_eval_supported", "ewn_policy_eval", "ewn_step_k_agent_supported", "ewn_step_k_agent"]
+           "ewn_policy_eval_supported", "ewn_policy_eval", "ewn_step_k_agent_supported", "ewn_step_k_agent",
+           "ewn_policy_eval_mcts_supported", "ewn_policy_eval_mcts"]
 AGENT = {"random": 0, "minimax": 1, "sample": 2, "mlp": 3}   # "mlp": the trained policy, through ewn_step_k_policy   # "sample": env.action_space.sample(), all six actions (EWN_AGENT_SAMPLE)
 AGENT_MCTS = 4   # ewn_agent.kind of the MCTS agent (ewn_step_k_agent only; ewn_step_k does not take it)
 
@@ -145,6 +146,8 @@ def load():
         "ewn_policy_eval": (i32, [cfgp, stp, i32, vp, C.POINTER(EwnRolloutOut), vp]),
         "ewn_step_k_agent_supported": (i32, [cfgp, C.POINTER(EwnAgent)]),
         "ewn_step_k_agent": (i32, [cfgp, stp, i32, C.POINTER(EwnAgent), C.POINTER(EwnRolloutOut), vp]),
+        "ewn_policy_eval_mcts_supported": (i32, [cfgp]),
+        "ewn_policy_eval_mcts": (i32, [cfgp, stp, i32, vp, C.POINTER(EwnRolloutOut), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -15,9 +15,10 @@ OBJ = os.path.join(HERE, "lib", "obj")
 # -ffp-contract=off: the fp64 heuristic and expectation sums must round exactly like the
 # reference's Python floats (no FMA contraction); no fast-math anywhere.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC"]
-# per translation unit.  ewn_policy.hip: no SLP vectorisation -- it turns pairs of fp32 operations into packed-fp32 instructions
+# per translation unit.  The units with matrix code (ewn_policy*.hip): no SLP vectorisation -- it turns pairs of fp32 operations into packed-fp32 instructions
 # (v_pk_add_f32 ...), which measured (tools/mfma_probe.hip) do not overlap with the bf16 matrix pipe the way plain VALU work does
-FILE_FLAGS = {"ewn_policy.hip": ["-fno-slp-vectorize"], "ewn_policy_eval.hip": ["-fno-slp-vectorize"]}
+FILE_FLAGS = {"ewn_policy.hip": ["-fno-slp-vectorize"], "ewn_policy_eval.hip": ["-fno-slp-vectorize"],
+              "ewn_policy_eval_mcts.hip": ["-fno-slp-vectorize"]}
 
 
 def stale():

@@ -13,6 +13,7 @@
 #include "ewn_lds.hpp"
 #include "ewn_step_d3.hpp"
 #include "ewn_rollout.hpp"
+#include "ewn_mcts_body.hpp"   // step_agent / step_opponent / lane_auto_reset, MctsRoll, rollout_mcts_body
 
 // ---------------------------------------------------------------- per-lane pieces
 
@@ -32,15 +33,6 @@ EWN_DEV void lane_reset(const Geom &g, const KCfg &c, u32 *rng, int lane, u32 se
     dice = r.first_dice(g.CN); // roll_dice :90-91
 }
 
-// the auto-reset inside a step: next_seed becomes the episode seed (the freed window is rebuilt by k_mt_refill afterwards)
-template <int NW>
-EWN_DEV void lane_auto_reset(const Geom &g, const KCfg &c, u32 *rng, int lane, GState<NW> &s, int &dice, LaneRng &r)
-{
-    r.next_episode(rng, c.N, lane, c.seed_stride, c.key, nullptr);
-    init_state<NW>(g, s);
-    dice = r.first_dice(g.CN);
-}
-
 // Generic step path: right after the step kernel, rebuild the window slots it freed (header field X > 0) and count
 // them ready.  One thread per lane, coalesced header reads, waves without a flagged lane leave at once.
 #define REFILL_BS 64
@@ -57,64 +49,6 @@ __global__ __launch_bounds__(REFILL_BS) void k_mt_refill(u32 *rng, int N, u32 W,
     for (u32 j = 1; j <= x; j++) // the slot freed j resets ago will serve episode e + 3 - j
         mt_window_lds(h.x + (3u - j) * stride, W, sm, t, rng_win_ptr(rng, N, W, lane, (cur + 3u - j) % 3u));
     rng_hdr_ptr(rng, lane)->w = rngf_make(h.w, cur, min(2u, RNGF_READY(h.w) + x), 0u, RNGF_Y(h.w));
-}
-
-struct StepRes { double reward; int term, trunc, info; };
-
-// Agent half of step(): envs/ewn.py:438-458 and training_ewn.py:44-66.
-// Returns true when the opponent must still reply.
-template <int NW>
-EWN_DEV bool step_agent(const Geom &g, const KCfg &c, GState<NW> &s, int &dice, int flag, int dir, LaneRng &r,
-                           int32_t *tol, StepRes &o)
-{
-    o.reward = 0.0; o.term = 0; o.trunc = 0; o.info = EWN_INFO_NONE;
-    const CubeSel cs = select_cubes(s.aliveP, dice);
-    const int k = cube_to_move(cs, flag == 1);
-    const bool valid = k >= 0 && dir >= 0 && dir <= 2 && dir_ok<0>(g, pos_of<0>(s, k), dir);
-    if (!valid) {
-        if (c.shaped) {
-            const int t = *tol - 1;
-            *tol = t;
-            if (t <= 0) { o.reward = -c.reward; o.term = 1; o.trunc = 1; o.info = EWN_INFO_INVALID_PLAYER; }
-            else { o.reward = c.illegal_reward; o.info = EWN_INFO_TOLERANCE; }
-        } else { o.reward = -c.reward; o.term = 1; o.trunc = 1; o.info = EWN_INFO_INVALID_PLAYER; }
-        return false;
-    }
-    apply_move<0, NW>(g, s, k, dir);
-    if (is_win<NW>(g, s)) { o.reward = c.reward; o.term = 1; o.info = EWN_INFO_WON; return false; }
-    dice = r.randint(1, g.CN + 1); // the opponent's dice, :458
-    return true;
-}
-
-// Opponent half: envs/ewn.py:464-486, training_ewn.py:75-99.
-template <int NW>
-EWN_DEV void step_opponent(const Geom &g, const KCfg &c, GState<NW> &s, int &dice, int oflag, int odir, LaneRng &r,
-                              double *prev_score, StepRes &o)
-{
-    const CubeSel cs = select_cubes(s.aliveN, dice);
-    const int k = cube_to_move(cs, oflag == 1);
-    const bool valid = k >= 0 && odir >= 0 && odir <= 2 && dir_ok<1>(g, pos_of<1>(s, k), odir);
-    if (!valid) { o.reward = 0.0; o.term = 1; o.trunc = 1; o.info = EWN_INFO_INVALID_OPP; return; }
-    apply_move<1, NW>(g, s, k, odir);
-    if (is_win<NW>(g, s)) { o.reward = -c.reward; o.term = 1; o.info = EWN_INFO_LOST; return; }
-    dice = r.randint(1, g.CN + 1); // :483
-    if (c.shaped) {
-        const double cur = evaluate<NW>(g, s, EWN_H_HYBRID);
-        o.reward = cur - *prev_score;
-        *prev_score = cur;
-    }
-}
-
-// RandomAgent.predict on the live env (classical_policies/random_policy.py:11-15):
-// uniform index into BOTTOM_RIGHT's legal list, drawn from the lane's own stream.
-template <int NW>
-EWN_DEV void policy_random(const Geom &g, const GState<NW> &s, int dice, LaneRng &r, int &oflag, int &odir)
-{
-    const int n = for_each_legal<1, NW>(g, s, dice, [](int, int, int) { return true; });
-    const int pick = r.randint(0, n);
-    int i = 0;
-    oflag = 0; odir = 0;
-    for_each_legal<1, NW>(g, s, dice, [&](int flag, int, int dir) { if (i == pick) { oflag = flag; odir = dir; } i++; return i <= pick; });
 }
 
 template <int NW, int DEPTH>
@@ -685,18 +619,7 @@ __global__ __launch_bounds__(BS) void k_mcts_rollout_lean(Geom g, int M, int tot
 // and between the two halves of a step the block's 256 lanes regroup into groups of 8..64 lanes that play the playouts of the
 // block's (game, root move) cells out of LDS -- the same generator, the same playout numbering, so the results are those of
 // k_mcts_rollout_lean bit for bit.  Block barriers separate the phases (the games of a block are in lock step).
-EWN_DEV PState pstate_from_gstate(const Geom &g, const GState<1> &c)
-{
-    u32 w[4] = { 0x40404040u, 0x40404040u, 0x40404040u, 0x40404040u };   // every cube off the board (pstate_load's encoding)
-    #pragma unroll
-    for (int k = 0; k < 6; k++) {
-        const u32 cp = (u32)pos_get<1>(c.posP, k), rp = (cp * g.div_magic) >> 16, cn = (u32)pos_get<1>(c.posN, k), rn = (cn * g.div_magic) >> 16;
-        if ((c.aliveP >> k) & 1u) w[k & 1] ^= (0x40u ^ (rp * 8u + (cp - rp * (u32)g.S))) << (8 * (k >> 1));
-        if ((c.aliveN >> k) & 1u) w[2 + (k & 1)] ^= (0x40u ^ (rn * 8u + (cn - rn * (u32)g.S))) << (8 * (k >> 1));
-    }
-    const PState st = { w[0], w[1], w[2], w[3] };
-    return st;
-}
+// (k_rollout_mcts below; pstate_from_gstate, MctsRoll and MR_GPB are in ewn_mcts_body.hpp.)
 
 // ---------------------------------------------------------------- ewn_step_k for the geometries without a table image
 //
@@ -796,16 +719,13 @@ __global__ __launch_bounds__(BS) void k_rollout_generic(Geom g, KCfg c, KState s
     block_copy_out(st.board + (size_t)lane0 * g.cells, lds, nl * g.cells);
 }
 
-struct MctsRoll { int K, total, gl, agent_sample, strd, gpb; };   // strd: bytes per game of the dynamic LDS area (a record, or S*S)
-
 // mr.gpb games per block of BS threads: the rules run one thread per game (the block's first lanes), the playouts on all BS lanes.
 // Not 256 games per block: the playouts are where the time goes, and 65 536 games at 256 per block are 1 024 waves -- ONE per SIMD,
 // half the VALU issue rate and no latency hiding (measured: 767 us per step at MCTS(10 x 5) against 409 for the three-launch step;
 // 426 at 32 games per block).  The block barriers between the phases are what is left of the difference: the three-launch step
 // balances its playouts over the whole chip, this kernel over one block's cells.
-#define MR_GPB 128        // the most games a block takes (LDS arrays); the launcher picks mr.gpb <= MR_GPB (default 64)
-
-// Its twin: rollout_mcts_body below (ewn_step_k_agent's loop, the same phases with an agent of its own, the playout phase factored
+//
+// Its twin: rollout_mcts_body in ewn_mcts_body.hpp (ewn_step_k_agent's loop, the same phases with an agent of its own, the playout phase factored
 // into mcts_playout_phase).  A fix to the state load, the trajectory rows or the write-back here belongs there too.
 __global__ __launch_bounds__(BS) void k_rollout_mcts(Geom g, KCfg c, KState st, MctsRoll mr, RollBuf B)
 {
@@ -898,205 +818,6 @@ __global__ __launch_bounds__(BS) void k_rollout_mcts(Geom g, KCfg c, KState st, 
             int oflag = 0, odir = 0, j = 0;
             for_each_legal<0, 1>(g, cst, dice, [&](int flag, int, int dir) { if (j == best) { oflag = flag; odir = dir; } j++; return j <= best; });
             step_opponent<1>(g, c, s, dice, oflag, odir, r, nullptr, o);
-        }
-        if (active) {
-            ret_acc += o.reward; n_steps++; n_eps += o.term; n_wins += o.info == EWN_INFO_WON ? 1 : 0;
-            if (o.term) { if (c.autoreset) lane_auto_reset<1>(g, c, st.rng, lane, s, dice, r); else frozen = true; }
-        }
-        // ---- this step's trajectory row
-        if (live) {
-            const size_t oo = (size_t)kstep * c.N + lane;
-            if (B.t_action) ((uint16_t *)B.t_action)[oo] = (uint16_t)((uint8_t)aflag | ((uint16_t)(uint8_t)adir << 8));
-            if (B.t_dice) B.t_dice[oo] = (int8_t)dice;
-            if (B.t_reward) B.t_reward[oo] = o.reward;
-            if (B.t_term) B.t_term[oo] = (uint8_t)o.term;
-            if (B.t_trunc) B.t_trunc[oo] = (uint8_t)o.trunc;
-            if (B.t_info) B.t_info[oo] = (uint8_t)o.info;
-        }
-        if (B.t_board) {
-            if (live) encode_board<1>(g, s, lds + tid * g.cells);
-            __syncthreads();
-            block_copy_out(B.t_board + ((size_t)kstep * c.N + lane0) * g.cells, lds, nl * g.cells);
-            __syncthreads();
-        }
-        if (B.t_rec) { // one aligned record per lane-step: board | dice | action | flags | padding (ewn_rollout_out.record)
-            if (live) {
-                int8_t *rec = lds + tid * mr.strd;
-                for (int i = g.cells; i < mr.strd; i++) rec[i] = 0;
-                encode_board<1>(g, s, rec);
-                rec[g.cells] = (int8_t)dice; rec[g.cells + 1] = (int8_t)aflag; rec[g.cells + 2] = (int8_t)adir;
-                rec[g.cells + 3] = (int8_t)o.term; rec[g.cells + 4] = (int8_t)o.trunc; rec[g.cells + 5] = (int8_t)o.info;
-            }
-            __syncthreads();
-            block_copy_out((int8_t *)B.t_rec + ((size_t)kstep * c.N + lane0) * mr.strd, lds, nl * mr.strd);
-            __syncthreads();
-        }
-    }
-    if (live) encode_board<1>(g, s, lds + tid * g.cells);
-    if (live) {
-        if (!frozen0) { *rng_hdr_ptr(st.rng, lane) = r.header(); st.dice[lane] = (int8_t)dice; }
-        st.done[lane] = frozen ? 1 : 0;
-        if (B.ret_sum) B.ret_sum[lane] += ret_acc;
-        if (B.n_steps) B.n_steps[lane] += n_steps;
-        if (B.n_episodes) B.n_episodes[lane] += n_eps;
-        if (B.n_wins) B.n_wins[lane] += n_wins;
-    }
-    __syncthreads();
-    block_copy_out(st.board + (size_t)lane0 * g.cells, lds, nl * g.cells);
-}
-
-// the agent of k_rollout_mcts_agent (ewn_step_k_agent): minimax max_depth / heuristic, or MCTS with `total` playouts per root move in
-// groups of 2^gl lanes on the playout stream of evaluation step t = step_base + kstep: obs_word(lane_offset + lane, 'MCTS', key_t),
-// key_t = key + 0x9E3779B97F4A7C15 * (t + 1) -- what tournament.evaluate's per-step loop passes to predict_mcts
-struct AgentRoll { int depth, heur, total, gl; u32 step_base; u64 key; };
-
-// One flat Monte-Carlo decision (mcts.py:47-69) for every game of the block whose owner thread passes n_root > 0, its start position,
-// dice and playout stream already in pb0 / pdice / pword[tid]: `total` playouts per (game, root move) cell, BOTTOM_RIGHT replying
-// first, a group of 2^gl lanes per cell; a group that has finished its cell takes the next unplayed one (results do not depend on who
-// plays what).  Leaves the wins per root move in wins[tid] (-1: no such move).  Every thread of the block calls it (block barriers).
-EWN_DEV void mcts_playout_phase(const Geom &g, const PlayTab *T, const PState *pb0, const u32 *pword, const int8_t *pdice, int (*wins)[6],
-                                uint16_t *livec, int *nlive_s, int *next_slot, int *nextc, int *myslot, int tid, bool owner, int n_root,
-                                int total, int gl, int tc, int glane, int grp)
-{
-    if (owner) {
-        #pragma unroll
-        for (int i = 0; i < 6; i++) wins[tid][i] = i < n_root ? 0 : -1;
-    }
-    if (tid == 0) { *nlive_s = 0; *next_slot = BS >> gl; }
-    __syncthreads();
-    if (n_root > 0) { const int base = atomicAdd(nlive_s, n_root); for (int i = 0; i < n_root; i++) livec[base + i] = (uint16_t)(tid * 8 + i); }
-    __syncthreads();
-    const int nlive = *nlive_s;
-    int slot = grp;
-    while (slot < nlive) {
-        const int cell = livec[slot], gi = cell >> 3, i = cell & 7;
-        if (glane == 0) nextc[grp] = tc;   // same wave as the lanes that read it: LDS operations of a wave execute in order
-        PState b0 = pb0[gi];
-        int w;
-        if (playout_root_move(T, b0, g.S, pdice[gi], i)) w = glane < total ? (total - glane + tc - 1) >> gl : 0;   // TOP_LEFT has won
-        else w = run_playouts<1>(T, b0, g.S, pword[gi], (u32)(i * total), glane, total, &nextc[grp]);         // BOTTOM_RIGHT replies first
-        for (int off = tc >> 1; off > 0; off >>= 1) w += __shfl_down(w, off, tc);
-        if (glane == 0) { wins[gi][i] = w; myslot[grp] = atomicAdd(next_slot, 1); }
-        __builtin_amdgcn_wave_barrier();
-        slot = myslot[grp];
-        __builtin_amdgcn_wave_barrier();
-    }
-    __syncthreads();
-}
-
-// np.argmax over the root moves' wins (first maximum), then that entry of the legal list of the observation (mcts.py:68)
-EWN_DEV void mcts_pick(const Geom &g, const GState<1> &obs, int dice, const int *w6, int &flag, int &dir)
-{
-    int best = 0, bw = -1;
-    #pragma unroll
-    for (int i = 0; i < 6; i++) { const int w = w6[i]; if (w > bw) { bw = w; best = i; } }
-    int f = 0, d = 0, j = 0;
-    for_each_legal<0, 1>(g, obs, dice, [&](int fl, int, int dr) { if (j == best) { f = fl; d = dr; } j++; return j <= best; });
-    flag = f; dir = d;
-}
-
-// k_rollout_mcts's loop with an agent of its own.  AG: 1 minimax (ar.depth, ar.heur), 2 MCTS (a playout phase over the agent's
-// observation before the agent half).  OPP: 0 RandomAgent, 1 minimax (c.depth, c.heur), 2 MCTS (its playout phase between the two
-// halves).  The minimax searches (AG 1's agent, OPP 1's opponent: one of them per instance) are the table-driven fast_d3 of
-// k_predict_minimax_fast / ewn_step's table path, on the rules thread, from an image of the search's table in LDS (S = board size;
-// 0 = no search, no table).  k_rollout_mcts itself keeps its own text: routed through this body, its RandomAgent / sample instance
-// compiled to different register allocation (129 -> 132 VGPRs), and that instance must stay the code it is.
-template <int AG, int OPP, int S>
-EWN_DEV void rollout_mcts_body(const Geom &g, const KCfg &c, const KState &st, const MctsRoll &mr, const RollBuf &B, const AgentRoll &ar)
-{
-    extern __shared__ __attribute__((aligned(16))) int8_t lds[];   // [MR_GPB][strd]: packed boards in and out, trajectory rows in between
-    __shared__ PlayTab T;
-    __shared__ PState pb0[MR_GPB];
-    __shared__ u32 pword[MR_GPB];
-    __shared__ int8_t pdice[MR_GPB];
-    __shared__ int wins[MR_GPB][6];
-    __shared__ uint16_t livec[MR_GPB * 6];
-    __shared__ int nlive_s, next_slot;
-    __shared__ int nextc[BS / 8], myslot[BS / 8];
-    constexpr int TS = S ? S : 5;
-    [[maybe_unused]] const FastTab<TS> *ft = nullptr;
-    if constexpr (S != 0) {   // LDS-DMA behind the boards area, waited for at the first barrier
-        int8_t *tb = lds + ((mr.gpb * mr.strd + 15) & ~15);
-        tables_to_lds<FAST_TAB_BYTES(TS)>(tb, (const int8_t *)B.tables);
-        ft = (const FastTab<TS> *)tb;
-    }
-    playtab_build(&T, g.S);
-    const int tid = (int)threadIdx.x, lane0 = (int)blockIdx.x * mr.gpb, nl = min(mr.gpb, c.N - lane0), lane = lane0 + tid;
-    const bool owner = tid < mr.gpb, live = owner && lane < c.N;
-    uint4 hdr = make_uint4(0u, 0u, 0u, 0u);
-    int dice = 1;
-    bool frozen = true;
-    if (live) { hdr = *rng_hdr_ptr(st.rng, lane); dice = st.dice[lane]; frozen = st.done[lane] != 0; }
-    const bool frozen0 = frozen;
-    block_copy_in(lds, st.board + (size_t)lane0 * g.cells, nl * g.cells);
-    if constexpr (S != 0) lds_dma_wait();
-    __syncthreads();
-    GState<1> s;
-    decode_board<1>(g, lds + (live ? tid : 0) * g.cells, s);
-    LaneRng r; r.load(c.rng_kind, hdr, rng_win_ptr(st.rng, c.N, c.W, live ? lane : 0, RNGF_CUR(hdr.w)), c.W, c.key);
-    r.begin_kernel();
-    double ret_acc = 0.0;
-    int n_steps = 0, n_eps = 0, n_wins = 0;
-    const int tc = 1 << mr.gl, glane = tid & (tc - 1), grp = tid >> mr.gl;
-    const int atc = 1 << ar.gl, aglane = tid & (atc - 1), agrp = tid >> ar.gl;   // the agent's playout groups (AG 2)
-
-    for (int kstep = 0; kstep < mr.K; kstep++) {
-        const bool active = live && !frozen;
-        StepRes o; o.reward = 0.0; o.term = (live && frozen) ? 1 : 0; o.trunc = 0; o.info = EWN_INFO_NONE;
-        int aflag = 0, adir = 0, n_root = 0;
-        bool reply = false;
-        GState<1> cst = s;
-        if constexpr (AG == 2) {
-            // MctsAgent.predict(env.board, env.dice): the agent's observation as it stands, its root moves, its playout stream
-            int a_root = 0;
-            if (active) {
-                pb0[tid] = pstate_from_gstate(g, s);
-                pdice[tid] = (int8_t)dice;
-                const u64 key_t = ar.key + 0x9E3779B97F4A7C15ull * ((u64)ar.step_base + (u64)kstep + 1ull);
-                pword[tid] = PlayoutRng::obs_word((u32)(c.lane_offset + lane), 0x4D435453u, key_t);
-                a_root = for_each_legal<0, 1>(g, s, dice, [](int, int, int) { return true; });
-            }
-            mcts_playout_phase(g, &T, pb0, pword, pdice, wins, livec, &nlive_s, &next_slot, nextc, myslot, tid, owner, a_root, ar.total,
-                               ar.gl, atc, aglane, agrp);
-            if (active) mcts_pick(g, s, dice, wins[tid], aflag, adir);
-        }
-        if (active) {
-            if constexpr (AG == 1) {   // ExpectiMinimaxAgent.predict on the agent's observation (TOP_LEFT to move): k_predict_minimax_fast
-                aflag = -1; adir = -1;
-                if (ar.heur == EWN_H_TWO_MIN_DIST) fast_d3<TS, true>(ft, s, dice, ar.depth, aflag, adir);
-                else fast_d3<TS, false>(ft, s, dice, ar.depth, aflag, adir);
-            }
-            r.prefetch();
-            r.begin_step();
-            reply = step_agent<1>(g, c, s, dice, aflag, adir, r, nullptr, o);      // envs/ewn.py:438-458
-            if constexpr (OPP == 2) {
-                if (reply) { // MctsAgent.predict's input: the canonical observation (envs/ewn.py:289-296), its root moves, its playout stream
-                    cst = canonicalize<1>(g, s);
-                    pb0[tid] = pstate_from_gstate(g, cst);
-                    pdice[tid] = (int8_t)dice;
-                    pword[tid] = PlayoutRng::obs_word(r.seed_mix() * 0x9E3779B1u + r.draws(), 0x4D435453u, c.key);
-                    n_root = for_each_legal<0, 1>(g, cst, dice, [](int, int, int) { return true; });
-                }
-            } else if (reply) {
-                int oflag = 0, odir = 0;
-                if constexpr (OPP == 0) policy_random<1>(g, s, dice, r, oflag, odir);
-                else {   // the minimax opponent on its canonical observation, as ewn_step's table path searches it
-                    cst = canonicalize<1>(g, s);
-                    if (c.heur == EWN_H_TWO_MIN_DIST) fast_d3<TS, true>(ft, cst, dice, c.depth, oflag, odir);
-                    else fast_d3<TS, false>(ft, cst, dice, c.depth, oflag, odir);
-                }
-                step_opponent<1>(g, c, s, dice, oflag, odir, r, nullptr, o);              // envs/ewn.py:464-486
-            }
-        }
-        if constexpr (OPP == 2) {
-            // ---- the playouts of the block's (game, root move) cells, then the opponent's half (envs/ewn.py:464-486)
-            mcts_playout_phase(g, &T, pb0, pword, pdice, wins, livec, &nlive_s, &next_slot, nextc, myslot, tid, owner, n_root, mr.total,
-                               mr.gl, tc, glane, grp);
-            if (reply) {
-                int oflag = 0, odir = 0;
-                mcts_pick(g, cst, dice, wins[tid], oflag, odir);
-                step_opponent<1>(g, c, s, dice, oflag, odir, r, nullptr, o);
-            }
         }
         if (active) {
             ret_acc += o.reward; n_steps++; n_eps += o.term; n_wins += o.info == EWN_INFO_WON ? 1 : 0;

@@ -36,7 +36,8 @@ struct RollCfg {
 struct RollBuf {
     int8_t *board; int8_t *dice; uint8_t *done; u32 *rng;
     const void *tables;        // table image of the opponent's search (ewn_fast.hpp)
-    const void *agent_tables;  // table image of the agent's search; == tables when both use the same image (or the agent is random)
+    const void *agent_tables;  // table image of the agent's search; == tables when both use the same image (or the agent is random).
+                               // rollout_mcts_body<3, ., .> (ewn_mcts_body.hpp): the agent's image is the actor-critic's flat fp32 parameters
     // trajectory [K][N]..., each may be NULL
     int8_t *t_board; int8_t *t_dice; int8_t *t_action; double *t_reward; uint8_t *t_term; uint8_t *t_trunc; uint8_t *t_info;
     uint8_t *t_rec;            // [K][N][EWN_TRAJ_RECORD_STRIDE(S)] one aligned record per lane-step (ewn_rollout_out.record), or NULL

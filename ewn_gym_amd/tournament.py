@@ -69,7 +69,8 @@ def evaluate(agent, opponent, num=1024, board_size=5, cube_layer=3, rng="mt19937
     Returns per-episode scores (float64 tensor), episode lengths and summary statistics.
     When both sides are engine policies the table-driven kernels cover (RandomAgent, 'hybrid' minimax; cube_layer 3) the whole
     predict/step loop runs on the device, `chunk` steps per launch (ewn_step_k); an MCTS agent, or a minimax agent against MCTS, likewise
-    through ewn_step_k_agent (cube_layer 3, boards 5..8); an "mlp" agent wherever ewn_policy_eval serves the opponent and geometry;
+    through ewn_step_k_agent (cube_layer 3, boards 5..8); an "mlp" agent wherever ewn_policy_eval (RandomAgent, minimax) or
+    ewn_policy_eval_mcts (the MCTS opponent) serves the opponent and geometry;
     otherwise one policy evaluation + one ewn_step per step (use_rollout=False forces that loop).  The engines give the per-step loop's
     per-episode results, the MCTS agent's included: its playouts at step t use key + 0x9E3779B97F4A7C15 * (t + 1) either way
     ("engine" in the result says which one ran)."""
@@ -102,14 +103,18 @@ def evaluate(agent, opponent, num=1024, board_size=5, cube_layer=3, rng="mt19937
         if getattr(model, "S", board_size) != board_size:
             raise ValueError("evaluate: the model plays %dx%d boards, the evaluation is on %dx%d" % (model.S, model.S, board_size, board_size))
         params = flat_policy_params(model).to(env.device)
-        if use_rollout and env.supports_policy_eval() and params.numel() == env.policy_param_count():
+        # the engine's call for this opponent (the MCTS opponent's playout stream is keyed by the lane's RNG header, so the chunking
+        # changes nothing there either), or None: the per-step loop below
+        engine = ("ewn_policy_eval" if env.supports_policy_eval() else
+                  "ewn_policy_eval_mcts" if env.supports_policy_eval_mcts() else None)
+        if use_rollout and engine is not None and params.numel() == env.policy_param_count():
             totals = env.alloc_totals()
             for _ in range(0, max_steps, chunk):
                 env.eval_policy(chunk, params, totals)
                 if bool((env.done != 0).all()):
                     break
             env.check_rng()
-            return _totals_result(totals, num, "ewn_policy_eval")
+            return _totals_result(totals, num, engine)
         policy = lambda b, d, t: model.act(b, d, deterministic=True)[0]   # noqa: E731
     else:
         policy = _policy(agent, cube_layer, key)

@@ -39,6 +39,9 @@ def main():
     ap.add_argument("--timesteps_per_epoch", "-t", type=int, default=200000)
     ap.add_argument("--eval_episode_num", "-ee", type=int, default=256)
     ap.add_argument("--eval_max_depth", type=int, default=5)
+    ap.add_argument("--eval_opponent", default="minimax", choices=["minimax", "mcts", "random"],
+                    help="opponent of the per-epoch evaluation (train.py evaluates against minimax; eval_A2C.py takes any of the three)")
+    ap.add_argument("--eval_num_simulations", type=int, default=10, help="--eval_opponent mcts: simulations per root move (x 5 env copies)")
     ap.add_argument("--board_size", type=int, default=5)
     ap.add_argument("--cube_layer", type=int, default=3)
     ap.add_argument("--opponent_policy", "-op", default="random")
@@ -82,12 +85,13 @@ def main():
     best = trainer.best_score   # -1 for a fresh run; a resumed one keeps its best model until it is beaten
     for epoch in range(a.epoch_num):
         stats = trainer.learn(a.timesteps_per_epoch // world)   # dict of the last update's statistics
-        # train.py:73-81: evaluate on the UN-shaped env against minimax(depth 5), seeds 0..n-1, deterministic actions
-        # (the model's argmax in the engine, ewn_policy_eval, where it serves the configuration; else per step)
+        # train.py:73-81: evaluate on the UN-shaped env against minimax(depth 5) (or --eval_opponent), seeds 0..n-1, deterministic
+        # actions (the model's argmax in the engine, ewn_policy_eval / ewn_policy_eval_mcts, where it serves the configuration; else per step)
         n_eval = a.eval_episode_num // world
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        r = evaluate({"kind": "mlp", "model": trainer.model}, {"kind": "minimax", "max_depth": a.eval_max_depth}, num=n_eval,
+        eval_opp = {"kind": a.eval_opponent, "max_depth": a.eval_max_depth, "num_simulations": a.eval_num_simulations}
+        r = evaluate({"kind": "mlp", "model": trainer.model}, eval_opp, num=n_eval,
                      board_size=a.board_size, cube_layer=a.cube_layer, rng="mt19937", seed_offset=rank * n_eval)
         eval_s = time.perf_counter() - t0    # evaluate() ends on a host sync (its win count)
         c = all_reduce_counters(torch.tensor([r["wins"], r["episodes"]], dtype=torch.int64, device="cuda"))

@@ -294,11 +294,16 @@ class VecEWN:
     def supports_policy_eval(self):
         return self.tables is not None and self.lib.ewn_policy_eval_supported(C.byref(self.cfg)) == 1
 
+    def supports_policy_eval_mcts(self):
+        """the same against this env's flat Monte-Carlo opponent (ewn_policy_eval_mcts; no table image needed)"""
+        return self.lib.ewn_policy_eval_mcts_supported(C.byref(self.cfg)) == 1
+
     def eval_policy(self, K, params, totals, action=None):
         """Play K steps of every lane in one launch, the agent playing the argmax of the actor-critic whose flat fp32 parameter vector
         is `params` (a2c.ActorCritic.parameters() order), on the un-shaped env without auto-reset.  totals: dict from alloc_totals
         (required, ADDED to); action: optional int8 [>= K, N, 2] (row k of a lane is written only if the lane played step k).
-        Buffers of the wrong shape, dtype or layout raise ValueError before anything is launched."""
+        Buffers of the wrong shape, dtype or layout raise ValueError before anything is launched.  An env whose opponent is MCTS is
+        served by ewn_policy_eval_mcts, every other by ewn_policy_eval: the same arguments, the same contract."""
         N = self.N
         if not (isinstance(params, torch.Tensor) and params.dtype == torch.float32 and params.is_cuda and params.is_contiguous()
                 and params.dim() == 1 and params.numel() == self.policy_param_count()):
@@ -318,8 +323,12 @@ class VecEWN:
                 K, N, _describe(action)))
         out = EwnRolloutOut(None, None, _ptr(action), None, None, None, None, _ptr(totals["return_sum"]), _ptr(totals["n_steps"]),
                             _ptr(totals["n_episodes"]), _ptr(totals["n_wins"]), None)
-        check(self.lib.ewn_policy_eval(C.byref(self.cfg), C.byref(self._st), int(K), _ptr(params), C.byref(out), _stream()),
-              "ewn_policy_eval")
+        if self.cfg.opponent_kind == OPP["mcts"]:
+            check(self.lib.ewn_policy_eval_mcts(C.byref(self.cfg), C.byref(self._st), int(K), _ptr(params), C.byref(out), _stream()),
+                  "ewn_policy_eval_mcts")
+        else:
+            check(self.lib.ewn_policy_eval(C.byref(self.cfg), C.byref(self._st), int(K), _ptr(params), C.byref(out), _stream()),
+                  "ewn_policy_eval")
         return self.board, self.dice
 
     # -- K env steps per launch with an MCTS agent, or a minimax agent against the MCTS opponent (ewn_step_k_agent; eval_pairs.py:10-35)

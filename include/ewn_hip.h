@@ -296,7 +296,8 @@ int ewn_step_k_policy(const ewn_config *cfg, const ewn_state *st, int K, const e
  * one episode per lane, against RandomAgent or minimax max_depth 1..6 ('hybrid', 'min_dist', 'attk'; max_depth 5 / 6 through the
  * closed-form search), on MT19937-compat or Philox dice; cube_layer 3, board sizes 5 and 7.  The same transitions as the agent's
  * argmax fed to ewn_step step by step.  Not served ('two_min_dist', 'sim_winrate', MCTS opponents, shaped or auto-resetting envs,
- * other geometries): ewn_policy_eval returns EWN_EUNSUPPORTED.  ewn_step_k_policy / EWN_AGENT_MLP stay as documented above. */
+ * other geometries): ewn_policy_eval returns EWN_EUNSUPPORTED.  ewn_step_k_policy / EWN_AGENT_MLP stay as documented above.
+ * The MCTS opponent has a call of its own: ewn_policy_eval_mcts (below). */
 /* 1 if ewn_policy_eval serves cfg, 0 if not, < 0 for an invalid cfg; decided on the host */
 int ewn_policy_eval_supported(const ewn_config *cfg);
 /* K >= 1 steps of every lane, the agent = argmax of the actor-critic `params` (ewn_policy.params layout); un-shaped, no auto-reset.
@@ -306,6 +307,19 @@ int ewn_policy_eval_supported(const ewn_config *cfg);
  * stepped, so a caller loops launches until ewn_state.done is set everywhere.  The MT19937-compat overflow flag is kept in the lane's
  * RNG header as ewn_step keeps it. */
 int ewn_policy_eval(const ewn_config *cfg, const ewn_state *st, int K, const float *params, const ewn_rollout_out *out, void *stream);
+
+/* ---- ... against the flat Monte-Carlo opponent (eval_A2C.py --opponent_policy mcts): opponent_kind EWN_OPP_MCTS, cube_layer 3, board
+ * sizes 5 and 7, MT19937-compat or Philox dice, un-shaped, no auto-reset; everything else well-formed: EWN_EUNSUPPORTED, unlaunched.
+ * The same transitions as the agent's argmax fed to ewn_step step by step: the opponent's playout stream is the one ewn_step and
+ * ewn_step_k use (keyed by the lane's RNG header, not by a step index, so where a caller cuts its launches changes nothing). */
+/* 1 if ewn_policy_eval_mcts serves cfg, 0 if not, < 0 for an invalid cfg; decided on the host */
+int ewn_policy_eval_mcts_supported(const ewn_config *cfg);
+/* ewn_policy_eval's contract with the flat Monte-Carlo opponent of cfg (num_simulations x num_env_copies playouts per
+ * root move): K >= 1 steps of every lane, agent = argmax of the actor-critic `params`, un-shaped, no auto-reset, one
+ * launch, no scratch, ewn_state.tables not needed.  out: the four totals required (ADDED to), out->action optional
+ * (row k of lane n written only if the lane played step k), every other pointer NULL (EWN_EINVAL). */
+int ewn_policy_eval_mcts(const ewn_config *cfg, const ewn_state *st, int K, const float *params,
+                         const ewn_rollout_out *out, void *stream);
 
 /* ---- the A2C update on the records of ewn_step_k_policy: stable_baselines3 A2C.train as train.py:35-63, 148 configures it ----
  * (n-step returns = GAE with lambda 1, no advantage normalisation; loss = policy gradient + vf_coef * MSE(returns, values) +
