@@ -27,7 +27,8 @@ EXPORTS = ["ewn_abi_version", "ewn_strerror", "ewn_rng_words", "ewn_step_scratch
            "ewn_policy_param_count", "ewn_step_k_policy", "ewn_a2c_scratch_bytes", "ewn_a2c_grad", "ewn_a2c_apply",
            "ewn_ppo_scratch_bytes", "ewn_ppo_prepare", "ewn_ppo_shuffle", "ewn_ppo_grad", "ewn_ppo_apply",
            "ewn_policy_eval_supported", "ewn_policy_eval", "ewn_step_k_agent_supported", "ewn_step_k_agent",
-           "ewn_policy_eval_mcts_supported", "ewn_policy_eval_mcts"]
+           "ewn_policy_eval_mcts_supported", "ewn_policy_eval_mcts",
+           "ewn_step_k_selfplay_supported", "ewn_step_k_selfplay", "ewn_policy_eval_vs_supported", "ewn_policy_eval_vs"]
 AGENT = {"random": 0, "minimax": 1, "sample": 2, "mlp": 3}   # "mlp": the trained policy, through ewn_step_k_policy   # "sample": env.action_space.sample(), all six actions (EWN_AGENT_SAMPLE)
 AGENT_MCTS = 4   # ewn_agent.kind of the MCTS agent (ewn_step_k_agent only; ewn_step_k does not take it)
 
@@ -70,6 +71,10 @@ class EwnAgent(C.Structure):  # struct ewn_agent (ewn_step_k_agent)
 class EwnPolicy(C.Structure):  # struct ewn_policy
     _fields_ = [("params", C.c_void_p), ("deterministic", C.c_int32), ("record_initial_obs", C.c_int32), ("noise_key", C.c_uint64),
                 ("logits", C.c_void_p), ("value", C.c_void_p), ("noise", C.c_void_p)]
+
+
+class EwnOpponentPolicy(C.Structure):  # struct ewn_opponent_policy (ewn_step_k_selfplay, ewn_policy_eval_vs)
+    _fields_ = [("params", C.c_void_p), ("deterministic", C.c_int32), ("noise_key", C.c_uint64), ("action", C.c_void_p)]
 
 
 class EwnA2cHyper(C.Structure):  # struct ewn_a2c_hyper
@@ -148,6 +153,10 @@ def load():
         "ewn_step_k_agent": (i32, [cfgp, stp, i32, C.POINTER(EwnAgent), C.POINTER(EwnRolloutOut), vp]),
         "ewn_policy_eval_mcts_supported": (i32, [cfgp]),
         "ewn_policy_eval_mcts": (i32, [cfgp, stp, i32, vp, C.POINTER(EwnRolloutOut), vp]),
+        "ewn_step_k_selfplay_supported": (i32, [cfgp, C.POINTER(EwnPolicy)]),
+        "ewn_step_k_selfplay": (i32, [cfgp, stp, i32, C.POINTER(EwnPolicy), C.POINTER(EwnOpponentPolicy), C.POINTER(EwnRolloutOut), vp]),
+        "ewn_policy_eval_vs_supported": (i32, [cfgp]),
+        "ewn_policy_eval_vs": (i32, [cfgp, stp, i32, vp, C.POINTER(EwnOpponentPolicy), C.POINTER(EwnRolloutOut), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -284,7 +284,74 @@ class A2CTrainer:
         self._warm = False
 
 
-class FusedA2CTrainer:
+def opponent_refresh_due(updates_done, every):
+    """Self-play schedule: the frozen opponent takes the live parameters after update number `updates_done` (1-based) when that is a
+    multiple of `every`; every < 1: never (it keeps the parameters it started with)."""
+    return every >= 1 and updates_done >= 1 and updates_done % every == 0
+
+
+class PolicyOpponent:
+    """The fused trainers' `opponent=`: None (the env's own opponent), "self" (a frozen copy of the live parameters, refreshed every
+    `opponent_update_every` updates), a checkpoint path or an ActorCritic (loaded once, never refreshed).  The opponent's parameters are
+    a second flat fp32 device vector the rollout kernel reads (ewn_step_k_selfplay); the gradient kernels read the agent's records only.
+    The reference's opponent plays the ARGMAX (opponent_action passes deterministic=True, envs/ewn.py:294-295): that is
+    opponent_deterministic=True here.  The trainers' default samples the opponent's action instead (opponent_deterministic=False: a frozen
+    argmax opponent is one fixed line of play per dice sequence), which is NOT the reference's mode; the evaluation plays the argmax.
+    The `predict` arithmetic itself (stable_baselines3) is not vendored -- parity unpinned, like the agent's."""
+
+    opp_params = None
+
+    def _init_opponent(self, opponent, opponent_update_every, opponent_deterministic, seed):
+        self.opponent_update_every, self.opponent_deterministic = int(opponent_update_every), bool(opponent_deterministic)
+        self.n_updates = 0
+        self._opp_refresh = False
+        self.opp_noise_key = ((0 if seed is None else int(seed)) * 0xD1B54A32D192ED03 + 0x4F5050) & 0xFFFFFFFFFFFFFFFF
+        if opponent is None:
+            return
+        if not self.env.supports_selfplay_rollout():
+            from . import _lib
+            raise _lib.EwnError("this env configuration has no self-play rollout kernel (ewn_step_k_selfplay: Philox dice, cube_layer 3, "
+                                "5x5 / 7x7)")
+        if isinstance(opponent, str) and opponent == "self":
+            self.opp_params = self.params.clone()
+            self._opp_refresh = True
+        else:
+            if isinstance(opponent, str):
+                from .tournament import load_policy
+                opponent = load_policy(opponent, self.env.S, self.env.L, device=self.device)
+            flat = opponent.flat_parameters().to(self.device)
+            if flat.numel() != self.params.numel():
+                raise ValueError("opponent: %d parameters, this env's actor-critic has %d" % (flat.numel(), self.params.numel()))
+            self.opp_params = flat.clone()
+
+    def _opponent_kwargs(self):
+        if self.opp_params is None:
+            return {}
+        return dict(opponent_params=self.opp_params, opponent_deterministic=self.opponent_deterministic, opponent_noise_key=self.opp_noise_key)
+
+    def _opponent_loaded(self, sd):
+        """after load(): the frozen copy of a self-play run is the checkpoint's (its own if saved, else the resumed parameters), and
+        the refresh schedule goes on where it stopped"""
+        self.n_updates = int(sd.get("n_updates", 0))
+        if self._opp_refresh:
+            self.opp_params.copy_(sd["opp_params"] if "opp_params" in sd else self.params)
+
+    def _opponent_state(self):
+        sd = {"n_updates": self.n_updates}
+        if self._opp_refresh:
+            sd["opp_params"] = self.opp_params
+        return sd
+
+    def _after_update(self):
+        """count the update; when the schedule says so, a device-to-device copy on the current stream (behind the update's kernels)"""
+        self.n_updates += 1
+        if self._opp_refresh and opponent_refresh_due(self.n_updates, self.opponent_update_every):
+            self.opp_params.copy_(self.params)
+            return True
+        return False
+
+
+class FusedA2CTrainer(PolicyOpponent):
     """A2C with the whole loop in the engine (BASELINE config 4): the n-step rollout is ONE kernel (ewn_step_k_policy: policy
     network on the matrix cores, Gumbel-max sampling, shaped env step, opponent search, records), the update three more
     (ewn_a2c_grad: value pass, policy pass, reduction; ewn_a2c_apply: global-norm clip + RMSprop) -- no torch operator on the
@@ -296,10 +363,10 @@ class FusedA2CTrainer:
     best_score = -1.0
 
     def __init__(self, env, n_steps=5, learning_rate=7e-4, gamma=0.99, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, seed=None,
-                 rms_alpha=0.99, rms_eps=1e-5, use_graph=True):
+                 rms_alpha=0.99, rms_eps=1e-5, use_graph=True, opponent=None, opponent_update_every=100, opponent_deterministic=False):
         import ctypes as C
         from . import _lib
-        if not env.supports_policy_rollout():
+        if opponent is None and not env.supports_policy_rollout():
             raise _lib.EwnError("this env configuration has no policy-driven rollout kernel (ewn_step_k_policy): use A2CTrainer")
         self.env, self.lib, self.C = env, env.lib, C
         self.device = env.board.device
@@ -313,6 +380,7 @@ class FusedA2CTrainer:
             off += p.numel()
         assert off == env.policy_param_count()
         self._sync_parameters()
+        self._init_opponent(opponent, opponent_update_every, opponent_deterministic, seed)
         self.sq_avg = torch.zeros_like(self.params)
         self.grad = torch.zeros(self.params.numel() + 8, dtype=torch.float32, device=self.device)
         self.grad_norm = torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -341,7 +409,7 @@ class FusedA2CTrainer:
         from ._lib import check
         from .vec_env import _ptr, _stream
         C, env = self.C, self.env
-        env.rollout_policy(self.n_steps, self.params, traj=self.traj, noise_key=self.noise_key)
+        env.rollout_policy(self.n_steps, self.params, traj=self.traj, noise_key=self.noise_key, **self._opponent_kwargs())
         check(self.lib.ewn_a2c_grad(C.byref(env.cfg), self.n_steps, _ptr(self.traj["record"]), _ptr(self.traj["reward"]), _ptr(self.params),
                                     C.byref(self.hyper), _ptr(self.grad), _ptr(self.scratch), _stream()), "ewn_a2c_grad")
         if self.world > 1 or self.force_collective:   # the one collective of the training path: the flat gradient (52 KB), summed; apply divides by the world size
@@ -361,6 +429,7 @@ class FusedA2CTrainer:
         else:
             self._launch()
             self._warm = True
+        self._after_update()
         self.num_timesteps += self.n_steps * self.env.N
         return self.grad
 
@@ -383,7 +452,7 @@ class FusedA2CTrainer:
 
     def save(self, path):
         torch.save({"algorithm": self.algorithm, "fused": True, "params": self.params, "sq_avg": self.sq_avg,
-                    "num_timesteps": self.num_timesteps, "best_score": float(self.best_score)}, path)
+                    "num_timesteps": self.num_timesteps, "best_score": float(self.best_score), **self._opponent_state()}, path)
 
     def load(self, path):
         sd = torch.load(path, map_location=self.device, weights_only=True)
@@ -393,4 +462,5 @@ class FusedA2CTrainer:
         self.sq_avg.copy_(sd["sq_avg"])
         self.num_timesteps = sd["num_timesteps"]
         self.best_score = float(sd.get("best_score", -1.0))
+        self._opponent_loaded(sd)
 

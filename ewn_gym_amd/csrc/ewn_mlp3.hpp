@@ -126,6 +126,18 @@ EWN_DEV u32x4 mlp3_bytes_operand(u32 lo, u32 hi)
     }
     return o;
 }
+// the same of the NEGATED bytes (the opponent's view of a board, envs/ewn.py:294); an empty cell stays +0
+EWN_DEV u32x4 mlp3_bytes_operand_neg(u32 lo, u32 hi)
+{
+    const u32 w[2] = { lo, hi };
+    u32x4 o;
+    #pragma unroll
+    for (int d = 0; d < 4; d++) {
+        const float f0 = (float)-(int)(int8_t)((w[d >> 1] >> (16 * (d & 1))) & 0xFFu), f1 = (float)-(int)(int8_t)((w[d >> 1] >> (16 * (d & 1) + 8)) & 0xFFu);
+        o[d] = mlp3_pack(__float_as_uint(f0), __float_as_uint(f1));
+    }
+    return o;
+}
 // feature `first + q` (q = 0 .. 7 are this operand's slots) set to 1.0 when q == hot
 EWN_DEV u32x4 mlp3_onehot(u32x4 o, int hot)
 {

@@ -22,7 +22,7 @@ engine: ewn_step_k_policy + ewn_ppo_prepare / _shuffle / _grad / _apply, one hip
 import torch
 import torch.nn as nn
 
-from .a2c import A2CTrainer, all_reduce_gradients, n_step_returns
+from .a2c import A2CTrainer, PolicyOpponent, all_reduce_gradients, n_step_returns
 
 
 class PPOTrainer(A2CTrainer):
@@ -85,7 +85,7 @@ class PPOTrainer(A2CTrainer):
         return stats
 
 
-class FusedPPOTrainer:
+class FusedPPOTrainer(PolicyOpponent):
     """PPOTrainer's update with the whole loop in the engine: the n-step rollout is ONE kernel (ewn_step_k_policy), then
     ewn_ppo_prepare (behaviour-policy log-probabilities, values, GAE advantages and returns of every sample), ewn_ppo_shuffle (every
     epoch's minibatch order, on the device) and per minibatch ewn_ppo_grad (value pass, policy pass, reduction) + ewn_ppo_apply
@@ -98,12 +98,13 @@ class FusedPPOTrainer:
     best_score = -1.0
 
     def __init__(self, env, n_steps=32, batch_size=None, n_epochs=10, learning_rate=3e-4, gamma=0.99, gae_lambda=0.95, clip_range=0.2,
-                 normalize_advantage=True, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, seed=None, use_graph=True):
+                 normalize_advantage=True, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, seed=None, use_graph=True, opponent=None,
+                 opponent_update_every=100, opponent_deterministic=False):
         import ctypes as C
         import torch.distributed as dist
         from . import _lib
         from .a2c import ActorCritic
-        if not env.supports_policy_rollout():
+        if opponent is None and not env.supports_policy_rollout():
             raise _lib.EwnError("this env configuration has no policy-driven rollout kernel (ewn_step_k_policy): use PPOTrainer")
         self.env, self.lib, self.C = env, env.lib, C
         self.device = env.board.device
@@ -117,6 +118,7 @@ class FusedPPOTrainer:
             off += p.numel()
         assert off == env.policy_param_count()
         self._sync_parameters()
+        self._init_opponent(opponent, opponent_update_every, opponent_deterministic, seed)
         self.exp_avg = torch.zeros_like(self.params)
         self.exp_avg_sq = torch.zeros_like(self.params)
         self.step = torch.zeros(1, dtype=torch.int32, device=self.device)   # Adam steps taken; also keys the shuffle
@@ -162,7 +164,7 @@ class FusedPPOTrainer:
         K, total, B = self.n_steps, self.n_steps * env.N, self.batch_size
         cfg, hp = C.byref(env.cfg), C.byref(self.hyper)
         rec, params, samples, grad, scratch = _ptr(self.traj["record"]), _ptr(self.params), _ptr(self.samples), _ptr(self.grad), _ptr(self.scratch)
-        env.rollout_policy(K, self.params, traj=self.traj, noise_key=self.noise_key)
+        env.rollout_policy(K, self.params, traj=self.traj, noise_key=self.noise_key, **self._opponent_kwargs())
         check(lib.ewn_ppo_prepare(cfg, K, rec, _ptr(self.traj["reward"]), params, hp, samples, _stream()), "ewn_ppo_prepare")
         check(lib.ewn_ppo_shuffle(total, self.n_epochs, self.shuffle_key, _ptr(self.step), _ptr(self.perm), _stream()), "ewn_ppo_shuffle")
         base = self.perm.data_ptr()
@@ -187,6 +189,7 @@ class FusedPPOTrainer:
         else:
             self._launch()
             self._warm = True
+        self._after_update()
         self.num_timesteps += self.n_steps * self.env.N
         return self.grad
 
@@ -211,7 +214,7 @@ class FusedPPOTrainer:
     def save(self, path):
         torch.save({"algorithm": self.algorithm, "fused": True, "params": self.params, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,
                     "step": self.step, "noise_key": self.noise_key, "shuffle_key": self.shuffle_key, "num_timesteps": self.num_timesteps,
-                    "best_score": float(self.best_score)}, path)
+                    "best_score": float(self.best_score), **self._opponent_state()}, path)
 
     def load(self, path):
         """a checkpoint of this trainer, or of PPOTrainer (its module state and Adam state mapped onto the flat vectors)"""
@@ -240,3 +243,4 @@ class FusedPPOTrainer:
             self.step.fill_(step)
         self.num_timesteps = sd["num_timesteps"]
         self.best_score = float(sd.get("best_score", -1.0))
+        self._opponent_loaded(sd)

@@ -71,9 +71,13 @@ def evaluate(agent, opponent, num=1024, board_size=5, cube_layer=3, rng="mt19937
     predict/step loop runs on the device, `chunk` steps per launch (ewn_step_k); an MCTS agent, or a minimax agent against MCTS, likewise
     through ewn_step_k_agent (cube_layer 3, boards 5..8); an "mlp" agent wherever ewn_policy_eval (RandomAgent, minimax) or
     ewn_policy_eval_mcts (the MCTS opponent) serves the opponent and geometry;
+    an "mlp" agent against an "mlp" opponent ({"kind": "mlp", "model": ...}: the opponent model's argmax on its canonical view)
+    through ewn_policy_eval_vs, the only path for a model opponent (no other agent kind plays one);
     otherwise one policy evaluation + one ewn_step per step (use_rollout=False forces that loop).  The engines give the per-step loop's
     per-episode results, the MCTS agent's included: its playouts at step t use key + 0x9E3779B97F4A7C15 * (t + 1) either way
     ("engine" in the result says which one ran)."""
+    if opponent["kind"] == "mlp":
+        return _evaluate_vs_model(agent, opponent, num, board_size, cube_layer, rng, seed_offset, key, max_steps, chunk)
     env = VecEWN(num, board_size=board_size, cube_layer=cube_layer, opponent_policy=opponent["kind"],
                  max_depth=opponent.get("max_depth", 3), heuristic=opponent.get("heuristic", "hybrid"),
                  num_simulations=opponent.get("num_simulations", 10), num_env_copies=opponent.get("num_env_copies", 5),
@@ -136,6 +140,29 @@ def evaluate(agent, opponent, num=1024, board_size=5, cube_layer=3, rng="mt19937
             "ci95": [lo, hi], "avg_score": float(score.mean().item()), "avg_length": float(length.float().mean().item())}
 
 
+def _evaluate_vs_model(agent, opponent, num, board_size, cube_layer, rng, seed_offset, key, max_steps, chunk):
+    """model against model: ewn_policy_eval_vs, both sides deterministic.  There is no per-step path for a model opponent (ewn_step has
+    none), so anything the engine does not serve raises."""
+    if not (isinstance(agent, dict) and agent.get("kind") == "mlp"):
+        raise ValueError("evaluate: a model opponent ({'kind': 'mlp'}) is played by a model agent only (ewn_policy_eval_vs)")
+    for side in (agent, opponent):
+        if getattr(side["model"], "S", board_size) != board_size:
+            raise ValueError("evaluate: a model plays %dx%d boards, the evaluation is on %dx%d" % (side["model"].S, side["model"].S, board_size, board_size))
+    env = VecEWN(num, board_size=board_size, cube_layer=cube_layer, opponent_policy="random", rng=rng, autoreset=False,
+                 philox_key=key ^ 0x5DEECE66D)
+    if not env.supports_policy_eval_vs():
+        raise ValueError("evaluate: ewn_policy_eval_vs does not serve %dx%d boards with cube_layer %d" % (board_size, board_size, cube_layer))
+    env.reset(seeds=torch.arange(seed_offset, seed_offset + num, dtype=torch.int64).to(torch.int32))
+    params, opp = flat_policy_params(agent["model"]).to(env.device), flat_policy_params(opponent["model"]).to(env.device)
+    totals = env.alloc_totals()
+    for _ in range(0, max_steps, chunk):
+        env.eval_policy(chunk, params, totals, opponent_params=opp)
+        if bool((env.done != 0).all()):
+            break
+    env.check_rng()
+    return _totals_result(totals, num, "ewn_policy_eval_vs")
+
+
 def tournament(names=("random", "minimax", "mcts"), num=1024, max_depth=5, num_simulations=10, num_env_copies=5,
                board_size=5, cube_layer=3, heuristic="hybrid", rng="mt19937"):
     """eval_pairs.py:10-35: every (agent, opponent) pair, 1024 episodes, depth 5, 10 simulations by default."""
@@ -186,6 +213,7 @@ def main():
                                              "trained policy against each listed opponent (counterpart of eval_A2C.py)")
     ap.add_argument("--agents", nargs="+", default=["random", "minimax", "mcts"])
     ap.add_argument("--model", default=None, help="checkpoint (best.pt) of any of the trainers: evaluate its deterministic policy")
+    ap.add_argument("--opponent_model", default=None, help="with --model: a second checkpoint that plays the opponent (its argmax)")
     ap.add_argument("--num", type=int, default=1024)
     ap.add_argument("--max_depth", type=int, default=5)
     ap.add_argument("--heuristic", default="hybrid")
@@ -195,7 +223,14 @@ def main():
     ap.add_argument("--cube_layer", type=int, default=3)
     ap.add_argument("--rng", default="mt19937")
     a = ap.parse_args()
-    if a.model is not None:
+    if a.opponent_model is not None:
+        if a.model is None:
+            ap.error("--opponent_model needs --model")
+        r = evaluate({"kind": "mlp", "model": load_policy(a.model, a.board_size, a.cube_layer)},
+                     {"kind": "mlp", "model": load_policy(a.opponent_model, a.board_size, a.cube_layer)},
+                     num=a.num, board_size=a.board_size, cube_layer=a.cube_layer, rng=a.rng)
+        t = {"model vs opponent_model": {k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}}
+    elif a.model is not None:
         model = load_policy(a.model, a.board_size, a.cube_layer)
         t = evaluate_model(model, a.agents, a.num, a.max_depth, a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer,
                            a.heuristic, a.rng)

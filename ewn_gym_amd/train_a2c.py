@@ -44,7 +44,10 @@ def main():
     ap.add_argument("--eval_num_simulations", type=int, default=10, help="--eval_opponent mcts: simulations per root move (x 5 env copies)")
     ap.add_argument("--board_size", type=int, default=5)
     ap.add_argument("--cube_layer", type=int, default=3)
-    ap.add_argument("--opponent_policy", "-op", default="random")
+    ap.add_argument("--opponent_policy", "-op", default="random",
+                    help="random, minimax, mcts; or self-play with the fused trainers: 'self' (a frozen copy of the live parameters) or the "
+                         "path of a checkpoint (loaded once)")
+    ap.add_argument("--opponent_update_every", type=int, default=100, help="--opponent_policy self: refresh the frozen copy every N updates")
     ap.add_argument("--max_depth", type=int, default=3)
     ap.add_argument("--goal_reward", type=float, default=10.0)
     ap.add_argument("--illegal_move_reward", type=float, default=-1.0)
@@ -61,7 +64,17 @@ def main():
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
         dist.init_process_group("nccl")
     lo, hi = lane_range(a.num_envs * world, world, rank)
+    if a.reference_quirks and a.opponent_policy not in ("random", "minimax", "mcts"):
+        raise SystemExit("--reference_quirks drops the opponent (MinimaxEnv plays RandomAgent whatever it is given): it cannot be combined "
+                         "with a model opponent, --opponent_policy %s" % a.opponent_policy)
     opp, reward = (("random", 1.0) if a.reference_quirks else (a.opponent_policy, a.goal_reward))
+    model_opp = None
+    if opp not in ("random", "minimax", "mcts"):   # a model opponent: the rollout kernel plays it, the env's own opponent is not used
+        model_opp, opp = opp, "random"
+        if a.trainer == "torch" or (a.algorithm == "PPO" and a.trainer != "fused"):
+            raise SystemExit("--opponent_policy %s: a model opponent is played by the fused trainers only (--trainer fused); the torch "
+                             "trainers step the env with ewn_step, which has no policy opponent" % model_opp)
+    okw = {} if model_opp is None else dict(opponent=model_opp, opponent_update_every=a.opponent_update_every)
     env = VecEWN(a.num_envs, board_size=a.board_size, cube_layer=a.cube_layer, opponent_policy=opp, max_depth=a.max_depth,
                  rng="philox", shaped=True, reward=reward, illegal_move_reward=a.illegal_move_reward,
                  illegal_move_tolerance=a.illegal_move_tolerance, autoreset=True, lane_offset=lo,
@@ -71,9 +84,10 @@ def main():
     if a.algorithm == "PPO":   # train.py:39-49: SB3's PPO with batch_size and learning_rate given, the rest at its defaults (ewn_gym_amd/ppo.py)
         from .ppo import FusedPPOTrainer, PPOTrainer
         cls = FusedPPOTrainer if a.trainer == "fused" else PPOTrainer   # auto keeps the torch trainer for PPO
-        trainer = cls(env, n_steps=a.n_steps, batch_size=a.batch_size, n_epochs=a.n_epochs, learning_rate=a.learning_rate, seed=mseed)
-    elif a.trainer == "fused" or (a.trainer == "auto" and env.supports_policy_rollout()):
-        trainer = FusedA2CTrainer(env, n_steps=a.n_steps, learning_rate=a.learning_rate, seed=mseed)
+        trainer = cls(env, n_steps=a.n_steps, batch_size=a.batch_size, n_epochs=a.n_epochs, learning_rate=a.learning_rate, seed=mseed,
+                      **okw)
+    elif a.trainer == "fused" or model_opp is not None or (a.trainer == "auto" and env.supports_policy_rollout()):
+        trainer = FusedA2CTrainer(env, n_steps=a.n_steps, learning_rate=a.learning_rate, seed=mseed, **okw)
     else:
         trainer = A2CTrainer(env, n_steps=a.n_steps, learning_rate=a.learning_rate, seed=mseed)
     if a.checkpoint is not None:      # train.py:137-139: resume the model (and here the optimiser and the step counter too)

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import AGENT, AGENT_MCTS, HEUR, OPP, RNG, EwnAgent, EwnConfig, EwnPolicy, EwnRolloutOut, EwnState, EwnStepOut, check
+from ._lib import AGENT, AGENT_MCTS, HEUR, OPP, RNG, EwnAgent, EwnConfig, EwnOpponentPolicy, EwnPolicy, EwnRolloutOut, EwnState, EwnStepOut, check
 
 
 def _require_gpu(device):
@@ -70,7 +70,10 @@ class VecEWN:
         self.lib = _lib.load()
         opp = str(opponent_policy)
         if opp not in OPP:
-            raise _lib.EwnError("opponent policy %r is not supported by the HIP engine (random, minimax, mcts)" % opp)
+            raise _lib.EwnError("opponent policy %r is not supported by the HIP engine (random, minimax, mcts); a trained model as the "
+                                "opponent is served by rollout_policy(..., opponent_params=) and eval_policy(..., opponent_params=) "
+                                "(ewn_step_k_selfplay / ewn_policy_eval_vs), by tournament.evaluate(opponent={'kind': 'mlp', ...}) and by "
+                                "the fused trainers' opponent=, not by step()" % opp)
         if heuristic not in HEUR:
             raise _lib.EwnError("heuristic %r is not supported (hybrid, min_dist, two_min_dist, attk, sim_winrate)" % heuristic)
         self.N, self.S, self.L = int(n_lanes), int(board_size), int(cube_layer)
@@ -257,14 +260,45 @@ class VecEWN:
     def supports_policy_rollout(self):
         return self.tables is not None and self.lib.ewn_step_k_supported(C.byref(self.cfg), AGENT["mlp"], 0) == 1
 
-    def rollout_policy(self, K, params, traj=None, totals=None, deterministic=False, noise_key=0, logits=None, value=None, noise=None):
+    def supports_selfplay_rollout(self, value=False):
+        """rollout_policy(..., opponent_params=) is served (ewn_step_k_selfplay; value: with the value output).  The env's own opponent
+        settings do not matter to it."""
+        pol = EwnPolicy(None, 0, 0, 0, None, 1 if value else None, None)
+        return self.tables is not None and self.lib.ewn_step_k_selfplay_supported(C.byref(self.cfg), C.byref(pol)) == 1
+
+    def supports_policy_eval_vs(self):
+        """eval_policy(..., opponent_params=) is served (ewn_policy_eval_vs)"""
+        return self.tables is not None and self.lib.ewn_policy_eval_vs_supported(C.byref(self.cfg)) == 1
+
+    def _opponent_struct(self, what, K, opponent_params, deterministic, noise_key, action):
+        N = self.N
+        if not (isinstance(opponent_params, torch.Tensor) and opponent_params.dtype == torch.float32 and opponent_params.is_cuda
+                and opponent_params.is_contiguous() and opponent_params.dim() == 1 and opponent_params.numel() == self.policy_param_count()):
+            raise ValueError("%s: opponent_params must be a contiguous float32 device vector of %d elements, got %s" % (
+                what, self.policy_param_count(), _describe(opponent_params)))
+        if action is not None and not (isinstance(action, torch.Tensor) and action.dtype == torch.int8 and action.is_cuda
+                                       and action.is_contiguous() and action.dim() == 3 and action.shape[0] >= K
+                                       and tuple(action.shape[1:]) == (N, 3)):
+            raise ValueError("%s: opponent_action must be a contiguous int8 device tensor of shape [>= %d, %d, 3], got %s" % (
+                what, K, N, _describe(action)))
+        return EwnOpponentPolicy(_ptr(opponent_params), int(bool(deterministic)), int(noise_key) & 0xFFFFFFFFFFFFFFFF, _ptr(action))
+
+    def rollout_policy(self, K, params, traj=None, totals=None, deterministic=False, noise_key=0, logits=None, value=None, noise=None,
+                       opponent_params=None, opponent_deterministic=False, opponent_noise_key=0, opponent_action=None):
         """Play K steps of every lane in one launch, actions sampled from the actor-critic whose flat fp32 parameter vector is
         `params` (a2c.ActorCritic.flat order).  traj: dict from alloc_rollout (a record layout allocated with initial_obs=True gets
         K + 1 rows); logits [K, N, 5] / value [K, N] / noise [K, N, 5] float32: optional per-step outputs of the policy.  Buffers of the
-        wrong shape, dtype or layout raise ValueError before anything is launched."""
+        wrong shape, dtype or layout raise ValueError before anything is launched.
+        opponent_params: a second parameter vector (may be `params` itself) that plays the opponent instead of the env's own
+        (ewn_step_k_selfplay): sampled unless opponent_deterministic, noise under opponent_noise_key; opponent_action: optional int8
+        [>= K, N, 3], the opponent's {dice, flag, dir} per step ({0, 0, 0}: it did not move)."""
         traj, totals = traj or {}, totals or {}
         assert params.dtype == torch.float32 and params.is_contiguous() and params.numel() == self.policy_param_count()
         N = self.N
+        if opponent_params is None and opponent_action is not None:
+            raise ValueError("rollout_policy: opponent_action needs opponent_params")
+        opp = None if opponent_params is None else self._opponent_struct("rollout_policy", K, opponent_params, opponent_deterministic,
+                                                                         opponent_noise_key, opponent_action)
         for name, t, shape in (("logits", logits, (N, 5)), ("value", value, (N,)), ("noise", noise, (N, 5))):
             if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_cuda and t.is_contiguous()
                                       and t.dim() == 1 + len(shape) and t.shape[0] >= K and tuple(t.shape[1:]) == shape):
@@ -286,6 +320,10 @@ class VecEWN:
                             _ptr(totals.get("return_sum")), _ptr(totals.get("n_steps")), _ptr(totals.get("n_episodes")),
                             _ptr(totals.get("n_wins")), _ptr(traj.get("record")))
         pol = EwnPolicy(_ptr(params), int(bool(deterministic)), rec0, int(noise_key) & 0xFFFFFFFFFFFFFFFF, _ptr(logits), _ptr(value), _ptr(noise))
+        if opp is not None:
+            check(self.lib.ewn_step_k_selfplay(C.byref(self.cfg), C.byref(self._st), int(K), C.byref(pol), C.byref(opp), C.byref(out),
+                                               _stream()), "ewn_step_k_selfplay")
+            return self.board, self.dice
         check(self.lib.ewn_step_k_policy(C.byref(self.cfg), C.byref(self._st), int(K), C.byref(pol), C.byref(out), _stream()),
               "ewn_step_k_policy")
         return self.board, self.dice
@@ -298,13 +336,21 @@ class VecEWN:
         """the same against this env's flat Monte-Carlo opponent (ewn_policy_eval_mcts; no table image needed)"""
         return self.lib.ewn_policy_eval_mcts_supported(C.byref(self.cfg)) == 1
 
-    def eval_policy(self, K, params, totals, action=None):
+    def eval_policy(self, K, params, totals, action=None, opponent_params=None, opponent_action=None, opponent_deterministic=True,
+                    opponent_noise_key=0):
         """Play K steps of every lane in one launch, the agent playing the argmax of the actor-critic whose flat fp32 parameter vector
         is `params` (a2c.ActorCritic.parameters() order), on the un-shaped env without auto-reset.  totals: dict from alloc_totals
         (required, ADDED to); action: optional int8 [>= K, N, 2] (row k of a lane is written only if the lane played step k).
         Buffers of the wrong shape, dtype or layout raise ValueError before anything is launched.  An env whose opponent is MCTS is
-        served by ewn_policy_eval_mcts, every other by ewn_policy_eval: the same arguments, the same contract."""
+        served by ewn_policy_eval_mcts, every other by ewn_policy_eval: the same arguments, the same contract.
+        opponent_params: a second parameter vector that plays the opponent instead of the env's own (ewn_policy_eval_vs; its argmax
+        unless opponent_deterministic=False); opponent_action: optional int8 [>= K, N, 3], the opponent's {dice, flag, dir} of the steps a
+        lane plays ({0, 0, 0}: it did not move)."""
         N = self.N
+        if opponent_params is None and opponent_action is not None:
+            raise ValueError("eval_policy: opponent_action needs opponent_params")
+        opp = None if opponent_params is None else self._opponent_struct("eval_policy", K, opponent_params, opponent_deterministic,
+                                                                         opponent_noise_key, opponent_action)
         if not (isinstance(params, torch.Tensor) and params.dtype == torch.float32 and params.is_cuda and params.is_contiguous()
                 and params.dim() == 1 and params.numel() == self.policy_param_count()):
             raise ValueError("eval_policy: params must be a contiguous float32 device vector of %d elements, got %s" % (
@@ -323,7 +369,10 @@ class VecEWN:
                 K, N, _describe(action)))
         out = EwnRolloutOut(None, None, _ptr(action), None, None, None, None, _ptr(totals["return_sum"]), _ptr(totals["n_steps"]),
                             _ptr(totals["n_episodes"]), _ptr(totals["n_wins"]), None)
-        if self.cfg.opponent_kind == OPP["mcts"]:
+        if opp is not None:
+            check(self.lib.ewn_policy_eval_vs(C.byref(self.cfg), C.byref(self._st), int(K), _ptr(params), C.byref(opp), C.byref(out),
+                                              _stream()), "ewn_policy_eval_vs")
+        elif self.cfg.opponent_kind == OPP["mcts"]:
             check(self.lib.ewn_policy_eval_mcts(C.byref(self.cfg), C.byref(self._st), int(K), _ptr(params), C.byref(out), _stream()),
                   "ewn_policy_eval_mcts")
         else:

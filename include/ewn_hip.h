@@ -321,6 +321,39 @@ int ewn_policy_eval_mcts_supported(const ewn_config *cfg);
 int ewn_policy_eval_mcts(const ewn_config *cfg, const ewn_state *st, int K, const float *params,
                          const ewn_rollout_out *out, void *stream);
 
+/* ---- a trained policy as the OPPONENT (the reference's `A2C.load(opponent_policy)`, envs/ewn.py:265-296): self-play ----
+ * After the agent's move the opponent's actor-critic sees the canonical view np.rot90(-board, 2) with the opponent's dice
+ * (opponent_action, envs/ewn.py:289-296) and its [flag, dir] is played as it is.  A move that leaves the board, or that asks for
+ * a cube that is gone, ends the game as envs/ewn.py:469-473 does: reward 0, terminated, truncated, EWN_INFO_INVALID_OPP, board
+ * and dice left as they were after the agent's move.  The policy opponent draws NOTHING from the lane's dice stream (like the
+ * minimax opponent): per step the stream gives the opponent's dice and then the next dice.
+ * deterministic: 1 the argmax of each head (ewn_step_k_policy's comparisons, so ties break as the agent's do), 0 a Gumbel-max
+ * sample whose five uniforms are pol_uniform(w, i) of ewn_step_k_policy's noise with
+ *   w = fmix32(agent_hash(the step's agent-hash arguments, philox_key ^ noise_key) ^ 0x4F505031):
+ * the agent-hash stream at the START of the step under the opponent's own key, never the dice stream.  The reference's
+ * `predict` arithmetic (stable_baselines3) is not vendored: parity unpinned, as for the agent; both modes are offered.
+ * These calls do NOT read the opponent fields of cfg (opponent_kind, max_depth, heuristic, num_simulations, num_env_copies):
+ * any values there are accepted.  cube_layer 3, board sizes 5 and 7; anything else well-formed: EWN_EUNSUPPORTED, unlaunched. */
+typedef struct ewn_opponent_policy {
+    const float *params;     /* ewn_policy.params layout, device; may equal the agent's pointer; frozen for the launch */
+    int32_t deterministic;   /* 1: argmax, 0: Gumbel-max sample */
+    uint64_t noise_key;      /* sampling only */
+    int8_t *action;          /* [K][N][3] {dice, flag, dir} of the opponent's move in step k, {0, 0, 0} when it did not move; may be NULL */
+} ewn_opponent_policy;
+/* 1 if ewn_step_k_selfplay serves cfg with this pol (only pol->value is looked at; pol may be NULL), 0 if not, < 0 for an
+ * invalid cfg.  Philox dice only; 7x7 with pol->value set is not served (three weight images do not fit the CU's LDS). */
+int ewn_step_k_selfplay_supported(const ewn_config *cfg, const ewn_policy *pol);
+/* ewn_step_k_policy's contract with the opponent = opp.  opp->action row k of lane n is written for every lane (a frozen
+ * lane: {0, 0, 0}). */
+int ewn_step_k_selfplay(const ewn_config *cfg, const ewn_state *st, int K, const ewn_policy *pol, const ewn_opponent_policy *opp,
+                        const ewn_rollout_out *out, void *stream);
+/* 1 if ewn_policy_eval_vs serves cfg, 0 if not, < 0 for an invalid cfg: un-shaped, no auto-reset, either dice kind */
+int ewn_policy_eval_vs_supported(const ewn_config *cfg);
+/* ewn_policy_eval's contract with the opponent = opp (ewn_state.tables is needed, as there).  opp->action row k of lane n is
+ * written only if the lane played step k of this call, like out->action. */
+int ewn_policy_eval_vs(const ewn_config *cfg, const ewn_state *st, int K, const float *params, const ewn_opponent_policy *opp,
+                       const ewn_rollout_out *out, void *stream);
+
 /* ---- the A2C update on the records of ewn_step_k_policy: stable_baselines3 A2C.train as train.py:35-63, 148 configures it ----
  * (n-step returns = GAE with lambda 1, no advantage normalisation; loss = policy gradient + vf_coef * MSE(returns, values) +
  * ent_coef * (-entropy), a mean over the n_steps x lanes batch; clip_grad_norm_(max_grad_norm); RMSprop(alpha, eps)).  SB3 is not
