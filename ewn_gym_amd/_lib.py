@@ -21,7 +21,7 @@ INFO_MESSAGES = {
 }
 
 EXPORTS = ["ewn_abi_version", "ewn_strerror", "ewn_rng_words", "ewn_step_scratch_bytes", "ewn_tables_bytes",
-           "ewn_build_tables", "ewn_init_aux", "ewn_reset",
+           "ewn_build_tables", "ewn_tables_rank_offset", "ewn_init_aux", "ewn_reset",
            "ewn_step", "ewn_legal_actions", "ewn_apply_action", "ewn_playout_wins", "ewn_evaluate", "ewn_predict_minimax", "ewn_predict_random",
            "ewn_predict_mcts", "ewn_step_k", "ewn_step_k_supported", "ewn_predict_minimax_sim", "ewn_lanes_per_game", "ewn_roll_dice",
            "ewn_policy_param_count", "ewn_step_k_policy", "ewn_a2c_scratch_bytes", "ewn_a2c_grad", "ewn_a2c_apply",
@@ -122,6 +122,7 @@ def load():
         "ewn_step_scratch_bytes": (C.c_int64, [cfgp]),
         "ewn_tables_bytes": (C.c_int64, [i32, i32]),
         "ewn_build_tables": (i32, [i32, i32, vp]),
+        "ewn_tables_rank_offset": (i32, [i32, i32, i32]),
         "ewn_init_aux": (i32, [cfgp, stp, vp]),
         "ewn_reset": (i32, [cfgp, stp, vp, vp, vp]),
         "ewn_roll_dice": (i32, [cfgp, stp, vp, vp]),

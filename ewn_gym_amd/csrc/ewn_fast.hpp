@@ -33,6 +33,11 @@
 // and a value lookup needs no address arithmetic (measured round 2: every u16 / f64 table read cost one half-rate VALU shift).
 #define FAST_NONE8 (1023u * 8u)             // "no such reply": val = +inf
 #define FAST_KNONE (0x8000u | FAST_NONE8)   // key (see d3_search) of a cube that is not on the board
+// rank[] row stride: 64 entries + 2 of padding = 132 B = 33 dwords.  A 16-bit LDS read banks by (byte address / 4) % 32 within each
+// 32-lane half; with 128-B rows (exactly 32 dwords) the bank was (iy / 2) % 32 whatever ix is, and the lanes of a half -- 16
+// unrelated games whose iy takes two dozen values on 16 banks -- met there with distinct addresses.  With 33 dwords per row the
+// bank is (ix + iy / 2) % 32.  Row 0 keeps its place, so rank[0] / rank[1] (see build_fast_tables) stay at byte 0 / 2.
+#define FAST_RANK_ROW 66
 
 template <int S> struct MaskOf { typedef u32 type; };
 template <> struct MaskOf<6> { typedef u64 type; };
@@ -43,8 +48,9 @@ template <int S>
 struct FastTab {
     static constexpr int CELLS = S * S;
     // one side's (level t, count n) is the 6-bit index t*8 + n (t <= 7, n <= 6); a leaf is the pair (ix of the P side, iy of the
-    // N side).  rank[(ix << 6) | iy] = 8 x the rank of (0 + x) - y among the table's distinct values: 1 = lowest ... nv = +10
-    uint16_t rank[64 * 64];
+    // N side).  rank[ft_index(ix, iy)] = 8 x the rank of (0 + x) - y among the table's distinct values: 1 = lowest ... nv = +10
+    // (rows of FAST_RANK_ROW entries; ft_index / ft_addr below are the only places that know the layout)
+    uint16_t rank[64 * FAST_RANK_ROW];
     double val[FAST_NV];                         // rank -> leaf value (ascending); val[0] = -inf (rank 0 = "none"), unused ranks = +inf
     double val6[FAST_NV];                        // rank -> value / 6.0 (IEEE quotient, host-computed)
     uint8_t lvl_guard[8];                        // lvl[-1]: v_ffbh_u32 answers -1 for an empty 32-bit mask; level 0 + count 0 = the "-10" row
@@ -92,6 +98,8 @@ static inline bool fast_heur_step(int heur) { return fast_heur_lean(heur) || heu
 
 // LDS / device image size: the struct padded to 4 KiB so the LDS-DMA copy needs no tail handling
 #define FAST_TAB_BYTES(S) ((int)((sizeof(FastTab<S>) + 4095) / 4096 * 4096))
+// the row padding of rank[] (256 B) fits the image's tail padding: every LDS budget that holds an image stays what it was
+static_assert(FAST_TAB_BYTES(5) == 32768 && FAST_TAB_BYTES(6) == 32768 && FAST_TAB_BYTES(7) == 32768 && FAST_TAB_BYTES(8) == 32768, "table image grew");
 
 
 EWN_DEV int clz_m(u32 m) { return __clz((int)m); }       // 32 for m == 0
@@ -127,8 +135,10 @@ template <int S, bool H2> EWN_DEV u32 ft_side_h(const FastTab<S> *Tb, typename M
 {
     if constexpr (H2) return ft_side2<S>(Tb, m); else return ft_side<S>(Tb, m);
 }
-// byte address of a leaf's entry inside rank[]
-EWN_DEV u32 ft_addr(u32 ix, u32 iy) { return (ix << 7) | (iy << 1); }
+// a leaf's entry inside rank[]: its index (host and device) and its byte address (a 24-bit multiply and a shift-add: as many
+// instructions as the shift and shift-or of the unpadded layout)
+static inline __host__ __device__ constexpr int ft_index(int ix, int iy) { return ix * FAST_RANK_ROW + iy; }
+EWN_DEV u32 ft_addr(u32 ix, u32 iy) { return ix * (u32)(2 * FAST_RANK_ROW) + (iy << 1); }
 template <int S> EWN_DEV u32 ft_rank8(const FastTab<S> *Tb, u32 addr) { return *(const uint16_t *)((const char *)Tb->rank + addr); }
 template <int S> EWN_DEV double ft_val(const FastTab<S> *Tb, u32 r8) { return *(const double *)((const char *)Tb->val + r8); }
 template <int S> EWN_DEV double ft_val6(const FastTab<S> *Tb, u32 r8) { return *(const double *)((const char *)Tb->val6 + r8); }
@@ -272,8 +282,9 @@ static int build_fast_tables(FastTab<S> *T, int variant = 0, int heur = 0)
             // ... and column 0 of the other rows (BOTTOM_RIGHT has no cube left: TOP_LEFT has won, :41-44) answers +10: the leaves of
             // the max_depth 5 / 6 search (ewn_search_d5.hpp) that take the last cube land there
             const uint16_t unused_rank = (heur != 2 && iy == 0 && ix != 0) ? (uint16_t)T->nv : m10;
-            T->rank[ix * IXN + iy] = (uint16_t)(8 * (used ? (uint16_t)(1 + (std::lower_bound(all.begin(), all.end(), e[(size_t)ix * IXN + iy]) - all.begin())) : unused_rank));
+            T->rank[ft_index(ix, iy)] = (uint16_t)(8 * (used ? (uint16_t)(1 + (std::lower_bound(all.begin(), all.end(), e[(size_t)ix * IXN + iy]) - all.begin())) : unused_rank));
         }
+    static_assert(ft_index(0, 0) == 0 && ft_index(0, 1) == 1, "rkf's fixed addresses 0 and 2 are rank[0] and rank[1]");
     T->rank[0] = (uint16_t)FAST_NONE8; T->rank[1] = (uint16_t)(8 * m10); // unused (level 0, count 0) slots that d3_search's leaf index is steered to: "no such reply", -10
     return 0;
 }

@@ -975,6 +975,13 @@ int ewn_build_tables(int board_size, int cube_layer, void *host_out)
     return rc == 0 ? EWN_OK : EWN_EUNSUPPORTED;
 }
 
+int ewn_tables_rank_offset(int board_size, int ix, int iy)
+{
+    if (board_size < 5 || board_size > 8 || ix < 0 || ix >= 64 || iy < 0 || iy >= 64) return EWN_EINVAL;
+    // rank[] is the first member of FastTab<S> for every S
+    return (int)(offsetof(FastTab<5>, rank) + sizeof(uint16_t) * (size_t)ft_index(ix, iy));
+}
+
 int ewn_rng_words(const ewn_config *cfg)
 {
     Geom g; KCfg k;

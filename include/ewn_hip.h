@@ -155,6 +155,11 @@ int64_t ewn_step_scratch_bytes(const ewn_config *cfg);
  * caller then copies to the device and passes as ewn_state.tables / the `tables` argument. */
 int64_t ewn_tables_bytes(int board_size, int cube_layer);
 int ewn_build_tables(int board_size, int cube_layer, void *host_out);
+/* Byte offset, inside ONE image of ewn_build_tables()'s output, of the 16-bit leaf-rank entry of the pair (ix, iy), 0 <= ix, iy < 64
+ * (a side's index: level * 8 + count): the address every search kernel reads it at.  The layout of the rank table is otherwise
+ * private to ewn_fast.hpp; this query lets a test or a tool read an image without knowing it.  < 0: no tables for this board
+ * size, or an index out of range. */
+int ewn_tables_rank_offset(int board_size, int ix, int iy);
 
 /* Constructor-time state that reset() does not touch in the reference:
  * prev_score = evaluate(initial board) (training_ewn.py:35) and the tolerance

@@ -5,6 +5,7 @@
 For every configuration directory (rollout_k50, rollout_k50_notraj, step) it reads
   stats_kernel_stats.csv                      rocprofv3 --kernel-trace --stats (average duration of the dominant kernel)
   pmc_<COUNTERS>_counter_collection.csv       separate --pmc passes (FETCH_SIZE | WRITE_SIZE | SQ_INSTS_VALU | SQ wave cycles | ...)
+  pmc_lds_counter_collection.csv              the LDS-conflict pass (tools/pmc_lds.sh): bank / address conflict cycles, LDS-array cycles
 and writes per-launch averages of the dominant kernel.  HBM bytes = (2 x FETCH_SIZE + WRITE_SIZE) x 1024: the gfx950
 read-side correction of MI355X_MICROARCH.md applied in full, an upper bound for this mixed-width access pattern
 (profiles/README.md).  The file carries the sha256 of the kernel sources it was measured on (bench.py refuses a stale
@@ -58,6 +59,17 @@ def dominant(rows, want, filt=True):
         keep = full_launches(v) if filt else v
         out[c] = sum(keep) / len(keep)
     return k, out
+
+
+def lds_conflict(vals):
+    """how the LDS array serves the kernel's reads: conflict cycles per LDS instruction and as a share of the array's busy cycles"""
+    out = {c: vals[c] for c in ("SQ_LDS_BANK_CONFLICT", "SQ_LDS_ADDR_CONFLICT", "SQ_LDS_IDX_ACTIVE", "SQ_LDS_UNALIGNED_STALL") if c in vals}
+    if "SQ_LDS_BANK_CONFLICT" in vals:
+        if vals.get("SQ_INSTS_LDS"):
+            out["lds_bank_conflict_cycles_per_lds_inst"] = vals["SQ_LDS_BANK_CONFLICT"] / vals["SQ_INSTS_LDS"]
+        if vals.get("SQ_LDS_IDX_ACTIVE"):
+            out["lds_bank_conflict_share_of_idx_active"] = vals["SQ_LDS_BANK_CONFLICT"] / vals["SQ_LDS_IDX_ACTIVE"]
+    return out
 
 
 def main():
@@ -138,6 +150,7 @@ def main():
         for c in ("SQ_WAVE_CYCLES", "SQ_WAIT_ANY", "SQ_WAIT_INST_ANY", "SQ_ACTIVE_INST_VALU", "SQ_INSTS_LDS", "SQ_INSTS_SALU", "SQ_ACTIVE_INST_LDS", "SQ_WAVES"):
             if c in vals:
                 ent[c] = vals[c]
+        ent.update(lds_conflict(vals))
         if "SQ_WAVE_CYCLES" in vals and vals["SQ_WAVE_CYCLES"]:
             ent["wait_any_frac"] = vals.get("SQ_WAIT_ANY", 0.0) / vals["SQ_WAVE_CYCLES"]
             ent["active_valu_frac"] = vals.get("SQ_ACTIVE_INST_VALU", 0.0) / vals["SQ_WAVE_CYCLES"]

@@ -12,5 +12,7 @@ for c in FETCH_SIZE WRITE_SIZE SQ_INSTS_VALU "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT
   tag=$(echo $c | tr ' ' '+')
   rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/$name -o pmc_$tag -- python3 $R/bench.py $COMMON "$@" > $OUT/$name/pmc_$tag.json 2> $OUT/$name/pmc_$tag.err
 done
+# the LDS-conflict counters, a counters-only run of its own (tools/pmc_lds.sh)
+( cd $R && tools/pmc_lds.sh ${OUT#$R/} $name "$@" )
 python3 $R/bench.py $COMMON "$@" > $OUT/$name/bench.json 2> $OUT/$name/bench.err
 echo done $name

@@ -17,6 +17,8 @@ run_cfg() { # name, bench args...
     tag=$(echo $c | tr ' ' '+')
     rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/$name -o pmc_$tag -- python3 $R/bench.py $COMMON --steps 200 --warmup 20 "$@" > $OUT/$name/pmc_$tag.json 2> $OUT/$name/pmc_$tag.err
   done
+  # the LDS-conflict counters, a counters-only run of its own (tools/pmc_lds.sh)
+  ( cd $R && tools/pmc_lds.sh ${OUT#$R/} $name --steps 200 --warmup 20 "$@" )
   python3 $R/bench.py $COMMON "$@" > $OUT/$name/bench.json 2> $OUT/$name/bench.err
 }
 run_cfg rollout_k50 --steps-per-launch 50
