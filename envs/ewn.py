@@ -62,14 +62,21 @@ class EinsteinWuerfeltNichtEnv(_Base):
     # ------------------------------------------------------------------ engine plumbing
     def _engine_kwargs(self):
         kw = self._policy_kwargs
-        return dict(board_size=self.board.shape[0], cube_layer=self.cube_layer, opponent_policy=str(self._opponent_kind),
+        # a model opponent is set on the engine after it is built (_make_engine); the engine's own opponent is then not read
+        kind = "random" if self._opponent_model is not None else str(self._opponent_kind)
+        return dict(board_size=self.board.shape[0], cube_layer=self.cube_layer, opponent_policy=kind,
                     max_depth=kw.get("max_depth", 3), heuristic=kw.get("heuristic", "hybrid"),
                     num_simulations=kw.get("num_simulations", 10), num_env_copies=kw.get("num_env_copies", 5),
                     rng="mt19937", reward=self.reward, philox_key=int.from_bytes(os.urandom(8), "little"))
 
     def _make_engine(self):
         import ewn_gym_amd
-        return ewn_gym_amd.VecEWN(1, **self._engine_kwargs())
+        engine = ewn_gym_amd.VecEWN(1, **self._engine_kwargs())
+        if self._opponent_model is not None:
+            # the reference's model.predict(obs, deterministic=True) on np.rot90(-board, 2) (envs/ewn.py:289-296), inside the step kernel
+            self._opponent_params = self._opponent_model.flat_parameters().to(engine.device)
+            engine.set_opponent_model(self._opponent_params, deterministic=True)
+        return engine
 
     def _pull(self):
         self.board[:] = self._engine.board[0].cpu().numpy()     # in place: obs["board"] aliases env state upstream too
@@ -83,6 +90,7 @@ class EinsteinWuerfeltNichtEnv(_Base):
         """envs/ewn.py:265-287.  The reply itself is computed inside the fused step kernel;
         the agent object is kept for introspection (`env.opponent_policy`)."""
         from classical_policies import ExpectiMinimaxAgent, MctsAgent, RandomAgent
+        self._opponent_model = None
         if opponent_policy == ClassicalPolicy.random:
             self.opponent_policy = RandomAgent(self)
         elif opponent_policy == ClassicalPolicy.minimax:
@@ -93,8 +101,19 @@ class EinsteinWuerfeltNichtEnv(_Base):
         elif isinstance(opponent_policy, ClassicalPolicy):
             raise NotImplementedError("opponent policy %s is out of scope of the HIP engine" % opponent_policy)
         else:
+            # envs/ewn.py:287 loads the path with A2C.load; here it is a checkpoint of this project's trainers (best.pt of train_a2c:
+            # A2CTrainer / PPOTrainer / FusedA2CTrainer / FusedPPOTrainer), whose actor-critic then replies inside the step kernel
             assert isinstance(opponent_policy, str)
-            raise NotImplementedError("SB3 checkpoint opponents (A2C.load, envs/ewn.py:287) need stable_baselines3")
+            from ewn_gym_amd.tournament import load_policy
+            try:
+                self._opponent_model = load_policy(opponent_policy, self.board.shape[0], self.cube_layer)
+            except FileNotFoundError:
+                raise
+            except Exception as e:
+                raise NotImplementedError("opponent_policy=%r is not a checkpoint of this project's trainers (%s: %s); SB3 zip files "
+                                          "(A2C.load, envs/ewn.py:287) need stable_baselines3 and are out of scope"
+                                          % (opponent_policy, type(e).__name__, e)) from e
+            self.opponent_policy = self._opponent_model
         self._opponent_kind = opponent_policy
 
     def reset(self, seed: Optional[int] = None):

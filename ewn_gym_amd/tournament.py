@@ -72,7 +72,8 @@ def evaluate(agent, opponent, num=1024, board_size=5, cube_layer=3, rng="mt19937
     through ewn_step_k_agent (cube_layer 3, boards 5..8); an "mlp" agent wherever ewn_policy_eval (RandomAgent, minimax) or
     ewn_policy_eval_mcts (the MCTS opponent) serves the opponent and geometry;
     an "mlp" agent against an "mlp" opponent ({"kind": "mlp", "model": ...}: the opponent model's argmax on its canonical view)
-    through ewn_policy_eval_vs, the only path for a model opponent (no other agent kind plays one);
+    through ewn_policy_eval_vs, the only model opponent evaluate() itself plays (every other agent kind against a model:
+    evaluate_vs_model below);
     otherwise one policy evaluation + one ewn_step per step (use_rollout=False forces that loop).  The engines give the per-step loop's
     per-episode results, the MCTS agent's included: its playouts at step t use key + 0x9E3779B97F4A7C15 * (t + 1) either way
     ("engine" in the result says which one ran)."""
@@ -144,7 +145,8 @@ def _evaluate_vs_model(agent, opponent, num, board_size, cube_layer, rng, seed_o
     """model against model: ewn_policy_eval_vs, both sides deterministic.  There is no per-step path for a model opponent (ewn_step has
     none), so anything the engine does not serve raises."""
     if not (isinstance(agent, dict) and agent.get("kind") == "mlp"):
-        raise ValueError("evaluate: a model opponent ({'kind': 'mlp'}) is played by a model agent only (ewn_policy_eval_vs)")
+        raise ValueError("evaluate: a model opponent ({'kind': 'mlp'}) is played by a model agent only (ewn_policy_eval_vs); every other "
+                         "agent kind meets it in evaluate_vs_model (ewn_step_k_vs / ewn_step_vs)")
     for side in (agent, opponent):
         if getattr(side["model"], "S", board_size) != board_size:
             raise ValueError("evaluate: a model plays %dx%d boards, the evaluation is on %dx%d" % (side["model"].S, side["model"].S, board_size, board_size))
@@ -161,6 +163,100 @@ def _evaluate_vs_model(agent, opponent, num, board_size, cube_layer, rng, seed_o
             break
     env.check_rng()
     return _totals_result(totals, num, "ewn_policy_eval_vs")
+
+
+def _stand_in_random(env):
+    """RandomAgent on the hash stream ewn_step_k / ewn_step_k_vs draw the agent's action from (ewn_step_out.random_action's: one word
+    per (episode seed, draws so far, global lane, philox_key), read off the lane's RNG header), as a per-step policy: the ply-by-ply
+    loop then plays what the K-step launch plays.  Plumbing around ewn_legal_actions; the hash is a dozen integer ops per lane."""
+    from .vec_env import legal_actions
+    M = 0xFFFFFFFF
+
+    def fmix(h):
+        h = h ^ (h >> 16)
+        h = (h * 0x85EBCA6B) & M
+        h = h ^ (h >> 13)
+        h = (h * 0xC2B2AE35) & M
+        return h ^ (h >> 16)
+
+    def fmix_int(h):
+        h ^= h >> 16
+        h = (h * 0x85EBCA6B) & M
+        h ^= h >> 13
+        h = (h * 0xC2B2AE35) & M
+        return h ^ (h >> 16)
+
+    key = int(env.cfg.philox_key)
+    kterm = fmix_int((key & M) ^ 0x41474E54) ^ (((key >> 32) * 0x85EBCA6B) & M)
+    lane = torch.arange(env.N, dtype=torch.int64, device=env.device) + int(env.cfg.lane_offset)
+    philox = int(env.cfg.rng_kind) == 1
+
+    def policy(board, dice, t):
+        hdr = env.rng_state.view(-1)[:4 * env.N].view(env.N, 4).to(torch.int64) & M   # the headers lead the buffer (ewn_state.rng)
+        seed = hdr[:, 0] ^ ((hdr[:, 3] * 0x9E3779B9) & M) if philox else hdr[:, 0]
+        w = fmix(seed ^ fmix((hdr[:, 1] * 0x9E3779B1 + lane) & M) ^ kterm)
+        acts, n = legal_actions(board, dice, player=1, cube_layer=env.L)[:2]
+        n = n.to(torch.int64)
+        idx = ((w * n) >> 32).clamp(max=5)
+        a = acts.gather(1, idx[:, None, None].expand(-1, 1, 2))[:, 0]
+        return torch.where((n > 0)[:, None], a, torch.zeros_like(a)).contiguous()
+    return policy
+
+
+def evaluate_vs_model(agent, opponent, num=1024, board_size=5, cube_layer=3, rng="mt19937", seed_offset=0, key=12345, max_steps=400,
+                      use_rollout=True, chunk=16, deterministic=True):
+    """Any agent against a trained policy as the env's opponent (the reference's eval_random.py / eval_minimax.py / eval_mcts.py run on an
+    env built with opponent_policy=<path>).  opponent: {"kind": "mlp", "model": a2c.ActorCritic}; it plays its argmax on its canonical
+    view (deterministic=False: samples).  agent: as in evaluate().  RandomAgent and 'hybrid' minimax run K steps per launch
+    (ewn_step_k_vs, engine "ewn_step_k_vs"); the MCTS agent, callables, the other heuristics and use_rollout=False go ply by ply through
+    step() (ewn_step_vs, engine "ewn_step_vs") -- both give the same per-episode results for the random and minimax agents; an "mlp"
+    agent is evaluate()'s model-against-model path (ewn_policy_eval_vs)."""
+    if not (isinstance(opponent, dict) and opponent.get("kind") == "mlp"):
+        raise ValueError("evaluate_vs_model: the opponent is {'kind': 'mlp', 'model': ...}; evaluate() plays the classical opponents")
+    if isinstance(agent, dict) and agent.get("kind") == "mlp":
+        return _evaluate_vs_model(agent, opponent, num, board_size, cube_layer, rng, seed_offset, key, max_steps, chunk)
+    model = opponent["model"]
+    if getattr(model, "S", board_size) != board_size:
+        raise ValueError("evaluate_vs_model: the model plays %dx%d boards, the evaluation is on %dx%d" % (model.S, model.S, board_size, board_size))
+    env = VecEWN(num, board_size=board_size, cube_layer=cube_layer, opponent_policy="random", rng=rng, autoreset=False,
+                 philox_key=key ^ 0x5DEECE66D)
+    if not env.supports_step_vs():
+        raise ValueError("evaluate_vs_model: ewn_step_vs does not serve %dx%d boards with cube_layer %d" % (board_size, board_size, cube_layer))
+    env.set_opponent_model(flat_policy_params(model).to(env.device), deterministic=deterministic, noise_key=key)
+    env.reset(seeds=torch.arange(seed_offset, seed_offset + num, dtype=torch.int64).to(torch.int32))
+    if (use_rollout and isinstance(agent, dict) and agent["kind"] in ("random", "minimax") and agent.get("heuristic", "hybrid") == "hybrid"
+            and env.supports_rollout(agent["kind"], agent.get("max_depth", 3))):
+        totals = env.alloc_totals()
+        for _ in range(0, max_steps, chunk):
+            env.rollout(chunk, agent=agent["kind"], agent_max_depth=agent.get("max_depth", 3), totals=totals)
+            if bool((env.done != 0).all()):
+                break
+        env.check_rng()
+        return _totals_result(totals, num, "ewn_step_k_vs")
+    policy = _stand_in_random(env) if isinstance(agent, dict) and agent.get("kind") == "random" else _policy(agent, cube_layer, key)
+    score = torch.zeros(num, dtype=torch.float64, device=env.device)
+    length = torch.zeros(num, dtype=torch.int32, device=env.device)
+    for t in range(max_steps):
+        alive = env.done == 0
+        if not bool(alive.any()):
+            break
+        _, _, reward, terminated, _, _ = env.step(policy(env.board, env.dice, t))
+        just = alive & (terminated != 0)
+        score = torch.where(just, reward, score)
+        length += alive.to(torch.int32)
+    env.check_rng()
+    return _totals_result({"return_sum": score, "n_steps": length}, num, "ewn_step_vs")
+
+
+def evaluate_agents_vs_model(model, names=("random", "minimax", "mcts"), num=1024, max_depth=5, num_simulations=10, num_env_copies=5,
+                             board_size=5, cube_layer=3, heuristic="hybrid", rng="mt19937"):
+    """every listed classical agent against the model as the opponent"""
+    table = {}
+    for a in names:
+        agent = {"kind": a, "max_depth": max_depth, "heuristic": heuristic, "num_simulations": num_simulations, "num_env_copies": num_env_copies}
+        r = evaluate_vs_model(agent, {"kind": "mlp", "model": model}, num=num, board_size=board_size, cube_layer=cube_layer, rng=rng)
+        table["%s vs opponent_model" % a] = {k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}
+    return table
 
 
 def tournament(names=("random", "minimax", "mcts"), num=1024, max_depth=5, num_simulations=10, num_env_copies=5,
@@ -213,7 +309,8 @@ def main():
                                              "trained policy against each listed opponent (counterpart of eval_A2C.py)")
     ap.add_argument("--agents", nargs="+", default=["random", "minimax", "mcts"])
     ap.add_argument("--model", default=None, help="checkpoint (best.pt) of any of the trainers: evaluate its deterministic policy")
-    ap.add_argument("--opponent_model", default=None, help="with --model: a second checkpoint that plays the opponent (its argmax)")
+    ap.add_argument("--opponent_model", default=None, help="a checkpoint that plays the opponent (its argmax): against --model, or "
+                                                           "without --model against every agent of --agents")
     ap.add_argument("--num", type=int, default=1024)
     ap.add_argument("--max_depth", type=int, default=5)
     ap.add_argument("--heuristic", default="hybrid")
@@ -223,9 +320,10 @@ def main():
     ap.add_argument("--cube_layer", type=int, default=3)
     ap.add_argument("--rng", default="mt19937")
     a = ap.parse_args()
-    if a.opponent_model is not None:
-        if a.model is None:
-            ap.error("--opponent_model needs --model")
+    if a.opponent_model is not None and a.model is None:
+        t = evaluate_agents_vs_model(load_policy(a.opponent_model, a.board_size, a.cube_layer), a.agents, a.num, a.max_depth,
+                                     a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer, a.heuristic, a.rng)
+    elif a.opponent_model is not None:
         r = evaluate({"kind": "mlp", "model": load_policy(a.model, a.board_size, a.cube_layer)},
                      {"kind": "mlp", "model": load_policy(a.opponent_model, a.board_size, a.cube_layer)},
                      num=a.num, board_size=a.board_size, cube_layer=a.cube_layer, rng=a.rng)

@@ -68,6 +68,7 @@ class VecEWN:
                  lane_offset=0, seed_stride=None, philox_key=0, mt_window=0, want_terminal_obs=False, device="cuda",
                  use_tables=True, want_random_action=False):
         self.lib = _lib.load()
+        self._opp_model = None     # set_opponent_model: (params, EwnOpponentPolicy for step(), deterministic, noise_key, action buffer)
         opp = str(opponent_policy)
         if opp not in OPP:
             raise _lib.EwnError("opponent policy %r is not supported by the HIP engine (random, minimax, mcts); a trained model as the "
@@ -136,9 +137,53 @@ class VecEWN:
         if not (isinstance(actions, torch.Tensor) and actions.dtype == torch.int8 and actions.is_cuda and actions.is_contiguous()):
             actions = self._actions.copy_(torch.as_tensor(actions).reshape(self.N, 2))
         assert actions.numel() == 2 * self.N
+        if self._opp_model is not None:
+            check(self.lib.ewn_step_vs(C.byref(self.cfg), C.byref(self._st), _ptr(actions), C.byref(self._opp_model[1]),
+                                       C.byref(self._out), _stream()), "ewn_step_vs")
+            return self.board, self.dice, self.reward, self.terminated, self.truncated, self.info
         check(self.lib.ewn_step(C.byref(self.cfg), C.byref(self._st), _ptr(actions), C.byref(self._out), _ptr(self.scratch),
                                 _stream()), "ewn_step")
         return self.board, self.dice, self.reward, self.terminated, self.truncated, self.info
+
+    # -- a trained policy as this env's opponent (the reference's `opponent_policy=<path>`, envs/ewn.py:265-296)
+    def supports_step_vs(self):
+        """step() / rollout() against a model are served (ewn_step_vs / ewn_step_k_vs): cube_layer 3 on 5x5 and 7x7, Philox dice or
+        MT19937-compat dice without auto-reset.  The env's own opponent settings do not matter to it."""
+        return self.tables is not None and self.lib.ewn_step_vs_supported(C.byref(self.cfg)) == 1
+
+    def set_opponent_model(self, params, deterministic=True, noise_key=0, opponent_action=None):
+        """Make the actor-critic whose flat fp32 device vector is `params` (a2c.ActorCritic.flat_parameters() order) this env's
+        opponent: it sees np.rot90(-board, 2) with its own dice and plays its argmax (deterministic=False: a Gumbel-max sample under
+        noise_key); a move that leaves the board or asks for a missing cube ends the episode with reward 0 ("Invalid move for
+        opponent!").  While a model is set step() runs ewn_step_vs, rollout() ewn_step_k_vs, rollout_policy() / eval_policy() take it as
+        their default opponent_params, and agent_rollout() raises.  opponent_action: optional int8 [N, 3] that step() fills with the
+        opponent's {dice, flag, dir} ({0, 0, 0}: it did not move).  params=None gives the env its own opponent back.  The vector is
+        read at every call, not copied: keep it alive and unchanged while it plays."""
+        if params is None:
+            if opponent_action is not None:
+                raise ValueError("set_opponent_model: opponent_action needs params")
+            self._opp_model = None
+            return
+        act3 = None
+        if opponent_action is not None:
+            if not (isinstance(opponent_action, torch.Tensor) and opponent_action.dtype == torch.int8 and opponent_action.is_cuda
+                    and opponent_action.is_contiguous() and tuple(opponent_action.shape) == (self.N, 3)):
+                raise ValueError("set_opponent_model: opponent_action must be a contiguous int8 device tensor of shape [%d, 3], got %s" % (
+                    self.N, _describe(opponent_action)))
+            act3 = opponent_action.unsqueeze(0)
+        st = self._opponent_struct("set_opponent_model", 1, params, deterministic, noise_key, act3)
+        if not self.supports_step_vs():
+            raise _lib.EwnError("set_opponent_model: ewn_step_vs does not serve this env (cube_layer 3 on 5x5 / 7x7 with the search "
+                                "tables; MT19937-compat dice only without auto-reset)")
+        if self.random_action is not None:
+            raise _lib.EwnError("set_opponent_model: want_random_action=True is ewn_step's fused RandomAgent; against a model use "
+                                "rollout(K, agent='random') or sample_legal_actions()")
+        self._opp_model = (params, st, bool(deterministic), int(noise_key), opponent_action)
+
+    def _model_opponent(self, what, K, action):
+        """the set model as the ewn_opponent_policy of a K-step call"""
+        params, _, det, nk, _ = self._opp_model
+        return self._opponent_struct(what, K, params, det, nk, action)
 
     # -- RandomAgent as a stateless device policy (classical_policies/random_policy.py:11-15)
     def sample_legal_actions(self, step, out=None, step_tensor=None):
@@ -167,9 +212,11 @@ class VecEWN:
 
     # -- K env steps per launch with an in-engine agent (ewn_step_k; eval_minimax.py:16-50's loop on the device)
     def supports_rollout(self, agent="random", agent_max_depth=3):
-        """True when ewn_step_k exists for this configuration and agent"""
+        """True when ewn_step_k (with a model set: ewn_step_k_vs) exists for this configuration and agent"""
         if agent not in AGENT:
             return False
+        if self._opp_model is not None:
+            return self.tables is not None and self.lib.ewn_step_k_vs_supported(C.byref(self.cfg), AGENT[agent], int(agent_max_depth)) == 1
         if self.tables is None and int(self.lib.ewn_tables_bytes(self.S, self.L)) > 0:
             return False           # use_tables=False on a table geometry (geometries WITHOUT a table image run the generic K-step kernel)
         return self.lib.ewn_step_k_supported(C.byref(self.cfg), AGENT[agent], int(agent_max_depth)) == 1
@@ -212,11 +259,15 @@ class VecEWN:
         return {"return_sum": torch.zeros(N, dtype=torch.float64, device=dev), "n_steps": torch.zeros(N, dtype=torch.int32, device=dev),
                 "n_episodes": torch.zeros(N, dtype=torch.int32, device=dev), "n_wins": torch.zeros(N, dtype=torch.int32, device=dev)}
 
-    def rollout(self, K, agent="random", agent_max_depth=3, traj=None, totals=None):
+    def rollout(self, K, agent="random", agent_max_depth=3, traj=None, totals=None, opponent_action=None):
         """Play K steps of every lane in one launch, the agent being RandomAgent ("random"), ExpectiMinimaxAgent(agent_max_depth)
         ("minimax") or env.action_space.sample() ("sample": all six actions, illegal ones included).
-        traj: dict from alloc_rollout (first dimension >= K) or None; totals: dict from alloc_totals or None."""
+        traj: dict from alloc_rollout (first dimension >= K) or None; totals: dict from alloc_totals or None.
+        With a model set (set_opponent_model) the opponent is the model (ewn_step_k_vs); opponent_action: optional int8 [>= K, N, 3],
+        its {dice, flag, dir} per step."""
         traj, totals = traj or {}, totals or {}
+        if opponent_action is not None and self._opp_model is None:
+            raise ValueError("rollout: opponent_action needs a model opponent (set_opponent_model)")
         _no_initial_obs(traj)
         for v in traj.values():
             assert v.shape[0] >= K and v.shape[1] == self.N
@@ -225,6 +276,11 @@ class VecEWN:
                             _ptr(col("terminated")), _ptr(col("truncated")), _ptr(col("info")),
                             _ptr(totals.get("return_sum")), _ptr(totals.get("n_steps")), _ptr(totals.get("n_episodes")),
                             _ptr(totals.get("n_wins")), _ptr(traj.get("record")))
+        if self._opp_model is not None:
+            opp = self._model_opponent("rollout", K, opponent_action)
+            check(self.lib.ewn_step_k_vs(C.byref(self.cfg), C.byref(self._st), int(K), AGENT[agent], int(agent_max_depth), C.byref(opp),
+                                         C.byref(out), _stream()), "ewn_step_k_vs")
+            return self.board, self.dice
         check(self.lib.ewn_step_k(C.byref(self.cfg), C.byref(self._st), int(K), AGENT[agent], int(agent_max_depth), C.byref(out),
                                   _stream()), "ewn_step_k")
         return self.board, self.dice
@@ -233,6 +289,8 @@ class VecEWN:
         """rollout(K, ...) with its arguments marshalled ONCE: returns a zero-argument callable that enqueues the launch (for loops that
         repeat the same call: one C-ABI call per invocation, a few microseconds of host time instead of the ~20 of building the structs).
         The buffers of traj / totals must stay alive as long as the callable is used."""
+        if self._opp_model is not None:
+            raise _lib.EwnError("bind_rollout: a model opponent is set; use rollout() (ewn_step_k_vs)")
         traj, totals = traj or {}, totals or {}
         _no_initial_obs(traj)
         for v in traj.values():
@@ -295,10 +353,13 @@ class VecEWN:
         traj, totals = traj or {}, totals or {}
         assert params.dtype == torch.float32 and params.is_contiguous() and params.numel() == self.policy_param_count()
         N = self.N
-        if opponent_params is None and opponent_action is not None:
+        if opponent_params is None and self._opp_model is not None:   # the set model plays, as set_opponent_model configured it
+            opp = self._model_opponent("rollout_policy", K, opponent_action)
+        elif opponent_params is None and opponent_action is not None:
             raise ValueError("rollout_policy: opponent_action needs opponent_params")
-        opp = None if opponent_params is None else self._opponent_struct("rollout_policy", K, opponent_params, opponent_deterministic,
-                                                                         opponent_noise_key, opponent_action)
+        else:
+            opp = None if opponent_params is None else self._opponent_struct("rollout_policy", K, opponent_params, opponent_deterministic,
+                                                                             opponent_noise_key, opponent_action)
         for name, t, shape in (("logits", logits, (N, 5)), ("value", value, (N,)), ("noise", noise, (N, 5))):
             if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_cuda and t.is_contiguous()
                                       and t.dim() == 1 + len(shape) and t.shape[0] >= K and tuple(t.shape[1:]) == shape):
@@ -347,10 +408,13 @@ class VecEWN:
         unless opponent_deterministic=False); opponent_action: optional int8 [>= K, N, 3], the opponent's {dice, flag, dir} of the steps a
         lane plays ({0, 0, 0}: it did not move)."""
         N = self.N
-        if opponent_params is None and opponent_action is not None:
+        if opponent_params is None and self._opp_model is not None:   # the set model plays, as set_opponent_model configured it
+            opp = self._model_opponent("eval_policy", K, opponent_action)
+        elif opponent_params is None and opponent_action is not None:
             raise ValueError("eval_policy: opponent_action needs opponent_params")
-        opp = None if opponent_params is None else self._opponent_struct("eval_policy", K, opponent_params, opponent_deterministic,
-                                                                         opponent_noise_key, opponent_action)
+        else:
+            opp = None if opponent_params is None else self._opponent_struct("eval_policy", K, opponent_params, opponent_deterministic,
+                                                                             opponent_noise_key, opponent_action)
         if not (isinstance(params, torch.Tensor) and params.dtype == torch.float32 and params.is_cuda and params.is_contiguous()
                 and params.dim() == 1 and params.numel() == self.policy_param_count()):
             raise ValueError("eval_policy: params must be a contiguous float32 device vector of %d elements, got %s" % (
@@ -398,7 +462,7 @@ class VecEWN:
         """True when ewn_step_k_agent serves this configuration and agent (an MCTS agent against RandomAgent, minimax or MCTS; a
         minimax agent against MCTS); decided on the host"""
         a = self._agent_struct(agent)
-        if a is None:
+        if a is None or self._opp_model is not None:
             return False
         if self.tables is None and (a.kind == AGENT["minimax"] or self.cfg.opponent_kind == OPP["minimax"]):
             return False           # use_tables=False: the minimax side searches from its table image
@@ -410,6 +474,9 @@ class VecEWN:
         key_t = key + 0x9E3779B97F4A7C15 * (step_base + k + 1) mod 2^64: tournament.evaluate's per-step loop at t = step_base + k.
         traj: dict from alloc_rollout (columns or record layout, first dimension >= K) or None; totals: dict from alloc_totals or None
         (ADDED to).  Buffers of the wrong shape, dtype or layout raise ValueError before anything is launched."""
+        if self._opp_model is not None:
+            raise _lib.EwnError("agent_rollout: a model opponent is set and ewn_step_k_agent has none; step the MCTS agent ply by ply "
+                                "(predict_mcts + step), or use rollout() for the random / minimax agents")
         a = self._agent_struct(agent, step_base, key)
         if a is None:
             raise ValueError("agent_rollout: agent must be {\"kind\": \"mcts\"|\"minimax\", ...} with a known heuristic, got %r" % (agent,))

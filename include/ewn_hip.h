@@ -359,6 +359,26 @@ int ewn_policy_eval_vs_supported(const ewn_config *cfg);
 int ewn_policy_eval_vs(const ewn_config *cfg, const ewn_state *st, int K, const float *params, const ewn_opponent_policy *opp,
                        const ewn_rollout_out *out, void *stream);
 
+/* ---- ... for ANY agent: the env `EinsteinWuerfeltNichtEnv(opponent_policy=<path>)` as eval_random.py, eval_minimax.py, play_gym.py and
+ * an SB3 wrapper step it.  The same opponent (view, argmax / Gumbel-max, noise word, illegal-move rule, nothing drawn from the dice
+ * stream) as above; a step here is, bit for bit, the step ewn_step_k_selfplay / ewn_policy_eval_vs make for the same agent action.
+ * cube_layer 3, board sizes 5 and 7, plain or cfg->shaped; Philox dice, or MT19937-compat dice without auto-reset (with it:
+ * EWN_EUNSUPPORTED).  The opponent fields of cfg are not read; ewn_state.tables is needed.  One kernel launch, no scratch. */
+/* 1 if ewn_step_vs serves cfg, 0 if not, < 0 for an invalid cfg; decided on the host */
+int ewn_step_vs_supported(const ewn_config *cfg);
+/* ewn_step's contract (actions, frozen lanes, auto-reset, terminal observation) with the opponent = opp; out->random_action must be
+ * NULL (EWN_EINVAL).  opp->action, if given, is [N][3]: written for every lane ({0, 0, 0}: the opponent did not move). */
+int ewn_step_vs(const ewn_config *cfg, const ewn_state *st, const int8_t *actions, const ewn_opponent_policy *opp, const ewn_step_out *out,
+                void *stream);
+/* 1 if ewn_step_k_vs serves (cfg, agent), 0 if not (EWN_AGENT_MLP: that is ewn_step_k_selfplay; EWN_AGENT_MCTS: not built), < 0 for
+ * an invalid cfg or agent.  EWN_AGENT_RANDOM / EWN_AGENT_SAMPLE, or EWN_AGENT_MINIMAX ('hybrid') of agent_max_depth 1..6. */
+int ewn_step_k_vs_supported(const ewn_config *cfg, int agent_kind, int agent_max_depth);
+/* ewn_step_k's contract (columns and / or records, totals ADDED to, out may be NULL) with the opponent = opp, plain or shaped: the same
+ * as K ewn_step_vs calls with the agent's action fed back.  The stand-in agents draw from ewn_step_k's hash stream; the minimax agent
+ * plays ewn_predict_minimax on the observation.  opp->action, if given, is [K][N][3], written for every lane. */
+int ewn_step_k_vs(const ewn_config *cfg, const ewn_state *st, int K, int agent_kind, int agent_max_depth,
+                  const ewn_opponent_policy *opp, const ewn_rollout_out *out, void *stream);
+
 /* ---- the A2C update on the records of ewn_step_k_policy: stable_baselines3 A2C.train as train.py:35-63, 148 configures it ----
  * (n-step returns = GAE with lambda 1, no advantage normalisation; loss = policy gradient + vf_coef * MSE(returns, values) +
  * ent_coef * (-entropy), a mean over the n_steps x lanes batch; clip_grad_norm_(max_grad_norm); RMSprop(alpha, eps)).  SB3 is not
