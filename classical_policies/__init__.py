@@ -10,6 +10,7 @@ from classical_policies.random_policy import RandomAgent
 from classical_policies.minimax import ExpectiMinimaxAgent, AlphaZeroMinimaxAgent
 from classical_policies.mcts import MctsAgent
 from classical_policies.alpha_zero import AlphaZeroAgent
+from classical_policies.model import ModelAgent
 
 # the names BASELINE.json's north_star uses
 RandomPolicy = RandomAgent
@@ -17,4 +18,4 @@ MiniMaxPolicy = ExpectiMinimaxAgent
 MCTSPolicy = MctsAgent
 
 __all__ = ["PolicyBase", "RandomAgent", "ExpectiMinimaxAgent", "MctsAgent", "AlphaZeroAgent", "AlphaZeroMinimaxAgent",
-           "RandomPolicy", "MiniMaxPolicy", "MCTSPolicy"]
+           "RandomPolicy", "MiniMaxPolicy", "MCTSPolicy", "ModelAgent"]

@@ -1,0 +1,64 @@
+"""ModelAgent: a trained actor-critic behind the `predict(obs) -> (action, None)` surface of this package -- what
+`model.predict(obs, deterministic=True)` is upstream (train.py:89, eval_A2C.py), ply by ply against an env.  The network runs in
+libewn_hip.so (ewn_predict_policy: the rollout kernel's arithmetic on the matrix pipe), not in torch."""
+import os
+
+import numpy as np
+
+from classical_policies.base import PolicyBase, obs_arrays
+
+
+class ModelAgent(PolicyBase):
+    def __init__(self, model_or_path, board_size=5, cube_layer=3, deterministic=True, key=0):
+        """model_or_path: an a2c.ActorCritic, its flat fp32 parameter vector (ActorCritic.flat_parameters() order), or the path of a
+        checkpoint of any of the trainers (tournament.load_policy).  deterministic=False samples from the policy, keyed by `key`."""
+        import torch
+        import ewn_gym_amd
+        from ewn_gym_amd.tournament import flat_policy_params, load_policy
+        self._ea = ewn_gym_amd
+        self.board_size, self.cube_layer, self.deterministic, self.key = board_size, cube_layer, bool(deterministic), int(key)
+        self._calls = 0
+        n = ewn_gym_amd._lib.load().ewn_policy_param_count(board_size, cube_layer)
+        if n < 0:
+            raise ValueError("ModelAgent: no policy network for %dx%d boards with cube_layer %d" % (board_size, board_size, cube_layer))
+        m = model_or_path
+        if isinstance(m, (str, os.PathLike)):
+            m = load_policy(m, board_size, cube_layer)         # raises ValueError on a checkpoint of another geometry
+        if isinstance(m, torch.Tensor):
+            params = m.detach().reshape(-1).to(torch.float32)
+        else:
+            if getattr(m, "S", board_size) != board_size:
+                raise ValueError("ModelAgent: the model plays %dx%d boards, the agent is built for %dx%d" % (m.S, m.S, board_size, board_size))
+            params = flat_policy_params(m)
+        if params.numel() != n:
+            raise ValueError("ModelAgent: %d parameters, a %dx%d actor-critic has %d" % (params.numel(), board_size, board_size, n))
+        self.params = params.to("cuda").contiguous()
+
+    def _on_device(self, boards, dice):
+        import torch
+        S = self.board_size
+        b = torch.as_tensor(np.asarray(boards) if not isinstance(boards, torch.Tensor) else boards)
+        d = torch.as_tensor(np.asarray(dice) if not isinstance(dice, torch.Tensor) else dice)
+        if b.numel() % (S * S) != 0 or b.shape[-1] != S:
+            raise ValueError("ModelAgent: boards of shape %s, the model plays %dx%d" % (list(b.shape), S, S))
+        dev = self.params.device
+        return b.to(dev).to(torch.int8).reshape(-1, S, S).contiguous(), d.to(dev).to(torch.int8).reshape(-1).contiguous()
+
+    def predict_batch(self, boards, dice, key=None, obs_id=None, return_logits=False, return_value=False):
+        """boards (M,S,S), dice (M,) device or host arrays -> int8 (M,2) device tensor (with the logits / values if asked for).  A
+        sampling agent draws under `key`; None: the agent's key advanced once per call, so that repeated calls differ."""
+        b, d = self._on_device(boards, dice)
+        if key is None:
+            key = (self.key + self._calls * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+            self._calls += 1
+        return self._ea.predict_policy(b, d, self.params, deterministic=self.deterministic, key=key, obs_id=obs_id,
+                                       return_logits=return_logits, return_value=return_value, cube_layer=self.cube_layer)
+
+    def predict(self, obs, **kwargs):
+        b, d = obs_arrays(obs)
+        return self.predict_batch(b, d)[0].cpu().numpy(), None     # np.array([flag, dir]), like SB3's model.predict
+
+    def policy_fn(self):
+        """(board, dice, t) -> actions, the callable tournament.evaluate takes; a sampling agent keys step t as
+        key + 0x9E3779B97F4A7C15 * (t + 1), like the MCTS agent of tournament._policy"""
+        return lambda b, d, t: self.predict_batch(b, d, key=(self.key + 0x9E3779B97F4A7C15 * (t + 1)) & 0xFFFFFFFFFFFFFFFF)

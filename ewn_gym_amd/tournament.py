@@ -44,6 +44,11 @@ def _policy(spec, cube_layer, key):
         return lambda b, d, t: predict_mcts(b, d, spec.get("num_simulations", 10), spec.get("num_env_copies", 5),
                                             key=(key + 0x9E3779B97F4A7C15 * (t + 1)) & 0xFFFFFFFFFFFFFFFF,
                                             cube_layer=cube_layer)[0]
+    if kind == "mlp":           # the model's policy through ewn_predict_policy; evaluate() itself plays this kind on its own paths
+        from classical_policies.model import ModelAgent
+        model = spec["model"]
+        return ModelAgent(model, board_size=getattr(model, "S", spec.get("board_size", 5)), cube_layer=cube_layer,
+                          deterministic=spec.get("deterministic", True), key=key).policy_fn()
     raise ValueError("unknown agent kind %r" % kind)
 
 

@@ -7,6 +7,7 @@ MiniMaxHeuristicEnv (envs/ewn.py, envs/training_ewn.py): the single-game drop-in
 classes in the top-level `envs` package are N=1 views of it.
 """
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -636,3 +637,63 @@ def predict_mcts(boards, dice, num_simulations=10, num_env_copies=5, key=0, obs_
     check(lib.ewn_predict_mcts(S, cube_layer, M, _ptr(b), _ptr(d), int(num_simulations), int(num_env_copies),
                                C.c_uint64(key), _ptr(ids), _ptr(acts), _ptr(wins), _stream()), "ewn_predict_mcts")
     return acts, wins
+
+
+def _policy_input(name, x, dtype, shape, dev):
+    """a tensor is taken as it is and must already be what the kernel reads; anything else (numpy, lists) is copied to the device"""
+    if not isinstance(x, torch.Tensor):
+        x = torch.as_tensor(np.asarray(x)).to(dtype).reshape(shape)
+        return x if dev.type != "cuda" else x.to(dev)
+    if x.dtype != dtype or x.numel() != math.prod(shape) or not x.is_contiguous():
+        raise ValueError("predict_policy: %s must be a contiguous %s tensor of %s elements, got %s" % (
+            name, str(dtype).replace("torch.", ""), " x ".join(map(str, shape)), _describe(x)))
+    return x.reshape(shape)
+
+
+def predict_policy(boards, dice, params, deterministic=True, key=0, obs_id=None, uniforms=None, return_logits=False, return_value=False,
+                   cube_layer=3):
+    """The trained actor-critic's predict on M observations (ewn_predict_policy; model.predict(obs, deterministic=True) upstream):
+    boards [S, S] or [M, S, S], dice [M], params the flat fp32 device vector of a2c.ActorCritic.flat_parameters() -> actions int8
+    [M, 2], or the tuple (actions, logits float32 [M, 5] if return_logits, value float32 [M] if return_value).  The network is the
+    rollout kernel's: a rollout_policy step replayed on its observation with its recorded noise row as `uniforms` returns the recorded
+    logits, value and action bit for bit.  deterministic=False samples (Gumbel-max): from `uniforms` (float32 [M, 5] in (0, 1)) when
+    given, else from a hash of (key, obs_id[m]) -- obs_id None: m.  Tensors are read in place and must be contiguous device tensors of
+    the kernel's dtype (int8 observations, float32 params / uniforms, int32 or uint32 obs_id); host arrays are copied over.  Anything
+    else raises ValueError before a launch."""
+    lib = _lib.load()
+    shp = tuple(boards.shape) if isinstance(boards, torch.Tensor) else np.asarray(boards).shape
+    if len(shp) == 2:
+        shp = (1,) + tuple(shp)
+    if len(shp) != 3 or shp[1] != shp[2]:
+        raise ValueError("predict_policy: boards must have shape [S, S] or [M, S, S], got %s" % (list(shp),))
+    M, S = int(shp[0]), int(shp[1])
+    P = lib.ewn_policy_param_count(S, int(cube_layer))
+    if P < 0:
+        raise ValueError("predict_policy: no policy network for %dx%d boards with cube_layer %d (served: cube_layer 3 on 5x5 and 7x7)" % (
+            S, S, cube_layer))
+    if not (isinstance(params, torch.Tensor) and params.dtype == torch.float32 and params.is_contiguous() and params.numel() == P):
+        raise ValueError("predict_policy: params must be a contiguous float32 tensor of %d elements (the %dx%d actor-critic), got %s" % (
+            P, S, S, _describe(params)))
+    dev = params.device
+    b = _policy_input("boards", boards, torch.int8, (M, S, S), dev)
+    d = _policy_input("dice", dice, torch.int8, (M,), dev)
+    u = None if uniforms is None else _policy_input("uniforms", uniforms, torch.float32, (M, 5), dev)
+    ids = None
+    if obs_id is not None:
+        if isinstance(obs_id, torch.Tensor) and obs_id.dtype == torch.uint32:
+            obs_id = obs_id.view(torch.int32)
+        if not isinstance(obs_id, torch.Tensor):
+            obs_id = np.asarray(obs_id).astype(np.uint32).view(np.int32)
+        ids = _policy_input("obs_id", obs_id, torch.int32, (M,), dev)
+    for name, t in (("params", params), ("boards", b), ("dice", d), ("uniforms", u), ("obs_id", ids)):
+        if t is not None and not (t.is_cuda and t.device == dev):
+            raise ValueError("predict_policy: %s must live on the GPU that holds params (%s), got %s" % (name, dev, _describe(t)))
+    acts = torch.zeros((M, 2), dtype=torch.int8, device=dev)
+    logits = torch.zeros((M, 5), dtype=torch.float32, device=dev) if return_logits else None
+    value = torch.zeros(M, dtype=torch.float32, device=dev) if return_value else None
+    with torch.cuda.device(dev):
+        check(lib.ewn_predict_policy(S, int(cube_layer), M, _ptr(b), _ptr(d), _ptr(params), int(bool(deterministic)),
+                                     C.c_uint64(int(key) & 0xFFFFFFFFFFFFFFFF), _ptr(ids), _ptr(u), _ptr(acts), _ptr(logits), _ptr(value),
+                                     _stream()), "ewn_predict_policy")
+    out = (acts,) + ((logits,) if return_logits else ()) + ((value,) if return_value else ())
+    return out[0] if len(out) == 1 else out

@@ -505,6 +505,22 @@ int ewn_predict_mcts(int board_size, int cube_layer, int M, const int8_t *boards
                      int num_simulations, int num_env_copies, uint64_t key, const uint32_t *obs_id, int8_t *actions,
                      int32_t *wins, void *stream);
 
+/* The trained actor-critic as a stateless policy: model.predict(obs, deterministic=True) of the reference (train.py:89, eval_A2C.py)
+ * on M observations, no env behind it.  params: the ewn_policy.params layout, [ewn_policy_param_count()] fp32; served where that
+ * count is (cube_layer 3, board sizes 5 and 7), EWN_EUNSUPPORTED elsewhere.  actions [M][2] is required; logits [M][5] and value [M]
+ * may be NULL (the value body runs only when value is given).  The network is ewn_step_k_policy's, operand for operand: a recorded
+ * step of a rollout, replayed here on its observation with its ewn_policy.noise row as `uniforms`, returns the recorded logits, value
+ * and action bit for bit.  deterministic != 0: a[0] = l1 > l0, a[1] = first argmax of (l2, l3, l4).  Otherwise the Gumbel-max of
+ * l[i] - ln(-ln u[i]): u = uniforms[m][0..4] (fp32 in (0, 1)) if given, else u[i] = ((fmix32(w + (i + 1) * 0x9E3779B9) >> 9) + 0.5) / 2^23
+ * with w = fmix32(fmix32(fmix32(id) ^ fmix32((uint32_t)key ^ 'AGNT') ^ (uint32_t)(key >> 32) * 0x85ebca6b) ^ 'PRED'), id = obs_id[m]
+ * (NULL = m), fmix32 the MurmurHash3 finaliser: a function of (key, id) alone, not of M or of the order of the observations.
+ * dice outside 1..6 is the caller's error (it selects no memory: the one-hot is arithmetic).  One kernel launch on `stream`, no
+ * allocation, no synchronisation, no scratch; M == 0 is EWN_OK without a launch.  Reads exactly boards[0 .. M*S*S), dice[0 .. M),
+ * obs_id[0 .. M), uniforms[0 .. 5 M); writes exactly the M rows of the outputs given. */
+int ewn_predict_policy(int board_size, int cube_layer, int M, const int8_t *boards, const int8_t *dice, const float *params,
+                       int deterministic, uint64_t key, const uint32_t *obs_id, const float *uniforms, int8_t *actions, float *logits,
+                       float *value, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
