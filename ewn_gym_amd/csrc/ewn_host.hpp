@@ -99,6 +99,9 @@ static inline int launch_status()
     return hipGetLastError() == hipSuccess ? EWN_OK : EWN_ELAUNCH;
 }
 
+// the answer of an ewn_*_supported call from a plan's code: 1 served, 0 not served, a negative code for a malformed configuration
+static inline int supported_answer(int rc) { return rc == EWN_OK ? 1 : (rc == EWN_EUNSUPPORTED ? 0 : rc); }
+
 // specialised depth-3 tables exist for cube_layer 3 and board sizes whose distinct leaf values fit 10-bit ranks
 static inline int64_t fast_tables_bytes(int S, int L)
 {

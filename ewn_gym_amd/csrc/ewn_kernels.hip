@@ -1213,12 +1213,12 @@ int ewn_step_k_supported(const ewn_config *cfg, int agent_kind, int agent_max_de
     Geom g; KCfg k;
     int rc = check_cfg(cfg, g, k);
     if (rc) return rc;
-    if (agent_kind == EWN_AGENT_MLP) { rc = ewn_policy_supported(cfg, g); return rc == EWN_OK ? 1 : (rc == EWN_EUNSUPPORTED ? 0 : rc); } // ewn_step_k_policy
-    if (cfg->opponent_kind == EWN_OPP_MCTS) { rc = mcts_rollout_plan(cfg, g, agent_kind); return rc == EWN_OK ? 1 : (rc == EWN_EUNSUPPORTED ? 0 : rc); }
+    if (agent_kind == EWN_AGENT_MLP) return supported_answer(ewn_policy_supported(cfg, g)); // ewn_step_k_policy
+    if (cfg->opponent_kind == EWN_OPP_MCTS) return supported_answer(mcts_rollout_plan(cfg, g, agent_kind));
     if (generic_rollout_plan(cfg, g, agent_kind) == EWN_OK) return 1;
     int T, opp, agent;
     rc = rollout_plan(cfg, g, k, agent_kind, agent_max_depth, T, opp, agent);
-    return rc == EWN_OK ? 1 : (rc == EWN_EUNSUPPORTED ? 0 : rc);
+    return supported_answer(rc);
 }
 
 int ewn_step_k(const ewn_config *cfg, const ewn_state *st, int K, int agent_kind, int agent_max_depth, const ewn_rollout_out *out,
@@ -1323,7 +1323,7 @@ int ewn_step_k_agent_supported(const ewn_config *cfg, const ewn_agent *agent)
     if (!agent) return EWN_ENULL;
     int ag; bool om;
     rc = agent_rollout_plan(cfg, g, agent, ag, om);
-    return rc == EWN_OK ? 1 : (rc == EWN_EUNSUPPORTED ? 0 : rc);
+    return supported_answer(rc);
 }
 
 int ewn_step_k_agent(const ewn_config *cfg, const ewn_state *st, int K, const ewn_agent *agent, const ewn_rollout_out *out, void *stream)

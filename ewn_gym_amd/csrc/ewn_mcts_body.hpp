@@ -256,15 +256,9 @@ EWN_DEV void rollout_mcts_body(const Geom &g, const KCfg &c, const KState &st, c
             if (!__syncthreads_or(active ? 1 : 0)) break;   // block-uniform: every game of the block is over, nothing is left to write
             const int wave = tid >> 6, wl = tid & 63;
             if (wave < NG::tiles(mr.gpb)) {
-                constexpr int CELLS = TS * TS;
                 const int j = wl & 31, h = wl >> 5, dj = odice[wave * 32 + j];
                 const int8_t *sj = oslot + (wave * 32 + j) * NG::OSTR + 8 * h;
-                auto xb = [&](int kb) {
-                    const uint2 v = *(const uint2 *)(sj + 16 * kb);
-                    u32x4 x = mlp3_bytes_operand(v.x, v.y);
-                    if (16 * kb + 15 >= CELLS && 16 * kb < CELLS + 7) x = mlp3_onehot(x, CELLS + dj - 1 - (16 * kb + 8 * h));
-                    return x;
-                };
+                auto xb = [&](int kb) { return pol_obs_operand<TS>(sj, kb, h, dj); };
                 f32x16 h1[2], h2[2];
                 float lo[MLP_NA];
                 mlp3_forward<TS, MLP_NA>(Wpi, wl, xb, h1, h2, lo);
@@ -274,8 +268,8 @@ EWN_DEV void rollout_mcts_body(const Geom &g, const KCfg &c, const KState &st, c
             if (active) {   // k_rollout_mlp's deterministic pick: strict comparisons, so ties break the same way
                 const float4 lg = *(const float4 *)(LG + tid * 8);
                 const float lg4 = LG[tid * 8 + 4];
-                aflag = lg.y > lg.x ? 1 : 0;
-                adir = lg.w > lg.z ? (lg4 > lg.w ? 2 : 1) : (lg4 > lg.z ? 2 : 0);
+                aflag = pol_pick_flag(lg.x, lg.y);
+                adir = pol_pick_dir(lg.z, lg.w, lg4);
             }
         }
         if (active) {

@@ -146,6 +146,44 @@ EWN_DEV u32x4 mlp3_onehot(u32x4 o, int hot)
     return o;
 }
 
+// The feature operand of k-block kb for lane half h out of a game's zero-padded LDS slot (the `xb` of mlp3_forward in every kernel that
+// runs the net on the observation as it stands): sj = the slot + 8 h, so the eight bytes at sj + 16 kb are features 16 kb + 8 h .. + 7
+// (board cells; the slot's bytes past the board are zero), and the dice one-hot (features CELLS .. CELLS + 6, dj = the game's dice) is
+// set by arithmetic: a dice outside 1 .. 6 sets nothing or another slot, it indexes nothing
+template <int S>
+EWN_DEV u32x4 pol_obs_operand(const int8_t *sj, int kb, int h, int dj)
+{
+    constexpr int CELLS = S * S;
+    const uint2 v = *(const uint2 *)(sj + 16 * kb);
+    u32x4 o = mlp3_bytes_operand(v.x, v.y);
+    if (16 * kb + 15 >= CELLS && 16 * kb < CELLS + 7) o = mlp3_onehot(o, CELLS + dj - 1 - (16 * kb + 8 * h));
+    return o;
+}
+// The same of the opponent's canonical view, np.rot90(-board, 2) (envs/ewn.py:289-296): view cell f = -(slot byte CELLS - 1 - f);
+// sj = the slot itself.  The eight features 16 kb + 8 h + jj of a lane are the slot bytes CELLS - 1 - (16 kb + 8 h) downwards: three
+// aligned words (CELLS = 1 mod 4 on both boards), two v_perm_b32 that reverse them, then the agent's conversion, negated.  Features
+// from CELLS on have no cell: masked (their bytes would lie in front of the slot); the one-hot is the opponent's dice.
+template <int S>
+EWN_DEV u32x4 pol_opp_operand(const int8_t *sj, int kb, int h, int dj)
+{
+    constexpr int CELLS = S * S;
+    static_assert(CELLS % 8 == 1, "the reversed view's word alignment");
+    const int base = CELLS - 9 - (16 * kb + 8 * h);              // a multiple of 4; >= 0: all eight features are cells
+    const u32 *wp = (const u32 *)(sj + (base < 0 ? 0 : base));
+    const u32 d0 = wp[0], d1 = wp[1], d2 = wp[2];               // slot bytes base .. base + 11 (< the slot's stride)
+    u32 lo = __builtin_amdgcn_perm(d2, d1, 0x01020304u), hi = __builtin_amdgcn_perm(d1, d0, 0x01020304u);
+    if (base < 0) { lo = base == -8 ? (d0 & 0xFFu) : 0u; hi = 0u; }   // feature CELLS - 1 = slot byte 0 alone, or nothing
+    u32x4 o = mlp3_bytes_operand_neg(lo, hi);
+    if (16 * kb + 15 >= CELLS && 16 * kb < CELLS + 7) o = mlp3_onehot(o, CELLS + dj - 1 - (16 * kb + 8 * h));
+    return o;
+}
+
+// The action out of the five (noised) logits, MultiDiscrete([2, 3]): a[0] = argmax(z0, z1), a[1] = argmax(z2, z3, z4).  Strict
+// comparisons, so ties break towards the lower index at every site.  Value-returning on purpose: the form with reference
+// out-parameters compiles the rollout kernels to a different schedule.
+EWN_DEV int pol_pick_flag(float z0, float z1) { return z1 > z0 ? 1 : 0; }
+EWN_DEV int pol_pick_dir(float z2, float z3, float z4) { return z3 > z2 ? (z4 > z3 ? 2 : 1) : (z4 > z2 ? 2 : 0); }
+
 // one net's forward parameters, PyTorch layout in global memory -> the LDS image.  net: 0 policy (5 logits), 1 value (1 output).
 template <int S>
 EWN_DEV void mlp3_pack_fwd(int8_t *img, const float *P, int net, int tid, int nthreads)

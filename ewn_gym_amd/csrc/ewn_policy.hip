@@ -1,9 +1,7 @@
 // ewn_policy.hip -- the policy-driven rollout (ewn_step_k_policy), its evaluation form (ewn_policy_eval: instances in
 // ewn_policy_eval.hip), the fused A2C update (ewn_a2c_*) and the fused PPO update (ewn_ppo_*): kernels in ewn_policy.hpp /
 // ewn_a2c.hpp / ewn_ppo.hpp, C ABI here.
-#include "ewn_host.hpp"
-#include "ewn_lds.hpp"
-#include "ewn_policy.hpp"
+#include "ewn_policy_host.hpp"
 #include "ewn_a2c.hpp"
 #include "ewn_a2c3.hpp"
 #include "ewn_ppo.hpp"
@@ -11,7 +9,7 @@
 // which instantiation serves the configuration: opp 0 minimax (table image, max_depth 1-4), 1 RandomAgent
 static int policy_plan(const ewn_config *cfg, const Geom &g, int &opp)
 {
-    if (fast_tables_bytes(g.S, g.L) <= 0 || (g.S != 5 && g.S != 7)) return EWN_EUNSUPPORTED;
+    if (!pol_geometry(g)) return EWN_EUNSUPPORTED;
     if (cfg->rng_kind != EWN_RNG_PHILOX) return EWN_EUNSUPPORTED;
     if (cfg->opponent_kind == EWN_OPP_RANDOM) opp = 1;
     else if (cfg->opponent_kind == EWN_OPP_MINIMAX && fast_heur_lean(cfg->heuristic) && cfg->max_depth <= 4) opp = 0;
@@ -39,26 +37,16 @@ template <int S, int OPP, int NT, int TRJ = 0>
 static int pol_launch(const PolCfg &pc, const PolBuf &pb, hipStream_t s)
 {
     if constexpr (TRJ == 0 && OPP == 0) {
-        // the trainer's call (FusedA2CTrainer): records from the initial observation on + the reward column, nothing else per step,
-        // sampled actions, no value output -- the instance that knows it at compile time
-        const bool trainer = pb.t_rec && pb.t_reward && pc.rec0 && !pc.want_value && !pc.deterministic && !pb.t_board && !pb.t_dice && !pb.t_action
-                             && !pb.t_term && !pb.t_trunc && !pb.t_info && !pb.t_logits && !pb.t_value && !pb.t_noise;
-        if (trainer) return pol_launch<S, OPP, NT, 1>(pc, pb, s);
+        if (pol_trainer_call(pc, pb)) return pol_launch<S, OPP, NT, 1>(pc, pb, s);   // the instance that knows it at compile time
     }
-    auto kern = k_rollout_mlp<S, OPP, NT, TRJ>;
-    const size_t lds = pol_lds_bytes<S, NT>(pc.want_value != 0);
-    if (lds > 160 * 1024) return EWN_EUNSUPPORTED;
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return EWN_ELAUNCH;
-    const int gpb = NT / 2;
-    kern<<<dim3((unsigned)((pc.N + gpb - 1) / gpb)), NT, lds, s>>>(pc, pb);
-    return launch_status();
+    return pol_launch_games(k_rollout_mlp<S, OPP, NT, TRJ>, pc.N, NT, pol_lds_bytes<S, NT>(pc.want_value != 0), s, pc, pb);
 }
 
 template <int S>
 static int pol_dispatch(const PolCfg &pc, const PolBuf &pb, int opp, hipStream_t s)
 {
     // 512 threads (256 games) per block where the block's LDS fits the CU, else 256
-    const bool big = pol_lds_bytes<S, 512>(pc.want_value != 0) <= 160 * 1024;
+    const bool big = pol_lds_bytes<S, 512>(pc.want_value != 0) <= POL_LDS_MAX;
     if (opp == 0) return big ? pol_launch<S, 0, 512>(pc, pb, s) : pol_launch<S, 0, 256>(pc, pb, s);
     return big ? pol_launch<S, 1, 512>(pc, pb, s) : pol_launch<S, 1, 256>(pc, pb, s);
 }
@@ -69,28 +57,12 @@ int ewn_step_k_policy(const ewn_config *cfg, const ewn_state *st, int K, const e
     int rc = check_cfg(cfg, g, k);
     if (rc) return rc;
     if (K < 1) return EWN_EINVAL;
-    if (!st || !st->board || !st->dice || !st->done || !st->rng || !st->tables || !pol || !pol->params) return EWN_ENULL;
-    if (cfg->shaped && (!st->prev_score || !st->tolerance)) return EWN_ENULL;
+    if (pol_state_missing(st, true, cfg->shaped != 0) || !pol || !pol->params) return EWN_ENULL;
     int opp;
     rc = policy_plan(cfg, g, opp);
     if (rc) return rc;
-    PolCfg pc;
-    pc.N = k.N; pc.autoreset = k.autoreset; pc.lane_offset = k.lane_offset; pc.depth = k.depth; pc.K = K;
-    pc.shaped = k.shaped; pc.refresh = k.refresh; pc.deterministic = pol->deterministic ? 1 : 0; pc.want_value = pol->value ? 1 : 0;
-    pc.rec0 = pol->record_initial_obs ? 1 : 0;
-    pc.seed_stride = k.seed_stride; pc.W = k.W; pc.reward = k.reward; pc.illegal_reward = k.illegal_reward;
-    pc.key = k.key; pc.noise_key = pol->noise_key;
-    PolBuf pb;
-    memset(&pb, 0, sizeof(pb));
-    pb.board = st->board; pb.dice = st->dice; pb.done = st->done; pb.rng = st->rng; pb.prev_score = st->prev_score; pb.tolerance = st->tolerance;
-    pb.tables = opp == 1 ? st->tables : fast_image(st->tables, g.S, g.L, cfg->max_depth, cfg->heuristic);
-    pb.params = pol->params;
-    pb.t_logits = pol->logits; pb.t_value = pol->value; pb.t_noise = pol->noise;
-    if (out) {
-        pb.t_board = out->board; pb.t_dice = out->dice; pb.t_action = out->action; pb.t_reward = out->reward;
-        pb.t_term = out->terminated; pb.t_trunc = out->truncated; pb.t_info = out->info; pb.t_rec = out->record;
-        pb.ret_sum = out->return_sum; pb.n_steps = out->n_steps; pb.n_episodes = out->n_episodes; pb.n_wins = out->n_wins;
-    }
+    const PolCfg pc = pol_cfg(k, K, pol);
+    const PolBuf pb = pol_buf_rollout(st, opp == 1 ? st->tables : fast_image(st->tables, g.S, g.L, cfg->max_depth, cfg->heuristic), pol, out);
     hipStream_t s = (hipStream_t)stream;
     return g.S == 5 ? pol_dispatch<5>(pc, pb, opp, s) : pol_dispatch<7>(pc, pb, opp, s);
 }
@@ -101,7 +73,7 @@ int ewn_step_k_policy(const ewn_config *cfg, const ewn_state *st, int K, const e
 // 1 RandomAgent, 2 minimax max_depth 5 / 6 (the closed form: the (level, count) images only, not 'two_min_dist')
 static int policy_eval_plan(const ewn_config *cfg, const Geom &g, int &opp)
 {
-    if (fast_tables_bytes(g.S, g.L) <= 0 || (g.S != 5 && g.S != 7)) return EWN_EUNSUPPORTED;
+    if (!pol_geometry(g)) return EWN_EUNSUPPORTED;
     if (cfg->shaped || cfg->autoreset) return EWN_EUNSUPPORTED;
     if (cfg->opponent_kind == EWN_OPP_RANDOM) opp = 1;
     else if (cfg->opponent_kind == EWN_OPP_MINIMAX && fast_heur_lean(cfg->heuristic)) opp = cfg->max_depth > 4 ? 2 : 0;
@@ -116,7 +88,7 @@ int ewn_policy_eval_supported(const ewn_config *cfg)
     if (rc) return rc;
     int opp;
     rc = policy_eval_plan(cfg, g, opp);
-    return rc == EWN_OK ? 1 : (rc == EWN_EUNSUPPORTED ? 0 : rc);
+    return supported_answer(rc);
 }
 
 int ewn_policy_eval(const ewn_config *cfg, const ewn_state *st, int K, const float *params, const ewn_rollout_out *out, void *stream)
@@ -125,24 +97,15 @@ int ewn_policy_eval(const ewn_config *cfg, const ewn_state *st, int K, const flo
     int rc = check_cfg(cfg, g, k);
     if (rc) return rc;
     if (K < 1) return EWN_EINVAL;
-    if (!st || !st->board || !st->dice || !st->done || !st->rng || !st->tables || !params || !out) return EWN_ENULL;
-    if (!out->return_sum || !out->n_steps || !out->n_episodes || !out->n_wins) return EWN_ENULL;
-    if (out->board || out->dice || out->reward || out->terminated || out->truncated || out->info || out->record) return EWN_EINVAL;
+    if (pol_state_missing(st, true, false) || !params || !out) return EWN_ENULL;
+    rc = pol_eval_out_check(out);
+    if (rc) return rc;
     int opp;
     rc = policy_eval_plan(cfg, g, opp);
     if (rc) return rc;
-    PolCfg pc;
-    memset(&pc, 0, sizeof(pc));
-    pc.N = k.N; pc.lane_offset = k.lane_offset; pc.depth = k.depth; pc.K = K;
-    pc.deterministic = 1;
-    pc.seed_stride = k.seed_stride; pc.W = k.W; pc.reward = k.reward; pc.illegal_reward = k.illegal_reward; pc.key = k.key;
-    PolBuf pb;
-    memset(&pb, 0, sizeof(pb));
-    pb.board = st->board; pb.dice = st->dice; pb.done = st->done; pb.rng = st->rng;
-    pb.tables = opp == 1 ? st->tables : fast_image(st->tables, g.S, g.L, cfg->max_depth, cfg->heuristic);
-    pb.params = params;
-    pb.t_action = out->action;
-    pb.ret_sum = out->return_sum; pb.n_steps = out->n_steps; pb.n_episodes = out->n_episodes; pb.n_wins = out->n_wins;
+    const PolCfg pc = pol_cfg(k, K, nullptr);
+    PolBuf pb = pol_buf(st, opp == 1 ? st->tables : fast_image(st->tables, g.S, g.L, cfg->max_depth, cfg->heuristic), params);
+    pb.t_action = out->action; pol_fill_totals(pb, out);
     return ewn_launch_policy_eval(pc, pb, g.S, opp, k.rng_kind, (hipStream_t)stream);
 }
 
@@ -186,11 +149,11 @@ template <int S>
 static int a2c_grad_launch(const A2cCfg &ac, A2cBuf ab, float *grad, hipStream_t s)
 {
     constexpr size_t lds = A2c3Geo<S>::lds_bytes();
-    static_assert(lds <= 160 * 1024, "weight images + the gradient image must fit the CU's LDS");
+    static_assert(lds <= POL_LDS_MAX, "weight images + the gradient image must fit the CU's LDS");
     auto kv = k_a2c_grad3<S, 1>;
     auto kp = k_a2c_grad3<S, 0>;
-    if (hipFuncSetAttribute((const void *)kv, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return EWN_ELAUNCH;
-    if (hipFuncSetAttribute((const void *)kp, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return EWN_ELAUNCH;
+    if (hipFuncSetAttribute((const void *)kv, hipFuncAttributeMaxDynamicSharedMemorySize, POL_LDS_MAX) != hipSuccess) return EWN_ELAUNCH;
+    if (hipFuncSetAttribute((const void *)kp, hipFuncAttributeMaxDynamicSharedMemorySize, POL_LDS_MAX) != hipSuccess) return EWN_ELAUNCH;
     const int blocks = a2c_blocks(ac.N, 4);
     kv<<<blocks, 256, lds, s>>>(ac, ab);         // value pass first: it leaves the advantages for the policy pass
     kp<<<blocks, 256, lds, s>>>(ac, ab);
@@ -274,12 +237,8 @@ int ewn_ppo_prepare(const ewn_config *cfg, int K, const uint8_t *record, const d
     const PpoCfg c = ppo_cfg(k, K, 1, hp);
     const int blocks = (k.N + 127) / 128;            // one 32-lane tile per wave
     hipStream_t s = (hipStream_t)stream;
-    auto launch = [&](auto kern, size_t lds) {
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return EWN_ELAUNCH;
-        kern<<<blocks, 256, lds, s>>>(c, b);
-        return launch_status();
-    };
-    static_assert(2 * Mlp3Geo<7>::FWD_BYTES <= 160 * 1024, "both nets' forward images must fit the CU's LDS");
+    auto launch = [&](auto kern, size_t lds) { return pol_launch_kernel(kern, blocks, 256, lds, 0, POL_LDS_MAX, s, c, b); };   // always opts in
+    static_assert(2 * Mlp3Geo<7>::FWD_BYTES <= POL_LDS_MAX, "both nets' forward images must fit the CU's LDS");
     return g.S == 5 ? launch(k_ppo_prepare<5>, 2 * (size_t)Mlp3Geo<5>::FWD_BYTES) : launch(k_ppo_prepare<7>, 2 * (size_t)Mlp3Geo<7>::FWD_BYTES);
 }
 
@@ -300,11 +259,11 @@ template <int S>
 static int ppo_grad_launch(const PpoCfg &c, const PpoBuf &b, float *grad, hipStream_t s)
 {
     constexpr size_t lds = Ppo3Geo<S>::lds_bytes();
-    static_assert(lds <= 160 * 1024, "weight images + the gradient image must fit the CU's LDS");
+    static_assert(lds <= POL_LDS_MAX, "weight images + the gradient image must fit the CU's LDS");
     auto kv = k_ppo_grad3<S, 1>;
     auto kp = k_ppo_grad3<S, 0>;
-    if (hipFuncSetAttribute((const void *)kv, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return EWN_ELAUNCH;
-    if (hipFuncSetAttribute((const void *)kp, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return EWN_ELAUNCH;
+    if (hipFuncSetAttribute((const void *)kv, hipFuncAttributeMaxDynamicSharedMemorySize, POL_LDS_MAX) != hipSuccess) return EWN_ELAUNCH;
+    if (hipFuncSetAttribute((const void *)kp, hipFuncAttributeMaxDynamicSharedMemorySize, POL_LDS_MAX) != hipSuccess) return EWN_ELAUNCH;
     const int blocks = a2c_blocks(c.B, 4);
     kv<<<blocks, 256, lds, s>>>(c, b);           // value pass first: it leaves the advantage sums for the policy pass
     kp<<<blocks, 256, lds, s>>>(c, b);

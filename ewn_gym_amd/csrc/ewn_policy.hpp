@@ -70,10 +70,18 @@ EWN_DEV float pol_uniform(u32 w0, int i)
 
 // ln x on v_log_f32 (log2, ~1 ulp) -- the Gumbel noise -ln(-ln u) ten times per game and step; the library logf is ~20 instructions each
 EWN_DEV float pol_log(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
+// Gumbel noise of a uniform in (0, 1)
+EWN_DEV float pol_gumbel(float u) { return -pol_log(-pol_log(u)); }
 
 // the policy opponent's noise word: fmix32(the step's agent hash under (key ^ its noise_key) ^ this), so an opponent that shares the
 // agent's noise_key still draws its own noise
 #define POL_OPP_SALT 0x4F505031u
+// ... taken before the step moves the stream, and keyed like the agent's own word (k_rollout_mlp: episode, draws so far, lane, tolerance
+// left).  k_rollout_mlp_vs and k_step_vs both call this, so a step of one is a step of the other, bit for bit
+EWN_DEV u32 pol_opp_noise_word(u32 seed_mix, int tol, u32 draws, int lane_global, u64 key, u64 opp_noise_key)
+{
+    return fmix32(agent_hash(seed_mix ^ ((u32)tol * 0x632BE5ABu), draws, (u32)lane_global, key ^ opp_noise_key) ^ POL_OPP_SALT);
+}
 
 // OPP 0: minimax max_depth 1-4 on a (level, count) table image; 1: RandomAgent; 2: minimax max_depth 5 / 6 on such an image (the
 // closed form, d5_dispatch; TRJ 2 only).  RNGK: the dice, 1 Philox; 0 MT19937-compat (TRJ 2 only: one episode per lane).

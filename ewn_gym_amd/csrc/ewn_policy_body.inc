@@ -1,7 +1,10 @@
 // ewn_policy_body.inc -- the text of k_rollout_mlp / k_rollout_mlp_vs (ewn_policy.hpp), included into both kernels: in scope are the
 // template parameters S, OPP, NT, TRJ, RNGK and the arguments PolCfg c, PolBuf B, PolOpp O.  One text, so that the policy opponent is
 // the same env step as every other opponent; included, not called, so that k_rollout_mlp stays the kernel it was, instruction for
-// instruction (a wrapper around an inlined body compiles to a different register allocation).
+// instruction (a wrapper around an inlined body compiles to a different register allocation).  With k_step_vs and k_predict_mlp it
+// shares small value-returning helpers only (pol_obs_operand, pol_opp_operand, pol_pick_*, pol_gumbel, pol_opp_noise_word): those compile
+// to the instructions of the text written out (diff the units' device assembly against the parent's after touching one); the whole
+// opponent-network block as a helper, or a pick through reference parameters, do not.
     constexpr bool FIX = TRJ == 1, EV = TRJ == 2;
     static_assert(EV || (OPP != 2 && RNGK == 1), "the depth-5 opponent and the MT19937-compat dice are evaluation-only");
     const bool want_value = !FIX && !EV && c.want_value, deterministic = EV || (!FIX && c.deterministic), rec0 = FIX || (!EV && c.rec0);
@@ -70,12 +73,7 @@
             const int j = lane & 31, h = lane >> 5;
             const int dj = __builtin_amdgcn_ds_bpermute((2 * j) << 2, dice);          // game j's dice (its lanes are 2 j, 2 j + 1)
             const int8_t *sj = slots + (wave * 32 + j) * STR + 8 * h;
-            auto xb = [&](int kb) {
-                const uint2 v = *(const uint2 *)(sj + 16 * kb);
-                u32x4 o = mlp3_bytes_operand(v.x, v.y);
-                if (16 * kb + 15 >= CELLS && 16 * kb < CELLS + 7) o = mlp3_onehot(o, CELLS + dj - 1 - (16 * kb + 8 * h));
-                return o;
-            };
+            auto xb = [&](int kb) { return pol_obs_operand<S>(sj, kb, h, dj); };
             f32x16 h1[2], h2[2];
             float lo[MLP_NA];
             mlp3_forward<S, MLP_NA>(Wpi, lane, xb, h1, h2, lo);
@@ -97,13 +95,13 @@
         // the policy opponent's noise: the same hash under its own key, taken here, before the step moves the stream
         u32 w0o = 0u;
         if constexpr (OPP == 3)
-            w0o = fmix32(agent_hash(r.seed_mix() ^ ((u32)tol * 0x632BE5ABu), r.draws(), (u32)(c.lane_offset + game), c.key ^ O.noise_key) ^ POL_OPP_SALT);
+            w0o = pol_opp_noise_word(r.seed_mix(), tol, r.draws(), c.lane_offset + game, c.key, O.noise_key);
         float u[5], gn[5];
         #pragma unroll
-        for (int i = 0; i < 5; i++) { u[i] = pol_uniform(w0, i); gn[i] = deterministic ? 0.0f : -pol_log(-pol_log(u[i])); }
+        for (int i = 0; i < 5; i++) { u[i] = pol_uniform(w0, i); gn[i] = deterministic ? 0.0f : pol_gumbel(u[i]); }
         const float z0 = lg.x + gn[0], z1 = lg.y + gn[1], z2 = lg.z + gn[2], z3 = lg.w + gn[3], z4 = lg4 + gn[4];
-        const int aflag = z1 > z0 ? 1 : 0;
-        const int adir = z3 > z2 ? (z4 > z3 ? 2 : 1) : (z4 > z2 ? 2 : 0);
+        const int aflag = pol_pick_flag(z0, z1);
+        const int adir = pol_pick_dir(z2, z3, z4);
         if (!FIX && !EV && writer) {
             const size_t o = (size_t)kstep * c.N + game;
             if (B.t_logits) { float *p = B.t_logits + o * 5; p[0] = lg.x; p[1] = lg.y; p[2] = lg.z; p[3] = lg.w; p[4] = lg4; }
@@ -139,26 +137,13 @@
         if constexpr (OPP == 2) d5_dispatch<S, T>(Tb, s, dice, sub, oflag, odir);
         const int odice = dice;                            // the opponent's dice where it replies
         if constexpr (OPP == 3) {
-            // ---- the opponent's network on its canonical view, np.rot90(-board, 2) (envs/ewn.py:289-296): view cell f = -(slot byte
-            // CELLS - 1 - f).  The eight features 16 kb + 8 h + jj of a lane are the slot bytes CELLS - 1 - (16 kb + 8 h) downwards: three
-            // aligned words (CELLS = 1 mod 4 on both boards), two v_perm_b32 that reverse them, then the agent's conversion, negated.
-            // Features from CELLS on have no cell: masked (their bytes would lie in front of the slot); the one-hot is the opponent's dice.
-            static_assert(CELLS % 8 == 1, "the reversed view's word alignment");
+            // ---- the opponent's network on its canonical view of the same slots (pol_opp_operand, ewn_mlp3.hpp)
             __builtin_amdgcn_wave_barrier();               // the agent's moves are in the slots
             {
                 const int j = lane & 31, h = lane >> 5;
                 const int dj = __builtin_amdgcn_ds_bpermute((2 * j) << 2, dice);
                 const int8_t *sj = slots + (wave * 32 + j) * STR;
-                auto xo = [&](int kb) {
-                    const int base = CELLS - 9 - (16 * kb + 8 * h);              // a multiple of 4; >= 0: all eight features are cells
-                    const u32 *wp = (const u32 *)(sj + (base < 0 ? 0 : base));
-                    const u32 d0 = wp[0], d1 = wp[1], d2 = wp[2];               // slot bytes base .. base + 11 (< STR)
-                    u32 lo = __builtin_amdgcn_perm(d2, d1, 0x01020304u), hi = __builtin_amdgcn_perm(d1, d0, 0x01020304u);
-                    if (base < 0) { lo = base == -8 ? (d0 & 0xFFu) : 0u; hi = 0u; }   // feature CELLS - 1 = slot byte 0 alone, or nothing
-                    u32x4 o = mlp3_bytes_operand_neg(lo, hi);
-                    if (16 * kb + 15 >= CELLS && 16 * kb < CELLS + 7) o = mlp3_onehot(o, CELLS + dj - 1 - (16 * kb + 8 * h));
-                    return o;
-                };
+                auto xo = [&](int kb) { return pol_opp_operand<S>(sj, kb, h, dj); };
                 f32x16 h1[2], h2[2];
                 float lo[MLP_NA];
                 mlp3_forward<S, MLP_NA>(Wop, lane, xo, h1, h2, lo);
@@ -170,10 +155,10 @@
             __builtin_amdgcn_wave_barrier();
             float on[5];
             #pragma unroll
-            for (int i = 0; i < 5; i++) on[i] = O.deterministic ? 0.0f : -pol_log(-pol_log(pol_uniform(w0o, i)));
+            for (int i = 0; i < 5; i++) on[i] = O.deterministic ? 0.0f : pol_gumbel(pol_uniform(w0o, i));
             const float y0 = og.x + on[0], y1 = og.y + on[1], y2 = og.z + on[2], y3 = og.w + on[3], y4 = og4 + on[4];
-            oflag = y1 > y0 ? 1 : 0;
-            odir = y3 > y2 ? (y4 > y3 ? 2 : 1) : (y4 > y2 ? 2 : 0);
+            oflag = pol_pick_flag(y0, y1);
+            odir = pol_pick_dir(y2, y3, y4);
         }
         if (reply) {
             const u32 e = pk_sel<S>(Tb, s.posP, dice);

@@ -1,36 +1,20 @@
 // ewn_policy_eval.hip -- the evaluation instances of the policy-driven rollout (k_rollout_mlp<S, OPP, NT, 2, RNGK>, ewn_policy.hpp):
 // a deterministic policy against RandomAgent or minimax max_depth 1-6 on MT19937-compat or Philox dice, one episode per lane.  The C ABI
 // (ewn_policy_eval / ewn_policy_eval_supported) is in ewn_policy.hip; this unit holds the launcher and the kernel instances.
-#include "ewn_host.hpp"
-#include "ewn_lds.hpp"
-#include "ewn_policy.hpp"
-
-// Threads per block by lane count.  An evaluation is small (20 .. 1 024 games) and its step is one wave's latency chain (network,
-// then the opponent's search), so the waves are spread one per CU while that is possible: 64 threads = 32 games per block up to
-// 8 192 games (256 blocks), 256 threads beyond.  EWN_EVAL_NT (64 / 256) overrides it (tuning; DESIGN.md has the measurements).
-static int eval_threads(int n_games)
-{
-    static const int forced = [] { const char *e = getenv("EWN_EVAL_NT"); return e ? atoi(e) : 0; }();
-    if (forced == 64 || forced == 256) return forced;
-    return n_games <= 8192 ? 64 : 256;
-}
+#include "ewn_policy_host.hpp"
 
 template <int S, int OPP, int RNGK, int NT>
 static int eval_launch(const PolCfg &pc, const PolBuf &pb, hipStream_t s)
 {
-    auto kern = k_rollout_mlp<S, OPP, NT, 2, RNGK>;
     constexpr size_t lds = pol_lds_bytes<S, NT>(false);
-    static_assert(lds <= 160 * 1024, "table image + weight image + the block's game slots must fit the CU's LDS");
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return EWN_ELAUNCH;
-    constexpr int gpb = NT / 2;
-    kern<<<dim3((unsigned)((pc.N + gpb - 1) / gpb)), NT, lds, s>>>(pc, pb);
-    return launch_status();
+    static_assert(lds <= POL_LDS_MAX, "table image + weight image + the block's game slots must fit the CU's LDS");
+    return pol_launch_games(k_rollout_mlp<S, OPP, NT, 2, RNGK>, pc.N, NT, lds, s, pc, pb);
 }
 
 template <int S, int OPP, int RNGK>
 static int eval_by_nt(const PolCfg &pc, const PolBuf &pb, hipStream_t s)
 {
-    return eval_threads(pc.N) == 64 ? eval_launch<S, OPP, RNGK, 64>(pc, pb, s) : eval_launch<S, OPP, RNGK, 256>(pc, pb, s);
+    return pol_eval_threads(pc.N) == 64 ? eval_launch<S, OPP, RNGK, 64>(pc, pb, s) : eval_launch<S, OPP, RNGK, 256>(pc, pb, s);
 }
 
 template <int S, int OPP>

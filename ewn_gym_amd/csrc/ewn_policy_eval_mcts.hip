@@ -4,6 +4,7 @@
 // code is built with -fno-slp-vectorize (build.py FILE_FLAGS, ewn_mlp3.hpp) and ewn_kernels.hip, where the body's other instances
 // live, is not.
 #include "ewn_mcts_body.hpp"
+#include "ewn_policy_host.hpp"
 
 template <int S>
 __global__ __launch_bounds__(BS) void k_policy_eval_mcts(Geom g, KCfg c, KState st, MctsRoll mr, RollBuf B, AgentRoll ar)
@@ -25,18 +26,14 @@ static int policy_eval_mcts_plan(const ewn_config *cfg, const Geom &g)
 template <int S>
 static int policy_eval_mcts_launch(const Geom &g, const KCfg &k, const KState &ks, const MctsRoll &mr, const RollBuf &rb, hipStream_t s)
 {
-    auto kern = k_policy_eval_mcts<S>;
     constexpr size_t worst = MctsNet<S>::lds_bytes(MR_GPB, RecGeo<S>::STR);
     static_assert(worst <= 128 * 1024, "boards + weight image + observation slots must fit the CU's LDS beside the body's static arrays");
     const size_t lds = MctsNet<S>::lds_bytes(mr.gpb, mr.strd);
     // A kernel gets 64 KB of LDS by default.  ewn_step_k_agent asks for more above 64 KB of dynamic LDS; here the threshold is 48 KB,
     // so that the body's static arrays (9 616 bytes) never decide whether a launch fits: 7x7 from 32 games per block on is below
-    // 64 KB dynamic and above it with them.  Asked per launch, as there: the attribute belongs to the current device's copy of the
-    // kernel, and a process may drive several devices; it is a host-side call.
-    if (lds > 48 * 1024 && hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)worst) != hipSuccess) return EWN_ELAUNCH;
+    // 64 KB dynamic and above it with them.
     const AgentRoll ar = { 0, 0, 0, 3, 0u, 0ull };
-    kern<<<dim3((unsigned)((k.N + mr.gpb - 1) / mr.gpb)), BS, lds, s>>>(g, k, ks, mr, rb, ar);
-    return launch_status();
+    return pol_launch_kernel(k_policy_eval_mcts<S>, (unsigned)((k.N + mr.gpb - 1) / mr.gpb), BS, lds, 48 * 1024, worst, s, g, k, ks, mr, rb, ar);
 }
 
 int ewn_policy_eval_mcts_supported(const ewn_config *cfg)
@@ -44,7 +41,7 @@ int ewn_policy_eval_mcts_supported(const ewn_config *cfg)
     Geom g; KCfg k;
     int rc = check_cfg(cfg, g, k);
     if (rc == EWN_OK) rc = policy_eval_mcts_plan(cfg, g);   // a configuration check_cfg itself calls unsupported (cube_layer 2) answers 0 too
-    return rc == EWN_OK ? 1 : (rc == EWN_EUNSUPPORTED ? 0 : rc);
+    return supported_answer(rc);
 }
 
 int ewn_policy_eval_mcts(const ewn_config *cfg, const ewn_state *st, int K, const float *params, const ewn_rollout_out *out, void *stream)
@@ -53,16 +50,15 @@ int ewn_policy_eval_mcts(const ewn_config *cfg, const ewn_state *st, int K, cons
     int rc = check_cfg(cfg, g, k);
     if (rc) return rc;
     if (K < 1) return EWN_EINVAL;
-    if (!st || !st->board || !st->dice || !st->done || !st->rng || !params || !out) return EWN_ENULL;
-    if (!out->return_sum || !out->n_steps || !out->n_episodes || !out->n_wins) return EWN_ENULL;
-    if (out->board || out->dice || out->reward || out->terminated || out->truncated || out->info || out->record) return EWN_EINVAL;
+    if (pol_state_missing(st, false, false) || !params || !out) return EWN_ENULL;    // the MCTS opponent reads no table image
+    rc = pol_eval_out_check(out);
+    if (rc) return rc;
     rc = policy_eval_mcts_plan(cfg, g);
     if (rc) return rc;
     RollBuf rb;
     memset(&rb, 0, sizeof(rb));
     rb.agent_tables = params;   // the agent's image: AG 3 has no search table, the body packs the actor-critic's parameters from here
-    rb.t_action = out->action;
-    rb.ret_sum = out->return_sum; rb.n_steps = out->n_steps; rb.n_episodes = out->n_episodes; rb.n_wins = out->n_wins;
+    rb.t_action = out->action; pol_fill_totals(rb, out);
     // games per block: ewn_step_k_agent's rule for its MCTS-only instances (8 .. MR_GPB, about 2 048 blocks)
     int gpb = 8;
     while (gpb < MR_GPB && (long long)k.N / (2 * gpb) >= 2048) gpb *= 2;

@@ -2,23 +2,19 @@
 // ewn_predict_* family that the reference's `model.predict(obs, deterministic=True)` (train.py:89, eval_A2C.py) maps to: M boards and
 // M dice in, M actions (and optionally the logits and the value) out, no env behind it.  The arithmetic is the rollout kernel's
 // (k_rollout_mlp, ewn_policy_body.inc): the same LDS weight images (mlp3_pack_fwd), the same feature operands out of zero-padded
-// per-sample slots (mlp3_bytes_operand + mlp3_onehot), the same mlp3_forward, the same comparison chain -- so a recorded rollout step
-// replayed here gives the recorded logits, value and action bit for bit.  A unit of its own: nothing of the existing units is touched,
-// they compile to the code they were.
+// per-sample slots (pol_obs_operand), the same mlp3_forward, the same noise and pick (pol_gumbel, pol_pick_flag / pol_pick_dir) -- so a
+// recorded rollout step replayed here gives the recorded logits, value and action bit for bit.
 //
 // Sampling (deterministic == 0): action = Gumbel-max of z[i] = logit[i] + g[i], g[i] = -ln(-ln u[i]) on pol_log, i = 0 .. 4.
 //   uniforms given:  u[i] = uniforms[m][i] as it is (a rollout's recorded ewn_policy.noise replays its actions)
 //   otherwise:       u[i] = pol_uniform(w, i),  w = fmix32(agent_hash(0, 0, id, key) ^ PRED_POL_SALT),  id = obs_id ? obs_id[m] : m
 // i.e. w = fmix32(fmix32(fmix32(id) ^ fmix32((u32)key ^ 'AGNT') ^ (u32)(key >> 32) * 0x85ebca6b) ^ 'PRED') and
 // u[i] = ((fmix32(w + (i + 1) * 0x9E3779B9) >> 9) + 0.5) / 2^23: a pure function of (key, id), whatever M, the tiling or the order.
-#include "ewn_host.hpp"
-#include "ewn_lds.hpp"
-#include "ewn_policy.hpp"
+#include "ewn_policy_host.hpp"
 
 #define PRED_POL_SALT 0x50524544u   // 'PRED': the salt of this call's noise word; no other user of `key` hashes with it
 #define PRED_NT 256                  // threads per block: four waves, one 32-observation tile each per trip
 #define PRED_MAX_BLOCKS 256          // one block per CU (A2C_MAX_BLOCKS' reasoning); more tiles than that are walked grid-stride
-#define PRED_LDS_MAX (160 * 1024)
 
 // LDS of k_predict_mlp<S, .>: weight image(s) | per wave 32 slots of RecGeo<S>::STR bytes | per wave the tile's packed boards (+ 16:
 // the slot builder reads whole dwords, the last of them up to 7 bytes past the last board)
@@ -94,15 +90,9 @@ __global__ __launch_bounds__(PRED_NT, 1) void k_predict_mlp(int M, int determini
         }
         __builtin_amdgcn_wave_barrier();
         // ---- the network(s): the tile's 32 samples are the 32 columns of the MFMA tiles (sample j = column j, both lane halves); lane
-        // (j, h) turns bytes 16 kb + 8 h .. + 7 of sample j's slot into the eight bf16 of its k-block operand and sets the dice one-hot
-        // (features CELLS .. CELLS + 6) by arithmetic: a dice outside 1 .. 6 sets nothing or another slot, it indexes nothing
+        // (j, h) turns bytes 16 kb + 8 h .. + 7 of sample j's slot into the eight bf16 of its k-block operand (pol_obs_operand)
         const int8_t *sj = slots + j * STR + 8 * h;
-        auto xb = [&](int kb) {
-            const uint2 v = *(const uint2 *)(sj + 16 * kb);
-            u32x4 o = mlp3_bytes_operand(v.x, v.y);
-            if (16 * kb + 15 >= CELLS && 16 * kb < CELLS + 7) o = mlp3_onehot(o, CELLS + dj - 1 - (16 * kb + 8 * h));
-            return o;
-        };
+        auto xb = [&](int kb) { return pol_obs_operand<S>(sj, kb, h, dj); };
         f32x16 h1[2], h2[2];
         float lo[MLP_NA];
         mlp3_forward<S, MLP_NA>(Wpi, lane, xb, h1, h2, lo);
@@ -117,12 +107,12 @@ __global__ __launch_bounds__(PRED_NT, 1) void k_predict_mlp(int M, int determini
                 #pragma unroll
                 for (int i = 0; i < 5; i++) {
                     const float u = B.uniforms ? B.uniforms[m * 5 + i] : pol_uniform(w, i);
-                    gn[i] = -pol_log(-pol_log(u));
+                    gn[i] = pol_gumbel(u);
                 }
             }
             const float z0 = lo[0] + gn[0], z1 = lo[1] + gn[1], z2 = lo[2] + gn[2], z3 = lo[3] + gn[3], z4 = lo[4] + gn[4];
-            const int aflag = z1 > z0 ? 1 : 0;
-            const int adir = z3 > z2 ? (z4 > z3 ? 2 : 1) : (z4 > z2 ? 2 : 0);
+            const int aflag = pol_pick_flag(z0, z1);
+            const int adir = pol_pick_dir(z2, z3, z4);
             B.actions[m * 2] = (int8_t)aflag; B.actions[m * 2 + 1] = (int8_t)adir;
             if (B.logits) { float *p = B.logits + m * 5; p[0] = lo[0]; p[1] = lo[1]; p[2] = lo[2]; p[3] = lo[3]; p[4] = lo[4]; }
             if constexpr (WANT_VALUE) B.value[m] = vo[0];
@@ -133,14 +123,11 @@ __global__ __launch_bounds__(PRED_NT, 1) void k_predict_mlp(int M, int determini
 template <int S, bool WANT_VALUE>
 static int pred_launch(int M, int deterministic, u64 key, const PredBuf &pb, hipStream_t s)
 {
-    auto kern = k_predict_mlp<S, WANT_VALUE>;
     constexpr size_t lds = PredGeo<S>::lds_bytes(WANT_VALUE);
-    static_assert(lds <= PRED_LDS_MAX, "weight image(s) + the block's slots and staging must fit the CU's LDS");
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, PRED_LDS_MAX) != hipSuccess)
-        return EWN_ELAUNCH;
+    static_assert(lds <= POL_LDS_MAX, "weight image(s) + the block's slots and staging must fit the CU's LDS");
     const int tiles = (M - 1) / 32 + 1, need = (tiles + PredGeo<S>::NW - 1) / PredGeo<S>::NW;
-    kern<<<dim3((unsigned)(need < PRED_MAX_BLOCKS ? need : PRED_MAX_BLOCKS)), PRED_NT, lds, s>>>(M, deterministic, key, pb);
-    return launch_status();
+    return pol_launch_kernel(k_predict_mlp<S, WANT_VALUE>, (unsigned)(need < PRED_MAX_BLOCKS ? need : PRED_MAX_BLOCKS), PRED_NT, lds, 64 * 1024,
+                             POL_LDS_MAX, s, M, deterministic, key, pb);
 }
 
 template <int S>

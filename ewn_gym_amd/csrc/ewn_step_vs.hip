@@ -1,28 +1,15 @@
 // ewn_step_vs.hip -- a trained policy as the env's opponent for ANY agent (the reference's `opponent_policy=<path>` env,
 // envs/ewn.py:265-296): k_step_vs (ewn_step_vs.hpp), one step per launch with the caller's actions (C ABI: ewn_step_vs, ewn_step's
-// contract) and K steps per launch with a classical agent (ewn_step_k_vs, ewn_step_k's contract).  A unit of its own: nothing of the
-// existing units is touched, they compile to the code they were.
-#include "ewn_host.hpp"
-#include "ewn_lds.hpp"
+// contract) and K steps per launch with a classical agent (ewn_step_k_vs, ewn_step_k's contract).  A unit of its own for the build's
+// sake (the instances compile in parallel); the host plumbing it shares with the other policy units is ewn_policy_host.hpp.
+#include "ewn_policy_host.hpp"
 #include "ewn_step_vs.hpp"
-
-#define SV_LDS_MAX (160 * 1024)
-
-// the configurations the calls serve; the opponent fields of cfg are not read (vs_check's substitution, ewn_selfplay.hip: the copy handed
-// to check_cfg names RandomAgent)
-static int sv_check(const ewn_config *cfg, ewn_config &c2, Geom &g, KCfg &k)
-{
-    if (!cfg) return EWN_ENULL;
-    c2 = *cfg;
-    c2.opponent_kind = EWN_OPP_RANDOM; c2.max_depth = 1; c2.heuristic = EWN_H_HYBRID; c2.num_simulations = 1; c2.num_env_copies = 1;
-    return check_cfg(&c2, g, k);
-}
 
 // cube_layer 3 on 5x5 and 7x7, plain or shaped; Philox dice, or MT19937-compat dice without auto-reset (the windows of an auto-resetting
 // lane are rebuilt between launches by ewn_step's own machinery, which this kernel does not carry)
 static int sv_plan(const ewn_config *cfg, const Geom &g)
 {
-    if (fast_tables_bytes(g.S, g.L) <= 0 || (g.S != 5 && g.S != 7)) return EWN_EUNSUPPORTED;
+    if (!pol_geometry(g)) return EWN_EUNSUPPORTED;
     if (cfg->rng_kind == EWN_RNG_MT19937 && cfg->autoreset) return EWN_EUNSUPPORTED;
     return EWN_OK;
 }
@@ -41,30 +28,18 @@ static int sv_agent(int agent_kind, int agent_max_depth, int &ag)
     return EWN_EINVAL;
 }
 
-// ewn_policy_eval's rule (ewn_policy_eval.hip): one wave per block up to 8 192 games, 256 threads beyond; EWN_EVAL_NT overrides it
-static int sv_threads(int n_games)
-{
-    static const int forced = [] { const char *e = getenv("EWN_EVAL_NT"); return e ? atoi(e) : 0; }();
-    if (forced == 64 || forced == 256) return forced;
-    return n_games <= 8192 ? 64 : 256;
-}
-
 template <int S, int NT, int AG, int RNGK>
 static int sv_launch(const VsCfg &vc, const VsBuf &vb, hipStream_t s)
 {
-    auto kern = k_step_vs<S, NT, AG, RNGK>;
     constexpr size_t lds = pol_lds_bytes<S, NT>(false);
-    static_assert(lds <= SV_LDS_MAX, "table image + one weight image + the block's game slots must fit the CU's LDS");
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SV_LDS_MAX) != hipSuccess) return EWN_ELAUNCH;
-    constexpr int gpb = NT / 2;
-    kern<<<dim3((unsigned)((vc.N + gpb - 1) / gpb)), NT, lds, s>>>(vc, vb);
-    return launch_status();
+    static_assert(lds <= POL_LDS_MAX, "table image + one weight image + the block's game slots must fit the CU's LDS");
+    return pol_launch_games(k_step_vs<S, NT, AG, RNGK>, vc.N, NT, lds, s, vc, vb);
 }
 
 template <int S, int AG, int RNGK>
 static int sv_by_nt(const VsCfg &vc, const VsBuf &vb, hipStream_t s)
 {
-    return sv_threads(vc.N) == 64 ? sv_launch<S, 64, AG, RNGK>(vc, vb, s) : sv_launch<S, 256, AG, RNGK>(vc, vb, s);
+    return pol_eval_threads(vc.N) == 64 ? sv_launch<S, 64, AG, RNGK>(vc, vb, s) : sv_launch<S, 256, AG, RNGK>(vc, vb, s);
 }
 
 template <int S, int AG>
@@ -94,7 +69,7 @@ static VsBuf sv_buf(const ewn_state *st, const ewn_opponent_policy *opp)
 {
     VsBuf vb;
     memset(&vb, 0, sizeof(vb));
-    vb.board = st->board; vb.dice = st->dice; vb.done = st->done; vb.rng = st->rng; vb.prev_score = st->prev_score; vb.tolerance = st->tolerance;
+    pol_fill_state(vb, st);
     vb.tables = st->tables;
     vb.opp_params = opp->params; vb.o_action = opp->action;
     return vb;
@@ -103,20 +78,19 @@ static VsBuf sv_buf(const ewn_state *st, const ewn_opponent_policy *opp)
 int ewn_step_vs_supported(const ewn_config *cfg)
 {
     ewn_config c2; Geom g; KCfg k;
-    int rc = sv_check(cfg, c2, g, k);
+    int rc = pol_check_cfg_blind(cfg, c2, g, k);
     if (rc == EWN_OK) rc = sv_plan(&c2, g);
-    return rc == EWN_OK ? 1 : (rc == EWN_EUNSUPPORTED ? 0 : rc);
+    return supported_answer(rc);
 }
 
 int ewn_step_vs(const ewn_config *cfg, const ewn_state *st, const int8_t *actions, const ewn_opponent_policy *opp, const ewn_step_out *out,
                 void *stream)
 {
     ewn_config c2; Geom g; KCfg k;
-    int rc = sv_check(cfg, c2, g, k);
+    int rc = pol_check_cfg_blind(cfg, c2, g, k);
     if (rc) return rc;
-    if (!st || !st->board || !st->dice || !st->done || !st->rng || !st->tables || !actions || !opp || !opp->params || !out) return EWN_ENULL;
+    if (pol_state_missing(st, true, c2.shaped != 0) || !actions || !opp || !opp->params || !out) return EWN_ENULL;
     if (!out->reward || !out->terminated || !out->truncated || !out->info) return EWN_ENULL;
-    if (c2.shaped && (!st->prev_score || !st->tolerance)) return EWN_ENULL;
     if (out->random_action) return EWN_EINVAL;             // RandomAgent.predict fused into the step is ewn_step's (and ewn_step_k_vs plays it)
     rc = sv_plan(&c2, g);
     if (rc) return rc;
@@ -132,10 +106,10 @@ int ewn_step_k_vs_supported(const ewn_config *cfg, int agent_kind, int agent_max
 {
     ewn_config c2; Geom g; KCfg k;
     int ag;
-    int rc = sv_check(cfg, c2, g, k);
+    int rc = pol_check_cfg_blind(cfg, c2, g, k);
     if (rc == EWN_OK) rc = sv_agent(agent_kind, agent_max_depth, ag);
     if (rc == EWN_OK) rc = sv_plan(&c2, g);
-    return rc == EWN_OK ? 1 : (rc == EWN_EUNSUPPORTED ? 0 : rc);
+    return supported_answer(rc);
 }
 
 int ewn_step_k_vs(const ewn_config *cfg, const ewn_state *st, int K, int agent_kind, int agent_max_depth, const ewn_opponent_policy *opp,
@@ -143,24 +117,19 @@ int ewn_step_k_vs(const ewn_config *cfg, const ewn_state *st, int K, int agent_k
 {
     ewn_config c2; Geom g; KCfg k;
     int ag = 1;
-    int rc = sv_check(cfg, c2, g, k);
+    int rc = pol_check_cfg_blind(cfg, c2, g, k);
     if (rc) return rc;
     if (K < 1) return EWN_EINVAL;
     rc = sv_agent(agent_kind, agent_max_depth, ag);
     if (rc) return rc;
-    if (!st || !st->board || !st->dice || !st->done || !st->rng || !st->tables || !opp || !opp->params) return EWN_ENULL;
-    if (c2.shaped && (!st->prev_score || !st->tolerance)) return EWN_ENULL;
+    if (pol_state_missing(st, true, c2.shaped != 0) || !opp || !opp->params) return EWN_ENULL;
     rc = sv_plan(&c2, g);
     if (rc) return rc;
     VsCfg vc = sv_cfg(k, K, opp);
     vc.agent_depth = agent_max_depth; vc.agent_sample = agent_kind == EWN_AGENT_SAMPLE ? 1 : 0;
     VsBuf vb = sv_buf(st, opp);
     if (ag != 1) vb.tables = fast_image(st->tables, g.S, g.L, agent_max_depth, EWN_H_HYBRID);   // the image of the agent's search
-    if (out) {
-        vb.t_board = out->board; vb.t_dice = out->dice; vb.t_action = out->action; vb.t_reward = out->reward;
-        vb.t_term = out->terminated; vb.t_trunc = out->truncated; vb.t_info = out->info; vb.t_rec = out->record;
-        vb.ret_sum = out->return_sum; vb.n_steps = out->n_steps; vb.n_episodes = out->n_episodes; vb.n_wins = out->n_wins;
-    }
+    pol_fill_trajectory(vb, out);
     hipStream_t s = (hipStream_t)stream;
     if (ag == 3) return sv_by_board<3>(vc, vb, g.S, k.rng_kind, s);
     if (ag == 4) return sv_by_board<4>(vc, vb, g.S, k.rng_kind, s);

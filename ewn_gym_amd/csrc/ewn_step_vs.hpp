@@ -8,7 +8,7 @@
 //   per launch   table image -> LDS (LDS-DMA); ONE forward image of the opponent's parameters (mlp3_pack_fwd, net 0);
 //                boards -> registers (d3_decode) and per-game LDS slots (rec_slot_build)
 //   per env step the agent's action; agent half (plain or shaped: tolerance, prev_score); the opponent's dice; the opponent's network
-//                on np.rot90(-board, 2) read straight out of the slots (the `xo` operand of ewn_policy_body.inc); argmax or Gumbel-max;
+//                on np.rot90(-board, 2) read straight out of the slots (pol_opp_operand, ewn_mlp3.hpp); argmax or Gumbel-max;
 //                opponent half (an impossible move ends the game: EWN_INFO_INVALID_OPP, reward 0); shaped reward; auto-reset or freeze;
 //                this step's outputs
 //   after the last step the state goes back once
@@ -50,7 +50,6 @@ __global__ __launch_bounds__(NT, 2) void k_step_vs(VsCfg c, VsBuf B)
     constexpr int T = 2, GPB = NT / T, CELLS = S * S, STR = RecGeo<S>::STR;
     using Q3 = Mlp3Geo<S>;
     static_assert(Q3::FWD_BYTES % 16 == 0, "image alignment");
-    static_assert(pol_lds_bytes<S, NT>(false) <= 160 * 1024, "table image + one weight image + the block's game slots must fit the CU's LDS");
     extern __shared__ __attribute__((aligned(16))) int8_t lds[];
     int8_t *tb = lds;
     int8_t *Wop = lds + FAST_TAB_BYTES(S);
@@ -118,7 +117,7 @@ __global__ __launch_bounds__(NT, 2) void k_step_vs(VsCfg c, VsBuf B)
             else d5_dispatch<S, T>(Tb, f, dice, sub, aflag, adir);
         }
         // the opponent's noise: k_rollout_mlp_vs's word (ewn_policy_body.inc), taken here, before the step moves the stream
-        const u32 w0o = fmix32(agent_hash(r.seed_mix() ^ ((u32)tol * 0x632BE5ABu), r.draws(), (u32)(c.lane_offset + game), c.key ^ c.opp_noise_key) ^ POL_OPP_SALT);
+        const u32 w0o = pol_opp_noise_word(r.seed_mix(), tol, r.draws(), c.lane_offset + game, c.key, c.opp_noise_key);
         // ---- agent half, envs/ewn.py:438-458 / envs/training_ewn.py:44-66
         bool reply = false;
         if (active) {
@@ -143,24 +142,14 @@ __global__ __launch_bounds__(NT, 2) void k_step_vs(VsCfg c, VsBuf B)
             }
         }
         const int odice = dice;                            // the opponent's dice where it replies
-        // ---- the opponent's network on its canonical view, np.rot90(-board, 2) (envs/ewn.py:289-296): view cell f = -(slot byte
-        // CELLS - 1 - f); the operand of ewn_policy_body.inc, run by every lane of the wave (its 32 games are the tile's 32 columns)
-        static_assert(CELLS % 8 == 1, "the reversed view's word alignment");
+        // ---- the opponent's network on its canonical view (pol_opp_operand, ewn_mlp3.hpp), run by every lane of the wave (its 32 games
+        // are the tile's 32 columns)
         __builtin_amdgcn_wave_barrier();                   // the agent's moves are in the slots
         {
             const int j = lane & 31, h = lane >> 5;
             const int dj = __builtin_amdgcn_ds_bpermute((2 * j) << 2, dice);          // game j's dice (its lanes are 2 j, 2 j + 1)
             const int8_t *sj = slots + (wave * 32 + j) * STR;
-            auto xo = [&](int kb) {
-                const int base = CELLS - 9 - (16 * kb + 8 * h);                  // a multiple of 4; >= 0: all eight features are cells
-                const u32 *wp = (const u32 *)(sj + (base < 0 ? 0 : base));
-                const u32 d0 = wp[0], d1 = wp[1], d2 = wp[2];                   // slot bytes base .. base + 11 (< STR)
-                u32 lo = __builtin_amdgcn_perm(d2, d1, 0x01020304u), hi = __builtin_amdgcn_perm(d1, d0, 0x01020304u);
-                if (base < 0) { lo = base == -8 ? (d0 & 0xFFu) : 0u; hi = 0u; }   // feature CELLS - 1 = slot byte 0 alone, or nothing
-                u32x4 o = mlp3_bytes_operand_neg(lo, hi);
-                if (16 * kb + 15 >= CELLS && 16 * kb < CELLS + 7) o = mlp3_onehot(o, CELLS + dj - 1 - (16 * kb + 8 * h));
-                return o;
-            };
+            auto xo = [&](int kb) { return pol_opp_operand<S>(sj, kb, h, dj); };
             f32x16 h1[2], h2[2];
             float lo[MLP_NA];
             mlp3_forward<S, MLP_NA>(Wop, lane, xo, h1, h2, lo);
@@ -172,10 +161,10 @@ __global__ __launch_bounds__(NT, 2) void k_step_vs(VsCfg c, VsBuf B)
         __builtin_amdgcn_wave_barrier();
         float on[5];
         #pragma unroll
-        for (int i = 0; i < 5; i++) on[i] = c.opp_deterministic ? 0.0f : -pol_log(-pol_log(pol_uniform(w0o, i)));
+        for (int i = 0; i < 5; i++) on[i] = c.opp_deterministic ? 0.0f : pol_gumbel(pol_uniform(w0o, i));
         const float y0 = og.x + on[0], y1 = og.y + on[1], y2 = og.z + on[2], y3 = og.w + on[3], y4 = og4 + on[4];
-        const int oflag = y1 > y0 ? 1 : 0;
-        const int odir = y3 > y2 ? (y4 > y3 ? 2 : 1) : (y4 > y2 ? 2 : 0);
+        const int oflag = pol_pick_flag(y0, y1);
+        const int odir = pol_pick_dir(y2, y3, y4);
         // ---- opponent half, envs/ewn.py:464-486
         if (reply) {
             const int k = pk_cube(pk_sel<S>(Tb, s.posP, dice), oflag == 1);
