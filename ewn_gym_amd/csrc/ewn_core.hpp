@@ -251,6 +251,20 @@ EWN_DEV int for_each_legal(const Geom &g, const GState<NW> &s, int dice, F &&f)
     return n;
 }
 
+// len(get_legal_actions()), and entry n of that list: its flag, cube and direction (left as they are when the list is shorter)
+template <int SIDE, int NW>
+EWN_DEV int legal_count(const Geom &g, const GState<NW> &s, int dice)
+{
+    return for_each_legal<SIDE, NW>(g, s, dice, [](int, int, int) { return true; });
+}
+
+template <int SIDE, int NW>
+EWN_DEV void legal_nth(const Geom &g, const GState<NW> &s, int dice, int n, int &flag, int &k, int &dir)
+{
+    int i = 0;
+    for_each_legal<SIDE, NW>(g, s, dice, [&](int fl, int kk, int dr) { if (i == n) { flag = fl; k = kk; dir = dr; } i++; return i <= n; });
+}
+
 // ---------------------------------------------------------------- heuristics
 
 // min over a side's cubes of max(S-1-row, S-1-col): BOTH sides are measured to the

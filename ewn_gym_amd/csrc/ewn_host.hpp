@@ -102,6 +102,27 @@ static inline int launch_status()
 // the answer of an ewn_*_supported call from a plan's code: 1 served, 0 not served, a negative code for a malformed configuration
 static inline int supported_answer(int rc) { return rc == EWN_OK ? 1 : (rc == EWN_EUNSUPPORTED ? 0 : rc); }
 
+// the fillers of a zeroed kernel argument struct (RollBuf, PolBuf, VsBuf: the same field names) from the caller's ewn_rollout_out.
+// An evaluation writes the totals and optionally the action column, nothing else.
+template <class Buf>
+static inline void fill_totals(Buf &b, const ewn_rollout_out *out)
+{
+    b.ret_sum = out->return_sum; b.n_steps = out->n_steps; b.n_episodes = out->n_episodes; b.n_wins = out->n_wins;
+}
+
+// every column of a rollout's `out` (which may be NULL: nothing is written then) and the totals
+template <class Buf>
+static inline void fill_trajectory(Buf &b, const ewn_rollout_out *out)
+{
+    if (!out) return;
+    b.t_board = out->board; b.t_dice = out->dice; b.t_action = out->action; b.t_reward = out->reward;
+    b.t_term = out->terminated; b.t_trunc = out->truncated; b.t_info = out->info; b.t_rec = out->record;
+    fill_totals(b, out);
+}
+
+// bytes per game of the LDS staging area of the one-thread-per-game K-step kernels: a record of ewn_rollout_out.record (or a board)
+static inline int traj_record_stride(const Geom &g) { return EWN_TRAJ_RECORD_STRIDE(g.S); }
+
 // specialised depth-3 tables exist for cube_layer 3 and board sizes whose distinct leaf values fit 10-bit ranks
 static inline int64_t fast_tables_bytes(int S, int L)
 {

@@ -1,8 +1,10 @@
-// ewn_mcts_body.hpp -- K env steps per launch against the flat Monte-Carlo opponent with an agent of its own: rollout_mcts_body (the
-// loop of ewn_step_k_agent's kernels and of ewn_policy_eval_mcts's), its playout phase, and the per-lane rules they share with the
-// generic kernels of ewn_kernels.hip (step_agent / step_opponent / policy_random / lane_auto_reset).  A header because the body is
-// instantiated in two translation units: ewn_kernels.hip (AG 1 / 2: the minimax and MCTS agents) and ewn_policy_eval_mcts.hip (AG 3:
-// the actor-critic, whose matrix code is built with -fno-slp-vectorize, a flag ewn_kernels.hip must not get).
+// ewn_mcts_body.hpp -- K env steps per launch with one thread per game for the rules: rollout_mcts_body (the loop of k_rollout_mcts,
+// of ewn_step_k_agent's kernels and of ewn_policy_eval_mcts's), its playout phase, and what it shares with the generic kernels of
+// ewn_kernels.hip: the per-lane rules (step_agent / step_opponent / policy_random / lane_auto_reset) and the one copy of the stand-in
+// agent, the trajectory row and the write-back (stand_in_action / traj_columns_store / traj_blocks_store / rollout_write_back, also
+// k_rollout_generic's).  A header because the body is instantiated in two translation units: ewn_kernels.hip (AG 0 / 1 / 2: the
+// stand-in, minimax and MCTS agents) and ewn_policy_eval_mcts.hip (AG 3: the actor-critic, whose matrix code is built with
+// -fno-slp-vectorize, a flag ewn_kernels.hip must not get).
 #pragma once
 #include "ewn_host.hpp"
 #include "ewn_playout.hpp"
@@ -79,6 +81,85 @@ EWN_DEV void policy_random(const Geom &g, const GState<NW> &s, int dice, LaneRng
     for_each_legal<1, NW>(g, s, dice, [&](int flag, int, int dir) { if (i == pick) { oflag = flag; odir = dir; } i++; return i <= pick; });
 }
 
+// The stand-in agent of ewn_step_k: RandomAgent.predict (the hash pick of ewn_step_out.random_action) or, with agent_sample,
+// env.action_space.sample() (all six actions).  Draws nothing from the lane's stream.
+template <int NW>
+EWN_DEV void stand_in_action(const Geom &g, const KCfg &c, const GState<NW> &s, int dice, const LaneRng &r, int lane, int agent_sample,
+                             int &aflag, int &adir)
+{
+    const u32 w = agent_hash(r.seed_mix(), r.draws(), (u32)(c.lane_offset + lane), c.key);
+    if (agent_sample) { const int a6 = (int)__umulhi(w, 6u); aflag = a6 >= 3 ? 1 : 0; adir = a6 - 3 * aflag; }
+    else {
+        const int n = legal_count<0, NW>(g, s, dice);
+        int k;
+        if (n > 0) legal_nth<0, NW>(g, s, dice, (int)__umulhi(w, (u32)n), aflag, k, adir);
+    }
+}
+
+// A lane's totals over the steps of a launch (ewn_rollout_out.return_sum / n_steps / n_episodes / n_wins)
+struct LaneTotals {
+    double ret = 0.0;
+    int steps = 0, eps = 0, wins = 0;
+    EWN_DEV void count(const StepRes &o) { ret += o.reward; steps++; eps += o.term; wins += o.info == EWN_INFO_WON ? 1 : 0; }
+};
+
+// One lane's entries of a trajectory row, index = step * N + lane: the columns of ewn_rollout_out that the caller asked for
+EWN_DEV void traj_columns_store(const RollBuf &B, size_t index, int aflag, int adir, int dice, const StepRes &o)
+{
+    if (B.t_action) ((uint16_t *)B.t_action)[index] = (uint16_t)((uint8_t)aflag | ((uint16_t)(uint8_t)adir << 8));
+    if (B.t_dice) B.t_dice[index] = (int8_t)dice;
+    if (B.t_reward) B.t_reward[index] = o.reward;
+    if (B.t_term) B.t_term[index] = (uint8_t)o.term;
+    if (B.t_trunc) B.t_trunc[index] = (uint8_t)o.trunc;
+    if (B.t_info) B.t_info[index] = (uint8_t)o.info;
+}
+
+// A block's part of a trajectory row, row0 = step * N + the block's first lane, nl lanes: the boards, then the records, each staged in
+// lds ([.][strd], one slot per thread that owns a game) and copied out in coalesced pieces.  Every thread of the block calls it
+// (block barriers); lds holds nothing the caller still needs.
+template <int NW>
+EWN_DEV void traj_blocks_store(const Geom &g, const RollBuf &B, int8_t *lds, int strd, int tid, bool live, size_t row0, int nl,
+                               const GState<NW> &s, int dice, int aflag, int adir, const StepRes &o)
+{
+    if (B.t_board) {
+        if (live) encode_board<NW>(g, s, lds + tid * g.cells);
+        __syncthreads();
+        block_copy_out(B.t_board + row0 * g.cells, lds, nl * g.cells);
+        __syncthreads();
+    }
+    if (B.t_rec) { // one aligned record per lane-step: board | dice | action | flags | padding (ewn_rollout_out.record)
+        if (live) {
+            int8_t *rec = lds + tid * strd;
+            for (int i = g.cells; i < strd; i++) rec[i] = 0;
+            encode_board<NW>(g, s, rec);
+            rec[g.cells] = (int8_t)dice; rec[g.cells + 1] = (int8_t)aflag; rec[g.cells + 2] = (int8_t)adir;
+            rec[g.cells + 3] = (int8_t)o.term; rec[g.cells + 4] = (int8_t)o.trunc; rec[g.cells + 5] = (int8_t)o.info;
+        }
+        __syncthreads();
+        block_copy_out((int8_t *)B.t_rec + row0 * strd, lds, nl * strd);
+        __syncthreads();
+    }
+}
+
+// After the last step: the board through lds, the RNG header and the dice unless the lane was frozen when the launch began (its state
+// is not the launch's to touch), the done flag, the totals added to the caller's.  Every thread of the block calls it (block barrier).
+template <int NW>
+EWN_DEV void rollout_write_back(const Geom &g, const KState &st, const RollBuf &B, int8_t *lds, int tid, bool live, int lane, int lane0,
+                                int nl, const GState<NW> &s, int dice, const LaneRng &r, bool frozen0, bool frozen, const LaneTotals &tot)
+{
+    if (live) {
+        encode_board<NW>(g, s, lds + tid * g.cells);
+        if (!frozen0) { *rng_hdr_ptr(st.rng, lane) = r.header(); st.dice[lane] = (int8_t)dice; }
+        st.done[lane] = frozen ? 1 : 0;
+        if (B.ret_sum) B.ret_sum[lane] += tot.ret;
+        if (B.n_steps) B.n_steps[lane] += tot.steps;
+        if (B.n_episodes) B.n_episodes[lane] += tot.eps;
+        if (B.n_wins) B.n_wins[lane] += tot.wins;
+    }
+    __syncthreads();
+    block_copy_out(st.board + (size_t)lane0 * g.cells, lds, nl * g.cells);
+}
+
 // the canonical observation of a game as the playouts' byte-per-cube start position
 EWN_DEV PState pstate_from_gstate(const Geom &g, const GState<1> &c)
 {
@@ -144,9 +225,9 @@ EWN_DEV void mcts_pick(const Geom &g, const GState<1> &obs, int dice, const int 
     int best = 0, bw = -1;
     #pragma unroll
     for (int i = 0; i < 6; i++) { const int w = w6[i]; if (w > bw) { bw = w; best = i; } }
-    int f = 0, d = 0, j = 0;
-    for_each_legal<0, 1>(g, obs, dice, [&](int fl, int, int dr) { if (j == best) { f = fl; d = dr; } j++; return j <= best; });
-    flag = f; dir = d;
+    int k;
+    flag = 0; dir = 0;
+    legal_nth<0, 1>(g, obs, dice, best, flag, k, dir);
 }
 
 // The dynamic LDS of the AG 3 instances behind the boards area: the policy net's forward image (mlp3_pack_fwd), then per game of the
@@ -164,12 +245,12 @@ template <int S> struct MctsNet {
     static_assert(Mlp3Geo<S>::FWD_BYTES % 16 == 0, "image alignment");
 };
 
-// k_rollout_mcts's loop with an agent of its own.  AG: 1 minimax (ar.depth, ar.heur), 2 MCTS (a playout phase over the agent's
-// observation before the agent half), 3 the actor-critic's argmax (below).  OPP: 0 RandomAgent, 1 minimax (c.depth, c.heur), 2 MCTS
-// (its playout phase between the two halves).  The minimax searches (AG 1's agent, OPP 1's opponent: one of them per instance) are the table-driven fast_d3 of
+// K env steps of mr.gpb games per block.  AG: 0 ewn_step_k's stand-in agent (mr.agent_sample; ar is not read), 1 minimax (ar.depth,
+// ar.heur), 2 MCTS (a playout phase over the agent's observation before the agent half), 3 the actor-critic's argmax (below).  OPP: 0 RandomAgent,
+// 1 minimax (c.depth, c.heur), 2 MCTS (its playout phase between the two halves).  The minimax searches (AG 1's agent, OPP 1's opponent: one of them per instance) are the table-driven fast_d3 of
 // k_predict_minimax_fast / ewn_step's table path, on the rules thread, from an image of the search's table in LDS (S = board size;
-// 0 = no search, no table).  k_rollout_mcts itself keeps its own text: routed through this body, its RandomAgent / sample instance
-// compiled to different register allocation (129 -> 132 VGPRs), and that instance must stay the code it is.
+// 0 = no search, no table).  k_rollout_mcts (ewn_kernels.hip: ewn_step_k against the MCTS opponent) is the instance <0, 2, 0>;
+// DESIGN.md 4e has the measurement that let its own copy of this loop go.
 //
 // AG 3 (ewn_policy_eval_mcts): OPP 2 only, un-shaped, no auto-reset.  B.agent_tables = the actor-critic's flat fp32
 // parameters; S = the board size of Mlp3Geo<S>, no table image.  The action row of a lane is written only for the steps it plays,
@@ -223,8 +304,7 @@ EWN_DEV void rollout_mcts_body(const Geom &g, const KCfg &c, const KState &st, c
     decode_board<1>(g, lds + (live ? tid : 0) * g.cells, s);
     LaneRng r; r.load(c.rng_kind, hdr, rng_win_ptr(st.rng, c.N, c.W, live ? lane : 0, RNGF_CUR(hdr.w)), c.W, c.key);
     r.begin_kernel();
-    double ret_acc = 0.0;
-    int n_steps = 0, n_eps = 0, n_wins = 0;
+    LaneTotals tot;
     const int tc = 1 << mr.gl, glane = tid & (tc - 1), grp = tid >> mr.gl;
     const int atc = 1 << ar.gl, aglane = tid & (atc - 1), agrp = tid >> ar.gl;   // the agent's playout groups (AG 2)
 
@@ -234,6 +314,9 @@ EWN_DEV void rollout_mcts_body(const Geom &g, const KCfg &c, const KState &st, c
         int aflag = 0, adir = 0, n_root = 0;
         bool reply = false;
         GState<1> cst = s;
+        if constexpr (AG == 0) {
+            if (active) stand_in_action<1>(g, c, s, dice, r, lane, mr.agent_sample, aflag, adir);
+        }
         if constexpr (AG == 2) {
             // MctsAgent.predict(env.board, env.dice): the agent's observation as it stands, its root moves, its playout stream
             int a_root = 0;
@@ -242,7 +325,7 @@ EWN_DEV void rollout_mcts_body(const Geom &g, const KCfg &c, const KState &st, c
                 pdice[tid] = (int8_t)dice;
                 const u64 key_t = ar.key + 0x9E3779B97F4A7C15ull * ((u64)ar.step_base + (u64)kstep + 1ull);
                 pword[tid] = PlayoutRng::obs_word((u32)(c.lane_offset + lane), 0x4D435453u, key_t);
-                a_root = for_each_legal<0, 1>(g, s, dice, [](int, int, int) { return true; });
+                a_root = legal_count<0, 1>(g, s, dice);
             }
             mcts_playout_phase(g, &T, pb0, pword, pdice, wins, livec, &nlive_s, &next_slot, nextc, myslot, tid, owner, a_root, ar.total,
                                ar.gl, atc, aglane, agrp);
@@ -287,7 +370,7 @@ EWN_DEV void rollout_mcts_body(const Geom &g, const KCfg &c, const KState &st, c
                     pb0[tid] = pstate_from_gstate(g, cst);
                     pdice[tid] = (int8_t)dice;
                     pword[tid] = PlayoutRng::obs_word(r.seed_mix() * 0x9E3779B1u + r.draws(), 0x4D435453u, c.key);
-                    n_root = for_each_legal<0, 1>(g, cst, dice, [](int, int, int) { return true; });
+                    n_root = legal_count<0, 1>(g, cst, dice);
                 }
             } else if (reply) {
                 int oflag = 0, odir = 0;
@@ -311,50 +394,15 @@ EWN_DEV void rollout_mcts_body(const Geom &g, const KCfg &c, const KState &st, c
             }
         }
         if (active) {
-            ret_acc += o.reward; n_steps++; n_eps += o.term; n_wins += o.info == EWN_INFO_WON ? 1 : 0;
+            tot.count(o);
             if (o.term) { if (c.autoreset) lane_auto_reset<1>(g, c, st.rng, lane, s, dice, r); else frozen = true; }
         }
         // ---- this step's trajectory row (AG 3, as ewn_policy_eval: the action of a lane that played this step, nothing else)
         if constexpr (AG == 3) {
             if (active && B.t_action)
                 ((uint16_t *)B.t_action)[(size_t)kstep * c.N + lane] = (uint16_t)((uint8_t)aflag | ((uint16_t)(uint8_t)adir << 8));
-        } else if (live) {
-            const size_t oo = (size_t)kstep * c.N + lane;
-            if (B.t_action) ((uint16_t *)B.t_action)[oo] = (uint16_t)((uint8_t)aflag | ((uint16_t)(uint8_t)adir << 8));
-            if (B.t_dice) B.t_dice[oo] = (int8_t)dice;
-            if (B.t_reward) B.t_reward[oo] = o.reward;
-            if (B.t_term) B.t_term[oo] = (uint8_t)o.term;
-            if (B.t_trunc) B.t_trunc[oo] = (uint8_t)o.trunc;
-            if (B.t_info) B.t_info[oo] = (uint8_t)o.info;
-        }
-        if (B.t_board) {
-            if (live) encode_board<1>(g, s, lds + tid * g.cells);
-            __syncthreads();
-            block_copy_out(B.t_board + ((size_t)kstep * c.N + lane0) * g.cells, lds, nl * g.cells);
-            __syncthreads();
-        }
-        if (B.t_rec) { // one aligned record per lane-step: board | dice | action | flags | padding (ewn_rollout_out.record)
-            if (live) {
-                int8_t *rec = lds + tid * mr.strd;
-                for (int i = g.cells; i < mr.strd; i++) rec[i] = 0;
-                encode_board<1>(g, s, rec);
-                rec[g.cells] = (int8_t)dice; rec[g.cells + 1] = (int8_t)aflag; rec[g.cells + 2] = (int8_t)adir;
-                rec[g.cells + 3] = (int8_t)o.term; rec[g.cells + 4] = (int8_t)o.trunc; rec[g.cells + 5] = (int8_t)o.info;
-            }
-            __syncthreads();
-            block_copy_out((int8_t *)B.t_rec + ((size_t)kstep * c.N + lane0) * mr.strd, lds, nl * mr.strd);
-            __syncthreads();
-        }
+        } else if (live) traj_columns_store(B, (size_t)kstep * c.N + lane, aflag, adir, dice, o);
+        traj_blocks_store<1>(g, B, lds, mr.strd, tid, live, (size_t)kstep * c.N + lane0, nl, s, dice, aflag, adir, o);
     }
-    if (live) encode_board<1>(g, s, lds + tid * g.cells);
-    if (live) {
-        if (!frozen0) { *rng_hdr_ptr(st.rng, lane) = r.header(); st.dice[lane] = (int8_t)dice; }
-        st.done[lane] = frozen ? 1 : 0;
-        if (B.ret_sum) B.ret_sum[lane] += ret_acc;
-        if (B.n_steps) B.n_steps[lane] += n_steps;
-        if (B.n_episodes) B.n_episodes[lane] += n_eps;
-        if (B.n_wins) B.n_wins[lane] += n_wins;
-    }
-    __syncthreads();
-    block_copy_out(st.board + (size_t)lane0 * g.cells, lds, nl * g.cells);
+    rollout_write_back<1>(g, st, B, lds, tid, live, lane, lane0, nl, s, dice, r, frozen0, frozen, tot);
 }

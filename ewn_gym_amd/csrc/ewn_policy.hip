@@ -105,7 +105,7 @@ int ewn_policy_eval(const ewn_config *cfg, const ewn_state *st, int K, const flo
     if (rc) return rc;
     const PolCfg pc = pol_cfg(k, K, nullptr);
     PolBuf pb = pol_buf(st, opp == 1 ? st->tables : fast_image(st->tables, g.S, g.L, cfg->max_depth, cfg->heuristic), params);
-    pb.t_action = out->action; pol_fill_totals(pb, out);
+    pb.t_action = out->action; fill_totals(pb, out);
     return ewn_launch_policy_eval(pc, pb, g.S, opp, k.rng_kind, (hipStream_t)stream);
 }
 

@@ -58,7 +58,7 @@ int ewn_policy_eval_mcts(const ewn_config *cfg, const ewn_state *st, int K, cons
     RollBuf rb;
     memset(&rb, 0, sizeof(rb));
     rb.agent_tables = params;   // the agent's image: AG 3 has no search table, the body packs the actor-critic's parameters from here
-    rb.t_action = out->action; pol_fill_totals(rb, out);
+    rb.t_action = out->action; fill_totals(rb, out);
     // games per block: ewn_step_k_agent's rule for its MCTS-only instances (8 .. MR_GPB, about 2 048 blocks)
     int gpb = 8;
     while (gpb < MR_GPB && (long long)k.N / (2 * gpb) >= 2048) gpb *= 2;

@@ -64,28 +64,12 @@ static inline PolCfg pol_cfg(const KCfg &k, int K, const ewn_policy *pol)
     return pc;
 }
 
-// the fillers of a zeroed kernel argument struct: PolBuf and VsBuf carry the same field names (RollBuf too, for the trajectory and the
-// totals); `tables` is the caller's.  An evaluation writes the totals and optionally the action column, nothing else.
+// the filler of a zeroed kernel argument struct's state: PolBuf and VsBuf carry the same field names; `tables` is the caller's.
+// (The trajectory and the totals: fill_trajectory / fill_totals, ewn_host.hpp.)
 template <class Buf>
 static inline void pol_fill_state(Buf &b, const ewn_state *st)
 {
     b.board = st->board; b.dice = st->dice; b.done = st->done; b.rng = st->rng; b.prev_score = st->prev_score; b.tolerance = st->tolerance;
-}
-
-template <class Buf>
-static inline void pol_fill_totals(Buf &b, const ewn_rollout_out *out)
-{
-    b.ret_sum = out->return_sum; b.n_steps = out->n_steps; b.n_episodes = out->n_episodes; b.n_wins = out->n_wins;
-}
-
-// every column of a rollout's `out` (which may be NULL: nothing is written then) and the totals
-template <class Buf>
-static inline void pol_fill_trajectory(Buf &b, const ewn_rollout_out *out)
-{
-    if (!out) return;
-    b.t_board = out->board; b.t_dice = out->dice; b.t_action = out->action; b.t_reward = out->reward;
-    b.t_term = out->terminated; b.t_trunc = out->truncated; b.t_info = out->info; b.t_rec = out->record;
-    pol_fill_totals(b, out);
 }
 
 static inline PolBuf pol_buf(const ewn_state *st, const void *tables, const float *params)
@@ -103,7 +87,7 @@ static inline PolBuf pol_buf_rollout(const ewn_state *st, const void *tables, co
 {
     PolBuf pb = pol_buf(st, tables, pol->params);
     pb.t_logits = pol->logits; pb.t_value = pol->value; pb.t_noise = pol->noise;
-    pol_fill_trajectory(pb, out);
+    fill_trajectory(pb, out);
     return pb;
 }
 

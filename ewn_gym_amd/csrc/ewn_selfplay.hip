@@ -115,7 +115,7 @@ int ewn_policy_eval_vs(const ewn_config *cfg, const ewn_state *st, int K, const 
     PolCfg pc = pol_cfg(k, K, nullptr);
     pc.depth = 0;
     PolBuf pb = pol_buf(st, st->tables, params);
-    pb.t_action = out->action; pol_fill_totals(pb, out);
+    pb.t_action = out->action; fill_totals(pb, out);
     const PolOpp po = pol_opp(opp);
     hipStream_t s = (hipStream_t)stream;
     return g.S == 5 ? eval_vs_by_rng<5>(pc, pb, po, k.rng_kind, s) : eval_vs_by_rng<7>(pc, pb, po, k.rng_kind, s);

@@ -129,7 +129,7 @@ int ewn_step_k_vs(const ewn_config *cfg, const ewn_state *st, int K, int agent_k
     vc.agent_depth = agent_max_depth; vc.agent_sample = agent_kind == EWN_AGENT_SAMPLE ? 1 : 0;
     VsBuf vb = sv_buf(st, opp);
     if (ag != 1) vb.tables = fast_image(st->tables, g.S, g.L, agent_max_depth, EWN_H_HYBRID);   // the image of the agent's search
-    pol_fill_trajectory(vb, out);
+    fill_trajectory(vb, out);
     hipStream_t s = (hipStream_t)stream;
     if (ag == 3) return sv_by_board<3>(vc, vb, g.S, k.rng_kind, s);
     if (ag == 4) return sv_by_board<4>(vc, vb, g.S, k.rng_kind, s);

@@ -104,6 +104,48 @@ def test_record_layout_through_step_k(ea, tables, alloc, name, n, kw, lanes_per_
     assert int(tot["n_steps"].sum()) > 0
 
 
+SPARSE_CASES = [
+    # 8 games per block: a partial last block of 4
+    ("mcts-100", 100, dict(opponent_policy="mcts", num_simulations=3, num_env_copies=2, rng="philox")),
+    # 256 games per block: one game in the last block
+    ("generic-9x9-257", 257, dict(opponent_policy="random", rng="philox", board_size=9)),
+]
+SPARSE_RUNS = [("reward", "n_wins"), ("terminated", "action", "return_sum")]
+
+
+@pytest.mark.parametrize("name,n,kw", SPARSE_CASES, ids=[c[0] for c in SPARSE_CASES])
+def test_step_k_column_guards_one_at_a_time(ea, tables, alloc, name, n, kw):
+    """Every member of ewn_rollout_out is optional on its own in the one-thread-per-game K-step kernels: a call with a few members
+    non-NULL writes into them what the call with every member writes, and leaves the same state behind."""
+    from ewn_gym_amd._lib import AGENT, EwnRolloutOut, check
+    from ewn_gym_amd.vec_env import _ptr, _stream
+    K = 6
+    members = [f[0] for f in EwnRolloutOut._fields_]
+    with alloc.patch(tag=name):
+        env = ea.VecEWN(n, seed_stride=n, **kw)
+    assert env.supports_rollout("random")
+
+    def run(only):
+        with alloc.patch(tag="%s-%s" % (name, "+".join(only or ("all",)))):
+            bufs = dict(env.alloc_rollout(K), **env.alloc_totals())
+            bufs["record"] = env.alloc_rollout(K, layout="record")["record"]
+        env.reset(seeds=_seeds(n))
+        out = EwnRolloutOut(*[_ptr(bufs[m]) if only is None or m in only else None for m in members])
+        check(env.lib.ewn_step_k(C.byref(env.cfg), C.byref(env._st), K, AGENT["random"], 3, C.byref(out), _stream()), "ewn_step_k")
+        torch.cuda.synchronize()
+        return bufs, [t.clone() for t in (env.board, env.dice, env.done, env.rng_state)]
+
+    full, state = run(None)
+    assert int(full["n_steps"].sum()) > 0 and bool(full["action"].any())
+    for only in SPARSE_RUNS:
+        got, st = run(only)
+        for m in only:
+            assert torch.equal(got[m].view(torch.uint8), full[m].view(torch.uint8)), (only, m)
+        for a, b in zip(st, state):
+            assert torch.equal(a, b), only
+    _done(alloc, tables, name)
+
+
 # ---------------------------------------------------------------- ewn_step_k_policy
 
 def _policy_env(ea, alloc, S, n, tag):
