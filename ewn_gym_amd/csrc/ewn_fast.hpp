@@ -272,6 +272,8 @@ static int build_fast_tables(FastTab<S> *T, int variant = 0, int heur = 0)
         const double v = i == 0 ? -__builtin_inf() : (i <= T->nv ? all[i - 1] : __builtin_inf()); // unused ranks compare above every alpha
         volatile double q = v / 6.0;
         T->val[i] = v; T->val6[i] = q;
+        // d3_search starts a root's expectation from its first val6 term instead of 0.0 + term: the same bits unless the term is -0.0
+        if (q == 0.0 && __builtin_signbit(q)) return -1;
     }
     // the rank of -10: 1 for 'hybrid' and 'min_dist' (nothing lies below it), not for 'attk' (-(6 + 6) = -12 does)
     const uint16_t m10 = (uint16_t)(1 + (std::lower_bound(all.begin(), all.end(), -10.0) - all.begin()));

@@ -226,6 +226,9 @@ __device__ __forceinline__ double d5_search(const FastTab<S> *Tb, const RState<S
 // the better one (measured round 3: 6.53 -> 6.46 us per env step without the fences; without the priority switches 6.74)
 #define D3_STAGE_FENCE() __builtin_amdgcn_sched_barrier(0)
 #define D3_SEARCH_FENCE() do { if constexpr (!PERLANE) __builtin_amdgcn_sched_barrier(0); } while (0)   // inside d3_search
+// A rank as it comes out of its 16-bit LDS read, kept as a 32-bit value the compiler knows nothing about: knowing it to be below 2^16 it
+// narrows the prefix minima to v_min_u16 and then pays a zero-extension (v_and 0xffff) wherever one of them is used as an address.
+EWN_DEV u32 rank_u32(u32 r) { asm("" : "+v"(r)); return r; }
 #define D3_CUT 0x4000u    // key flag of d3_search: the reply loop stops inside this cube's replies (byte-offset ranks stay below 0x2000)
 
 // element `sub + T * i` of a six-element array held identically by the T lanes of a group, for the lane with index `sub`
@@ -327,14 +330,12 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
     // reply", +inf), a reply onto the origin rank[1] (-10, envs/minimax_ewn.py:45-47).  The exceptions steer the ADDRESS instead
     // of selecting the loaded value: a select on a loaded value makes the compiler branch around the LDS reads.
     u32 keep[KPT][3], fixed[KPT][3];
-    u32 mine_alive = 0;
     #pragma unroll
     for (int i = 0; i < KPT; i++) {
         const int k = sub + T * i;          // may be >= 6 for the last slot when 6 % T != 0: byte 6/7 = a cube that is off the board
         const int rb = pk_get(c.posN, k < 6 ? k : 6);
         rnk[i] = rb & 63;
         rclr[i] = ~(one << rnk[i]);
-        mine_alive |= ((rb & PK_OFF) ? 0u : 1u) << i;
         #pragma unroll
         for (int d = 0; d < 3; d++) {
             const u32 kf = Tb->rkf[d][rb];
@@ -353,6 +354,7 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
     // (the slot-task kernel's three roots ARE unrolled: 24 KB of code still fit, the direction becomes a constant: -1.5 %, 163 -> 152 VGPRs)
     constexpr int ROOT_UNROLL = PERLANE ? 3 : 1;
     const u32 rmL = slotL == 0 ? rm0 : rm1;
+    D3_PRIO_HI();   // once per call, not per root: the priority stays raised until the search returns (see below)
     #pragma unroll ROOT_UNROLL
     for (int r = 0; r < (PERLANE ? 3 : 6); r++) {
         const int slot = PERLANE ? slotL : (r >= 3 ? 1 : 0), dir = PERLANE ? r : r - 3 * slot;
@@ -371,7 +373,6 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
         constexpr int CH = KPT > 3 ? 3 : KPT; // cubes staged together: 9 leaves in flight; more only costs registers
         #pragma unroll
         for (int i0 = 0; i0 < KPT; i0 += CH) {
-            D3_PRIO_HI();
             M P2[CH][3], N2[CH][3];
             u32 lp[CH][3], ln[CH][3], a[CH][3];
             #pragma unroll
@@ -395,7 +396,7 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
                 #pragma unroll
                 for (int d = 0; d < 3; d++) {
                     const u32 ix = H2 ? lp[ii][d] : lp[ii][d] + (u32)popc_m(P2[ii][d]), iy = H2 ? ln[ii][d] : ln[ii][d] + (u32)popc_m(N2[ii][d]);
-                    a[ii][d] = ft_rank8<S>(Tb, (ft_addr(ix, iy) & keep[i0 + ii][d]) | fixed[i0 + ii][d]);
+                    a[ii][d] = rank_u32(ft_rank8<S>(Tb, (ft_addr(ix, iy) & keep[i0 + ii][d]) | fixed[i0 + ii][d]));
                 }
             }
             D3_SEARCH_FENCE();
@@ -415,16 +416,19 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
                 const int i = i0 + ii;
                 // per cube: `cut` = the value at which the reference's reply loop would stop inside this cube's replies
                 // (`worst <= alpha`, minimax.py:59-61; alpha = best so far), 0 if it would not.  The running minimum along a
-                // cube's replies is non-increasing (a0 >= p1 >= p2), so the loop stops at the first of them that is <= alpha.
-                // (three independent selects, last one wins: written as a nested conditional the compiler branches on it)
-                // The cube's key: D3_CUT | its cut value if it cuts, else 0x8000 | its minimum.  A cube that is off the board (or was just
-                // captured by the root move) reads garbage leaves above: its key is forced to "no such cube" here.
-                u32 key = 0x8000u | p2[ii];
-                key = v2[ii] <= best ? (p2[ii] | D3_CUT) : key;
-                key = v1[ii] <= best ? (p1[ii] | D3_CUT) : key;
-                key = va[ii] <= best ? (a[ii][0] | D3_CUT) : key;
-                const bool there = ((mine_alive >> i) & 1u) && rnk[i] != dest;
-                key = there ? key : FAST_KNONE;
+                // cube's replies is non-increasing (a0 >= p1 >= p2, as ranks and as values), so the loop stops at the first of
+                // them that is <= alpha, and "some reply cuts" is v2 <= best alone.
+                // The cube's key: D3_CUT | its cut value if it cuts, else 0x8000 | its minimum -- two selects for the rank (independent,
+                // last one wins: written as a nested conditional the compiler branches on it), one select between the two flags, one OR.
+                // A cube that is off the board needs nothing here: its position byte has no legal reply (rkf = 0 for bytes 64..127),
+                // so all three addresses were steered to rank[0], its minima are FAST_NONE8 with value +inf, which no `best`
+                // reaches, and the key comes out as 0x8000 | FAST_NONE8 = FAST_KNONE by itself.  Only the cube this root has just
+                // captured (root-dependent) reads garbage leaves above: its key is forced to "no such cube".
+                u32 rk = p2[ii];
+                rk = v1[ii] <= best ? p1[ii] : rk;
+                rk = va[ii] <= best ? a[ii][0] : rk;
+                u32 key = rk | (v2[ii] <= best ? D3_CUT : 0x8000u);
+                key = rnk[i] != dest ? key : FAST_KNONE;
                 publish<T>(key, i, tr); // after this every lane holds tr[k] for all six cubes (cube k = j + T*i lives in lane j)
             }
         }
@@ -452,9 +456,11 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
             const u32 w = (e != FAST_KNONE ? e : min(u, dn)) & 0x1FFFu;
             publish<T>(w, i, wq);
         }
-        double v = 0.0;
+        // expected_val += val / 6 in dice order, minimax.py:72.  The sum starts from its first term: 0.0 + x is x bit for bit unless
+        // x is -0.0, and no table holds one (build_fast_tables checks val6[])
+        double v = ft_val6<S>(Tb, wq[0]);
         #pragma unroll
-        for (int d = 0; d < 6; d++) v = v + ft_val6<S>(Tb, wq[d]); // expected_val += val / 6 in dice order, minimax.py:72
+        for (int d = 1; d < 6; d++) v = v + ft_val6<S>(Tb, wq[d]);
         v = term ? 10.0 : v;
         if (valid && v > best) { best = v; bflag = slot == 0 ? flag0 : 0; bdir = dir; if constexpr (PERLANE) bm = rmL | ((u32)dest << 16); }
     }
