@@ -46,4 +46,5 @@ class ExpectiMinimaxAgent(PolicyBase):
 class AlphaZeroMinimaxAgent(PolicyBase):
     def __init__(self, *args, **kwargs):
         raise NotImplementedError("AlphaZeroMinimaxAgent needs the un-vendored alpha_zero_models weights "
-                                  "(classical_policies/minimax.py:96-223); out of scope of the MI355X hot path")
+                                  "(classical_policies/minimax.py:96-223); classical_policies.ValueSearchAgent is the search on "
+                                  "a network trained here (one-ply lookahead on the actor-critic's own value net)")

@@ -62,3 +62,24 @@ class ModelAgent(PolicyBase):
         """(board, dice, t) -> actions, the callable tournament.evaluate takes; a sampling agent keys step t as
         key + 0x9E3779B97F4A7C15 * (t + 1), like the MCTS agent of tournament._policy"""
         return lambda b, d, t: self.predict_batch(b, d, key=(self.key + 0x9E3779B97F4A7C15 * (t + 1)) & 0xFFFFFFFFFFFFFFFF)
+
+
+class ValueSearchAgent(ModelAgent):
+    """The trained actor-critic searching one move ahead with its own value net (ewn_predict_lookahead): one agent move,
+    the opponent's best reply under every dice, the critic at the next agent-to-move state -- plain expectiminimax, no pruning.  This
+    project's counterpart of the reference's AlphaZeroMinimaxAgent (classical_policies/minimax.py:96-223: expectiminimax whose leaf
+    is a network's value), on the network the trainers here produce.  Always deterministic: the first maximum of Q."""
+
+    def __init__(self, model_or_path, board_size=5, cube_layer=3, terminal_value=1.0):
+        super().__init__(model_or_path, board_size=board_size, cube_layer=cube_layer, deterministic=True)
+        self.terminal_value = float(terminal_value)
+
+    def predict_batch(self, boards, dice, return_q=False):
+        """boards (M,S,S), dice (M,) device or host arrays -> int8 (M,2) device tensor (and the float32 (M,2,3) Q if asked for)"""
+        b, d = self._on_device(boards, dice)
+        return self._ea.predict_lookahead(b, d, self.params, terminal_value=self.terminal_value, return_q=return_q,
+                                          cube_layer=self.cube_layer)
+
+    def policy_fn(self):
+        """(board, dice, t) -> actions, the callable tournament.evaluate takes"""
+        return lambda b, d, t: self.predict_batch(b, d)

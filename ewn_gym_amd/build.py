@@ -19,7 +19,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
 # (v_pk_add_f32 ...), which measured (tools/mfma_probe.hip) do not overlap with the bf16 matrix pipe the way plain VALU work does
 FILE_FLAGS = {"ewn_policy.hip": ["-fno-slp-vectorize"], "ewn_policy_eval.hip": ["-fno-slp-vectorize"],
               "ewn_policy_eval_mcts.hip": ["-fno-slp-vectorize"], "ewn_selfplay.hip": ["-fno-slp-vectorize"],
-              "ewn_step_vs.hip": ["-fno-slp-vectorize"], "ewn_predict_policy.hip": ["-fno-slp-vectorize"]}
+              "ewn_step_vs.hip": ["-fno-slp-vectorize"], "ewn_predict_policy.hip": ["-fno-slp-vectorize"],
+              "ewn_predict_lookahead.hip": ["-fno-slp-vectorize"]}
 
 
 def stale():

@@ -1,0 +1,247 @@
+// ewn_predict_lookahead.hip -- one-ply lookahead on the trained critic (C ABI: ewn_predict_lookahead): what the actor-critic plays when
+// it searches one agent move and one reply ahead and asks its own value net at the next agent-to-move state.  Plain expectiminimax, NO
+// alpha-beta window: Q is a continuous function of the leaf values.  Per observation (b, d), agent = TOP_LEFT:
+//   Q[f][r]   = -inf                              the move of cube find_cube_to_move(f) in direction r leaves the board
+//             = +terminal_value                   b1 (the board after it) has the agent on the far corner or no opposing cube
+//             = 1/6 sum_{d1} R(b1, d1)            otherwise
+//   R(b1, d1) = min over BOTTOM_RIGHT's replies under d1 (cubes find_cube_to_move(True / False), directions that stay on the board) of
+//   W(reply)  = -terminal_value                   b2 (the board after the reply) has the opponent on (0, 0) or no agent cube
+//             = 1/6 sum_{d2} V(b2, d2)            otherwise; V = the value net, ewn_predict_policy's `value` for that observation
+//   action    = the first maximum of Q in (f, r) order (strict >, as pol_pick_*)
+// The dice only SELECTS among replies: a root has at most 6 cubes x 3 directions = 18 distinct replies, an observation 6 x 18 = 108 distinct
+// b2, each evaluated under six d2: at most 648 columns of the value net, 21 MFMA tiles.  The leaf arithmetic is ewn_predict_policy's
+// (mlp3_pack_fwd's image of net 1, pol_obs_operand on a zero-padded slot, mlp3_forward<S, 1>).
+#include "ewn_policy_host.hpp"
+
+#define LA_NT 256            // threads per block: four waves, one observation each per trip
+#define LA_MAX_BLOCKS 256    // one block per CU (PRED_MAX_BLOCKS' reasoning); more observations than that are walked grid-stride
+#define LA_REPLIES 18        // (reply cube 1 .. 6, direction 0 .. 2) per root
+#define LA_TUPLES 108        // (root 0 .. 5 = 3 f + r, reply): tuple t = 18 root + 3 (cube - 1) + direction
+#define LA_NONE (-1)         // a tuple's meta byte: no such reply (or a root that is not searched) ...
+#define LA_LOST (-2)         // ... a reply that wins for the opponent; >= 0: the b2's leaf slot
+
+// LDS of k_predict_lookahead<S>: the value net's image | per wave: the observation as a slot | cube positions | tuple meta | W | R | Q |
+// V [648] | 108 leaf slots of RecGeo<S>::STR bytes
+template <int S> struct LaGeo {
+    static constexpr int CELLS = S * S, STR = RecGeo<S>::STR, NW = LA_NT / 64;
+    static constexpr int O_BASE = 0;                          // the observation's board, zero past the board (a slot: copied whole)
+    static constexpr int O_POS = O_BASE + STR;                // [16] cell of agent cube k at k, of opposing cube k at 8 + k; 0xFF: absent
+    static constexpr int O_META = O_POS + 16;                 // [108] int8, padded to 112
+    static constexpr int O_W = O_META + 112;                  // [108] float: W(reply), +inf where there is none
+    static constexpr int O_R = O_W + LA_TUPLES * 4;           // [36] float: R(root, d1)
+    static constexpr int O_Q = O_R + 36 * 4;                  // [6] float, padded to 8
+    static constexpr int O_V = O_Q + 8 * 4;                   // [648] float: V(leaf slot, d2) at 6 slot + d2 - 1
+    static constexpr int O_SLOTS = O_V + LA_TUPLES * 6 * 4;
+    static constexpr int WAVE_BYTES = O_SLOTS + LA_TUPLES * STR;
+    static_assert(CELLS <= 64, "one lane per cell");
+    static_assert(STR % 16 == 0 && WAVE_BYTES % 16 == 0, "every region starts on a 16-byte boundary");
+    static constexpr size_t lds_bytes() { return (size_t)Mlp3Geo<S>::FWD_BYTES + (size_t)NW * WAVE_BYTES; }
+};
+
+struct LaBuf { const int8_t *boards; const int8_t *dice; const float *params; int8_t *actions; float *q; };
+
+// find_cube_to_move (envs/ewn.py:178-215) on a presence mask (bit k: cube k is on the board, k = 1 .. 6; P != 0), d = 1 .. 6: the dice's
+// cube, else the nearest larger / smaller one as asked for, else the other.  The same for both players: "larger" is the larger number
+EWN_DEV int la_find(int larger, int d, int P)
+{
+    if ((P >> d) & 1) return d;
+    const int up = P & ~((2 << d) - 1), dn = P & ((1 << d) - 1);
+    const int hi = up ? __builtin_ctz(up) : 0, lo = dn ? 31 - __builtin_clz(dn) : 0;
+    return larger ? (hi ? hi : lo) : (lo ? lo : hi);
+}
+
+// the agent's move of root `root` (= 3 f + r): code 0 it leaves the board, 1 it wins, 2 it is searched
+struct LaRoot { int code, cube, src, dst, PA1, PO1; };     // PA1 / PO1: the presence masks of b1
+
+template <int S>
+EWN_DEV LaRoot la_root(const int8_t *base, const uint8_t *pos, int PA, int PO, int c0, int c1, int root)
+{
+    const int f = root >= 3, r = root - 3 * f;
+    LaRoot o;
+    o.cube = f ? c1 : c0;
+    o.src = pos[o.cube];
+    const int x = o.src / S, y = o.src % S;
+    const bool on = (r == 1 || y < S - 1) && (r == 0 || x < S - 1);
+    o.dst = on ? o.src + (r == 0 ? 1 : r == 1 ? S : S + 1) : o.src;
+    const int v0 = base[o.dst];                                // what the move captures, own cubes included (envs/ewn.py:252-260)
+    o.PA1 = PA & ~(v0 > 0 ? 1 << (v0 & 7) : 0);
+    o.PO1 = PO & ~(v0 < 0 ? 1 << (-v0 & 7) : 0);
+    o.code = !on ? 0 : (o.dst == S * S - 1 || o.PO1 == 0) ? 1 : 2;
+    return o;
+}
+
+// Everything is per wave; nothing after the pack crosses a wave, so there is no block barrier in the loop.  Phases per observation:
+// (a) lanes enumerate the 108 tuples (two per lane) and write each distinct non-terminal b2 into the next free leaf slot (ballot ranks);
+// (b) the value net over tiles of 32 columns, column = 6 slot + d2 - 1; (c) W per tuple, R per (root, d1), Q per root, the pick, the stores.
+template <int S>
+__global__ __launch_bounds__(LA_NT, 1) void k_predict_lookahead(int M, float tv, LaBuf B)
+{
+    using P = LaGeo<S>;
+    using Q3 = Mlp3Geo<S>;
+    constexpr int CELLS = P::CELLS, STR = P::STR;
+    static_assert(Q3::FWD_BYTES % 16 == 0, "image alignment");
+    extern __shared__ __attribute__((aligned(16))) int8_t lds[];
+    int8_t *Wvf = lds;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int8_t *mine = lds + Q3::FWD_BYTES + wave * P::WAVE_BYTES;
+    int8_t *base = mine + P::O_BASE, *meta = mine + P::O_META, *slots = mine + P::O_SLOTS;
+    uint8_t *pos = (uint8_t *)(mine + P::O_POS);
+    float *Wt = (float *)(mine + P::O_W), *Rt = (float *)(mine + P::O_R), *Qt = (float *)(mine + P::O_Q), *Vt = (float *)(mine + P::O_V);
+    mlp3_pack_fwd<S>(Wvf, B.params, 1, threadIdx.x, LA_NT);
+    __syncthreads();
+
+    const float inf = __builtin_inff();
+    #pragma unroll 1
+    for (int m0 = (int)blockIdx.x * P::NW + wave; m0 < M; m0 += (int)gridDim.x * P::NW) {   // wave-uniform
+        const size_t m = (size_t)m0;
+        // ---- the observation: board -> base (zero past the board), cube positions, presence masks (all wave-uniform)
+        const int cell = lane < CELLS ? (int)B.boards[m * CELLS + lane] : 0;
+        int d = (int)B.dice[m];
+        d = d < 1 ? 1 : d > 6 ? 6 : d;
+        if (lane < STR) base[lane] = (int8_t)cell;
+        if (lane < 16) pos[lane] = 0xFFu;
+        __builtin_amdgcn_wave_barrier();
+        if (cell != 0 && cell >= -6 && cell <= 6) pos[cell > 0 ? cell : 8 - cell] = (uint8_t)lane;
+        __builtin_amdgcn_wave_barrier();
+        const u32 have = (u32)__builtin_amdgcn_ballot_w64(lane < 16 && pos[lane & 15] != 0xFFu);
+        const int PA = (int)(have & 0x7Eu), PO = (int)((have >> 8) & 0x7Eu);
+        // a row that is already over (check_win) or has no agent cube: action (0, 0), every Q -inf
+        if (PA == 0 || PO == 0 || base[0] < 0 || base[CELLS - 1] > 0) {
+            if (lane < 2) B.actions[m * 2 + lane] = 0;
+            if (B.q && lane < 6) B.q[m * 6 + lane] = -inf;
+            __builtin_amdgcn_wave_barrier();                   // base and pos are read: the next trip may overwrite them
+            continue;
+        }
+        const int c0 = la_find(0, d, PA), c1 = la_find(1, d, PA);   // both flags name one cube unless the dice's cube is gone (c1 == c0)
+        auto searched = [&](int root) { return root >= 3 && c1 == c0 ? root - 3 : root; };   // ... then roots 3 .. 5 are roots 0 .. 2
+
+        // ---- (a) tuple t = lane + 64 half: the reply of cube k in direction e to root `root`
+        int mt[2];
+        int src0[2], dst0[2], cub0[2], src1[2], dst1[2], cub1[2];
+        #pragma unroll
+        for (int half = 0; half < 2; half++) {
+            const int t = lane + 64 * half, root = t / LA_REPLIES, k = (t % LA_REPLIES) / 3 + 1, e = t % 3;
+            mt[half] = LA_NONE; src0[half] = dst0[half] = cub0[half] = src1[half] = dst1[half] = cub1[half] = 0;
+            if (t < LA_TUPLES && searched(root) == root) {
+                const LaRoot R = la_root<S>(base, pos, PA, PO, c0, c1, root);
+                if (R.code == 2 && ((R.PO1 >> k) & 1)) {
+                    const int s1 = pos[8 + k], x1 = s1 / S, y1 = s1 % S;
+                    if ((e == 1 || y1 > 0) && (e == 0 || x1 > 0)) {
+                        const int t1 = s1 - (e == 0 ? 1 : e == 1 ? S : S + 1);
+                        const int v1 = t1 == R.dst ? R.cube : t1 == R.src ? 0 : (int)base[t1];   // b1[t1]: what the reply captures
+                        const int PA2 = R.PA1 & ~(v1 > 0 ? 1 << (v1 & 7) : 0);
+                        mt[half] = (t1 == 0 || PA2 == 0) ? LA_LOST : 0;
+                        src0[half] = R.src; dst0[half] = R.dst; cub0[half] = R.cube; src1[half] = s1; dst1[half] = t1; cub1[half] = -k;
+                    }
+                }
+            }
+        }
+        const u64 leaf0 = __builtin_amdgcn_ballot_w64(mt[0] == 0), leaf1 = __builtin_amdgcn_ballot_w64(mt[1] == 0);
+        const int n0 = __builtin_popcountll(leaf0), nleaf = n0 + __builtin_popcountll(leaf1);   // <= 108
+        #pragma unroll
+        for (int half = 0; half < 2; half++) {
+            const u64 bal = half ? leaf1 : leaf0;
+            const int rank = (half ? n0 : 0) + (int)__builtin_amdgcn_mbcnt_hi((u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, 0u));
+            const int t = lane + 64 * half;
+            if (mt[half] == 0) {                               // b2 = the observation with the two moves applied, in their order
+                int8_t *sl = slots + rank * STR;
+                #pragma unroll
+                for (int w = 0; w < STR / 4; w++) ((u32 *)sl)[w] = ((const u32 *)base)[w];
+                sl[src0[half]] = 0; sl[dst0[half]] = (int8_t)cub0[half];
+                sl[src1[half]] = 0; sl[dst1[half]] = (int8_t)cub1[half];
+                mt[half] = rank;
+            }
+            if (t < LA_TUPLES) meta[t] = (int8_t)mt[half];
+        }
+        __builtin_amdgcn_wave_barrier();
+
+        // ---- (b) the value net: 32 columns per tile (both lane halves hold column lane & 31), column c = leaf slot c / 6 under d2 = c % 6 + 1
+        const int ncol = 6 * nleaf, j = lane & 31, h = lane >> 5;
+        #pragma unroll 1
+        for (int c00 = 0; c00 < ncol; c00 += 32) {             // wave-uniform
+            const int c = c00 + j;
+            const bool live = c < ncol;
+            const int slot = live ? c / 6 : 0, dj = live ? c % 6 + 1 : 0;   // a column past the last: slot 0 (written: nleaf >= 1), no dice
+            const int8_t *sj = slots + slot * STR + 8 * h;
+            auto xb = [&](int kb) { return pol_obs_operand<S>(sj, kb, h, dj); };
+            f32x16 h1[2], h2[2];
+            float vo[1];
+            mlp3_forward<S, 1>(Wvf, lane, xb, h1, h2, vo);
+            if (live && h == 0) Vt[c] = vo[0];
+        }
+        __builtin_amdgcn_wave_barrier();
+
+        // ---- (c) W per tuple: the mean over d2, in d2 order
+        #pragma unroll
+        for (int half = 0; half < 2; half++) {
+            const int t = lane + 64 * half;
+            if (t < LA_TUPLES) {
+                const int mm = meta[t];
+                float w = mm == LA_NONE ? inf : -tv;
+                if (mm >= 0) {
+                    const float *v = Vt + 6 * mm;
+                    w = (((((v[0] + v[1]) + v[2]) + v[3]) + v[4]) + v[5]) * (1.0f / 6.0f);
+                }
+                Wt[t] = w;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        // R per (root, d1): the minimum over the replies of the (at most two) cubes d1 selects; a non-terminal b1 always has a reply
+        if (lane < 36) {
+            const int root = searched(lane / 6), d1 = lane % 6 + 1;
+            const LaRoot R = la_root<S>(base, pos, PA, PO, c0, c1, root);
+            float r = 0.0f;
+            if (R.code == 2) {
+                const float *wa = Wt + root * LA_REPLIES + 3 * (la_find(0, d1, R.PO1) - 1), *wb = Wt + root * LA_REPLIES + 3 * (la_find(1, d1, R.PO1) - 1);
+                r = wa[0];
+                r = wa[1] < r ? wa[1] : r; r = wa[2] < r ? wa[2] : r;
+                r = wb[0] < r ? wb[0] : r; r = wb[1] < r ? wb[1] : r; r = wb[2] < r ? wb[2] : r;
+            }
+            Rt[lane] = r;
+        }
+        __builtin_amdgcn_wave_barrier();
+        // Q per root: the mean over d1, in d1 order
+        if (lane < 6) {
+            const int root = searched(lane);
+            const LaRoot R = la_root<S>(base, pos, PA, PO, c0, c1, root);
+            const float *r = Rt + 6 * lane;
+            float qv = (((((r[0] + r[1]) + r[2]) + r[3]) + r[4]) + r[5]) * (1.0f / 6.0f);
+            qv = R.code == 0 ? -inf : R.code == 1 ? tv : qv;
+            Qt[lane] = qv;
+            if (B.q) B.q[m * 6 + lane] = qv;
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (lane == 0) {
+            int best = 0;
+            float qb = Qt[0];
+            #pragma unroll
+            for (int i = 1; i < 6; i++) { const float qi = Qt[i]; if (qi > qb) { qb = qi; best = i; } }
+            B.actions[m * 2] = (int8_t)(best / 3); B.actions[m * 2 + 1] = (int8_t)(best % 3);
+        }
+        __builtin_amdgcn_wave_barrier();                       // this trip's LDS is read: the next may overwrite it
+    }
+}
+
+template <int S>
+static int la_launch(int M, float tv, const LaBuf &lb, hipStream_t s)
+{
+    constexpr size_t lds = LaGeo<S>::lds_bytes();
+    static_assert(lds <= POL_LDS_MAX, "the value net's image + four waves' slots and tables must fit the CU's LDS");
+    const int need = (M - 1) / LaGeo<S>::NW + 1;
+    return pol_launch_kernel(k_predict_lookahead<S>, (unsigned)(need < LA_MAX_BLOCKS ? need : LA_MAX_BLOCKS), LA_NT, lds, 64 * 1024, POL_LDS_MAX, s,
+                             M, tv, lb);
+}
+
+// ewn_predict_policy's order of refusals: arguments, geometry, the empty batch, pointers; then the terminal value -- all before the launch
+int ewn_predict_lookahead(int board_size, int cube_layer, int M, const int8_t *boards, const int8_t *dice, const float *params,
+                          float terminal_value, int8_t *actions, float *q, void *stream)
+{
+    if (M < 0) return EWN_EINVAL;
+    if (ewn_policy_param_count(board_size, cube_layer) < 0) return EWN_EUNSUPPORTED;
+    if (M == 0) return EWN_OK;
+    if (!boards || !dice || !params || !actions) return EWN_ENULL;
+    if (!std::isfinite(terminal_value)) return EWN_EINVAL;
+    LaBuf lb = { boards, dice, params, actions, q };
+    hipStream_t s = (hipStream_t)stream;
+    return board_size == 5 ? la_launch<5>(M, terminal_value, lb, s) : la_launch<7>(M, terminal_value, lb, s);
+}

@@ -639,14 +639,14 @@ def predict_mcts(boards, dice, num_simulations=10, num_env_copies=5, key=0, obs_
     return acts, wins
 
 
-def _policy_input(name, x, dtype, shape, dev):
+def _policy_input(name, x, dtype, shape, dev, who="predict_policy"):
     """a tensor is taken as it is and must already be what the kernel reads; anything else (numpy, lists) is copied to the device"""
     if not isinstance(x, torch.Tensor):
         x = torch.as_tensor(np.asarray(x)).to(dtype).reshape(shape)
         return x if dev.type != "cuda" else x.to(dev)
     if x.dtype != dtype or x.numel() != math.prod(shape) or not x.is_contiguous():
-        raise ValueError("predict_policy: %s must be a contiguous %s tensor of %s elements, got %s" % (
-            name, str(dtype).replace("torch.", ""), " x ".join(map(str, shape)), _describe(x)))
+        raise ValueError("%s: %s must be a contiguous %s tensor of %s elements, got %s" % (
+            who, name, str(dtype).replace("torch.", ""), " x ".join(map(str, shape)), _describe(x)))
     return x.reshape(shape)
 
 
@@ -697,3 +697,41 @@ def predict_policy(boards, dice, params, deterministic=True, key=0, obs_id=None,
                                      _stream()), "ewn_predict_policy")
     out = (acts,) + ((logits,) if return_logits else ()) + ((value,) if return_value else ())
     return out[0] if len(out) == 1 else out
+
+
+def predict_lookahead(boards, dice, params, terminal_value=1.0, return_q=False, cube_layer=3):
+    """What the trained actor-critic plays when it looks one move ahead with its own value net (ewn_predict_lookahead):
+    per observation and env action (f, r), Q = -inf for a move that leaves the board, +terminal_value for one that wins, otherwise the
+    mean over the opponent's dice of its best (minimal) reply, a reply being worth -terminal_value if it wins for the opponent and
+    else the mean over the agent's next dice of the value net there.  Plain expectiminimax, no pruning.  boards [S, S] or [M, S, S],
+    dice [M] (outside 1..6: clamped), params as predict_policy takes them -> actions int8 [M, 2] (the first maximum of Q), and with
+    return_q the float32 [M, 2, 3] Q as well.  A row that is already over, or has no agent cube, gets (0, 0) and six -inf.  The same
+    argument checks as predict_policy: anything the kernel cannot read in place raises ValueError before a launch."""
+    lib = _lib.load()
+    shp = tuple(boards.shape) if isinstance(boards, torch.Tensor) else np.asarray(boards).shape
+    if len(shp) == 2:
+        shp = (1,) + tuple(shp)
+    if len(shp) != 3 or shp[1] != shp[2]:
+        raise ValueError("predict_lookahead: boards must have shape [S, S] or [M, S, S], got %s" % (list(shp),))
+    M, S = int(shp[0]), int(shp[1])
+    P = lib.ewn_policy_param_count(S, int(cube_layer))
+    if P < 0:
+        raise ValueError("predict_lookahead: no policy network for %dx%d boards with cube_layer %d (served: cube_layer 3 on 5x5 and 7x7)" % (
+            S, S, cube_layer))
+    if not (isinstance(params, torch.Tensor) and params.dtype == torch.float32 and params.is_contiguous() and params.numel() == P):
+        raise ValueError("predict_lookahead: params must be a contiguous float32 tensor of %d elements (the %dx%d actor-critic), got %s" % (
+            P, S, S, _describe(params)))
+    if not math.isfinite(float(terminal_value)):
+        raise ValueError("predict_lookahead: terminal_value must be finite, got %r" % (terminal_value,))
+    dev = params.device
+    b = _policy_input("boards", boards, torch.int8, (M, S, S), dev, who="predict_lookahead")
+    d = _policy_input("dice", dice, torch.int8, (M,), dev, who="predict_lookahead")
+    for name, t in (("params", params), ("boards", b), ("dice", d)):
+        if not (t.is_cuda and t.device == dev):
+            raise ValueError("predict_lookahead: %s must live on the GPU that holds params (%s), got %s" % (name, dev, _describe(t)))
+    acts = torch.zeros((M, 2), dtype=torch.int8, device=dev)
+    q = torch.zeros((M, 2, 3), dtype=torch.float32, device=dev) if return_q else None
+    with torch.cuda.device(dev):
+        check(lib.ewn_predict_lookahead(S, int(cube_layer), M, _ptr(b), _ptr(d), _ptr(params), C.c_float(float(terminal_value)), _ptr(acts),
+                                        _ptr(q), _stream()), "ewn_predict_lookahead")
+    return (acts, q) if return_q else acts

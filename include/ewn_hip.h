@@ -521,6 +521,21 @@ int ewn_predict_policy(int board_size, int cube_layer, int M, const int8_t *boar
                        int deterministic, uint64_t key, const uint32_t *obs_id, const float *uniforms, int8_t *actions, float *logits,
                        float *value, void *stream);
 
+/* One-ply lookahead on the trained critic: what the actor-critic plays when it searches one agent move and one reply ahead and asks
+ * its own value net V (ewn_predict_policy's `value`) at the next agent-to-move state.  Per observation (agent = TOP_LEFT; dice outside
+ * 1..6 are clamped), for the six env actions (f, r):  Q[f][r] = -inf if the move of find_cube_to_move(f) in direction r leaves the
+ * board; +terminal_value if the board after it, b1, has the agent on the far corner or no opposing cube; otherwise
+ * 1/6 sum_{d1 = 1..6} min over BOTTOM_RIGHT's legal replies under d1 of W, W = -terminal_value if the board after the reply, b2, has
+ * the opponent on (0, 0) or no agent cube, else 1/6 sum_{d2 = 1..6} V(b2, d2).  Plain expectiminimax, no alpha-beta window: Q is a
+ * continuous function of the leaf values.  actions [M][2] (required): the first maximum of Q in (f, r) order (strict >); q [M][6] may
+ * be NULL.  A row that is already over (check_win) or has no agent cube gets action (0, 0) and six -inf.  params: the
+ * ewn_policy.params layout; served where ewn_policy_param_count() is (EWN_EUNSUPPORTED elsewhere); a non-finite terminal_value is
+ * EWN_EINVAL.  One kernel launch on `stream`, no allocation, no synchronisation, no scratch; M == 0 is EWN_OK without a launch.  Reads
+ * exactly boards[0 .. M*S*S), dice[0 .. M); writes exactly the M rows of the outputs given. */
+int ewn_predict_lookahead(int board_size, int cube_layer, int M, const int8_t *boards, const int8_t *dice,
+                          const float *params, float terminal_value, int8_t *actions /* [M][2] */,
+                          float *q /* [M][6], optional */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,108 @@
+"""Timing and playing strength of the one-ply lookahead on the trained critic.
+
+  python tools/lookahead_time.py [--runs 5] [--updates 600] [--episodes 1024]
+
+Part 1, per board (5x5, 7x7) and batch (M = 1, 1 024, 65 536): predict_lookahead (ewn_predict_lookahead, actions only) beside
+predict_policy on the same observations, alternated in the same process.  Each figure is the median of `--runs` timed windows after
+warm-up, a window being `launches` back-to-back calls between two device events with a synchronisation before and after; microseconds
+per call.  With it the mean number of leaf columns (distinct non-terminal reply positions x 6 dice) per observation, counted on the host
+from the rules on the first 1 024 observations.
+
+Part 2, 5x5: a FusedA2CTrainer trained as tools/eval_policy_time.py trains its model (shaped env, reward 10, RandomAgent, `--updates`
+updates), then over `--episodes` episodes (seeds 0 .. n-1, MT19937-compat dice) the win rate of its raw argmax policy and of its lookahead
+policy (terminal_value = the reward it was trained on) against RandomAgent and against minimax(5), with Wilson 95 % intervals.
+Prints one JSON line per row.  No pass bar: nothing here was measured before."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import ewn_gym_amd as ea  # noqa: E402
+from ewn_gym_amd.a2c import ActorCritic, FusedA2CTrainer  # noqa: E402
+from ewn_gym_amd.tournament import evaluate  # noqa: E402
+from tools.predict_policy_time import observations, timed  # noqa: E402
+
+
+def find_cube(present, d, larger):
+    if d in present:
+        return d
+    up = [k for k in range(d + 1, 7) if k in present]
+    dn = [k for k in range(d - 1, 0, -1) if k in present]
+    return ((up or dn) if larger else (dn or up))[0]
+
+
+def targets(board, k, sign):
+    """[(x, y, nx, ny)] of the moves of cube sign * k that stay on the board"""
+    S = board.shape[0]
+    x, y = (int(v) for v in np.argwhere(board == sign * k)[0])
+    return [(x, y, x + sign * dx, y + sign * dy) for dx, dy in ((0, 1), (1, 0), (1, 1)) if 0 <= x + sign * dx < S and 0 <= y + sign * dy < S]
+
+
+def leaf_columns(board, d):
+    """6 x the number of distinct non-terminal positions after (agent move, reply): what the kernel runs the value net on"""
+    if board[0, 0] < 0 or board[-1, -1] > 0 or not (board > 0).any() or not (board < 0).any():
+        return 0
+    mine = {int(v) for v in board.flat if v > 0}
+    n = 0
+    for c in {find_cube(mine, d, False), find_cube(mine, d, True)}:
+        for x, y, nx, ny in targets(board, c, 1):
+            b1 = board.copy()
+            b1[x, y], b1[nx, ny] = 0, c
+            if b1[-1, -1] > 0 or not (b1 < 0).any():
+                continue
+            for k in {-int(v) for v in b1.flat if v < 0}:
+                for x1, y1, nx1, ny1 in targets(b1, k, -1):
+                    b2 = b1.copy()
+                    b2[x1, y1], b2[nx1, ny1] = 0, -k
+                    n += not (b2[0, 0] < 0 or not (b2 > 0).any())
+    return 6 * n
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--updates", type=int, default=600)
+    ap.add_argument("--episodes", type=int, default=1024)
+    a = ap.parse_args()
+    for S in (5, 7):
+        torch.manual_seed(9)
+        params = ActorCritic(S, 6).cuda().flat_parameters()
+        for M in (1, 1024, 65536):
+            b, d = observations(S, M)
+            hb, hd = b[:1024].cpu().numpy(), d[:1024].cpu().numpy()
+            cols = float(np.mean([leaf_columns(hb[m], int(hd[m])) for m in range(hb.shape[0])]))
+            fns = {"predict_lookahead": lambda: ea.predict_lookahead(b, d, params), "predict_policy": lambda: ea.predict_policy(b, d, params)}
+            launches = 200 if M <= 1024 else 20
+            for fn in fns.values():                                       # warm-up
+                for _ in range(5):
+                    fn()
+            rows = {}
+            for _ in range(2):                                            # alternate the two, keep the later pass
+                for name, fn in fns.items():
+                    rows[name] = timed(fn, launches, a.runs)
+            print(json.dumps({"board": S, "M": M, "us_per_call_median_min_max": rows, "mean_leaf_columns_per_observation": round(cols, 1)}), flush=True)
+
+    S, N, reward = 5, 4096, 10.0
+    env = ea.VecEWN(N, board_size=S, opponent_policy="random", rng="philox", shaped=True, reward=reward, illegal_move_tolerance=10,
+                    autoreset=True, shaped_refresh_on_reset=True, philox_key=1)
+    env.reset(seeds=torch.arange(N, dtype=torch.int32))
+    tr = FusedA2CTrainer(env, n_steps=5, learning_rate=1e-3, seed=0)
+    for _ in range(a.updates):
+        tr.collect_and_update()
+    torch.cuda.synchronize()
+    for opp in ({"kind": "random"}, {"kind": "minimax", "max_depth": 5}):
+        for name, agent in (("argmax", {"kind": "mlp", "model": tr.model}),
+                            ("lookahead", {"kind": "mlp_lookahead", "model": tr.model, "terminal_value": reward})):
+            r = evaluate(agent, opp, num=a.episodes, board_size=S)
+            print(json.dumps({"policy": name, "opponent": opp["kind"] + ("(5)" if opp["kind"] == "minimax" else ""), "updates": a.updates,
+                              "episodes": r["episodes"], "wins": r["wins"], "win_rate": round(r["win_rate"], 4),
+                              "ci95": [round(x, 4) for x in r["ci95"]], "avg_length": round(r["avg_length"], 2), "engine": r["engine"]}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
