@@ -115,7 +115,11 @@ __device__ __forceinline__ double d5_search(const FastTab<S> *Tb, const RState<S
     typedef typename MaskOf<S>::type M;
     const M one = 1;
     const double inf = __builtin_inf();
-    const u32 rank10 = 8u * (u32)Tb->nv; // +10 is the largest value of the table (ranks travel as byte offsets, ewn_fast.hpp)
+    // a won position's +10 (ranks travel as byte offsets, ewn_fast.hpp).  On the (level, count) images it is the table's largest value;
+    // on the 'two_min_dist' image the differences of distance sums reach +11 on 7x7 and +13 on 8x8 and rank above it: step down to it
+    // (at most three entries; every image holds +10)
+    u32 rank10 = 8u * (u32)Tb->nv;
+    while (ft_val<S>(Tb, rank10) > 10.0) rank10 -= 8u;
     double best = -inf, alpha = -inf;
     bflag = 0; bdir = 0;
     const u32 e0 = pk_sel<S>(Tb, c.posP, dice), pp0 = pk_pair(c.posP, e0);

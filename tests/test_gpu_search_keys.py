@@ -198,16 +198,17 @@ def test_predict_on_constructed_positions(ea, S, heur):
         assert bad.size == 0, (S, heur, depth, bad[:5].tolist(), b[bad[:1]], d[bad[:1]])
 
 
-def _pair(ea, N, lo, hi, S, heur, key, autoreset=True):
-    """engine env of N lanes and oracle env of its lanes lo..hi, both holding the constructed positions (lane l: position 7 l mod M)"""
-    b, d = positions(S)
+def _pair(ea, N, lo, hi, S, heur, key, autoreset=True, max_depth=3, rng="philox", opponent="minimax", pos=None):
+    """engine env of N lanes and oracle env of its lanes lo..hi, both holding the constructed positions (lane l: position 7 l mod M);
+    pos: (boards, dice) to use instead of this module's positions(S)"""
+    b, d = positions(S) if pos is None else pos
     idx = (np.arange(N) * 7) % len(b)
-    kw = dict(board_size=S, max_depth=3, heuristic=heur, rng="philox", philox_key=key, autoreset=autoreset, seed_stride=N)
-    env = ea.VecEWN(N, opponent_policy="minimax", **kw)
+    kw = dict(board_size=S, max_depth=max_depth, heuristic=heur, rng=rng, philox_key=key, autoreset=autoreset, seed_stride=N)
+    env = ea.VecEWN(N, opponent_policy=opponent, **kw)
     seeds = (np.arange(N, dtype=np.uint64) * 7 + 1234).astype(np.uint32)
     env.reset(seeds=seeds)
     env.set_obs(b[idx], d[idx])
-    orc = po.OracleVecEnv(hi - lo, opponent="minimax", lane_offset=lo, **kw)
+    orc = po.OracleVecEnv(hi - lo, opponent=opponent, lane_offset=lo, **kw)
     orc.reset(seeds=seeds[lo:hi])
     orc.set_obs(b[idx[lo:hi]], d[idx[lo:hi]])
     return env, orc
