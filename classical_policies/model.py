@@ -68,17 +68,21 @@ class ValueSearchAgent(ModelAgent):
     """The trained actor-critic searching one move ahead with its own value net (ewn_predict_lookahead): one agent move,
     the opponent's best reply under every dice, the critic at the next agent-to-move state -- plain expectiminimax, no pruning.  This
     project's counterpart of the reference's AlphaZeroMinimaxAgent (classical_policies/minimax.py:96-223: expectiminimax whose leaf
-    is a network's value), on the network the trainers here produce.  Always deterministic: the first maximum of Q."""
+    is a network's value), on the network the trainers here produce.  Always deterministic: the first maximum of Q.  plies=2: two
+    moves ahead (agent, reply, agent, reply, critic)."""
 
-    def __init__(self, model_or_path, board_size=5, cube_layer=3, terminal_value=1.0):
+    def __init__(self, model_or_path, board_size=5, cube_layer=3, terminal_value=1.0, plies=1):
+        if plies not in (1, 2):
+            raise ValueError("ValueSearchAgent: plies must be 1 or 2, got %r" % (plies,))
         super().__init__(model_or_path, board_size=board_size, cube_layer=cube_layer, deterministic=True)
         self.terminal_value = float(terminal_value)
+        self.plies = int(plies)
 
     def predict_batch(self, boards, dice, return_q=False):
         """boards (M,S,S), dice (M,) device or host arrays -> int8 (M,2) device tensor (and the float32 (M,2,3) Q if asked for)"""
         b, d = self._on_device(boards, dice)
         return self._ea.predict_lookahead(b, d, self.params, terminal_value=self.terminal_value, return_q=return_q,
-                                          cube_layer=self.cube_layer)
+                                          cube_layer=self.cube_layer, plies=self.plies)
 
     def policy_fn(self):
         """(board, dice, t) -> actions, the callable tournament.evaluate takes"""

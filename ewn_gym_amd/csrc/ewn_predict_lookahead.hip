@@ -11,12 +11,10 @@
 // The dice only SELECTS among replies: a root has at most 6 cubes x 3 directions = 18 distinct replies, an observation 6 x 18 = 108 distinct
 // b2, each evaluated under six d2: at most 648 columns of the value net, 21 MFMA tiles.  The leaf arithmetic is ewn_predict_policy's
 // (mlp3_pack_fwd's image of net 1, pol_obs_operand on a zero-padded slot, mlp3_forward<S, 1>).
-#include "ewn_policy_host.hpp"
+#include "ewn_lookahead.hpp"
 
 #define LA_NT 256            // threads per block: four waves, one observation each per trip
 #define LA_MAX_BLOCKS 256    // one block per CU (PRED_MAX_BLOCKS' reasoning); more observations than that are walked grid-stride
-#define LA_REPLIES 18        // (reply cube 1 .. 6, direction 0 .. 2) per root
-#define LA_TUPLES 108        // (root 0 .. 5 = 3 f + r, reply): tuple t = 18 root + 3 (cube - 1) + direction
 #define LA_NONE (-1)         // a tuple's meta byte: no such reply (or a root that is not searched) ...
 #define LA_LOST (-2)         // ... a reply that wins for the opponent; >= 0: the b2's leaf slot
 
@@ -39,36 +37,6 @@ template <int S> struct LaGeo {
 };
 
 struct LaBuf { const int8_t *boards; const int8_t *dice; const float *params; int8_t *actions; float *q; };
-
-// find_cube_to_move (envs/ewn.py:178-215) on a presence mask (bit k: cube k is on the board, k = 1 .. 6; P != 0), d = 1 .. 6: the dice's
-// cube, else the nearest larger / smaller one as asked for, else the other.  The same for both players: "larger" is the larger number
-EWN_DEV int la_find(int larger, int d, int P)
-{
-    if ((P >> d) & 1) return d;
-    const int up = P & ~((2 << d) - 1), dn = P & ((1 << d) - 1);
-    const int hi = up ? __builtin_ctz(up) : 0, lo = dn ? 31 - __builtin_clz(dn) : 0;
-    return larger ? (hi ? hi : lo) : (lo ? lo : hi);
-}
-
-// the agent's move of root `root` (= 3 f + r): code 0 it leaves the board, 1 it wins, 2 it is searched
-struct LaRoot { int code, cube, src, dst, PA1, PO1; };     // PA1 / PO1: the presence masks of b1
-
-template <int S>
-EWN_DEV LaRoot la_root(const int8_t *base, const uint8_t *pos, int PA, int PO, int c0, int c1, int root)
-{
-    const int f = root >= 3, r = root - 3 * f;
-    LaRoot o;
-    o.cube = f ? c1 : c0;
-    o.src = pos[o.cube];
-    const int x = o.src / S, y = o.src % S;
-    const bool on = (r == 1 || y < S - 1) && (r == 0 || x < S - 1);
-    o.dst = on ? o.src + (r == 0 ? 1 : r == 1 ? S : S + 1) : o.src;
-    const int v0 = base[o.dst];                                // what the move captures, own cubes included (envs/ewn.py:252-260)
-    o.PA1 = PA & ~(v0 > 0 ? 1 << (v0 & 7) : 0);
-    o.PO1 = PO & ~(v0 < 0 ? 1 << (-v0 & 7) : 0);
-    o.code = !on ? 0 : (o.dst == S * S - 1 || o.PO1 == 0) ? 1 : 2;
-    return o;
-}
 
 // Everything is per wave; nothing after the pack crosses a wave, so there is no block barrier in the loop.  Phases per observation:
 // (a) lanes enumerate the 108 tuples (two per lane) and write each distinct non-terminal b2 into the next free leaf slot (ballot ranks);

@@ -49,11 +49,11 @@ def _policy(spec, cube_layer, key):
         model = spec["model"]
         return ModelAgent(model, board_size=getattr(model, "S", spec.get("board_size", 5)), cube_layer=cube_layer,
                           deterministic=spec.get("deterministic", True), key=key).policy_fn()
-    if kind == "mlp_lookahead":   # the model's one-ply lookahead on its own value net (ewn_predict_lookahead), ply by ply through ewn_step
+    if kind == "mlp_lookahead":   # the model's lookahead on its own value net (ewn_predict_lookahead; "plies": 2 the two-move one), ply by ply through ewn_step
         from classical_policies.model import ValueSearchAgent
         model = spec["model"]
         return ValueSearchAgent(model, board_size=getattr(model, "S", spec.get("board_size", 5)), cube_layer=cube_layer,
-                                terminal_value=spec.get("terminal_value", 1.0)).policy_fn()
+                                terminal_value=spec.get("terminal_value", 1.0), plies=spec.get("plies", 1)).policy_fn()
     raise ValueError("unknown agent kind %r" % kind)
 
 
@@ -74,7 +74,7 @@ def _totals_result(totals, num, engine):
 def evaluate(agent, opponent, num=1024, board_size=5, cube_layer=3, rng="mt19937", seed_offset=0, key=12345, max_steps=400,
              use_rollout=True, chunk=16):
     """agent: a dict like the opponent's, {"kind": "mlp", "model": a2c.ActorCritic} (its deterministic policy),
-    {"kind": "mlp_lookahead", "model": ..., terminal_value=} (its one-ply lookahead on its own value net, ply by ply), or a callable
+    {"kind": "mlp_lookahead", "model": ..., terminal_value=, plies=} (its lookahead on its own value net, ply by ply), or a callable
     policy (board, dice, t) -> actions.
     agent / opponent: dicts {"kind": "random"|"minimax"|"mcts", max_depth=, heuristic=, num_simulations=, num_env_copies=}.
     Returns per-episode scores (float64 tensor), episode lengths and summary statistics.
@@ -306,28 +306,31 @@ def load_policy(path, board_size=5, cube_layer=3, device="cuda"):
 
 def evaluate_model(model, names=("random", "minimax"), num=1024, max_depth=5, num_simulations=10, num_env_copies=5, board_size=5,
                    cube_layer=3, heuristic="hybrid", rng="mt19937", lookahead=False):
-    """eval_A2C.py's loop: the model's deterministic policy against every listed opponent; lookahead: and, beside each, its one-ply
-    lookahead policy ({"kind": "mlp_lookahead"}) on the same episodes"""
+    """eval_A2C.py's loop: the model's deterministic policy against every listed opponent; lookahead (1 / True, or 2): and, beside
+    each, its lookahead policy of that many moves ({"kind": "mlp_lookahead", "plies": ...}) on the same episodes"""
     table = {}
     for o in names:
         opp = {"kind": o, "max_depth": max_depth, "heuristic": heuristic, "num_simulations": num_simulations, "num_env_copies": num_env_copies}
         r = evaluate({"kind": "mlp", "model": model}, opp, num=num, board_size=board_size, cube_layer=cube_layer, rng=rng)
         table["model vs %s" % o] = {k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}
         if lookahead:
-            r = evaluate({"kind": "mlp_lookahead", "model": model}, opp, num=num, board_size=board_size, cube_layer=cube_layer, rng=rng)
-            table["lookahead vs %s" % o] = {k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}
+            plies = 2 if int(lookahead) == 2 else 1
+            r = evaluate({"kind": "mlp_lookahead", "model": model, "plies": plies}, opp, num=num, board_size=board_size, cube_layer=cube_layer,
+                         rng=rng)
+            table[("lookahead(2) vs %s" if plies == 2 else "lookahead vs %s") % o] = {k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}
     return table
 
 
-def main():
+def _parser():
     ap = argparse.ArgumentParser(description="agent-vs-opponent win-rate matrix (counterpart of eval_pairs.py); with --model, a "
                                              "trained policy against each listed opponent (counterpart of eval_A2C.py)")
     ap.add_argument("--agents", nargs="+", default=["random", "minimax", "mcts"])
     ap.add_argument("--model", default=None, help="checkpoint (best.pt) of any of the trainers: evaluate its deterministic policy")
     ap.add_argument("--opponent_model", default=None, help="a checkpoint that plays the opponent (its argmax): against --model, or "
                                                            "without --model against every agent of --agents")
-    ap.add_argument("--lookahead", action="store_true", help="with --model: beside the raw policy, its one-ply lookahead on its own "
-                                                             "value net (ewn_predict_lookahead) against the same opponents")
+    ap.add_argument("--lookahead", nargs="?", const=1, default=None, type=int, choices=(1, 2),
+                    help="with --model: beside the raw policy, its lookahead on its own value net (ewn_predict_lookahead) against the "
+                         "same opponents; the bare flag or 1: one move ahead, 2: two moves")
     ap.add_argument("--num", type=int, default=1024)
     ap.add_argument("--max_depth", type=int, default=5)
     ap.add_argument("--heuristic", default="hybrid")
@@ -336,6 +339,11 @@ def main():
     ap.add_argument("--board_size", type=int, default=5)
     ap.add_argument("--cube_layer", type=int, default=3)
     ap.add_argument("--rng", default="mt19937")
+    return ap
+
+
+def main():
+    ap = _parser()
     a = ap.parse_args()
     if a.lookahead and (a.model is None or a.opponent_model is not None):
         ap.error("--lookahead goes with --model and the classical opponents of --agents")
@@ -350,7 +358,7 @@ def main():
     elif a.model is not None:
         model = load_policy(a.model, a.board_size, a.cube_layer)
         t = evaluate_model(model, a.agents, a.num, a.max_depth, a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer,
-                           a.heuristic, a.rng, lookahead=a.lookahead)
+                           a.heuristic, a.rng, lookahead=a.lookahead or False)
     else:
         t = tournament(a.agents, a.num, a.max_depth, a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer,
                        a.heuristic, a.rng)

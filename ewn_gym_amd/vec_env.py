@@ -699,15 +699,94 @@ def predict_policy(boards, dice, params, deterministic=True, key=0, obs_id=None,
     return out[0] if len(out) == 1 else out
 
 
-def predict_lookahead(boards, dice, params, terminal_value=1.0, return_q=False, cube_layer=3):
+def _lookahead_shape(who, boards, cube_layer):
+    """(M, S) of boards [S, S] or [M, S, S]; ValueError where there is no policy network for the geometry"""
+    shp = tuple(boards.shape) if isinstance(boards, torch.Tensor) else np.asarray(boards).shape
+    if len(shp) == 2:
+        shp = (1,) + tuple(shp)
+    if len(shp) != 3 or shp[1] != shp[2]:
+        raise ValueError("%s: boards must have shape [S, S] or [M, S, S], got %s" % (who, list(shp)))
+    M, S = int(shp[0]), int(shp[1])
+    if _lib.load().ewn_policy_param_count(S, int(cube_layer)) < 0:
+        raise ValueError("%s: no policy network for %dx%d boards with cube_layer %d (served: cube_layer 3 on 5x5 and 7x7)" % (
+            who, S, S, cube_layer))
+    return M, S
+
+
+def _stage_inputs(who, named, cube_layer):
+    """the inputs of a lookahead stage, checked as predict_lookahead checks its own: named = [(name, x, dtype, shape of (M, S))], boards
+    first.  The device is the first tensor's (host arrays are copied there), and it must be a GPU."""
+    M, S = _lookahead_shape(who, named[0][1], cube_layer)
+    if M * 648 > 2 ** 31 - 1:
+        raise ValueError("%s: %d observations are %d leaf rows, more than 2^31 - 1: call in chunks" % (who, M, M * 648))
+    first = next((x for _, x, _, _ in named if isinstance(x, torch.Tensor)), None)
+    dev = first.device if first is not None else torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() \
+        else torch.device("cpu")
+    out = [_policy_input(name, x, dtype, shape(M, S), dev, who=who) for name, x, dtype, shape in named]
+    for (name, _, _, _), t in zip(named, out):
+        if not (t.is_cuda and t.device == dev):
+            raise ValueError("%s: %s must live on the GPU that holds %s (%s), got %s" % (who, name, named[0][0], dev, _describe(t)))
+    return M, S, dev, out
+
+
+def lookahead_expand(boards, dice, cube_layer=3):
+    """The leaves of predict_lookahead's tree as observations (ewn_lookahead_expand): boards [S, S] or [M, S, S], dice [M]
+    -> (leaf_boards int8 [M, 648, S, S], leaf_dice int8 [M, 648], kind int8 [M, 108]).  Tuple t = 18 (3 f + r) + 3 (cube - 1) + direction
+    is the agent's move (f, r) followed by the reply of the opponent's cube in that direction; kind[m, t] is 0 where there is no such
+    reply (or the root leaves the board, wins, or repeats roots 0..2), 1 where the reply wins for the opponent, 2 for a leaf.  Row
+    6 t + d2 - 1 holds the board after both moves and the dice d2 where kind is 2, a zero board and d2 elsewhere.  predict_lookahead's
+    argument checks."""
+    M, S, dev, (b, d) = _stage_inputs("lookahead_expand", [("boards", boards, torch.int8, lambda M, S: (M, S, S)),
+                                                           ("dice", dice, torch.int8, lambda M, S: (M,))], cube_layer)
+    lb = torch.empty((M, 648, S, S), dtype=torch.int8, device=dev)
+    ld = torch.empty((M, 648), dtype=torch.int8, device=dev)
+    kind = torch.empty((M, 108), dtype=torch.int8, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.load().ewn_lookahead_expand(S, int(cube_layer), M, _ptr(b), _ptr(d), _ptr(lb), _ptr(ld), _ptr(kind), _stream()),
+              "ewn_lookahead_expand")
+    return lb, ld, kind
+
+
+def lookahead_reduce(boards, dice, kind, leaf, terminal_value=1.0, return_q=False, cube_layer=3):
+    """Leaf values folded back into Q and the action (ewn_lookahead_reduce): boards, dice as lookahead_expand took them,
+    kind as it returned it, leaf float32 [M, 648] (a value per leaf row) or [M, 648, 6] (a q row per leaf row: its maximum is the
+    row's value) -> actions int8 [M, 2], with return_q the float32 [M, 2, 3] Q as well.  The arithmetic is predict_lookahead's: with
+    leaf = predict_policy(leaf rows, return_value=True)'s values the result is predict_lookahead's, bit for bit."""
+    who = "lookahead_reduce"
+    if not math.isfinite(float(terminal_value)):
+        raise ValueError("%s: terminal_value must be finite, got %r" % (who, terminal_value))
+    shp = tuple(leaf.shape) if isinstance(leaf, torch.Tensor) else np.asarray(leaf).shape
+    if not (len(shp) in (2, 3) and shp[1] == 648 and (len(shp) == 2 or shp[2] == 6)):
+        raise ValueError("%s: leaf must have shape [M, 648] or [M, 648, 6], got %s" % (who, list(shp)))
+    width = 6 if len(shp) == 3 else 1
+    M, S, dev, (b, d, k, lf) = _stage_inputs(who, [("boards", boards, torch.int8, lambda M, S: (M, S, S)),
+                                                  ("dice", dice, torch.int8, lambda M, S: (M,)),
+                                                  ("kind", kind, torch.int8, lambda M, S: (M, 108)),
+                                                  ("leaf", leaf, torch.float32, lambda M, S: (M, 648, width))], cube_layer)
+    acts = torch.zeros((M, 2), dtype=torch.int8, device=dev)
+    q = torch.zeros((M, 2, 3), dtype=torch.float32, device=dev) if return_q else None
+    with torch.cuda.device(dev):
+        check(_lib.load().ewn_lookahead_reduce(S, int(cube_layer), M, _ptr(b), _ptr(d), _ptr(k), _ptr(lf), width,
+                                               C.c_float(float(terminal_value)), _ptr(acts), _ptr(q), _stream()), "ewn_lookahead_reduce")
+    return (acts, q) if return_q else acts
+
+
+def predict_lookahead(boards, dice, params, terminal_value=1.0, return_q=False, cube_layer=3, plies=1, chunk=1024):
     """What the trained actor-critic plays when it looks one move ahead with its own value net (ewn_predict_lookahead):
     per observation and env action (f, r), Q = -inf for a move that leaves the board, +terminal_value for one that wins, otherwise the
     mean over the opponent's dice of its best (minimal) reply, a reply being worth -terminal_value if it wins for the opponent and
     else the mean over the agent's next dice of the value net there.  Plain expectiminimax, no pruning.  boards [S, S] or [M, S, S],
     dice [M] (outside 1..6: clamped), params as predict_policy takes them -> actions int8 [M, 2] (the first maximum of Q), and with
     return_q the float32 [M, 2, 3] Q as well.  A row that is already over, or has no agent cube, gets (0, 0) and six -inf.  The same
-    argument checks as predict_policy: anything the kernel cannot read in place raises ValueError before a launch."""
+    argument checks as predict_policy: anything the kernel cannot read in place raises ValueError before a launch.
+    plies=2 looks two moves ahead: the same tree with each leaf V(b2, d2) replaced by the maximum of the one-move Q at
+    (b2, d2) -- lookahead_expand, ewn_predict_lookahead on the 648 leaf rows per observation, lookahead_reduce -- `chunk` observations
+    at a time on scratch allocated once per call (about 49 KB per observation of the chunk at 7x7)."""
     lib = _lib.load()
+    if plies not in (1, 2):
+        raise ValueError("predict_lookahead: plies must be 1 or 2, got %r" % (plies,))
+    if int(chunk) < 1:
+        raise ValueError("predict_lookahead: chunk must be at least 1, got %r" % (chunk,))
     shp = tuple(boards.shape) if isinstance(boards, torch.Tensor) else np.asarray(boards).shape
     if len(shp) == 2:
         shp = (1,) + tuple(shp)
@@ -731,7 +810,32 @@ def predict_lookahead(boards, dice, params, terminal_value=1.0, return_q=False, 
             raise ValueError("predict_lookahead: %s must live on the GPU that holds params (%s), got %s" % (name, dev, _describe(t)))
     acts = torch.zeros((M, 2), dtype=torch.int8, device=dev)
     q = torch.zeros((M, 2, 3), dtype=torch.float32, device=dev) if return_q else None
+    if plies == 2:
+        return _predict_lookahead2(lib, S, int(cube_layer), M, b, d, params, float(terminal_value), acts, q, int(chunk))
     with torch.cuda.device(dev):
         check(lib.ewn_predict_lookahead(S, int(cube_layer), M, _ptr(b), _ptr(d), _ptr(params), C.c_float(float(terminal_value)), _ptr(acts),
                                         _ptr(q), _stream()), "ewn_predict_lookahead")
     return (acts, q) if return_q else acts
+
+
+def _predict_lookahead2(lib, S, L, M, b, d, params, tv, acts, q, chunk):
+    """predict_lookahead(plies=2) on checked inputs: per chunk of c observations expand -> ewn_predict_lookahead with q on the 648 c
+    leaf rows -> reduce at leaf_width 6; the scratch is one allocation per call, every row of it rewritten per chunk"""
+    dev = params.device
+    c = max(1, min(chunk, M, (2 ** 31 - 1) // 648))      # a chunk's 648 c leaf rows are counted in an int
+    lb = torch.empty((c * 648, S, S), dtype=torch.int8, device=dev)
+    ld = torch.empty(c * 648, dtype=torch.int8, device=dev)
+    kind = torch.empty((c, 108), dtype=torch.int8, device=dev)
+    la = torch.empty((c * 648, 2), dtype=torch.int8, device=dev)
+    lq = torch.empty((c * 648, 6), dtype=torch.float32, device=dev)
+    tvf = C.c_float(tv)
+    with torch.cuda.device(dev):
+        st = _stream()
+        for i in range(0, M, c):
+            n = min(c, M - i)
+            bi, di, ai, qi = b[i:i + n], d[i:i + n], acts[i:i + n], None if q is None else q[i:i + n]
+            check(lib.ewn_lookahead_expand(S, L, n, _ptr(bi), _ptr(di), _ptr(lb), _ptr(ld), _ptr(kind), st), "ewn_lookahead_expand")
+            check(lib.ewn_predict_lookahead(S, L, 648 * n, _ptr(lb), _ptr(ld), _ptr(params), tvf, _ptr(la), _ptr(lq), st), "ewn_predict_lookahead")
+            check(lib.ewn_lookahead_reduce(S, L, n, _ptr(bi), _ptr(di), _ptr(kind), _ptr(lq), 6, tvf, _ptr(ai), _ptr(qi), st),
+                  "ewn_lookahead_reduce")
+    return acts if q is None else (acts, q)

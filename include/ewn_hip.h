@@ -536,6 +536,32 @@ int ewn_predict_lookahead(int board_size, int cube_layer, int M, const int8_t *b
                           const float *params, float terminal_value, int8_t *actions /* [M][2] */,
                           float *q /* [M][6], optional */, void *stream);
 
+/* The two ends of ewn_predict_lookahead's tree as calls of their own, so that the leaves can be valued by something else than the plain
+ * critic -- by ewn_predict_lookahead itself: a two-move lookahead (agent, reply, agent, reply, critic).  Tuple t = 18 root + 3 (cube - 1)
+ * + direction, root = 3 f + r: the agent's move (f, r), then the reply of BOTTOM_RIGHT's cube `cube` in direction 0 left / 1 up /
+ * 2 up-left.  Leaf row of (m, t, d2) = (m * 108 + t) * 6 + d2 - 1: 648 rows per observation.
+ *
+ * ewn_lookahead_expand: kind [M][108] int8: 0 no such reply (the cube is not on b1, the reply leaves the board, the root leaves the
+ * board or wins, or roots 3..5 when both flags name one cube), 1 the reply wins for the opponent, 2 a leaf.  leaf_boards [648 M][S*S] and
+ * leaf_dice [648 M]: b2 (the observation after both moves) and d2 where kind == 2, an all-zero board and d2 elsewhere.  Every row is
+ * written on every call (a degenerate observation: 108 zeros, zero boards); nothing has to be cleared.
+ *
+ * ewn_lookahead_reduce: leaf [648 M][leaf_width] float, leaf_width 1 (a value) or 6 (a q row); a row's value is the maximum of its
+ * entries.  W = the six values of a kind-2 tuple summed in d2 order times 1/6f, -terminal_value for kind 1, +inf for kind 0; then R, Q
+ * and the action exactly as ewn_predict_lookahead takes them (the roots are read off boards and dice again; kind only selects, it never
+ * indexes; rows of leaf whose kind is not 2 are not read).  actions [M][2] is required, q [M][6] may be NULL.  With leaf = the `value`
+ * of ewn_predict_policy on expand's rows the result is ewn_predict_lookahead's, bit for bit.
+ *
+ * Both: EWN_EINVAL for M < 0 or 648 M > INT_MAX, EWN_EUNSUPPORTED where ewn_policy_param_count() is, EWN_OK without a launch for
+ * M == 0, EWN_ENULL for a missing required pointer, then (reduce) EWN_EINVAL for a non-finite terminal_value or a leaf_width other
+ * than 1 or 6.  One kernel launch on `stream`, no allocation, no synchronisation, no scratch. */
+int ewn_lookahead_expand(int board_size, int cube_layer, int M, const int8_t *boards, const int8_t *dice,
+                         int8_t *leaf_boards /* [648 M][S*S] */, int8_t *leaf_dice /* [648 M] */, int8_t *kind /* [M][108] */,
+                         void *stream);
+int ewn_lookahead_reduce(int board_size, int cube_layer, int M, const int8_t *boards, const int8_t *dice, const int8_t *kind,
+                         const float *leaf /* [648 M][leaf_width] */, int leaf_width, float terminal_value,
+                         int8_t *actions /* [M][2] */, float *q /* [M][6], optional */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

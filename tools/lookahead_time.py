@@ -1,6 +1,6 @@
-"""Timing and playing strength of the one-ply lookahead on the trained critic.
+"""Timing and playing strength of the lookahead on the trained critic (DESIGN.md sections 4k and 4l).
 
-  python tools/lookahead_time.py [--runs 5] [--updates 600] [--episodes 1024]
+  python tools/lookahead_time.py [--runs 5] [--updates 600] [--episodes 1024] [--plies 2]
 
 Part 1, per board (5x5, 7x7) and batch (M = 1, 1 024, 65 536): predict_lookahead (ewn_predict_lookahead, actions only) beside
 predict_policy on the same observations, alternated in the same process.  Each figure is the median of `--runs` timed windows after
@@ -11,7 +11,11 @@ from the rules on the first 1 024 observations.
 Part 2, 5x5: a FusedA2CTrainer trained as tools/eval_policy_time.py trains its model (shaped env, reward 10, RandomAgent, `--updates`
 updates), then over `--episodes` episodes (seeds 0 .. n-1, MT19937-compat dice) the win rate of its raw argmax policy and of its lookahead
 policy (terminal_value = the reward it was trained on) against RandomAgent and against minimax(5), with Wilson 95 % intervals.
-Prints one JSON line per row.  No pass bar: nothing here was measured before."""
+Prints one JSON line per row.  No pass bar: nothing here was measured before.
+
+--plies 2 (section 4l): part 1 becomes predict_lookahead(plies=2) beside predict_lookahead(plies=1) at M = 1 and 1 024, alternated in the
+same process, with the two stage calls (lookahead_expand, lookahead_reduce at leaf_width 6) timed alone; part 2 gains a lookahead(2) row
+per opponent: the same model, seeds, dice and terminal_value."""
 import argparse
 import json
 import os
@@ -68,8 +72,29 @@ def main():
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--updates", type=int, default=600)
     ap.add_argument("--episodes", type=int, default=1024)
+    ap.add_argument("--plies", type=int, default=1, choices=(1, 2))
     a = ap.parse_args()
-    for S in (5, 7):
+    for S in (5, 7) if a.plies == 2 else ():
+        torch.manual_seed(9)
+        params = ActorCritic(S, 6).cuda().flat_parameters()
+        for M in (1, 1024):
+            b, d = observations(S, M)
+            lb, ld, kind = ea.lookahead_expand(b, d)
+            lq = ea.predict_lookahead(lb.reshape(-1, S, S), ld.reshape(-1), params, return_q=True)[1].reshape(M, 648, 6)
+            fns = {"predict_lookahead plies=2": lambda: ea.predict_lookahead(b, d, params, plies=2),
+                   "predict_lookahead plies=1": lambda: ea.predict_lookahead(b, d, params),
+                   "lookahead_expand": lambda: ea.lookahead_expand(b, d), "lookahead_reduce width 6": lambda: ea.lookahead_reduce(b, d, kind, lq)}
+            launches = 200 if M == 1 else 20
+            for fn in fns.values():                                       # warm-up
+                for _ in range(3):
+                    fn()
+            rows = {}
+            for _ in range(2):                                            # alternate them, keep the later pass
+                for name, fn in fns.items():
+                    rows[name] = timed(fn, launches, a.runs)
+            print(json.dumps({"board": S, "M": M, "us_per_call_median_min_max": rows,
+                              "leaf_rows_per_observation": round(float((kind == 2).sum()) * 6 / M, 1)}), flush=True)
+    for S in (5, 7) if a.plies == 1 else ():
         torch.manual_seed(9)
         params = ActorCritic(S, 6).cuda().flat_parameters()
         for M in (1, 1024, 65536):
@@ -97,7 +122,8 @@ def main():
     torch.cuda.synchronize()
     for opp in ({"kind": "random"}, {"kind": "minimax", "max_depth": 5}):
         for name, agent in (("argmax", {"kind": "mlp", "model": tr.model}),
-                            ("lookahead", {"kind": "mlp_lookahead", "model": tr.model, "terminal_value": reward})):
+                            ("lookahead", {"kind": "mlp_lookahead", "model": tr.model, "terminal_value": reward}),
+                            ("lookahead(2)", {"kind": "mlp_lookahead", "model": tr.model, "terminal_value": reward, "plies": 2}))[:a.plies + 1]:
             r = evaluate(agent, opp, num=a.episodes, board_size=S)
             print(json.dumps({"policy": name, "opponent": opp["kind"] + ("(5)" if opp["kind"] == "minimax" else ""), "updates": a.updates,
                               "episodes": r["episodes"], "wins": r["wins"], "win_rate": round(r["win_rate"], 4),
