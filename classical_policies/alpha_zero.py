@@ -5,4 +5,5 @@ dense-network inference whose weights live in an un-vendored submodule; out of s
 class AlphaZeroAgent:
     def __init__(self, *args, **kwargs):
         raise NotImplementedError("AlphaZeroAgent needs the un-vendored alpha_zero_models weights; "
-                                  "out of scope of the MI355X hot path (SURVEY section 2, rows 13-14)")
+                                  "out of scope of the MI355X hot path (SURVEY section 2, rows 13-14).  Its idea, training a "
+                                  "network toward its own search, is ewn_gym_amd.distill.SearchDistillTrainer")

@@ -4,8 +4,8 @@ Only what the hot path needs: csrc/ (HIP kernels + C ABI), the ctypes binding, a
 VecEWN (the batched engine the drop-in `envs` / `classical_policies` packages wrap).
 """
 from ._lib import EwnError, INFO_MESSAGES, LIB_PATH  # noqa: F401
-from .vec_env import (VecEWN, apply_action, evaluate, legal_actions, lookahead_expand, lookahead_reduce, playout_wins,  # noqa: F401
-                      predict_mcts, predict_lookahead, predict_minimax, predict_policy, predict_random)
+from .vec_env import (VecEWN, apply_action, evaluate, legal_actions, lookahead_expand, lookahead_reduce, lookahead_targets,  # noqa: F401
+                      playout_wins, predict_mcts, predict_lookahead, predict_minimax, predict_policy, predict_random, sup_grad)
 
 __all__ = ["VecEWN", "EwnError", "INFO_MESSAGES", "legal_actions", "apply_action", "playout_wins", "evaluate", "predict_minimax", "predict_random",
-           "predict_mcts", "predict_policy", "predict_lookahead", "lookahead_expand", "lookahead_reduce"]
+           "predict_mcts", "predict_policy", "predict_lookahead", "lookahead_expand", "lookahead_reduce", "lookahead_targets", "sup_grad"]

@@ -30,7 +30,8 @@ EXPORTS = ["ewn_abi_version", "ewn_strerror", "ewn_rng_words", "ewn_step_scratch
            "ewn_policy_eval_mcts_supported", "ewn_policy_eval_mcts",
            "ewn_step_k_selfplay_supported", "ewn_step_k_selfplay", "ewn_policy_eval_vs_supported", "ewn_policy_eval_vs",
            "ewn_step_vs_supported", "ewn_step_vs", "ewn_step_k_vs_supported", "ewn_step_k_vs", "ewn_predict_policy",
-           "ewn_predict_lookahead", "ewn_lookahead_expand", "ewn_lookahead_reduce"]
+           "ewn_predict_lookahead", "ewn_lookahead_expand", "ewn_lookahead_reduce",
+           "ewn_sup_scratch_bytes", "ewn_sup_grad", "ewn_lookahead_targets"]
 AGENT = {"random": 0, "minimax": 1, "sample": 2, "mlp": 3}   # "mlp": the trained policy, through ewn_step_k_policy   # "sample": env.action_space.sample(), all six actions (EWN_AGENT_SAMPLE)
 AGENT_MCTS = 4   # ewn_agent.kind of the MCTS agent (ewn_step_k_agent only; ewn_step_k does not take it)
 
@@ -168,6 +169,9 @@ def load():
         "ewn_predict_lookahead": (i32, [i32, i32, i32, vp, vp, vp, C.c_float, vp, vp, vp]),
         "ewn_lookahead_expand": (i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp]),
         "ewn_lookahead_reduce": (i32, [i32, i32, i32, vp, vp, vp, vp, i32, C.c_float, vp, vp, vp]),
+        "ewn_sup_scratch_bytes": (C.c_int64, [i32, i32, i32]),
+        "ewn_sup_grad": (i32, [i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, vp]),
+        "ewn_lookahead_targets": (i32, [i32, vp, C.c_float, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

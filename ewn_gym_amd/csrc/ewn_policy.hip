@@ -1,10 +1,12 @@
 // ewn_policy.hip -- the policy-driven rollout (ewn_step_k_policy), its evaluation form (ewn_policy_eval: instances in
 // ewn_policy_eval.hip), the fused A2C update (ewn_a2c_*) and the fused PPO update (ewn_ppo_*): kernels in ewn_policy.hpp /
-// ewn_a2c.hpp / ewn_ppo.hpp, C ABI here.
+// ewn_a2c.hpp / ewn_ppo.hpp, C ABI here.  The supervised gradient on given observations and targets (ewn_sup_*, ewn_lookahead_targets:
+// ewn_sup.hpp) is the step body's third consumer and lives here with the other two (the reduce kernels link from this unit only).
 #include "ewn_policy_host.hpp"
 #include "ewn_a2c.hpp"
 #include "ewn_a2c3.hpp"
 #include "ewn_ppo.hpp"
+#include "ewn_sup.hpp"
 
 // which instantiation serves the configuration: opp 0 minimax (table image, max_depth 1-4), 1 RandomAgent
 static int policy_plan(const ewn_config *cfg, const Geom &g, int &opp)
@@ -304,5 +306,73 @@ int ewn_ppo_apply(const ewn_config *cfg, float *params, float *exp_avg, float *e
     const bool vec = ac.P <= 1024 * 4 * A2C_APPLY_V && ((uintptr_t)params | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq | (uintptr_t)grad) % 16 == 0;
     if (vec) k_ppo_apply<true><<<1, 1024, 0, (hipStream_t)stream>>>(ac, params, exp_avg, exp_avg_sq, step, grad, grad_norm_out);
     else k_ppo_apply<false><<<1, 1024, 0, (hipStream_t)stream>>>(ac, params, exp_avg, exp_avg_sq, step, grad, grad_norm_out);
+    return launch_status();
+}
+
+// ---------------------------------------------------------------- the supervised update (targets from outside: a search)
+
+// M is counted in 32-sample tiles by int arithmetic: a grid's worth of tiles past the last one must still fit an int
+#define SUP_MAX_M (INT32_MAX - 32 * 4 * (A2C_MAX_BLOCKS + 1))
+
+// scratch (4-byte aligned): partial [256][P] | stats [256][8] | up to 12 bytes of alignment | rows [M][STR] (16-byte aligned)
+static size_t sup_rows_offset(int64_t P) { return (size_t)A2C_MAX_BLOCKS * (size_t)(P + 8) * 4; }
+
+int64_t ewn_sup_scratch_bytes(int board_size, int cube_layer, int M)
+{
+    if (M < 1 || M > SUP_MAX_M) return EWN_EINVAL;
+    const int64_t P = ewn_policy_param_count(board_size, cube_layer);
+    if (P < 0) return EWN_EUNSUPPORTED;
+    return (int64_t)sup_rows_offset(P) + 16 + (int64_t)M * EWN_TRAJ_RECORD_STRIDE(board_size);
+}
+
+template <int S>
+static int sup_grad_launch(const SupCfg &c, SupBuf b, const int8_t *boards, const int8_t *dice, float *grad, void *scratch, hipStream_t s)
+{
+    constexpr size_t lds = Sup3Geo<S>::lds_bytes();
+    static_assert(lds <= POL_LDS_MAX, "weight images, the gradient image and the observation stash must fit the CU's LDS");
+    constexpr int64_t P = MlpGeo<S>::P;
+    b.partial = (float *)scratch;
+    b.stats = b.partial + (size_t)A2C_MAX_BLOCKS * P;
+    uint8_t *rows = (uint8_t *)(((uintptr_t)scratch + sup_rows_offset(P) + 15) & ~(uintptr_t)15);
+    b.rows = rows;
+    auto kv = k_sup_grad3<S, 1>;
+    auto kp = k_sup_grad3<S, 0>;
+    if (hipFuncSetAttribute((const void *)kv, hipFuncAttributeMaxDynamicSharedMemorySize, POL_LDS_MAX) != hipSuccess) return EWN_ELAUNCH;
+    if (hipFuncSetAttribute((const void *)kp, hipFuncAttributeMaxDynamicSharedMemorySize, POL_LDS_MAX) != hipSuccess) return EWN_ELAUNCH;
+    const size_t words = (size_t)c.M * (RecGeo<S>::STR / 4), need = (words + 255) / 256;
+    k_sup_rows<S><<<(unsigned)(need < 65536 ? need : 65536), 256, 0, s>>>(c.M, boards, dice, (u32 *)rows);
+    const int blocks = a2c_blocks(c.M, 4);
+    kv<<<blocks, 256, lds, s>>>(c, b);
+    kp<<<blocks, 256, lds, s>>>(c, b);
+    A2cRedBuf rb = { b.partial, b.stats, grad, blocks, (int)P };
+    a2c_reduce_launch(rb, s);
+    return launch_status();
+}
+
+int ewn_sup_grad(int board_size, int cube_layer, int M, const int8_t *boards, const int8_t *dice, const float *target_pi,
+                 const float *target_value, const float *weight, const float *params, float pi_coef, float vf_coef, float *grad,
+                 void *scratch, void *stream)
+{
+    if (M < 1 || M > SUP_MAX_M) return EWN_EINVAL;
+    if (ewn_policy_param_count(board_size, cube_layer) < 0) return EWN_EUNSUPPORTED;
+    if (!boards || !dice || !target_pi || !target_value || !params || !grad || !scratch) return EWN_ENULL;
+    if (!std::isfinite(pi_coef) || !std::isfinite(vf_coef) || pi_coef < 0.0f || vf_coef < 0.0f) return EWN_EINVAL;
+    if (((uintptr_t)scratch & 3) != 0) return EWN_EINVAL;       // partial and stats are float arrays
+    const SupCfg c = { M, pi_coef, vf_coef, 1.0f / (float)M };
+    SupBuf b;
+    memset(&b, 0, sizeof(b));
+    b.target_pi = target_pi; b.target_value = target_value; b.weight = weight; b.params = params;
+    hipStream_t s = (hipStream_t)stream;
+    return board_size == 5 ? sup_grad_launch<5>(c, b, boards, dice, grad, scratch, s) : sup_grad_launch<7>(c, b, boards, dice, grad, scratch, s);
+}
+
+int ewn_lookahead_targets(int M, const float *q, float temperature, float *target_pi, float *target_value, float *weight, void *stream)
+{
+    if (M < 0) return EWN_EINVAL;
+    if (M == 0) return EWN_OK;
+    if (!q || !target_pi || !target_value || !weight) return EWN_ENULL;
+    if (!std::isfinite(temperature) || temperature < 0.0f) return EWN_EINVAL;
+    const int need = (M + 255) / 256;
+    k_lookahead_targets<<<need < 4096 ? need : 4096, 256, 0, (hipStream_t)stream>>>(M, q, temperature, target_pi, target_value, weight);
     return launch_status();
 }

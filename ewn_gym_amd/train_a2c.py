@@ -1,5 +1,6 @@
 """Command-line counterpart of the reference's train.py (argument names follow train.py:162-259
-where they apply): A2C (or PPO: `python -m ewn_gym_amd.train_a2c PPO ...`) on VecEWN lanes instead of SubprocVecEnv workers, per-epoch evaluation
+where they apply): A2C (or PPO: `python -m ewn_gym_amd.train_a2c PPO ...`; or SEARCH: distillation of the lookahead search,
+ewn_gym_amd/distill.py) on VecEWN lanes instead of SubprocVecEnv workers, per-epoch evaluation
 against minimax on the un-shaped env (train.py:66-117), best-model checkpointing.
 
   python -m ewn_gym_amd.train_a2c --num_envs 4096 --epoch_num 10 --timesteps_per_epoch 200000
@@ -22,7 +23,12 @@ from .vec_env import VecEWN
 def main():
     ap = argparse.ArgumentParser(description="Trainer for EWN on VecEWN lanes (counterpart of the reference's train.py)")
     # train.py:174-184 selects the algorithm with a sub-command; A2C is the one built here
-    ap.add_argument("algorithm", nargs="?", default="A2C", choices=["A2C", "PPO"], help="train.py:174-184's sub-command")
+    ap.add_argument("algorithm", nargs="?", default="A2C", choices=["A2C", "PPO", "SEARCH"],
+                    help="train.py:174-184's sub-command; SEARCH: train toward the lookahead on the model's own critic (SearchDistillTrainer)")
+    ap.add_argument("--plies", type=int, default=1, choices=[1, 2], help="SEARCH: moves the lookahead looks ahead")
+    ap.add_argument("--temperature", type=float, default=0.0,
+                    help="SEARCH: 0 trains toward the search's action, > 0 toward the softmax of its Q / temperature")
+    ap.add_argument("--terminal_value", type=float, default=1.0, help="SEARCH: the value of a won (+) or lost (-) position in the lookahead")
     ap.add_argument("--batch_size", "-b", type=int, default=None,
                     help="PPO: minibatch size in samples of the n_steps x lanes rollout buffer (default: a quarter of it; train.py:178-183)")
     ap.add_argument("--n_epochs", type=int, default=10, help="PPO: passes over the rollout buffer per update (SB3 default)")
@@ -63,6 +69,9 @@ def main():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
         dist.init_process_group("nccl")
+    if a.algorithm == "SEARCH" and (a.trainer == "torch" or a.batch_size is not None):
+        raise SystemExit("SEARCH has one trainer, SearchDistillTrainer, whose update is one full batch in the engine: --trainer torch and "
+                         "--batch_size do not apply to it (--n_epochs is PPO's and is not read)")
     lo, hi = lane_range(a.num_envs * world, world, rank)
     if a.reference_quirks and a.opponent_policy not in ("random", "minimax", "mcts"):
         raise SystemExit("--reference_quirks drops the opponent (MinimaxEnv plays RandomAgent whatever it is given): it cannot be combined "
@@ -71,7 +80,7 @@ def main():
     model_opp = None
     if opp not in ("random", "minimax", "mcts"):   # a model opponent: the rollout kernel plays it, the env's own opponent is not used
         model_opp, opp = opp, "random"
-        if a.trainer == "torch" or (a.algorithm == "PPO" and a.trainer != "fused"):
+        if a.algorithm != "SEARCH" and (a.trainer == "torch" or (a.algorithm == "PPO" and a.trainer != "fused")):
             raise SystemExit("--opponent_policy %s: a model opponent is played by the fused trainers only (--trainer fused); the torch "
                              "trainers step the env with ewn_step, which has no policy opponent" % model_opp)
     okw = {} if model_opp is None else dict(opponent=model_opp, opponent_update_every=a.opponent_update_every)
@@ -86,6 +95,10 @@ def main():
         cls = FusedPPOTrainer if a.trainer == "fused" else PPOTrainer   # auto keeps the torch trainer for PPO
         trainer = cls(env, n_steps=a.n_steps, batch_size=a.batch_size, n_epochs=a.n_epochs, learning_rate=a.learning_rate, seed=mseed,
                       **okw)
+    elif a.algorithm == "SEARCH":
+        from .distill import SearchDistillTrainer
+        trainer = SearchDistillTrainer(env, n_steps=a.n_steps, learning_rate=a.learning_rate, temperature=a.temperature, plies=a.plies,
+                                       terminal_value=a.terminal_value, seed=mseed, **okw)
     elif a.trainer == "fused" or model_opp is not None or (a.trainer == "auto" and env.supports_policy_rollout()):
         trainer = FusedA2CTrainer(env, n_steps=a.n_steps, learning_rate=a.learning_rate, seed=mseed, **okw)
     else:

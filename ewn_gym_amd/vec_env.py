@@ -839,3 +839,78 @@ def _predict_lookahead2(lib, S, L, M, b, d, params, tv, acts, q, chunk):
             check(lib.ewn_lookahead_reduce(S, L, n, _ptr(bi), _ptr(di), _ptr(kind), _ptr(lq), 6, tvf, _ptr(ai), _ptr(qi), st),
                   "ewn_lookahead_reduce")
     return acts if q is None else (acts, q)
+
+
+def lookahead_targets(q, temperature=0.0):
+    """predict_lookahead's Q as training targets (ewn_lookahead_targets): q float32 [M, 2, 3] or [M, 6] on the GPU ->
+    (target_pi float32 [M, 5], target_value float32 [M], weight float32 [M]).  A row of six -inf (a finished observation) gets zeros
+    and weight 0; any other row weight 1 and its maximum as the value.  temperature 0: the search's action one-hot on both heads
+    ((0.5, 0.5) on the flag head when both flags move the same cube); temperature > 0: the softmax of q / temperature over the
+    moves that stay on the board, summed per head."""
+    who = "lookahead_targets"
+    t = float(temperature)
+    if not math.isfinite(t) or t < 0.0:
+        raise ValueError("%s: temperature must be finite and not negative, got %r" % (who, temperature))
+    shp = tuple(q.shape) if isinstance(q, torch.Tensor) else np.asarray(q).shape
+    if not (len(shp) in (2, 3) and math.prod(shp[1:]) == 6 and (len(shp) == 2 or shp[1:] == (2, 3))):
+        raise ValueError("%s: q must have shape [M, 2, 3] or [M, 6], got %s" % (who, list(shp)))
+    M = int(shp[0])
+    dev = q.device if isinstance(q, torch.Tensor) else torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() \
+        else torch.device("cpu")
+    qq = _policy_input("q", q, torch.float32, (M, 6), dev, who=who)
+    if not qq.is_cuda:
+        raise ValueError("%s: q must live on the GPU, got %s" % (who, _describe(qq)))
+    pi = torch.zeros((M, 5), dtype=torch.float32, device=dev)
+    val = torch.zeros(M, dtype=torch.float32, device=dev)
+    w = torch.zeros(M, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.load().ewn_lookahead_targets(M, _ptr(qq), C.c_float(t), _ptr(pi), _ptr(val), _ptr(w), _stream()), "ewn_lookahead_targets")
+    return pi, val, w
+
+
+def sup_grad(boards, dice, target_pi, target_value, params, weight=None, pi_coef=1.0, vf_coef=0.5, cube_layer=3, out=None, scratch=None):
+    """The gradient of a supervised loss on M given observations (ewn_sup_grad):
+        loss = mean_m w_m (pi_coef * CE(target_pi[m], policy heads) + vf_coef * (V - target_value[m])^2)
+    boards [S, S] or [M, S, S], dice [M], target_pi float32 [M, 5] (entries 0-1 the flag head, 2-4 the direction head; a head whose
+    entries are all zero is masked), target_value [M], weight [M] or None (ones), params as predict_policy takes them -> float32
+    [P + 8]: the gradient in the params layout, then the sums over the samples with weight > 0 of {w CE, w entropy, agreement
+    count, w, w (V - v*)^2, 0, 0, 0}.  A row whose weight is 0 is skipped altogether (its targets may be NaN or infinite).  out: a
+    float32 [P + 8] device tensor to write into; scratch: a 4-byte aligned uint8 device tensor of at least ewn_sup_scratch_bytes.  predict_policy's
+    argument checks: anything the kernels cannot read in place raises ValueError before a launch.  The step is ewn_a2c_apply."""
+    who = "sup_grad"
+    lib = _lib.load()
+    M, S = _lookahead_shape(who, boards, cube_layer)
+    if M < 1:
+        raise ValueError("%s: needs at least one observation (a mean over nothing is undefined)" % who)
+    P = lib.ewn_policy_param_count(S, int(cube_layer))
+    if not (isinstance(params, torch.Tensor) and params.dtype == torch.float32 and params.is_contiguous() and params.numel() == P):
+        raise ValueError("%s: params must be a contiguous float32 tensor of %d elements (the %dx%d actor-critic), got %s" % (
+            who, P, S, S, _describe(params)))
+    for name, v in (("pi_coef", pi_coef), ("vf_coef", vf_coef)):
+        if not math.isfinite(float(v)) or float(v) < 0.0:
+            raise ValueError("%s: %s must be finite and not negative, got %r" % (who, name, v))
+    dev = params.device
+    named = [("boards", _policy_input("boards", boards, torch.int8, (M, S, S), dev, who=who)),
+             ("dice", _policy_input("dice", dice, torch.int8, (M,), dev, who=who)),
+             ("target_pi", _policy_input("target_pi", target_pi, torch.float32, (M, 5), dev, who=who)),
+             ("target_value", _policy_input("target_value", target_value, torch.float32, (M,), dev, who=who)),
+             ("weight", None if weight is None else _policy_input("weight", weight, torch.float32, (M,), dev, who=who))]
+    nscr = int(lib.ewn_sup_scratch_bytes(S, int(cube_layer), M))
+    if out is not None:
+        named.append(("out", _policy_input("out", out, torch.float32, (P + 8,), dev, who=who)))
+    if scratch is not None and not (isinstance(scratch, torch.Tensor) and scratch.dtype == torch.uint8 and scratch.is_contiguous()
+                                    and scratch.numel() >= nscr and scratch.data_ptr() % 4 == 0):
+        raise ValueError("%s: scratch must be a contiguous, 4-byte aligned uint8 tensor of at least %d elements, got %s%s" % (
+            who, nscr, _describe(scratch), " at an address that is %d past a multiple of 4" % (scratch.data_ptr() % 4)
+            if isinstance(scratch, torch.Tensor) and scratch.data_ptr() % 4 else ""))
+    for name, t in [("params", params)] + named + [("scratch", scratch)]:
+        if t is not None and not (t.is_cuda and t.device == dev):
+            raise ValueError("%s: %s must live on the GPU that holds params (%s), got %s" % (who, name, dev, _describe(t)))
+    b, d, tp, tv, w = (t for _, t in named[:5])
+    grad = out if out is not None else torch.zeros(P + 8, dtype=torch.float32, device=dev)
+    if scratch is None:
+        scratch = torch.zeros(nscr, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.ewn_sup_grad(S, int(cube_layer), M, _ptr(b), _ptr(d), _ptr(tp), _ptr(tv), _ptr(w), _ptr(params), C.c_float(float(pi_coef)),
+                               C.c_float(float(vf_coef)), _ptr(grad), _ptr(scratch), _stream()), "ewn_sup_grad")
+    return grad

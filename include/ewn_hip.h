@@ -562,6 +562,40 @@ int ewn_lookahead_reduce(int board_size, int cube_layer, int M, const int8_t *bo
                          const float *leaf /* [648 M][leaf_width] */, int leaf_width, float terminal_value,
                          int8_t *actions /* [M][2] */, float *q /* [M][6], optional */, void *stream);
 
+/* ---- the supervised update on M given observations: targets from outside (a search: expert iteration) ----
+ * loss = (1/M) sum_m w_m (pi_coef CE_m + vf_coef (V_m - v*_m)^2),  CE_m = -sum_i p_i logsoftmax_head(i)(logits_m)_i, with
+ * p = target_pi[m][0..4] (entries 0-1 the flag head, 2-4 the direction head; the caller makes each head's mass 1, or 0 to mask the
+ * head), v* = target_value[m], w = weight[m] (weight NULL: all ones).  A sample whose w is not > 0 contributes nothing, by selection
+ * and not by multiplication, to the gradient and to every statistic: its targets may be NaN or infinite (ewn_predict_lookahead returns
+ * six -inf on a finished row).  The network, the bf16 x 3 arithmetic and the backward pass are ewn_a2c_grad's.
+ * grad [ewn_policy_param_count() + 8]: the gradient in the layout of ewn_policy.params (the policy pass writes the pi body and the
+ * action head, the value pass the vf body and the value head: with vf_coef == 0 the value entries are exactly 0, with pi_coef == 0
+ * the policy entries), then sums over the samples with w > 0: [P + 0] w CE, [P + 1] w (entropy of both heads), [P + 2] the number of
+ * samples whose pick (ewn_predict_policy's deterministic comparisons) is the target's first maximum on every head with target mass,
+ * [P + 3] w, [P + 4] w (V - v*)^2; [P + 5 .. P + 7] are exactly 0.  The optimiser step is ewn_a2c_apply (or ewn_ppo_apply): the same
+ * grad layout.  Refusals in this order: M < 1, or M above INT32_MAX - 32 896 (the tiles are counted in an int), EWN_EINVAL;
+ * EWN_EUNSUPPORTED where ewn_policy_param_count() is; EWN_ENULL for a missing pointer other than weight; EWN_EINVAL for a negative or
+ * non-finite coefficient, then for a scratch that is not 4-byte aligned.  scratch: ewn_sup_scratch_bytes() bytes, 4-byte aligned (8:
+ * the faster reduce kernel serves).  Reads
+ * exactly boards[0 .. M*S*S), dice[0 .. M) (dice outside 1..6: the caller's error, as in ewn_predict_policy) and the M rows of the
+ * targets.  Four launches on `stream`, no allocation, no synchronisation, no atomics: the same inputs give the same bits. */
+int64_t ewn_sup_scratch_bytes(int board_size, int cube_layer, int M);
+int ewn_sup_grad(int board_size, int cube_layer, int M, const int8_t *boards, const int8_t *dice,
+                 const float *target_pi /* [M][5] */, const float *target_value /* [M] */,
+                 const float *weight /* [M], may be NULL */, const float *params,
+                 float pi_coef, float vf_coef, float *grad /* [P + 8] */, void *scratch, void *stream);
+
+/* q rows of ewn_predict_lookahead -> the targets of ewn_sup_grad.  Per row the finite set is the entries above -inf.  Empty (a
+ * finished observation): five zeros, value 0, weight 0.  Otherwise weight 1 and value the maximum.  temperature == 0: the first
+ * maximum in (f, r) order under strict > (ewn_predict_lookahead's action) one-hot on both heads, except that the flag head gets
+ * (0.5, 0.5) when q[0][r*] and q[1][r*] have equal bit patterns (both flags name one cube).  temperature > 0:
+ * P(f, r) = exp((q - max) / temperature) / Z over the finite set; the flag head gets the sums over r, the direction head the sums
+ * over f, in index order.  M < 0: EWN_EINVAL; M == 0: EWN_OK without a launch; a missing pointer: EWN_ENULL; then a negative or
+ * non-finite temperature: EWN_EINVAL.  One launch. */
+int ewn_lookahead_targets(int M, const float *q /* [M][6] */, float temperature,
+                          float *target_pi /* [M][5] */, float *target_value /* [M] */,
+                          float *weight /* [M] */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
