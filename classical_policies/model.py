@@ -87,3 +87,48 @@ class ValueSearchAgent(ModelAgent):
     def policy_fn(self):
         """(board, dice, t) -> actions, the callable tournament.evaluate takes"""
         return lambda b, d, t: self.predict_batch(b, d)
+
+
+class EndgameAgent(PolicyBase):
+    """The exact move wherever an endgame table covers the position, `fallback`'s elsewhere.  table: an
+    ewn_gym_amd.EndgameTable or the path of a saved one; fallback: any policy of this package with predict_batch(boards, dice).
+    The fallback is asked for ALL rows of a batch and the exact actions are laid over its answer with one torch.where: no row
+    selection, so no host synchronisation and the same launches whatever the positions are; a sampling fallback therefore draws
+    for the covered rows too."""
+
+    def __init__(self, table, fallback):
+        import ewn_gym_amd
+        from ewn_gym_amd.endgame import EndgameTable
+        if isinstance(table, (str, os.PathLike)):
+            table = EndgameTable.load(table)
+        if not isinstance(table, EndgameTable):
+            raise ValueError("EndgameAgent: table must be an EndgameTable or the path of a saved one, got %s" % type(table).__name__)
+        if not callable(getattr(fallback, "predict_batch", None)):
+            raise ValueError("EndgameAgent: fallback must offer predict_batch(boards, dice), got %s" % type(fallback).__name__)
+        fs = getattr(fallback, "board_size", table.board_size)
+        if fs != table.board_size:
+            raise ValueError("EndgameAgent: the table is for %dx%d boards, the fallback plays %dx%d" % (
+                table.board_size, table.board_size, fs, fs))
+        self._ea = ewn_gym_amd
+        self.table, self.fallback, self.board_size = table, fallback, table.board_size
+
+    def predict_batch(self, boards, dice, return_covered=False):
+        """boards (M,S,S), dice (M,) device or host arrays -> int8 (M,2) device tensor (and the bool (M,) covered mask if asked for)"""
+        import torch
+        S, dev = self.board_size, self.table.table.device
+        b = torch.as_tensor(np.asarray(boards) if not isinstance(boards, torch.Tensor) else boards)
+        d = torch.as_tensor(np.asarray(dice) if not isinstance(dice, torch.Tensor) else dice)
+        if b.numel() % (S * S) != 0 or b.shape[-1] != S:
+            raise ValueError("EndgameAgent: boards of shape %s, the table is for %dx%d" % (list(b.shape), S, S))
+        b, d = b.to(dev).to(torch.int8).reshape(-1, S, S).contiguous(), d.to(dev).to(torch.int8).reshape(-1).contiguous()
+        exact, covered = self.table.lookup(b, d)
+        acts = torch.where(covered[:, None], exact, self.fallback.predict_batch(b, d).to(torch.int8))
+        return (acts, covered) if return_covered else acts
+
+    def predict(self, obs, **kwargs):
+        b, d = obs_arrays(obs)
+        return self.predict_batch(b, d)[0].cpu().numpy(), None
+
+    def policy_fn(self):
+        """(board, dice, t) -> actions, the callable tournament.evaluate takes"""
+        return lambda b, d, t: self.predict_batch(b, d)

@@ -1,0 +1,323 @@
+// ewn_endgame.hip -- exact endgame values (C ABI: ewn_endgame_table_bytes, ewn_endgame_build, ewn_endgame_lookup).
+// A position is seen from the side to move, before its dice: the mover is TOP_LEFT (positive cubes, goal cell C - 1, C = S * S).
+//   E(b) = fl((m_1 + ... + m_6) * fl(1/6))            fp32, summed in dice order
+//   m_d  = max over f in {0, 1}, r in {0, 1, 2} whose move stays on the board of G(b, d, f, r)
+//   G    = +1 if the move wins (it reaches C - 1 or leaves the other side without a cube), else -E(flip(b1)), b1 the board after it;
+//          flip turns the board by 180 degrees and swaps the sides.  The cube is find_cube_to_move(f) under d (la_find), and the move
+//          captures whatever stands on its target, own cubes included (la_root's rules).
+// Every ply lowers Phi(b) = the sum over all cubes of the Manhattan distance to the cube's own corner by at least 1, so the table is
+// filled level by level in Phi: a launch reads only entries of lower levels, which earlier launches on the same stream wrote.  No
+// atomics, no flag, no entry read in the launch that writes it.
+//
+// Table layout (version 1, EndgameTable.LAYOUT in ewn_gym_amd/endgame.py): a block per (ka, ko), ka-major, over 1 <= ka, ko <= K with
+// ka + ko <= T; inside it entry = side(agent) * n_ko + side(opponent), n_k = binom(6, k) * C^k;
+// side = rank of the 6-bit presence mask among the masks of its popcount (ascending) * C^k + the cells in cube-number order as a
+// base-C number, lowest cube number most significant.  Slots of positions that are not live (cubes sharing a cell, an agent cube on
+// C - 1, an opposing cube on 0) are never read; the build writes 0 there (the whole table is cleared first).
+#include "ewn_lookahead.hpp"
+
+#define EG_NT 256            // threads per block of both kernels
+#define EG_MAX_BLOCKS 9      // (ka, ko) blocks of a table: K <= 3
+
+struct EgMasks { uint8_t rank[64]; uint8_t unrank[4][20]; };   // rank[mask of cubes 1..6 >> 1]; unrank[popcount][rank]
+static constexpr EgMasks eg_make_masks()
+{
+    EgMasks t{};
+    int cnt[7] = {0, 0, 0, 0, 0, 0, 0};
+    for (int m = 0; m < 64; m++) {
+        const int k = __builtin_popcount((unsigned)m);
+        t.rank[m] = (uint8_t)cnt[k];
+        if (k <= 3) t.unrank[k][cnt[k]] = (uint8_t)m;
+        cnt[k]++;
+    }
+    return t;
+}
+__constant__ EgMasks EG_MASKS = eg_make_masks();
+
+struct EgGeo { int K, T; long long off[4][4]; };             // off[ka][ko]: the block's first entry (in floats); -1: not in the table
+
+template <int S> struct EgDim {
+    static constexpr int C = S * S;
+    static constexpr u32 pw(int k) { return k == 0 ? 1u : k == 1 ? (u32)C : k == 2 ? (u32)C * C : (u32)C * C * C; }
+    static constexpr u32 n(int k) { return (k == 1 ? 6u : k == 2 ? 15u : 20u) * pw(k); }
+};
+template <int S> EWN_DEV u32 eg_pw(int k) { return k == 1 ? EgDim<S>::pw(1) : k == 2 ? EgDim<S>::pw(2) : EgDim<S>::pw(3); }
+template <int S> EWN_DEV u32 eg_n(int k) { return k == 1 ? EgDim<S>::n(1) : k == 2 ? EgDim<S>::n(2) : EgDim<S>::n(3); }
+
+// a side as registers: M the presence mask (bit k: cube k, k = 1 .. 6), pos the cell of cube k in byte k - 1 (read only where M has k)
+EWN_DEV int eg_cell(u64 pos, int k) { return (int)((pos >> (8 * (k - 1))) & 0xFFull); }
+
+// the side's index; turned: as flip() shows it to the other side (cell c -> C - 1 - c)
+template <int S>
+EWN_DEV u32 eg_side(int M, u64 pos, bool turned)
+{
+    constexpr int C = S * S;
+    u32 v = EG_MASKS.rank[(M >> 1) & 63];
+    for (int m = M; m; m &= m - 1) {
+        const int c = eg_cell(pos, __builtin_ctz(m));
+        v = v * (u32)C + (u32)(turned ? C - 1 - c : c);
+    }
+    return v;
+}
+
+// G of the agent's cube `cube` (in Ma) in direction r; -inf where the move leaves the board.  Every index it forms is inside the table:
+// a move never adds a cube and never empties the mover's side, so 1 <= popcounts <= K, their sum <= T, and each side index < n_k.
+template <int S>
+EWN_DEV float eg_move(const float *tbl, const EgGeo &g, int Ma, int Mo, u64 pa, u64 po, int cube, int r)
+{
+    constexpr int C = S * S;
+    const int src = eg_cell(pa, cube), x = src / S, y = src % S;
+    if (!((r == 1 || y < S - 1) && (r == 0 || x < S - 1))) return -__builtin_inff();
+    const int dst = src + (r == 0 ? 1 : r == 1 ? S : S + 1);
+    int Ma1 = Ma, Mo1 = Mo;
+    #pragma unroll
+    for (int k = 1; k <= 6; k++) {
+        if (((Ma >> k) & 1) && eg_cell(pa, k) == dst) Ma1 &= ~(1 << k);
+        if (((Mo >> k) & 1) && eg_cell(po, k) == dst) Mo1 &= ~(1 << k);
+    }
+    if (dst == C - 1 || Mo1 == 0) return 1.0f;
+    const int sh = 8 * (cube - 1);
+    const u64 pa1 = (pa & ~(0xFFull << sh)) | ((u64)dst << sh);
+    const int ka1 = __builtin_popcount((unsigned)Mo1), ko1 = __builtin_popcount((unsigned)Ma1);   // of flip(b1): the sides swap
+    const long long idx = g.off[ka1][ko1] + (long long)eg_side<S>(Mo1, po, true) * (long long)eg_n<S>(ko1) + (long long)eg_side<S>(Ma1, pa1, true);
+    return -tbl[idx];
+}
+
+// E from the best move of each cube: m_d = max(best[cube of flag 0], best[cube of flag 1]); max is exact, so this is the definition's
+// maximum over (f, r) bit for bit
+template <int S>
+EWN_DEV float eg_value(const float *tbl, const EgGeo &g, int Ma, int Mo, u64 pa, u64 po)
+{
+    float best[3] = {0.0f, 0.0f, 0.0f};                            // per cube of Ma, in cube-number order (K <= 3)
+    int m = Ma;
+    #pragma unroll 1
+    for (int j = 0; j < 3 && m; j++, m &= m - 1) {
+        const int k = __builtin_ctz(m);
+        float b = -__builtin_inff();
+        #pragma unroll
+        for (int r = 0; r < 3; r++) { const float q = eg_move<S>(tbl, g, Ma, Mo, pa, po, k, r); b = q > b ? q : b; }
+        best[0] = j == 0 ? b : best[0]; best[1] = j == 1 ? b : best[1]; best[2] = j == 2 ? b : best[2];
+    }
+    float sum = 0.0f;
+    #pragma unroll
+    for (int d = 1; d <= 6; d++) {
+        const int j0 = __builtin_popcount((unsigned)(Ma & ((1 << la_find(0, d, Ma)) - 1))), j1 = __builtin_popcount((unsigned)(Ma & ((1 << la_find(1, d, Ma)) - 1)));
+        const float m0 = j0 == 0 ? best[0] : j0 == 1 ? best[1] : best[2], m1 = j1 == 0 ? best[0] : j1 == 1 ? best[1] : best[2];
+        const float md = m1 > m0 ? m1 : m0;
+        sum = d == 1 ? md : sum + md;
+    }
+    return sum * (1.0f / 6.0f);
+}
+
+// a side index decoded: false where two of its cubes share a cell or a cell of `occ` (the other side's), or a cube stands on `bad`.
+// phi: the sum of the cubes' Manhattan distances to their corner (far_goal: cell C - 1, else cell 0)
+template <int S>
+EWN_DEV bool eg_decode(u32 i, int k, int bad, bool far_goal, u64 &occ0, u64 &occ1, int &M, u64 &pos, int &phi)
+{
+    constexpr int C = S * S;
+    const u32 pw = eg_pw<S>(k);
+    u32 rem = i % pw;
+    M = (int)EG_MASKS.unrank[k][i / pw] << 1;
+    pos = 0; phi = 0;
+    bool ok = true;
+    int m = M;
+    #pragma unroll
+    for (int j = 0; j < 3; j++) {
+        if (j < k) {
+            const int cube = 31 - __builtin_clz((unsigned)m);    // the highest cube number holds the least significant digit
+            m &= ~(1 << cube);
+            const int c = (int)(rem % (u32)C);
+            rem /= (u32)C;
+            const int x = c / S, y = c % S;
+            phi += far_goal ? (S - 1 - x) + (S - 1 - y) : x + y;
+            const u64 bit = 1ull << (c & 63);
+            const bool hi = c >= 64;
+            ok = ok && c != bad && !((hi ? occ1 : occ0) & bit);
+            occ0 |= hi ? 0ull : bit; occ1 |= hi ? bit : 0ull;
+            pos |= (u64)c << (8 * (cube - 1));
+        }
+    }
+    return ok;
+}
+
+struct EgLevel {
+    int level, nblk;
+    struct { int ka, ko; u32 wg0, chunks; } b[EG_MAX_BLOCKS];   // workgroups wg0 .. : chunks per agent side index, EG_NT opposing side indices per chunk
+};
+
+// One Phi level.  A workgroup holds one agent side and EG_NT consecutive opposing sides, so the agent half of the decode is uniform
+// and an agent side that is invalid or already too far for this level retires the whole workgroup.
+template <int S>
+__global__ __launch_bounds__(EG_NT) void k_endgame_level(float *tbl, EgGeo g, EgLevel L)
+{
+    constexpr int C = S * S;
+    const u32 wg = blockIdx.x;
+    int bi = 0;
+    #pragma unroll 1
+    for (int i = 1; i < L.nblk; i++) if (wg >= L.b[i].wg0) bi = i;
+    const int ka = L.b[bi].ka, ko = L.b[bi].ko;
+    const u32 local = wg - L.b[bi].wg0, chunks = L.b[bi].chunks;
+    const u32 ia = local / chunks, io = (local % chunks) * EG_NT + threadIdx.x;
+    u64 occ0 = 0ull, occ1 = 0ull;
+    int Ma, Mo, phia, phio;
+    u64 pa, po;
+    if (!eg_decode<S>(ia, ka, C - 1, true, occ0, occ1, Ma, pa, phia)) return;
+    const int want = L.level - phia;
+    if (want < ko || want > ko * 2 * (S - 1) || io >= eg_n<S>(ko)) return;
+    if (!eg_decode<S>(io, ko, 0, false, occ0, occ1, Mo, po, phio) || phio != want) return;
+    tbl[g.off[ka][ko] + (long long)ia * (long long)eg_n<S>(ko) + (long long)io] = eg_value<S>(tbl, g, Ma, Mo, pa, po);
+}
+
+struct EgLookBuf { const float *tbl; const int8_t *boards; const int8_t *dice; int8_t *actions; float *q; float *value; uint8_t *covered; };
+
+// a lane per observation: the work is a handful of dependent gathers, nothing a wave could share
+template <int S>
+__global__ __launch_bounds__(EG_NT) void k_endgame_lookup(int M, EgGeo g, EgLookBuf B)
+{
+    constexpr int C = S * S;
+    const long long m = (long long)blockIdx.x * EG_NT + threadIdx.x;
+    if (m >= M) return;
+    const int8_t *b = B.boards + m * C;
+    int Ma = 0, Mo = 0, na = 0, no = 0;
+    u64 pa = 0, po = 0;
+    bool ok = true;
+    #pragma unroll 1
+    for (int c = 0; c < C; c++) {
+        const int v = b[c];
+        if (v == 0) continue;
+        const int k = v > 0 ? v : -v;
+        if (k > 6) { ok = false; continue; }
+        if (v > 0) { ok = ok && !((Ma >> k) & 1) && c != C - 1; Ma |= 1 << k; na++; pa |= (u64)c << (8 * (k - 1)); }
+        else       { ok = ok && !((Mo >> k) & 1) && c != 0;     Mo |= 1 << k; no++; po |= (u64)c << (8 * (k - 1)); }
+    }
+    ok = ok && na >= 1 && no >= 1 && na <= g.K && no <= g.K && na + no <= g.T;   // a cube number twice on a side: not a position
+    int d = (int)B.dice[m];
+    d = d < 1 ? 1 : d > 6 ? 6 : d;
+    const float ninf = -__builtin_inff();
+    float q[6] = {ninf, ninf, ninf, ninf, ninf, ninf}, val = 0.0f;
+    int best = 0;
+    if (ok) {
+        const int c0 = la_find(0, d, Ma), c1 = la_find(1, d, Ma);
+        #pragma unroll
+        for (int r = 0; r < 3; r++) q[r] = eg_move<S>(B.tbl, g, Ma, Mo, pa, po, c0, r);
+        #pragma unroll
+        for (int r = 0; r < 3; r++) q[3 + r] = c1 == c0 ? q[r] : eg_move<S>(B.tbl, g, Ma, Mo, pa, po, c1, r);
+        float qb = q[0];
+        #pragma unroll
+        for (int i = 1; i < 6; i++) if (q[i] > qb) { qb = q[i]; best = i; }
+        if (B.value) val = B.tbl[g.off[na][no] + (long long)eg_side<S>(Ma, pa, false) * (long long)eg_n<S>(no) + (long long)eg_side<S>(Mo, po, false)];
+    }
+    B.actions[m * 2] = (int8_t)(best / 3); B.actions[m * 2 + 1] = (int8_t)(best % 3);
+    if (B.q) {
+        #pragma unroll
+        for (int i = 0; i < 6; i++) B.q[m * 6 + i] = q[i];
+    }
+    if (B.value) B.value[m] = val;
+    if (B.covered) B.covered[m] = ok ? 1 : 0;
+}
+
+// ---------------------------------------------------------------- host
+static inline bool eg_params_ok(int S, int K, int T) { return S >= 3 && S <= 11 && K >= 1 && K <= 3 && T >= 2 && T <= 2 * K; }
+
+static inline long long eg_n_host(int S, int k)
+{
+    long long n = k == 1 ? 6 : k == 2 ? 15 : 20;
+    for (int i = 0; i < k; i++) n *= S * S;
+    return n;
+}
+
+// the block offsets, ka-major; returns the table's entries
+static long long eg_geo(int S, int K, int T, EgGeo &g)
+{
+    g.K = K; g.T = T;
+    long long total = 0;
+    for (int a = 0; a < 4; a++) for (int o = 0; o < 4; o++) g.off[a][o] = -1;
+    for (int a = 1; a <= K; a++)
+        for (int o = 1; o <= K; o++)
+            if (a + o <= T) { g.off[a][o] = total; total += eg_n_host(S, a) * eg_n_host(S, o); }
+    return total;
+}
+
+// the active (ka, ko) blocks of a level and its grid: EG_NT entries a workgroup, rounded up per agent side.  0: nothing at this level
+static unsigned long long eg_level(int S, int K, int T, int level, EgLevel &L)
+{
+    memset(&L, 0, sizeof(L));
+    L.level = level;
+    unsigned long long wg = 0;
+    for (int a = 1; a <= K; a++)
+        for (int o = 1; o <= K; o++) {
+            if (a + o > T || level < a + o || level > (a + o) * 2 * (S - 1)) continue;
+            const unsigned long long chunks = (unsigned long long)(eg_n_host(S, o) + EG_NT - 1) / EG_NT;
+            if (wg > 0x7FFFFFFFull) return wg;
+            L.b[L.nblk].ka = a; L.b[L.nblk].ko = o; L.b[L.nblk].wg0 = (u32)wg; L.b[L.nblk].chunks = (u32)chunks;
+            L.nblk++;
+            wg += chunks * (unsigned long long)eg_n_host(S, a);
+        }
+    return wg;
+}
+
+template <int S>
+static int eg_build(int K, int T, float *table, long long entries, const EgGeo &g, hipStream_t s)
+{
+    EgLevel L;
+    for (int level = 2; level <= 2 * T * (S - 1); level++)       // every level's grid must fit before anything is launched
+        if (eg_level(S, K, T, level, L) > 0x7FFFFFFFull) return EWN_EUNSUPPORTED;
+    if (hipMemsetAsync(table, 0, (size_t)entries * sizeof(float), s) != hipSuccess) return EWN_ELAUNCH;
+    for (int level = 2; level <= 2 * T * (S - 1); level++) {     // Phi >= 2: a live position has a cube a side, neither on its corner
+        const unsigned long long wg = eg_level(S, K, T, level, L);
+        if (wg == 0) continue;
+        k_endgame_level<S><<<dim3((unsigned)wg), dim3(EG_NT), 0, s>>>(table, g, L);
+        const int rc = launch_status();
+        if (rc != EWN_OK) return rc;
+    }
+    return EWN_OK;
+}
+
+template <int S>
+static int eg_lookup(int M, const EgGeo &g, const EgLookBuf &B, hipStream_t s)
+{
+    k_endgame_lookup<S><<<dim3((unsigned)((M - 1) / EG_NT + 1)), dim3(EG_NT), 0, s>>>(M, g, B);
+    return launch_status();
+}
+
+#define EG_BY_SIZE(S_, CALL)                                                                                          \
+    switch (S_) {                                                                                                     \
+    case 3: return CALL(3); case 4: return CALL(4); case 5: return CALL(5); case 6: return CALL(6); case 7: return CALL(7);   \
+    case 8: return CALL(8); case 9: return CALL(9); case 10: return CALL(10); default: return CALL(11);               \
+    }
+
+int64_t ewn_endgame_table_bytes(int board_size, int max_cubes, int max_total)
+{
+    if (!eg_params_ok(board_size, max_cubes, max_total)) return EWN_EINVAL;
+    EgGeo g;
+    return (int64_t)eg_geo(board_size, max_cubes, max_total, g) * (int64_t)sizeof(float);
+}
+
+int ewn_endgame_build(int board_size, int max_cubes, int max_total, float *table, int64_t table_bytes, void *stream)
+{
+    if (!eg_params_ok(board_size, max_cubes, max_total)) return EWN_EINVAL;
+    if (!table) return EWN_ENULL;
+    EgGeo g;
+    const long long entries = eg_geo(board_size, max_cubes, max_total, g);
+    if (table_bytes != (int64_t)entries * (int64_t)sizeof(float) || ((uintptr_t)table & 3u)) return EWN_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+#define EG_CALL(S_) eg_build<S_>(max_cubes, max_total, table, entries, g, s)
+    EG_BY_SIZE(board_size, EG_CALL)
+#undef EG_CALL
+}
+
+int ewn_endgame_lookup(int board_size, int max_cubes, int max_total, const float *table, int M, const int8_t *boards, const int8_t *dice,
+                       int8_t *actions, float *q, float *value, uint8_t *covered, void *stream)
+{
+    if (M < 0 || !eg_params_ok(board_size, max_cubes, max_total)) return EWN_EINVAL;
+    if (M == 0) return EWN_OK;
+    if (!table || !boards || !dice || !actions) return EWN_ENULL;
+    if ((uintptr_t)table & 3u) return EWN_EINVAL;
+    EgGeo g;
+    eg_geo(board_size, max_cubes, max_total, g);
+    EgLookBuf B = { table, boards, dice, actions, q, value, covered };
+    hipStream_t s = (hipStream_t)stream;
+#define EG_CALL(S_) eg_lookup<S_>(M, g, B, s)
+    EG_BY_SIZE(board_size, EG_CALL)
+#undef EG_CALL
+}

@@ -5,7 +5,8 @@ search is ewn_predict_lookahead (one or two moves ahead on the value net, DESIGN
 search's action, the critic toward the search's value, which bootstraps from the real terminal values (+-terminal_value) through
 its own leaves.  One update:
     rollout with the current policy (ewn_step_k_policy: only the visited observations are used, not the rewards)
-    -> predict_lookahead on the n_steps x lanes observations -> ewn_lookahead_targets -> ewn_sup_grad
+    -> predict_lookahead on the n_steps x lanes observations [-> the exact q where an endgame table covers the position, 4n]
+    -> ewn_lookahead_targets -> ewn_sup_grad
     -> [all-reduce of the flat gradient] -> ewn_a2c_apply (global-norm clip + RMSprop).
 """
 import ctypes as C
@@ -26,7 +27,7 @@ class SearchDistillTrainer(PolicyOpponent):
 
     def __init__(self, env, n_steps=5, learning_rate=7e-4, pi_coef=1.0, vf_coef=0.5, temperature=0.0, plies=1, terminal_value=1.0,
                  max_grad_norm=0.5, rms_alpha=0.99, rms_eps=1e-5, seed=None, opponent=None, opponent_update_every=100,
-                 opponent_deterministic=False):
+                 opponent_deterministic=False, endgame_table=None):
         import math
         from . import _lib
         if opponent is None and not env.supports_policy_rollout():
@@ -38,6 +39,17 @@ class SearchDistillTrainer(PolicyOpponent):
                 raise ValueError("SearchDistillTrainer: %s must be finite and not negative, got %r" % (name, v))
         if not math.isfinite(float(terminal_value)):
             raise ValueError("SearchDistillTrainer: terminal_value must be finite, got %r" % (terminal_value,))
+        if endgame_table is not None:
+            from .endgame import EndgameTable
+            if not float(terminal_value) > 0.0:
+                raise ValueError("SearchDistillTrainer: with an endgame table terminal_value must be positive (it scales the exact q), "
+                                 "got %r" % (terminal_value,))
+            if not isinstance(endgame_table, EndgameTable):
+                endgame_table = EndgameTable.load(endgame_table, device=env.board.device)
+            if endgame_table.board_size != env.S:
+                raise ValueError("SearchDistillTrainer: the endgame table is for %dx%d boards, the env plays %dx%d" % (
+                    endgame_table.board_size, endgame_table.board_size, env.S, env.S))
+        self.endgame_table = endgame_table   # None: the search's q alone; else its q is replaced by the exact one on covered rows
         self.env, self.lib = env, env.lib
         self.device = env.board.device
         if seed is not None:
@@ -87,6 +99,9 @@ class SearchDistillTrainer(PolicyOpponent):
         self._dice.view(K, N).copy_(self.traj["obs_dice"][:K])
         _, q = predict_lookahead(self._boards, self._dice, self.params, terminal_value=self.terminal_value, return_q=True,
                                  cube_layer=env.L, plies=self.plies)
+        if self.endgame_table is not None:     # the exact rows have -inf where the search's have: the same moves leave the board
+            _, covered, q_exact = self.endgame_table.lookup(self._boards, self._dice, return_q=True)
+            q = torch.where(covered[:, None, None], self.terminal_value * q_exact, q)
         target_pi, target_value, weight = lookahead_targets(q, self.temperature)
         sup_grad(self._boards, self._dice, target_pi, target_value, self.params, weight=weight, pi_coef=self.pi_coef, vf_coef=self.vf_coef,
                  cube_layer=env.L, out=self.grad, scratch=self.scratch)

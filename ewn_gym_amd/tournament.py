@@ -54,7 +54,30 @@ def _policy(spec, cube_layer, key):
         model = spec["model"]
         return ValueSearchAgent(model, board_size=getattr(model, "S", spec.get("board_size", 5)), cube_layer=cube_layer,
                                 terminal_value=spec.get("terminal_value", 1.0), plies=spec.get("plies", 1)).policy_fn()
+    if kind == "endgame":       # the exact move where the endgame table covers the position, the "fallback" spec's policy elsewhere
+        from classical_policies.model import EndgameAgent
+        if "table" not in spec or "fallback" not in spec:
+            raise ValueError("the endgame kind takes {'kind': 'endgame', 'table': an EndgameTable or its path, 'fallback': an agent spec}")
+        return EndgameAgent(spec["table"], _SpecPolicy(spec["fallback"], cube_layer, key)).policy_fn()
     raise ValueError("unknown agent kind %r" % kind)
+
+
+class _SpecPolicy:
+    """an agent spec behind predict_batch, for EndgameAgent's fallback; step t of the evaluation reaches the spec's policy through
+    EndgameAgent.policy_fn's single call per step"""
+
+    def __init__(self, spec, cube_layer, key):
+        if isinstance(spec, dict) and spec.get("kind") == "mlp":   # evaluate() plays a bare "mlp" agent itself; inside a wrapper it is the per-step policy
+            model = spec["model"]
+            self.fn = lambda b, d, t: model.act(b, d, deterministic=True)[0]
+        else:
+            self.fn = _policy(spec, cube_layer, key)
+        self.t = 0
+
+    def predict_batch(self, boards, dice):
+        a = self.fn(boards, dice, self.t)
+        self.t += 1
+        return a
 
 
 def flat_policy_params(model):
@@ -74,7 +97,9 @@ def _totals_result(totals, num, engine):
 def evaluate(agent, opponent, num=1024, board_size=5, cube_layer=3, rng="mt19937", seed_offset=0, key=12345, max_steps=400,
              use_rollout=True, chunk=16):
     """agent: a dict like the opponent's, {"kind": "mlp", "model": a2c.ActorCritic} (its deterministic policy),
-    {"kind": "mlp_lookahead", "model": ..., terminal_value=, plies=} (its lookahead on its own value net, ply by ply), or a callable
+    {"kind": "mlp_lookahead", "model": ..., terminal_value=, plies=} (its lookahead on its own value net, ply by ply),
+    {"kind": "endgame", "table": an EndgameTable or its path, "fallback": any of these dicts} (the exact move where the table covers
+    the position, the fallback's elsewhere, ply by ply), or a callable
     policy (board, dice, t) -> actions.
     agent / opponent: dicts {"kind": "random"|"minimax"|"mcts", max_depth=, heuristic=, num_simulations=, num_env_copies=}.
     Returns per-episode scores (float64 tensor), episode lengths and summary statistics.
@@ -305,10 +330,14 @@ def load_policy(path, board_size=5, cube_layer=3, device="cuda"):
 
 
 def evaluate_model(model, names=("random", "minimax"), num=1024, max_depth=5, num_simulations=10, num_env_copies=5, board_size=5,
-                   cube_layer=3, heuristic="hybrid", rng="mt19937", lookahead=False):
+                   cube_layer=3, heuristic="hybrid", rng="mt19937", lookahead=False, endgame_table=None):
     """eval_A2C.py's loop: the model's deterministic policy against every listed opponent; lookahead (1 / True, or 2): and, beside
-    each, its lookahead policy of that many moves ({"kind": "mlp_lookahead", "plies": ...}) on the same episodes"""
+    each, its lookahead policy of that many moves ({"kind": "mlp_lookahead", "plies": ...}) on the same episodes.  endgame_table (an
+    EndgameTable or its path): every agent plays the exact move where the table covers the position ({"kind": "endgame"}, ply by ply)"""
     table = {}
+    if endgame_table is not None:
+        return _evaluate_model_endgame(model, names, num, max_depth, num_simulations, num_env_copies, board_size, cube_layer, heuristic,
+                                       rng, lookahead, endgame_table)
     for o in names:
         opp = {"kind": o, "max_depth": max_depth, "heuristic": heuristic, "num_simulations": num_simulations, "num_env_copies": num_env_copies}
         r = evaluate({"kind": "mlp", "model": model}, opp, num=num, board_size=board_size, cube_layer=cube_layer, rng=rng)
@@ -318,6 +347,24 @@ def evaluate_model(model, names=("random", "minimax"), num=1024, max_depth=5, nu
             r = evaluate({"kind": "mlp_lookahead", "model": model, "plies": plies}, opp, num=num, board_size=board_size, cube_layer=cube_layer,
                          rng=rng)
             table[("lookahead(2) vs %s" if plies == 2 else "lookahead vs %s") % o] = {k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}
+    return table
+
+
+def _evaluate_model_endgame(model, names, num, max_depth, num_simulations, num_env_copies, board_size, cube_layer, heuristic, rng, lookahead,
+                            endgame_table):
+    """evaluate_model with every agent wrapped in the endgame kind; the table is loaded once"""
+    from .endgame import EndgameTable
+    t = endgame_table if isinstance(endgame_table, EndgameTable) else EndgameTable.load(endgame_table)
+    table = {}
+    agents = [("endgame+model vs %s", {"kind": "mlp", "model": model})]
+    if lookahead:
+        plies = 2 if int(lookahead) == 2 else 1
+        agents.append(("endgame+lookahead(2) vs %s" if plies == 2 else "endgame+lookahead vs %s", {"kind": "mlp_lookahead", "model": model, "plies": plies}))
+    for o in names:
+        opp = {"kind": o, "max_depth": max_depth, "heuristic": heuristic, "num_simulations": num_simulations, "num_env_copies": num_env_copies}
+        for label, spec in agents:
+            r = evaluate({"kind": "endgame", "table": t, "fallback": spec}, opp, num=num, board_size=board_size, cube_layer=cube_layer, rng=rng)
+            table[label % o] = {k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}
     return table
 
 
@@ -331,6 +378,9 @@ def _parser():
     ap.add_argument("--lookahead", nargs="?", const=1, default=None, type=int, choices=(1, 2),
                     help="with --model: beside the raw policy, its lookahead on its own value net (ewn_predict_lookahead) against the "
                          "same opponents; the bare flag or 1: one move ahead, 2: two moves")
+    ap.add_argument("--endgame_table", default=None,
+                    help="with --model: a saved EndgameTable; the model (and its --lookahead) plays the exact move wherever the table "
+                         "covers the position")
     ap.add_argument("--num", type=int, default=1024)
     ap.add_argument("--max_depth", type=int, default=5)
     ap.add_argument("--heuristic", default="hybrid")
@@ -347,6 +397,8 @@ def main():
     a = ap.parse_args()
     if a.lookahead and (a.model is None or a.opponent_model is not None):
         ap.error("--lookahead goes with --model and the classical opponents of --agents")
+    if a.endgame_table and (a.model is None or a.opponent_model is not None):
+        ap.error("--endgame_table goes with --model and the classical opponents of --agents")
     if a.opponent_model is not None and a.model is None:
         t = evaluate_agents_vs_model(load_policy(a.opponent_model, a.board_size, a.cube_layer), a.agents, a.num, a.max_depth,
                                      a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer, a.heuristic, a.rng)
@@ -358,7 +410,7 @@ def main():
     elif a.model is not None:
         model = load_policy(a.model, a.board_size, a.cube_layer)
         t = evaluate_model(model, a.agents, a.num, a.max_depth, a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer,
-                           a.heuristic, a.rng, lookahead=a.lookahead or False)
+                           a.heuristic, a.rng, lookahead=a.lookahead or False, endgame_table=a.endgame_table)
     else:
         t = tournament(a.agents, a.num, a.max_depth, a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer,
                        a.heuristic, a.rng)

@@ -29,6 +29,8 @@ def main():
     ap.add_argument("--temperature", type=float, default=0.0,
                     help="SEARCH: 0 trains toward the search's action, > 0 toward the softmax of its Q / temperature")
     ap.add_argument("--terminal_value", type=float, default=1.0, help="SEARCH: the value of a won (+) or lost (-) position in the lookahead")
+    ap.add_argument("--endgame_table", default=None,
+                    help="SEARCH: a saved EndgameTable; the search's q is replaced by the exact one wherever the table covers the position")
     ap.add_argument("--batch_size", "-b", type=int, default=None,
                     help="PPO: minibatch size in samples of the n_steps x lanes rollout buffer (default: a quarter of it; train.py:178-183)")
     ap.add_argument("--n_epochs", type=int, default=10, help="PPO: passes over the rollout buffer per update (SB3 default)")
@@ -72,6 +74,8 @@ def main():
     if a.algorithm == "SEARCH" and (a.trainer == "torch" or a.batch_size is not None):
         raise SystemExit("SEARCH has one trainer, SearchDistillTrainer, whose update is one full batch in the engine: --trainer torch and "
                          "--batch_size do not apply to it (--n_epochs is PPO's and is not read)")
+    if a.endgame_table is not None and a.algorithm != "SEARCH":
+        raise SystemExit("--endgame_table is read by SEARCH only")
     lo, hi = lane_range(a.num_envs * world, world, rank)
     if a.reference_quirks and a.opponent_policy not in ("random", "minimax", "mcts"):
         raise SystemExit("--reference_quirks drops the opponent (MinimaxEnv plays RandomAgent whatever it is given): it cannot be combined "
@@ -98,7 +102,7 @@ def main():
     elif a.algorithm == "SEARCH":
         from .distill import SearchDistillTrainer
         trainer = SearchDistillTrainer(env, n_steps=a.n_steps, learning_rate=a.learning_rate, temperature=a.temperature, plies=a.plies,
-                                       terminal_value=a.terminal_value, seed=mseed, **okw)
+                                       terminal_value=a.terminal_value, seed=mseed, endgame_table=a.endgame_table, **okw)
     elif a.trainer == "fused" or model_opp is not None or (a.trainer == "auto" and env.supports_policy_rollout()):
         trainer = FusedA2CTrainer(env, n_steps=a.n_steps, learning_rate=a.learning_rate, seed=mseed, **okw)
     else:

@@ -596,6 +596,36 @@ int ewn_lookahead_targets(int M, const float *q /* [M][6] */, float temperature,
                           float *target_pi /* [M][5] */, float *target_value /* [M] */,
                           float *weight /* [M] */, void *stream);
 
+/* ---- exact endgame values: a retrograde table over every position with few cubes left ----
+ * A position is seen from the side to move, before its dice; the mover is TOP_LEFT (the view ewn_predict_lookahead takes, and the one
+ * the opponent gets through flip(b) = the board turned by 180 degrees with the sides swapped).  With C = S * S:
+ *   E(b) = fl((m_1 + ... + m_6) * fl(1/6))      fp32, summed in dice order, one multiply
+ *   m_d  = max over f in {0, 1}, r in {0, 1, 2} whose move stays on the board of G(b, d, f, r)
+ *   G    = +1 if the move wins (it reaches cell C - 1, or the other side has no cube left after it), else -E(flip(b1)), b1 the board
+ *          after the move; the cube is find_cube_to_move(f) under d, and the move captures whatever stands on its target.
+ * (1 + E) / 2 is the mover's win probability under optimal play by both sides.  The table covers the positions with 1 .. max_cubes
+ * (1..3) cubes a side and at most max_total (2 .. 2 max_cubes) in all that are live: no agent cube on C - 1, no opposing cube on
+ * cell 0, cells in -6..6, no cube number twice on a side.  Boards 3x3 .. 11x11.  It holds sum over the covered (ka, ko) of n_ka n_ko
+ * floats, n_k = binom(6, k) C^k; the layout is the library's own (csrc/ewn_endgame.hip) and may change with the library.
+ *
+ * ewn_endgame_table_bytes: the table's size, or EWN_EINVAL for parameters outside the ranges above.
+ * ewn_endgame_build: fills the table on `stream`: one clear, then one launch per level of Phi = the sum of all cubes' Manhattan
+ * distances to their own corners (every ply lowers it), each reading only lower levels.  No atomics: the same bits on every build,
+ * whatever the buffer held; every slot is written (0 where the slot is not a live position).  Refusals in this order: EWN_EINVAL for
+ * the parameters, EWN_ENULL, EWN_EINVAL for a table_bytes other than ewn_endgame_table_bytes() or a table not 4-byte aligned, then
+ * EWN_EUNSUPPORTED for a table so large that a level does not fit one grid (2^31 - 1 workgroups of 256 entries).
+ * ewn_endgame_lookup: per observation (board, dice; dice outside 1..6 are clamped) q [M][6] = G under that dice in (f, r) order, -inf
+ * where the move leaves the board; actions [M][2] the first maximum of q (strict >); value [M] = E(b); covered [M] = 1.  A row that
+ * is not covered gets (0, 0), six -inf, value 0 and covered 0, and reads nothing from the table.  q, value and covered may be NULL.
+ * Refusals in this order: EWN_EINVAL for M < 0 or the parameters, EWN_OK without a launch for M == 0, EWN_ENULL, EWN_EINVAL for a
+ * table not 4-byte aligned.  One launch.  Reads exactly boards[0 .. M*C), dice[0 .. M); writes exactly the M rows of the outputs given.
+ * None of the three allocates or synchronises. */
+int64_t ewn_endgame_table_bytes(int board_size, int max_cubes, int max_total);
+int ewn_endgame_build(int board_size, int max_cubes, int max_total, float *table, int64_t table_bytes, void *stream);
+int ewn_endgame_lookup(int board_size, int max_cubes, int max_total, const float *table, int M, const int8_t *boards,
+                       const int8_t *dice, int8_t *actions /* [M][2] */, float *q /* [M][6], optional */,
+                       float *value /* [M], optional */, uint8_t *covered /* [M], optional */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
