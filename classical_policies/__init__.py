@@ -5,7 +5,8 @@
 AlphaZeroAgent / AlphaZeroMinimaxAgent are out of scope (un-vendored weights, SURVEY
 section 2 rows 12-14): they exist as names that raise on construction.  The search whose
 leaf is a network's value exists for the networks trained here: ValueSearchAgent (one-ply
-lookahead on the actor-critic's own value net, ewn_predict_lookahead), beside ModelAgent.
+lookahead on the actor-critic's own value net, ewn_predict_lookahead) and PuctAgent (a PUCT search on
+both of its heads, ewn_gym_amd.predict_puct: the counterpart of AlphaZeroMCTSAgent), beside ModelAgent.
 EndgameAgent plays the exact move where an endgame table covers the position and a fallback policy elsewhere.
 """
 from classical_policies.base import PolicyBase
@@ -13,7 +14,7 @@ from classical_policies.random_policy import RandomAgent
 from classical_policies.minimax import ExpectiMinimaxAgent, AlphaZeroMinimaxAgent
 from classical_policies.mcts import MctsAgent
 from classical_policies.alpha_zero import AlphaZeroAgent
-from classical_policies.model import EndgameAgent, ModelAgent, ValueSearchAgent
+from classical_policies.model import EndgameAgent, ModelAgent, PuctAgent, ValueSearchAgent
 
 # the names BASELINE.json's north_star uses
 RandomPolicy = RandomAgent
@@ -21,4 +22,4 @@ MiniMaxPolicy = ExpectiMinimaxAgent
 MCTSPolicy = MctsAgent
 
 __all__ = ["PolicyBase", "RandomAgent", "ExpectiMinimaxAgent", "MctsAgent", "AlphaZeroAgent", "AlphaZeroMinimaxAgent",
-           "RandomPolicy", "MiniMaxPolicy", "MCTSPolicy", "ModelAgent", "ValueSearchAgent", "EndgameAgent"]
+           "RandomPolicy", "MiniMaxPolicy", "MCTSPolicy", "ModelAgent", "ValueSearchAgent", "PuctAgent", "EndgameAgent"]

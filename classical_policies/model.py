@@ -89,6 +89,31 @@ class ValueSearchAgent(ModelAgent):
         return lambda b, d, t: self.predict_batch(b, d)
 
 
+class PuctAgent(ModelAgent):
+    """The trained actor-critic behind a PUCT search of `sims` simulations (ewn_gym_amd.predict_puct): the policy head
+    says where to look, the value head what a leaf is worth, chance nodes take the dice in a fixed stratified order.  This project's
+    counterpart of the reference's AlphaZeroMCTSAgent (classical_policies/alpha_zero/MCTS.py), on the network the trainers here
+    produce.  Always deterministic: a win on the board, else the most visited move.  sims=0 plays the first legal move unless one wins."""
+
+    def __init__(self, model_or_path, board_size=5, cube_layer=3, sims=64, c_puct=1.5, terminal_value=1.0):
+        from ewn_gym_amd.vec_env import _puct_numbers
+        self.sims = _puct_numbers("PuctAgent", sims, c_puct, terminal_value)
+        self.c_puct, self.terminal_value = float(c_puct), float(terminal_value)
+        super().__init__(model_or_path, board_size=board_size, cube_layer=cube_layer, deterministic=True)
+
+    def predict_batch(self, boards, dice, return_visits=False, return_q=False, return_value=False):
+        """boards (M,S,S), dice (M,) device or host arrays -> int8 (M,2) device tensor (and the int32 (M,2,3) root visits, the float32
+        (M,2,3) q and the float32 (M,) root value if asked for)"""
+        b, d = self._on_device(boards, dice)
+        return self._ea.predict_puct(b, d, self.params, sims=self.sims, c_puct=self.c_puct, terminal_value=self.terminal_value,
+                                     return_visits=return_visits, return_q=return_q, return_value=return_value,
+                                     cube_layer=self.cube_layer)
+
+    def policy_fn(self):
+        """(board, dice, t) -> actions, the callable tournament.evaluate takes"""
+        return lambda b, d, t: self.predict_batch(b, d)
+
+
 class EndgameAgent(PolicyBase):
     """The exact move wherever an endgame table covers the position, `fallback`'s elsewhere.  table: an
     ewn_gym_amd.EndgameTable or the path of a saved one; fallback: any policy of this package with predict_batch(boards, dice).

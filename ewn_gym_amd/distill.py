@@ -8,12 +8,32 @@ its own leaves.  One update:
     -> predict_lookahead on the n_steps x lanes observations [-> the exact q where an endgame table covers the position, 4n]
     -> ewn_lookahead_targets -> ewn_sup_grad
     -> [all-reduce of the flat gradient] -> ewn_a2c_apply (global-norm clip + RMSprop).
+search="puct"  puts predict_puct in the search's place and AlphaZero's target in the target's: the policy heads are
+trained toward the root's visit distribution (puct_targets), the critic toward the root's value.
 """
 import ctypes as C
 
 import torch
 
 from .a2c import ActorCritic, A2CTrainer, PolicyOpponent
+
+
+def puct_targets(visits, q, value, terminal_value=1.0):
+    """predict_puct's visits, q and value as training targets (plain torch, six numbers per row): visits [M, 2, 3], q float32
+    [M, 2, 3], value float32 [M] -> (target_pi float32 [M, 5], target_value float32 [M], weight float32 [M]).  The flag head's target
+    is sum_r visits / sum, the direction head's sum_f visits / sum; where both flags name one cube (flag 1 has no action of its own:
+    its q row is all -inf) the flag head gets (0.5, 0.5), lookahead_targets' convention.  target_value = terminal_value * value.
+    A row without visits (degenerate, or sims=0) gets zeros and weight 0."""
+    v = visits.reshape(-1, 2, 3).to(torch.float32)
+    tot = v.sum((1, 2))
+    live = tot > 0
+    den = torch.where(live, tot, torch.ones_like(tot))[:, None]
+    flag, direction = v.sum(2) / den, v.sum(1) / den
+    same = live & (q.reshape(-1, 2, 3)[:, 1] == float("-inf")).all(1)
+    flag = torch.where(same[:, None], torch.full_like(flag, 0.5), flag)
+    target_pi = torch.cat([flag, direction], 1) * live[:, None]
+    target_value = torch.where(live, float(terminal_value) * value.reshape(-1), torch.zeros_like(tot))
+    return target_pi.contiguous(), target_value.contiguous(), live.to(torch.float32)
 
 
 class SearchDistillTrainer(PolicyOpponent):
@@ -27,13 +47,18 @@ class SearchDistillTrainer(PolicyOpponent):
 
     def __init__(self, env, n_steps=5, learning_rate=7e-4, pi_coef=1.0, vf_coef=0.5, temperature=0.0, plies=1, terminal_value=1.0,
                  max_grad_norm=0.5, rms_alpha=0.99, rms_eps=1e-5, seed=None, opponent=None, opponent_update_every=100,
-                 opponent_deterministic=False, endgame_table=None):
+                 opponent_deterministic=False, endgame_table=None, search="lookahead", sims=64, c_puct=1.5):
         import math
         from . import _lib
         if opponent is None and not env.supports_policy_rollout():
             raise _lib.EwnError("this env configuration has no policy-driven rollout kernel (ewn_step_k_policy)")
+        if search not in ("lookahead", "puct"):
+            raise ValueError("SearchDistillTrainer: search must be 'lookahead' or 'puct', got %r" % (search,))
         if plies not in (1, 2):
             raise ValueError("SearchDistillTrainer: plies must be 1 or 2, got %r" % (plies,))
+        if search == "puct":
+            from .vec_env import _puct_numbers
+            _puct_numbers("SearchDistillTrainer", sims, c_puct, terminal_value)
         for name, v in (("pi_coef", pi_coef), ("vf_coef", vf_coef), ("temperature", temperature)):
             if not math.isfinite(float(v)) or float(v) < 0.0:
                 raise ValueError("SearchDistillTrainer: %s must be finite and not negative, got %r" % (name, v))
@@ -69,6 +94,7 @@ class SearchDistillTrainer(PolicyOpponent):
         self.n_steps, self.num_timesteps = int(n_steps), 0
         self.pi_coef, self.vf_coef, self.temperature = float(pi_coef), float(vf_coef), float(temperature)
         self.plies, self.terminal_value = int(plies), float(terminal_value)
+        self.search, self.sims, self.c_puct = search, int(sims), float(c_puct)
         world = 1
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized():
@@ -92,17 +118,28 @@ class SearchDistillTrainer(PolicyOpponent):
 
     def collect_and_update(self):
         from ._lib import check
-        from .vec_env import _ptr, _stream, lookahead_targets, predict_lookahead, sup_grad
+        from .vec_env import _ptr, _stream, lookahead_targets, predict_lookahead, predict_puct, sup_grad
         env, K, N, S = self.env, self.n_steps, self.env.N, self.env.S
         env.rollout_policy(K, self.params, traj=self.traj, noise_key=self.noise_key, **self._opponent_kwargs())
         self._boards.view(K, N, S, S).copy_(self.traj["obs_board"][:K])
         self._dice.view(K, N).copy_(self.traj["obs_dice"][:K])
-        _, q = predict_lookahead(self._boards, self._dice, self.params, terminal_value=self.terminal_value, return_q=True,
-                                 cube_layer=env.L, plies=self.plies)
-        if self.endgame_table is not None:     # the exact rows have -inf where the search's have: the same moves leave the board
-            _, covered, q_exact = self.endgame_table.lookup(self._boards, self._dice, return_q=True)
-            q = torch.where(covered[:, None, None], self.terminal_value * q_exact, q)
-        target_pi, target_value, weight = lookahead_targets(q, self.temperature)
+        if self.search == "puct":
+            _, visits, q, value = predict_puct(self._boards, self._dice, self.params, sims=self.sims, c_puct=self.c_puct,
+                                               terminal_value=self.terminal_value, return_visits=True, return_q=True, return_value=True,
+                                               cube_layer=env.L)
+            target_pi, target_value, weight = puct_targets(visits, q, value, self.terminal_value)
+            if self.endgame_table is not None:     # covered rows: the exact q's targets, as the lookahead's rows get them
+                _, covered, q_exact = self.endgame_table.lookup(self._boards, self._dice, return_q=True)
+                e_pi, e_value, e_weight = lookahead_targets(self.terminal_value * q_exact, self.temperature)
+                target_pi = torch.where(covered[:, None], e_pi, target_pi)
+                target_value, weight = torch.where(covered, e_value, target_value), torch.where(covered, e_weight, weight)
+        else:
+            _, q = predict_lookahead(self._boards, self._dice, self.params, terminal_value=self.terminal_value, return_q=True,
+                                     cube_layer=env.L, plies=self.plies)
+            if self.endgame_table is not None:     # the exact rows have -inf where the search's have: the same moves leave the board
+                _, covered, q_exact = self.endgame_table.lookup(self._boards, self._dice, return_q=True)
+                q = torch.where(covered[:, None, None], self.terminal_value * q_exact, q)
+            target_pi, target_value, weight = lookahead_targets(q, self.temperature)
         sup_grad(self._boards, self._dice, target_pi, target_value, self.params, weight=weight, pi_coef=self.pi_coef, vf_coef=self.vf_coef,
                  cube_layer=env.L, out=self.grad, scratch=self.scratch)
         if self.world > 1 or self.force_collective:   # the one collective: the flat gradient and its sums; apply divides by the world size
@@ -134,7 +171,8 @@ class SearchDistillTrainer(PolicyOpponent):
     def save(self, path):
         torch.save({"algorithm": self.algorithm, "fused": True, "params": self.params, "sq_avg": self.sq_avg,
                     "num_timesteps": self.num_timesteps, "best_score": float(self.best_score), "terminal_value": float(self.terminal_value),
-                    "plies": int(self.plies), **self._opponent_state()}, path)
+                    "plies": int(self.plies), "search": self.search, "sims": int(self.sims), "c_puct": float(self.c_puct),
+                    **self._opponent_state()}, path)
 
     def load(self, path):
         sd = torch.load(path, map_location=self.device, weights_only=True)
@@ -146,4 +184,6 @@ class SearchDistillTrainer(PolicyOpponent):
         self.best_score = float(sd.get("best_score", -1.0))
         self.terminal_value = float(sd.get("terminal_value", self.terminal_value))
         self.plies = int(sd.get("plies", self.plies))
+        self.search = sd.get("search", self.search)
+        self.sims, self.c_puct = int(sd.get("sims", self.sims)), float(sd.get("c_puct", self.c_puct))
         self._opponent_loaded(sd)

@@ -54,6 +54,11 @@ def _policy(spec, cube_layer, key):
         model = spec["model"]
         return ValueSearchAgent(model, board_size=getattr(model, "S", spec.get("board_size", 5)), cube_layer=cube_layer,
                                 terminal_value=spec.get("terminal_value", 1.0), plies=spec.get("plies", 1)).policy_fn()
+    if kind == "mlp_puct":      # the model's PUCT search on both of its heads (predict_puct), ply by ply through ewn_step
+        from classical_policies.model import PuctAgent
+        model = spec["model"]
+        return PuctAgent(model, board_size=getattr(model, "S", spec.get("board_size", 5)), cube_layer=cube_layer, sims=spec.get("sims", 64),
+                         c_puct=spec.get("c_puct", 1.5), terminal_value=spec.get("terminal_value", 1.0)).policy_fn()
     if kind == "endgame":       # the exact move where the endgame table covers the position, the "fallback" spec's policy elsewhere
         from classical_policies.model import EndgameAgent
         if "table" not in spec or "fallback" not in spec:
@@ -98,6 +103,7 @@ def evaluate(agent, opponent, num=1024, board_size=5, cube_layer=3, rng="mt19937
              use_rollout=True, chunk=16):
     """agent: a dict like the opponent's, {"kind": "mlp", "model": a2c.ActorCritic} (its deterministic policy),
     {"kind": "mlp_lookahead", "model": ..., terminal_value=, plies=} (its lookahead on its own value net, ply by ply),
+    {"kind": "mlp_puct", "model": ..., sims=, c_puct=, terminal_value=} (its PUCT search on both of its heads, ply by ply),
     {"kind": "endgame", "table": an EndgameTable or its path, "fallback": any of these dicts} (the exact move where the table covers
     the position, the fallback's elsewhere, ply by ply), or a callable
     policy (board, dice, t) -> actions.
@@ -330,10 +336,11 @@ def load_policy(path, board_size=5, cube_layer=3, device="cuda"):
 
 
 def evaluate_model(model, names=("random", "minimax"), num=1024, max_depth=5, num_simulations=10, num_env_copies=5, board_size=5,
-                   cube_layer=3, heuristic="hybrid", rng="mt19937", lookahead=False, endgame_table=None):
+                   cube_layer=3, heuristic="hybrid", rng="mt19937", lookahead=False, endgame_table=None, puct=None):
     """eval_A2C.py's loop: the model's deterministic policy against every listed opponent; lookahead (1 / True, or 2): and, beside
     each, its lookahead policy of that many moves ({"kind": "mlp_lookahead", "plies": ...}) on the same episodes.  endgame_table (an
-    EndgameTable or its path): every agent plays the exact move where the table covers the position ({"kind": "endgame"}, ply by ply)"""
+    EndgameTable or its path): every agent plays the exact move where the table covers the position ({"kind": "endgame"}, ply by ply).
+    puct (a number of simulations): and its PUCT search of that budget ({"kind": "mlp_puct", "sims": ...}), rows "puct(SIMS) vs ..." """
     table = {}
     if endgame_table is not None:
         return _evaluate_model_endgame(model, names, num, max_depth, num_simulations, num_env_copies, board_size, cube_layer, heuristic,
@@ -347,6 +354,10 @@ def evaluate_model(model, names=("random", "minimax"), num=1024, max_depth=5, nu
             r = evaluate({"kind": "mlp_lookahead", "model": model, "plies": plies}, opp, num=num, board_size=board_size, cube_layer=cube_layer,
                          rng=rng)
             table[("lookahead(2) vs %s" if plies == 2 else "lookahead vs %s") % o] = {k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}
+        if puct is not None:
+            r = evaluate({"kind": "mlp_puct", "model": model, "sims": int(puct)}, opp, num=num, board_size=board_size, cube_layer=cube_layer,
+                         rng=rng)
+            table["puct(%d) vs %s" % (int(puct), o)] = {k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}
     return table
 
 
@@ -378,6 +389,9 @@ def _parser():
     ap.add_argument("--lookahead", nargs="?", const=1, default=None, type=int, choices=(1, 2),
                     help="with --model: beside the raw policy, its lookahead on its own value net (ewn_predict_lookahead) against the "
                          "same opponents; the bare flag or 1: one move ahead, 2: two moves")
+    ap.add_argument("--puct", default=None, type=int, metavar="SIMS",
+                    help="with --model: beside the raw policy, its PUCT search of SIMS simulations (predict_puct) against the same "
+                         "opponents, rows \"puct(SIMS) vs ...\"")
     ap.add_argument("--endgame_table", default=None,
                     help="with --model: a saved EndgameTable; the model (and its --lookahead) plays the exact move wherever the table "
                          "covers the position")
@@ -397,6 +411,10 @@ def main():
     a = ap.parse_args()
     if a.lookahead and (a.model is None or a.opponent_model is not None):
         ap.error("--lookahead goes with --model and the classical opponents of --agents")
+    if a.puct is not None and (a.model is None or a.opponent_model is not None or a.endgame_table):
+        ap.error("--puct goes with --model and the classical opponents of --agents, without --endgame_table")
+    if a.puct is not None and not 0 <= a.puct <= 4096:
+        ap.error("--puct takes 0..4096 simulations")
     if a.endgame_table and (a.model is None or a.opponent_model is not None):
         ap.error("--endgame_table goes with --model and the classical opponents of --agents")
     if a.opponent_model is not None and a.model is None:
@@ -410,7 +428,7 @@ def main():
     elif a.model is not None:
         model = load_policy(a.model, a.board_size, a.cube_layer)
         t = evaluate_model(model, a.agents, a.num, a.max_depth, a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer,
-                           a.heuristic, a.rng, lookahead=a.lookahead or False, endgame_table=a.endgame_table)
+                           a.heuristic, a.rng, lookahead=a.lookahead or False, endgame_table=a.endgame_table, puct=a.puct)
     else:
         t = tournament(a.agents, a.num, a.max_depth, a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer,
                        a.heuristic, a.rng)

@@ -20,11 +20,16 @@ from .tournament import evaluate
 from .vec_env import VecEWN
 
 
-def main():
+def _parser():
     ap = argparse.ArgumentParser(description="Trainer for EWN on VecEWN lanes (counterpart of the reference's train.py)")
     # train.py:174-184 selects the algorithm with a sub-command; A2C is the one built here
     ap.add_argument("algorithm", nargs="?", default="A2C", choices=["A2C", "PPO", "SEARCH"],
                     help="train.py:174-184's sub-command; SEARCH: train toward the lookahead on the model's own critic (SearchDistillTrainer)")
+    ap.add_argument("--search", default="lookahead", choices=["lookahead", "puct"],
+                    help="SEARCH: the expert: the lookahead on the critic, or a PUCT search on both heads whose root visit distribution "
+                         "is the policy target (predict_puct)")
+    ap.add_argument("--sims", type=int, default=64, help="SEARCH --search puct: simulations per observation (0..4096)")
+    ap.add_argument("--c_puct", type=float, default=1.5, help="SEARCH --search puct: the exploration constant")
     ap.add_argument("--plies", type=int, default=1, choices=[1, 2], help="SEARCH: moves the lookahead looks ahead")
     ap.add_argument("--temperature", type=float, default=0.0,
                     help="SEARCH: 0 trains toward the search's action, > 0 toward the softmax of its Q / temperature")
@@ -64,7 +69,11 @@ def main():
                     help="reproduce MinimaxEnv's ctor-argument dropping: RandomAgent opponent, reward 1.0 (SURVEY App. D1)")
     ap.add_argument("--seed", "--env_seed", dest="seed", type=int, default=9487)
     ap.add_argument("--save_dir", default="models")
-    a = ap.parse_args()
+    return ap
+
+
+def main():
+    a = _parser().parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     if world > 1:
@@ -74,6 +83,8 @@ def main():
     if a.algorithm == "SEARCH" and (a.trainer == "torch" or a.batch_size is not None):
         raise SystemExit("SEARCH has one trainer, SearchDistillTrainer, whose update is one full batch in the engine: --trainer torch and "
                          "--batch_size do not apply to it (--n_epochs is PPO's and is not read)")
+    if a.search != "lookahead" and a.algorithm != "SEARCH":
+        raise SystemExit("--search is read by SEARCH only")
     if a.endgame_table is not None and a.algorithm != "SEARCH":
         raise SystemExit("--endgame_table is read by SEARCH only")
     lo, hi = lane_range(a.num_envs * world, world, rank)
@@ -102,7 +113,8 @@ def main():
     elif a.algorithm == "SEARCH":
         from .distill import SearchDistillTrainer
         trainer = SearchDistillTrainer(env, n_steps=a.n_steps, learning_rate=a.learning_rate, temperature=a.temperature, plies=a.plies,
-                                       terminal_value=a.terminal_value, seed=mseed, endgame_table=a.endgame_table, **okw)
+                                       terminal_value=a.terminal_value, seed=mseed, endgame_table=a.endgame_table, search=a.search,
+                                       sims=a.sims, c_puct=a.c_puct, **okw)
     elif a.trainer == "fused" or model_opp is not None or (a.trainer == "auto" and env.supports_policy_rollout()):
         trainer = FusedA2CTrainer(env, n_steps=a.n_steps, learning_rate=a.learning_rate, seed=mseed, **okw)
     else:

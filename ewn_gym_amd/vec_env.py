@@ -914,3 +914,189 @@ def sup_grad(boards, dice, target_pi, target_value, params, weight=None, pi_coef
         check(lib.ewn_sup_grad(S, int(cube_layer), M, _ptr(b), _ptr(d), _ptr(tp), _ptr(tv), _ptr(w), _ptr(params), C.c_float(float(pi_coef)),
                                C.c_float(float(vf_coef)), _ptr(grad), _ptr(scratch), _stream()), "ewn_sup_grad")
     return grad
+
+
+PUCT_LAYOUT = 1        # the version of a PUCT tree's layout (csrc/ewn_puct.hip); begin writes it into every header
+PUCT_MAX_SIMS = 4096
+
+
+def _puct_sections(S, sims):
+    """a PUCT tree's sections: ({name: (byte offset, dtype, shape per tree)}, bytes of one tree)"""
+    N = sims + 1
+    secs, o = {}, 0
+    for name, dt, shape in (("hdr", torch.int32, (8,)), ("n", torch.int32, (N, 6)), ("w", torch.float32, (N, 6)),
+                            ("p", torch.float32, (N, 6)), ("child", torch.int16, (N, 6, 6)), ("cn", torch.int16, (N, 6, 6)),
+                            ("parent", torch.int16, (N, 4)), ("kind", torch.int8, (N, 6)), ("dice", torch.int8, (N,)),
+                            ("board", torch.int8, (N, S, S))):
+        secs[name] = (o, dt, shape)
+        o += (math.prod(shape) * dt.itemsize + 3) // 4 * 4
+    return secs, o
+
+
+def _puct_numbers(who, sims, c_puct=0.0, terminal_value=1.0):
+    if not (isinstance(sims, (int, np.integer)) and 0 <= int(sims) <= PUCT_MAX_SIMS):
+        raise ValueError("%s: sims must be an integer in 0..%d, got %r" % (who, PUCT_MAX_SIMS, sims))
+    if not math.isfinite(float(c_puct)) or float(c_puct) < 0.0:
+        raise ValueError("%s: c_puct must be finite and not negative, got %r" % (who, c_puct))
+    if not math.isfinite(float(terminal_value)) or not float(terminal_value) > 0.0:
+        raise ValueError("%s: terminal_value must be finite and positive, got %r" % (who, terminal_value))
+    return int(sims)
+
+
+def _puct_tree(who, tree, S, sims, cube_layer=3):
+    """the checked tree buffer: a contiguous uint8 device tensor [M, tree_bytes] at a 4-byte aligned address -> (M, tree_bytes)"""
+    nb = int(_lib.load().ewn_puct_tree_bytes(int(S), int(cube_layer), sims))
+    if nb < 0:
+        raise ValueError("%s: no policy network for %dx%d boards with cube_layer %d (served: cube_layer 3 on 5x5 and 7x7)" % (
+            who, S, S, cube_layer))
+    if not (isinstance(tree, torch.Tensor) and tree.dtype == torch.uint8 and tree.dim() == 2 and tree.shape[1] == nb
+            and tree.is_contiguous() and tree.data_ptr() % 4 == 0):
+        raise ValueError("%s: tree must be a contiguous, 4-byte aligned uint8 tensor [M, %d] (puct_begin's, for sims=%d on %dx%d), got %s" % (
+            who, nb, sims, S, S, _describe(tree)))
+    return int(tree.shape[0]), nb
+
+
+def puct_tree_views(tree, board_size, sims):
+    """Tensor views onto the sections of puct_begin's trees (uint8 [M, tree_bytes]; layout PUCT_LAYOUT), nothing is
+    copied: count, done, pending, degenerate int32 [M]; n int32, w, p float32 [M, sims + 1, 6] per node and edge a = 3 f + r;
+    child, cn int16 [M, sims + 1, 6, 6] per node, edge and dice d' - 1; parent int16 [M, sims + 1, 4] (node, edge, dice, 0; the
+    root: -1, 0, 0, 0); kind int8 [M, sims + 1, 6]; dice int8 [M, sims + 1]; board int8 [M, sims + 1, S, S].  Rows of nodes
+    count .. sims are as puct_begin left them: zeros, child -1."""
+    sims = _puct_numbers("puct_tree_views", sims)
+    S = int(board_size)
+    secs, nb = _puct_sections(S, sims)
+    if not (isinstance(tree, torch.Tensor) and tree.dtype == torch.uint8 and tree.dim() == 2 and tree.shape[1] == nb
+            and tree.stride(1) == 1 and tree.stride(0) % 4 == 0 and tree.storage_offset() % 4 == 0):
+        raise ValueError("puct_tree_views: tree must be a uint8 tensor [M, %d] (puct_begin's, for sims=%d on %dx%d), got %s" % (
+            nb, sims, S, S, _describe(tree)))
+    out = {}
+    for name, (o, dt, shape) in secs.items():
+        out[name] = tree[:, o:o + math.prod(shape) * dt.itemsize].view(dt).unflatten(1, shape)
+    hdr = out.pop("hdr")
+    out.update(count=hdr[:, 0], done=hdr[:, 1], pending=hdr[:, 2], degenerate=hdr[:, 3])
+    return out
+
+
+def puct_begin(boards, dice, sims, cube_layer=3):
+    """The trees of a PUCT search on M observations (ewn_puct_begin): boards [S, S] or [M, S, S], dice [M] (outside
+    1..6: clamped) -> (tree uint8 [M, tree_bytes], leaf_boards int8 [M, S, S], leaf_dice int8 [M]).  Every byte of the trees is
+    written; the root is the pending leaf and the leaf row its observation, except where the observation is already over or a side
+    has no cube: that tree is degenerate and its leaf row a zero board with dice 1.  predict_lookahead's argument checks."""
+    who = "puct_begin"
+    sims = _puct_numbers(who, sims)
+    M, S, dev, (b, d) = _stage_inputs(who, [("boards", boards, torch.int8, lambda M, S: (M, S, S)),
+                                            ("dice", dice, torch.int8, lambda M, S: (M,))], cube_layer)
+    lib = _lib.load()
+    nb = int(lib.ewn_puct_tree_bytes(S, int(cube_layer), sims))
+    tree = torch.empty((M, nb), dtype=torch.uint8, device=dev)
+    lb = torch.empty((M, S, S), dtype=torch.int8, device=dev)
+    ld = torch.empty(M, dtype=torch.int8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.ewn_puct_begin(S, int(cube_layer), M, sims, _ptr(b), _ptr(d), _ptr(tree), _ptr(lb), _ptr(ld), _stream()), "ewn_puct_begin")
+    return tree, lb, ld
+
+
+def puct_advance(tree, logits, value, leaf_boards, leaf_dice, sims, c_puct=1.5, terminal_value=1.0, board_size=None, cube_layer=3):
+    """One round of the search (ewn_puct_advance): logits float32 [M, 5] and value float32 [M] are predict_policy's on
+    the leaf rows.  Per tree the pending leaf is evaluated (priors from the logits, v = value / terminal_value clamped to [-1, 1])
+    and backed up; then, while fewer than `sims` simulations have begun, one more walks down to a new leaf, or ends at once on a
+    winning move.  tree, leaf_boards and leaf_dice are updated in place (a tree without a pending leaf: a zero board with dice 1) and
+    returned.  board_size: taken from leaf_boards [M, S, S] when None.  sims + 1 rounds after puct_begin complete the search."""
+    who = "puct_advance"
+    sims = _puct_numbers(who, sims, c_puct, terminal_value)
+    for name, t in (("tree", tree), ("leaf_boards", leaf_boards), ("leaf_dice", leaf_dice)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s: %s is updated in place and must be a tensor, got %s" % (who, name, _describe(t)))
+    if board_size is not None and not (leaf_boards.dim() == 3 and leaf_boards.shape[1] == int(board_size)):
+        raise ValueError("%s: leaf_boards must have shape [M, %d, %d], got %s" % (who, int(board_size), int(board_size), list(leaf_boards.shape)))
+    M, S, dev, (lb, lg, v, ld) = _stage_inputs(who, [("leaf_boards", leaf_boards, torch.int8, lambda M, S: (M, S, S)),
+                                                    ("logits", logits, torch.float32, lambda M, S: (M, 5)),
+                                                    ("value", value, torch.float32, lambda M, S: (M,)),
+                                                    ("leaf_dice", leaf_dice, torch.int8, lambda M, S: (M,))], cube_layer)
+    Mt, _ = _puct_tree(who, tree, S, sims, cube_layer)
+    if Mt != M or not (tree.is_cuda and tree.device == dev):
+        raise ValueError("%s: tree must hold %d trees on %s, got %s" % (who, M, dev, _describe(tree)))
+    with torch.cuda.device(dev):
+        check(_lib.load().ewn_puct_advance(S, int(cube_layer), M, sims, C.c_float(float(c_puct)), C.c_float(float(terminal_value)), _ptr(tree),
+                                           _ptr(lg), _ptr(v), _ptr(lb), _ptr(ld), _stream()), "ewn_puct_advance")
+    return tree, leaf_boards, leaf_dice
+
+
+def puct_result(tree, board_size, sims, return_visits=False, return_q=False, return_value=False, cube_layer=3):
+    """What the search found at the roots (ewn_puct_result) -> actions int8 [M, 2], or the tuple (actions, visits int32
+    [M, 2, 3] if return_visits, q float32 [M, 2, 3] if return_q, value float32 [M] if return_value).  The action is the first root
+    move that wins if there is one, else the first maximum of the visits over the searched moves; q is -inf where (f, r) is no
+    action, +1 where it wins, else W / N (0 unvisited), value sum W / sum N, both in units of the terminal value.  A degenerate row:
+    (0, 0), zero visits, six -inf, 0."""
+    who = "puct_result"
+    sims = _puct_numbers(who, sims)
+    S = int(board_size)
+    M, _ = _puct_tree(who, tree, S, sims, cube_layer)
+    if not tree.is_cuda:
+        raise ValueError("%s: tree must live on the GPU, got %s" % (who, _describe(tree)))
+    dev = tree.device
+    acts = torch.zeros((M, 2), dtype=torch.int8, device=dev)
+    visits = torch.zeros((M, 2, 3), dtype=torch.int32, device=dev) if return_visits else None
+    q = torch.zeros((M, 2, 3), dtype=torch.float32, device=dev) if return_q else None
+    val = torch.zeros(M, dtype=torch.float32, device=dev) if return_value else None
+    with torch.cuda.device(dev):
+        check(_lib.load().ewn_puct_result(S, int(cube_layer), M, _ptr(tree), _ptr(acts), _ptr(visits), _ptr(q), _ptr(val), _stream()),
+              "ewn_puct_result")
+    out = (acts,) + tuple(t for t in (visits, q, val) if t is not None)
+    return out[0] if len(out) == 1 else out
+
+
+def predict_puct(boards, dice, params, sims=64, c_puct=1.5, terminal_value=1.0, return_visits=False, return_q=False, return_value=False,
+                 cube_layer=3, chunk=1024):
+    """What the trained actor-critic plays after a PUCT search of `sims` simulations on its own two heads: the policy
+    head says where to look, the value head what a leaf is worth, a move that wins on the board is worth +1 and is played; the
+    opponent's and the agent's later dice are chance nodes sampled in a fixed stratified order, so the search is deterministic.
+    boards [S, S] or [M, S, S], dice [M] (outside 1..6: clamped), params as predict_policy takes them -> actions int8 [M, 2], or the
+    tuple (actions, visits int32 [M, 2, 3], q float32 [M, 2, 3], value float32 [M]) of what was asked for, as puct_result returns
+    them.  sims=0: no search, zero visits, the first legal move unless one wins.  The stages are puct_begin, then sims + 1 rounds of
+    ewn_predict_policy on the leaf rows and puct_advance, then puct_result, `chunk` observations at a time on scratch allocated once
+    per call (a tree is 256 bytes per simulation at 5x5, 280 at 7x7).  predict_lookahead's argument checks."""
+    who = "predict_puct"
+    lib = _lib.load()
+    sims = _puct_numbers(who, sims, c_puct, terminal_value)
+    if int(chunk) < 1:
+        raise ValueError("%s: chunk must be at least 1, got %r" % (who, chunk))
+    M, S = _lookahead_shape(who, boards, cube_layer)
+    L = int(cube_layer)
+    P = lib.ewn_policy_param_count(S, L)
+    if not (isinstance(params, torch.Tensor) and params.dtype == torch.float32 and params.is_contiguous() and params.numel() == P):
+        raise ValueError("%s: params must be a contiguous float32 tensor of %d elements (the %dx%d actor-critic), got %s" % (
+            who, P, S, S, _describe(params)))
+    dev = params.device
+    b = _policy_input("boards", boards, torch.int8, (M, S, S), dev, who=who)
+    d = _policy_input("dice", dice, torch.int8, (M,), dev, who=who)
+    for name, t in (("params", params), ("boards", b), ("dice", d)):
+        if not (t.is_cuda and t.device == dev):
+            raise ValueError("%s: %s must live on the GPU that holds params (%s), got %s" % (who, name, dev, _describe(t)))
+    acts = torch.zeros((M, 2), dtype=torch.int8, device=dev)
+    visits = torch.zeros((M, 2, 3), dtype=torch.int32, device=dev) if return_visits else None
+    q = torch.zeros((M, 2, 3), dtype=torch.float32, device=dev) if return_q else None
+    val = torch.zeros(M, dtype=torch.float32, device=dev) if return_value else None
+    c = max(1, min(int(chunk), M))
+    nb = int(lib.ewn_puct_tree_bytes(S, L, sims))
+    tree = torch.empty((c, nb), dtype=torch.uint8, device=dev)
+    lb = torch.empty((c, S, S), dtype=torch.int8, device=dev)
+    ld = torch.empty(c, dtype=torch.int8, device=dev)
+    la = torch.empty((c, 2), dtype=torch.int8, device=dev)
+    lg = torch.empty((c, 5), dtype=torch.float32, device=dev)
+    lv = torch.empty(c, dtype=torch.float32, device=dev)
+    cp, tv = C.c_float(float(c_puct)), C.c_float(float(terminal_value))
+    with torch.cuda.device(dev):
+        st = _stream()
+        for i in range(0, M, c):
+            n = min(c, M - i)
+            sl = slice(i, i + n)
+            check(lib.ewn_puct_begin(S, L, n, sims, _ptr(b[sl]), _ptr(d[sl]), _ptr(tree), _ptr(lb), _ptr(ld), st), "ewn_puct_begin")
+            for _ in range(sims + 1):
+                check(lib.ewn_predict_policy(S, L, n, _ptr(lb), _ptr(ld), _ptr(params), 1, C.c_uint64(0), None, None, _ptr(la), _ptr(lg),
+                                             _ptr(lv), st), "ewn_predict_policy")
+                check(lib.ewn_puct_advance(S, L, n, sims, cp, tv, _ptr(tree), _ptr(lg), _ptr(lv), _ptr(lb), _ptr(ld), st), "ewn_puct_advance")
+            check(lib.ewn_puct_result(S, L, n, _ptr(tree), _ptr(acts[sl]), _ptr(None if visits is None else visits[sl]),
+                                      _ptr(None if q is None else q[sl]), _ptr(None if val is None else val[sl]), st), "ewn_puct_result")
+    out = (acts,) + tuple(t for t in (visits, q, val) if t is not None)
+    return out[0] if len(out) == 1 else out

@@ -562,6 +562,38 @@ int ewn_lookahead_reduce(int board_size, int cube_layer, int M, const int8_t *bo
                          const float *leaf /* [648 M][leaf_width] */, int leaf_width, float terminal_value,
                          int8_t *actions /* [M][2] */, float *q /* [M][6], optional */, void *stream);
 
+/* ---- a PUCT search on the trained actor-critic, staged like the above: tree kernels at the two ends, ewn_predict_policy in the
+ * middle (which holds the definition: nodes, edges, chance by the least visited dice, selection, backup, result).
+ * A tree is ewn_puct_tree_bytes() bytes, 4-byte aligned, trees back to back; its layout is documented in DESIGN.md 4o and in
+ * csrc/ewn_puct.hip and carries a version in its header.  sims: 0 .. 4096 simulations, a tree holds at most sims + 1 nodes.
+ *
+ * ewn_puct_tree_bytes: bytes of one tree; EWN_EUNSUPPORTED where ewn_policy_param_count() is, else EWN_EINVAL for sims outside 0 .. 4096.
+ * ewn_puct_begin: writes every byte of the M trees (nothing has to be cleared), makes the root the pending leaf -- or marks the tree
+ * degenerate where the observation is already over or a side has no cube -- and writes the M leaf rows: leaf_boards [M][S*S],
+ * leaf_dice [M] (dice outside 1..6 are clamped; a degenerate tree: a zero board with dice 1).
+ * ewn_puct_advance: per tree, if a leaf is pending, evaluates it from row m of logits [M][5] / value [M] (ewn_predict_policy's
+ * outputs on the leaf rows) and backs up; then, if fewer than `sims` simulations have begun, runs one down to its pending leaf or
+ * its immediate end at a winning move.  Writes row m of leaf_boards / leaf_dice on every call: the pending observation, or a zero
+ * board with dice 1.  The tree is updated in place; `sims` is the one begin was given (a tree of another budget is left alone).
+ * sims + 1 calls after begin complete the search.
+ * ewn_puct_result: actions [M][2] (required): the first root move that wins if there is one, else the first maximum (strict >) of
+ * the root's visits over the searched moves; visits [M][6] int32, q [M][6] (-inf not an action, +1 wins, W / N or 0 searched, in
+ * units of the terminal value) and value [M] (sum W / sum N or 0) may be NULL.  A degenerate row: (0, 0), zero visits, six -inf, 0.
+ *
+ * Refusals in this order: EWN_EINVAL for M < 0 or M > INT_MAX / 64, EWN_EUNSUPPORTED where ewn_policy_param_count() is, EWN_OK
+ * without a launch for M == 0, EWN_ENULL for a missing required pointer, then EWN_EINVAL for sims outside 0 .. 4096, a tree that is
+ * not 4-byte aligned, a terminal_value that is not finite and positive, or a c_puct that is not finite and >= 0.  Each is one kernel
+ * launch on `stream`, no allocation, no synchronisation, no atomics, no random numbers: the same inputs give the same bits. */
+int64_t ewn_puct_tree_bytes(int board_size, int cube_layer, int sims);
+int ewn_puct_begin(int board_size, int cube_layer, int M, int sims, const int8_t *boards, const int8_t *dice, void *tree,
+                   int8_t *leaf_boards /* [M][S*S] */, int8_t *leaf_dice /* [M] */, void *stream);
+int ewn_puct_advance(int board_size, int cube_layer, int M, int sims, float c_puct, float terminal_value, void *tree,
+                     const float *logits /* [M][5] */, const float *value /* [M] */, int8_t *leaf_boards, int8_t *leaf_dice,
+                     void *stream);
+int ewn_puct_result(int board_size, int cube_layer, int M, const void *tree, int8_t *actions /* [M][2] */,
+                    int32_t *visits /* [M][6], optional */, float *q /* [M][6], optional */, float *value /* [M], optional */,
+                    void *stream);
+
 /* ---- the supervised update on M given observations: targets from outside (a search: expert iteration) ----
  * loss = (1/M) sum_m w_m (pi_coef CE_m + vf_coef (V_m - v*_m)^2),  CE_m = -sum_i p_i logsoftmax_head(i)(logits_m)_i, with
  * p = target_pi[m][0..4] (entries 0-1 the flag head, 2-4 the direction head; the caller makes each head's mass 1, or 0 to mask the
