@@ -191,8 +191,7 @@ __global__ __launch_bounds__(EG_NT) void k_endgame_lookup(int M, EgGeo g, EgLook
         else       { ok = ok && !((Mo >> k) & 1) && c != 0;     Mo |= 1 << k; no++; po |= (u64)c << (8 * (k - 1)); }
     }
     ok = ok && na >= 1 && no >= 1 && na <= g.K && no <= g.K && na + no <= g.T;   // a cube number twice on a side: not a position
-    int d = (int)B.dice[m];
-    d = d < 1 ? 1 : d > 6 ? 6 : d;
+    const int d = la_dice((int)B.dice[m]);
     const float ninf = -__builtin_inff();
     float q[6] = {ninf, ninf, ninf, ninf, ninf, ninf}, val = 0.0f;
     int best = 0;

@@ -1,6 +1,7 @@
 // ewn_lookahead_stages.hip -- the two ends of ewn_predict_lookahead's tree as kernels of their own (C ABI: ewn_lookahead_expand,
 // ewn_lookahead_reduce).  expand writes every (agent move, reply) tuple's b2 under the six d2 out as observations, with a
-// kind byte per tuple; reduce folds a value per such observation back into Q and the action, 4k's phase (c) operation for operation.
+// kind byte per tuple; reduce folds a value per such observation back into Q and the action.  Both read the tree through the helpers
+// k_predict_lookahead reads it through (ewn_lookahead.hpp: la_observation, la_root, la_fold), so the chain is that kernel's arithmetic.
 // Between them the caller evaluates the leaves with what it likes: the plain critic (ewn_predict_policy's value: the chain then IS
 // ewn_predict_lookahead) or ewn_predict_lookahead itself (its q rows: a two-move lookahead).  No network runs here.
 #include "ewn_lookahead.hpp"
@@ -19,24 +20,6 @@
 struct LsExpandBuf { const int8_t *boards; const int8_t *dice; int8_t *leaf_boards; int8_t *leaf_dice; int8_t *kind; };
 struct LsReduceBuf { const int8_t *boards; const int8_t *dice; const int8_t *kind; const float *leaf; int8_t *actions; float *q; };
 
-// the observation into LDS, as k_predict_lookahead reads it: board -> base, cube positions, presence masks (wave-uniform).  Returns
-// whether the row is searched: not already over (check_win) and an agent cube on the board
-template <int S>
-EWN_DEV bool ls_observation(const int8_t *boards, size_t m, int lane, int8_t *base, uint8_t *pos, int &PA, int &PO)
-{
-    constexpr int CELLS = S * S;
-    static_assert(CELLS <= 64, "one lane per cell");
-    const int cell = lane < CELLS ? (int)boards[m * CELLS + lane] : 0;
-    base[lane] = (int8_t)cell;
-    if (lane < 16) pos[lane] = 0xFFu;
-    __builtin_amdgcn_wave_barrier();
-    if (cell != 0 && cell >= -6 && cell <= 6) pos[cell > 0 ? cell : 8 - cell] = (uint8_t)lane;
-    __builtin_amdgcn_wave_barrier();
-    const u32 have = (u32)__builtin_amdgcn_ballot_w64(lane < 16 && pos[lane & 15] != 0xFFu);
-    PA = (int)(have & 0x7Eu); PO = (int)((have >> 8) & 0x7Eu);
-    return !(PA == 0 || PO == 0 || base[0] < 0 || base[CELLS - 1] > 0);
-}
-
 // A tuple's record: lo = kind | src0 << 8 | dst0 << 16 | cube0 << 24 (the agent's move), hi = src1 | dst1 << 8 | cube1 << 16 (the reply,
 // cube1 = -k as a byte); all zero unless kind == 2.  Every one of the 648 rows of the observation is stored on every trip.
 template <int S>
@@ -53,9 +36,8 @@ __global__ __launch_bounds__(LS_NT) void k_lookahead_expand(int M, LsExpandBuf B
     for (int m0 = (int)blockIdx.x * (LS_NT / 64) + wave; m0 < M; m0 += (int)gridDim.x * (LS_NT / 64)) {   // wave-uniform
         const size_t m = (size_t)m0;
         int PA, PO;
-        const bool live = ls_observation<S>(B.boards, m, lane, base, pos, PA, PO);
-        int d = (int)B.dice[m];
-        d = d < 1 ? 1 : d > 6 ? 6 : d;
+        const bool live = la_observation<S, 64>(B.boards + m * CELLS, lane, base, pos, PA, PO);
+        const int d = la_dice((int)B.dice[m]);
         const int c0 = live ? la_find(0, d, PA) : 0, c1 = live ? la_find(1, d, PA) : 0;
         #pragma unroll
         for (int half = 0; half < 2; half++) {
@@ -105,11 +87,12 @@ __global__ __launch_bounds__(LS_NT) void k_lookahead_expand(int M, LsExpandBuf B
     }
 }
 
-// 4k's phase (c) on leaf values handed in: W per tuple, R per (root, d1), Q per root, the pick.  WIDTH entries per leaf row, the row's
-// value their maximum.  The roots are read off the observation again; `kind` only selects among values, it never indexes.
+// 4k's phase (c) on leaf values handed in: W per tuple, then la_fold (R per (root, d1), Q per root, the pick).  WIDTH entries per leaf
+// row, the row's value their maximum.  The roots are read off the observation again; `kind` only selects among values, it never indexes.
 template <int S, int WIDTH>
 __global__ __launch_bounds__(LS_NT) void k_lookahead_reduce(int M, float tv, LsReduceBuf B)
 {
+    constexpr int CELLS = S * S;
     __shared__ __attribute__((aligned(16))) int8_t lds[(LS_NT / 64) * LS_REDUCE_WAVE];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     int8_t *base = lds + wave * LS_REDUCE_WAVE;
@@ -121,18 +104,10 @@ __global__ __launch_bounds__(LS_NT) void k_lookahead_reduce(int M, float tv, LsR
     for (int m0 = (int)blockIdx.x * (LS_NT / 64) + wave; m0 < M; m0 += (int)gridDim.x * (LS_NT / 64)) {   // wave-uniform
         const size_t m = (size_t)m0;
         int PA, PO;
-        const bool live = ls_observation<S>(B.boards, m, lane, base, pos, PA, PO);
-        int d = (int)B.dice[m];
-        d = d < 1 ? 1 : d > 6 ? 6 : d;
-        // a row that is already over (check_win) or has no agent cube: action (0, 0), every Q -inf
-        if (!live) {
-            if (lane < 2) B.actions[m * 2 + lane] = 0;
-            if (B.q && lane < 6) B.q[m * 6 + lane] = -inf;
-            __builtin_amdgcn_wave_barrier();                   // base and pos are read: the next trip may overwrite them
-            continue;
-        }
-        const int c0 = la_find(0, d, PA), c1 = la_find(1, d, PA);   // both flags name one cube unless the dice's cube is gone (c1 == c0)
-        auto searched = [&](int root) { return root >= 3 && c1 == c0 ? root - 3 : root; };   // ... then roots 3 .. 5 are roots 0 .. 2
+        const bool live = la_observation<S, 64>(B.boards + m * CELLS, lane, base, pos, PA, PO);
+        const int d = la_dice((int)B.dice[m]);
+        if (!live) { la_row_over(B.actions, B.q, m, lane); continue; }
+        const int c0 = la_find(0, d, PA), c1 = la_find(1, d, PA);
 
         // W per tuple: the mean over d2 of the row's value, in d2 order
         #pragma unroll
@@ -157,52 +132,14 @@ __global__ __launch_bounds__(LS_NT) void k_lookahead_reduce(int M, float tv, LsR
             }
         }
         __builtin_amdgcn_wave_barrier();
-        // R per (root, d1): the minimum over the replies of the (at most two) cubes d1 selects; a non-terminal b1 always has a reply
-        if (lane < 36) {
-            const int root = searched(lane / 6), d1 = lane % 6 + 1;
-            const LaRoot R = la_root<S>(base, pos, PA, PO, c0, c1, root);
-            float r = 0.0f;
-            if (R.code == 2) {
-                const float *wa = Wt + root * LA_REPLIES + 3 * (la_find(0, d1, R.PO1) - 1), *wb = Wt + root * LA_REPLIES + 3 * (la_find(1, d1, R.PO1) - 1);
-                r = wa[0];
-                r = wa[1] < r ? wa[1] : r; r = wa[2] < r ? wa[2] : r;
-                r = wb[0] < r ? wb[0] : r; r = wb[1] < r ? wb[1] : r; r = wb[2] < r ? wb[2] : r;
-            }
-            Rt[lane] = r;
-        }
-        __builtin_amdgcn_wave_barrier();
-        // Q per root: the mean over d1, in d1 order
-        if (lane < 6) {
-            const int root = searched(lane);
-            const LaRoot R = la_root<S>(base, pos, PA, PO, c0, c1, root);
-            const float *r = Rt + 6 * lane;
-            float qv = (((((r[0] + r[1]) + r[2]) + r[3]) + r[4]) + r[5]) * (1.0f / 6.0f);
-            qv = R.code == 0 ? -inf : R.code == 1 ? tv : qv;
-            Qt[lane] = qv;
-            if (B.q) B.q[m * 6 + lane] = qv;
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (lane == 0) {
-            int best = 0;
-            float qb = Qt[0];
-            #pragma unroll
-            for (int i = 1; i < 6; i++) { const float qi = Qt[i]; if (qi > qb) { qb = qi; best = i; } }
-            B.actions[m * 2] = (int8_t)(best / 3); B.actions[m * 2 + 1] = (int8_t)(best % 3);
-        }
-        __builtin_amdgcn_wave_barrier();                       // this trip's LDS is read: the next may overwrite it
+        la_fold<S>(base, pos, PA, PO, c0, c1, Wt, Rt, Qt, tv, B.actions, B.q, m, lane);
     }
-}
-
-static inline unsigned ls_blocks(int M)
-{
-    const int need = (M - 1) / (LS_NT / 64) + 1;
-    return (unsigned)(need < LS_MAX_BLOCKS ? need : LS_MAX_BLOCKS);
 }
 
 template <class Kern, class... Args>
 static int ls_launch(Kern kern, int M, hipStream_t s, const Args &...args)
 {
-    return pol_launch_kernel(kern, ls_blocks(M), LS_NT, 0, 64 * 1024, POL_LDS_MAX, s, M, args...);
+    return pol_launch_kernel(kern, la_blocks(M, LS_NT / 64, LS_MAX_BLOCKS), LS_NT, 0, 64 * 1024, POL_LDS_MAX, s, M, args...);
 }
 
 // ewn_predict_lookahead's order of refusals: arguments, geometry, the empty batch, pointers; then the values -- all before the launch

@@ -10,7 +10,8 @@
 //   action    = the first maximum of Q in (f, r) order (strict >, as pol_pick_*)
 // The dice only SELECTS among replies: a root has at most 6 cubes x 3 directions = 18 distinct replies, an observation 6 x 18 = 108 distinct
 // b2, each evaluated under six d2: at most 648 columns of the value net, 21 MFMA tiles.  The leaf arithmetic is ewn_predict_policy's
-// (mlp3_pack_fwd's image of net 1, pol_obs_operand on a zero-padded slot, mlp3_forward<S, 1>).
+// (mlp3_pack_fwd's image of net 1, pol_obs_operand on a zero-padded slot, mlp3_forward<S, 1>).  The observation in LDS, the roots
+// and the fold of W into Q and the action are ewn_lookahead.hpp's helpers, the ones ewn_lookahead_stages.hip calls.
 #include "ewn_lookahead.hpp"
 
 #define LA_NT 256            // threads per block: four waves, one observation each per trip
@@ -39,8 +40,9 @@ template <int S> struct LaGeo {
 struct LaBuf { const int8_t *boards; const int8_t *dice; const float *params; int8_t *actions; float *q; };
 
 // Everything is per wave; nothing after the pack crosses a wave, so there is no block barrier in the loop.  Phases per observation:
-// (a) lanes enumerate the 108 tuples (two per lane) and write each distinct non-terminal b2 into the next free leaf slot (ballot ranks);
-// (b) the value net over tiles of 32 columns, column = 6 slot + d2 - 1; (c) W per tuple, R per (root, d1), Q per root, the pick, the stores.
+// (a) lanes enumerate the 108 tuples (two per lane) and write each distinct non-terminal b2 into the next free leaf slot (ballot
+// ranks); (b) the value net over tiles of 32 columns, column = 6 slot + d2 - 1; (c) W per tuple, then la_fold: R per (root, d1), Q per
+// root, the pick, the stores.
 template <int S>
 __global__ __launch_bounds__(LA_NT, 1) void k_predict_lookahead(int M, float tv, LaBuf B)
 {
@@ -62,26 +64,11 @@ __global__ __launch_bounds__(LA_NT, 1) void k_predict_lookahead(int M, float tv,
     #pragma unroll 1
     for (int m0 = (int)blockIdx.x * P::NW + wave; m0 < M; m0 += (int)gridDim.x * P::NW) {   // wave-uniform
         const size_t m = (size_t)m0;
-        // ---- the observation: board -> base (zero past the board), cube positions, presence masks (all wave-uniform)
-        const int cell = lane < CELLS ? (int)B.boards[m * CELLS + lane] : 0;
-        int d = (int)B.dice[m];
-        d = d < 1 ? 1 : d > 6 ? 6 : d;
-        if (lane < STR) base[lane] = (int8_t)cell;
-        if (lane < 16) pos[lane] = 0xFFu;
-        __builtin_amdgcn_wave_barrier();
-        if (cell != 0 && cell >= -6 && cell <= 6) pos[cell > 0 ? cell : 8 - cell] = (uint8_t)lane;
-        __builtin_amdgcn_wave_barrier();
-        const u32 have = (u32)__builtin_amdgcn_ballot_w64(lane < 16 && pos[lane & 15] != 0xFFu);
-        const int PA = (int)(have & 0x7Eu), PO = (int)((have >> 8) & 0x7Eu);
-        // a row that is already over (check_win) or has no agent cube: action (0, 0), every Q -inf
-        if (PA == 0 || PO == 0 || base[0] < 0 || base[CELLS - 1] > 0) {
-            if (lane < 2) B.actions[m * 2 + lane] = 0;
-            if (B.q && lane < 6) B.q[m * 6 + lane] = -inf;
-            __builtin_amdgcn_wave_barrier();                   // base and pos are read: the next trip may overwrite them
-            continue;
-        }
-        const int c0 = la_find(0, d, PA), c1 = la_find(1, d, PA);   // both flags name one cube unless the dice's cube is gone (c1 == c0)
-        auto searched = [&](int root) { return root >= 3 && c1 == c0 ? root - 3 : root; };   // ... then roots 3 .. 5 are roots 0 .. 2
+        int PA, PO;
+        const int d = la_dice((int)B.dice[m]);
+        const bool live = la_observation<S, STR>(B.boards + m * CELLS, lane, base, pos, PA, PO);
+        if (!live) { la_row_over(B.actions, B.q, m, lane); continue; }
+        const int c0 = la_find(0, d, PA), c1 = la_find(1, d, PA);
 
         // ---- (a) tuple t = lane + 64 half: the reply of cube k in direction e to root `root`
         int mt[2];
@@ -90,7 +77,7 @@ __global__ __launch_bounds__(LA_NT, 1) void k_predict_lookahead(int M, float tv,
         for (int half = 0; half < 2; half++) {
             const int t = lane + 64 * half, root = t / LA_REPLIES, k = (t % LA_REPLIES) / 3 + 1, e = t % 3;
             mt[half] = LA_NONE; src0[half] = dst0[half] = cub0[half] = src1[half] = dst1[half] = cub1[half] = 0;
-            if (t < LA_TUPLES && searched(root) == root) {
+            if (t < LA_TUPLES && la_searched(root, c0, c1) == root) {
                 const LaRoot R = la_root<S>(base, pos, PA, PO, c0, c1, root);
                 if (R.code == 2 && ((R.PO1 >> k) & 1)) {
                     const int s1 = pos[8 + k], x1 = s1 / S, y1 = s1 % S;
@@ -154,39 +141,7 @@ __global__ __launch_bounds__(LA_NT, 1) void k_predict_lookahead(int M, float tv,
             }
         }
         __builtin_amdgcn_wave_barrier();
-        // R per (root, d1): the minimum over the replies of the (at most two) cubes d1 selects; a non-terminal b1 always has a reply
-        if (lane < 36) {
-            const int root = searched(lane / 6), d1 = lane % 6 + 1;
-            const LaRoot R = la_root<S>(base, pos, PA, PO, c0, c1, root);
-            float r = 0.0f;
-            if (R.code == 2) {
-                const float *wa = Wt + root * LA_REPLIES + 3 * (la_find(0, d1, R.PO1) - 1), *wb = Wt + root * LA_REPLIES + 3 * (la_find(1, d1, R.PO1) - 1);
-                r = wa[0];
-                r = wa[1] < r ? wa[1] : r; r = wa[2] < r ? wa[2] : r;
-                r = wb[0] < r ? wb[0] : r; r = wb[1] < r ? wb[1] : r; r = wb[2] < r ? wb[2] : r;
-            }
-            Rt[lane] = r;
-        }
-        __builtin_amdgcn_wave_barrier();
-        // Q per root: the mean over d1, in d1 order
-        if (lane < 6) {
-            const int root = searched(lane);
-            const LaRoot R = la_root<S>(base, pos, PA, PO, c0, c1, root);
-            const float *r = Rt + 6 * lane;
-            float qv = (((((r[0] + r[1]) + r[2]) + r[3]) + r[4]) + r[5]) * (1.0f / 6.0f);
-            qv = R.code == 0 ? -inf : R.code == 1 ? tv : qv;
-            Qt[lane] = qv;
-            if (B.q) B.q[m * 6 + lane] = qv;
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (lane == 0) {
-            int best = 0;
-            float qb = Qt[0];
-            #pragma unroll
-            for (int i = 1; i < 6; i++) { const float qi = Qt[i]; if (qi > qb) { qb = qi; best = i; } }
-            B.actions[m * 2] = (int8_t)(best / 3); B.actions[m * 2 + 1] = (int8_t)(best % 3);
-        }
-        __builtin_amdgcn_wave_barrier();                       // this trip's LDS is read: the next may overwrite it
+        la_fold<S>(base, pos, PA, PO, c0, c1, Wt, Rt, Qt, tv, B.actions, B.q, m, lane);
     }
 }
 
@@ -195,9 +150,7 @@ static int la_launch(int M, float tv, const LaBuf &lb, hipStream_t s)
 {
     constexpr size_t lds = LaGeo<S>::lds_bytes();
     static_assert(lds <= POL_LDS_MAX, "the value net's image + four waves' slots and tables must fit the CU's LDS");
-    const int need = (M - 1) / LaGeo<S>::NW + 1;
-    return pol_launch_kernel(k_predict_lookahead<S>, (unsigned)(need < LA_MAX_BLOCKS ? need : LA_MAX_BLOCKS), LA_NT, lds, 64 * 1024, POL_LDS_MAX, s,
-                             M, tv, lb);
+    return pol_launch_kernel(k_predict_lookahead<S>, la_blocks(M, LaGeo<S>::NW, LA_MAX_BLOCKS), LA_NT, lds, 64 * 1024, POL_LDS_MAX, s, M, tv, lb);
 }
 
 // ewn_predict_policy's order of refusals: arguments, geometry, the empty batch, pointers; then the terminal value -- all before the launch

@@ -5,7 +5,8 @@
 // no random number enters: the chance nodes are a stratified sample of the dice (the least visited dice first).
 //
 // A wave per tree.  Per-edge state (N, W, P, kind, child[.][d'], cn[.][d']) of edge a is read and written by lane a alone, in every
-// kernel: a tree's values never travel between lanes through global memory, only through LDS and cross-lane reads.
+// kernel: a tree's values never travel between lanes through global memory, only through LDS and cross-lane reads.  The node's board
+// goes to LDS by ewn_lookahead.hpp's la_observation, so that la_find and la_root apply unchanged.
 #include "ewn_lookahead.hpp"
 #include <climits>
 
@@ -64,25 +65,6 @@ EWN_DEV PuTree pu_tree(uint8_t *trees, size_t m, const PuLayout &L)
     return T;
 }
 
-// A board into LDS the way ewn_lookahead_stages.hip's ls_observation does it (board -> base, cube positions, presence masks), so
-// that la_find and la_root apply unchanged.  Returns whether the position is searched: not over, cubes on both sides.
-template <int S>
-EWN_DEV bool pu_observation(const int8_t *board, int lane, int8_t *base, uint8_t *pos, int &PA, int &PO)
-{
-    constexpr int CELLS = S * S;
-    static_assert(CELLS <= 64, "one lane per cell");
-    __builtin_amdgcn_wave_barrier();                           // what was there is read
-    const int cell = lane < CELLS ? (int)board[lane] : 0;
-    base[lane] = (int8_t)cell;
-    if (lane < 16) pos[lane] = 0xFFu;
-    __builtin_amdgcn_wave_barrier();
-    if (cell != 0 && cell >= -6 && cell <= 6) pos[cell > 0 ? cell : 8 - cell] = (uint8_t)lane;
-    __builtin_amdgcn_wave_barrier();
-    const u32 have = (u32)__builtin_amdgcn_ballot_w64(lane < 16 && pos[lane & 15] != 0xFFu);
-    PA = (int)(have & 0x7Eu); PO = (int)((have >> 8) & 0x7Eu);
-    return !(PA == 0 || PO == 0 || base[0] < 0 || base[CELLS - 1] > 0);
-}
-
 // lane a's edge of the node in LDS under dice d: kind and the move (lanes 6 .. 63: kind 0)
 struct PuEdge { int kind, src, dst, cube; bool one; };         // one: both flags name one cube
 
@@ -139,9 +121,9 @@ __global__ __launch_bounds__(PU_NT) void k_puct_begin(int M, int sims, PuLayout 
         if (threadIdx.x < 64) {
             const PuTree T = pu_tree(B.tree, m, L);
             int PA, PO;
-            const bool live = pu_observation<S>(B.boards + m * CELLS, lane, lds, pos, PA, PO);
-            int d = (int)B.dice[m];
-            d = d < 1 ? 1 : d > 6 ? 6 : d;
+            __builtin_amdgcn_wave_barrier();                   // what was there is read
+            const bool live = la_observation<S, 64>(B.boards + m * CELLS, lane, lds, pos, PA, PO);
+            const int d = la_dice((int)B.dice[m]);
             if (lane < CELLS) {
                 T.board[lane] = lds[lane];
                 B.leaf_boards[m * CELLS + lane] = live ? lds[lane] : (int8_t)0;
@@ -179,7 +161,8 @@ __global__ __launch_bounds__(PU_NT) void k_puct_advance(int M, int sims, float c
         if (ok) {
             if (pending >= 0) {                                // ---- evaluation: priors from the logits, then backup of v
                 int PA, PO;
-                pu_observation<S>(T.board + (size_t)pending * CELLS, lane, base, pos, PA, PO);
+                __builtin_amdgcn_wave_barrier();               // what was there is read
+                la_observation<S, 64>(T.board + (size_t)pending * CELLS, lane, base, pos, PA, PO);
                 if (PA != 0 && PO != 0) {
                     const PuEdge E = pu_edge<S>(base, pos, PA, PO, (int)T.dice[pending], lane);
                     const float *lg = B.logits + m * 5;
@@ -212,7 +195,8 @@ __global__ __launch_bounds__(PU_NT) void k_puct_advance(int M, int sims, float c
                 #pragma unroll 1
                 for (int step = 0; step < L.nodes; step++) {   // a path holds at most `count` nodes
                     int PA, PO;
-                    pu_observation<S>(T.board + (size_t)j * CELLS, lane, base, pos, PA, PO);
+                    __builtin_amdgcn_wave_barrier();           // what was there is read
+                    la_observation<S, 64>(T.board + (size_t)j * CELLS, lane, base, pos, PA, PO);
                     if (PA == 0 || PO == 0) break;
                     const PuEdge E = pu_edge<S>(base, pos, PA, PO, (int)T.dice[j], lane);
                     const int nn = lane < 6 ? T.n[6 * j + lane] : 0;
@@ -332,12 +316,6 @@ __global__ __launch_bounds__(PU_NT) void k_puct_result(int S, int M, PuResultBuf
     }
 }
 
-static inline unsigned pu_blocks(int M, int per_block)
-{
-    const int need = (M - 1) / per_block + 1;
-    return (unsigned)(need < PU_MAX_BLOCKS ? need : PU_MAX_BLOCKS);
-}
-
 // ewn_lookahead_expand's order of refusals: arguments, geometry, the empty batch, pointers; then the values -- all before the launch
 static inline int pu_refuse(int board_size, int cube_layer, int M)
 {
@@ -363,7 +341,7 @@ int ewn_puct_begin(int board_size, int cube_layer, int M, int sims, const int8_t
     const PuLayout L = pu_layout(board_size, sims);
     PuBeginBuf b = { boards, dice, (uint8_t *)tree, leaf_boards, leaf_dice };
     hipStream_t s = (hipStream_t)stream;
-    const unsigned blocks = pu_blocks(M, 1);
+    const unsigned blocks = la_blocks(M, 1, PU_MAX_BLOCKS);
     return board_size == 5 ? pol_launch_kernel(k_puct_begin<5>, blocks, PU_NT, 0, 64 * 1024, POL_LDS_MAX, s, M, sims, L, b)
                            : pol_launch_kernel(k_puct_begin<7>, blocks, PU_NT, 0, 64 * 1024, POL_LDS_MAX, s, M, sims, L, b);
 }
@@ -380,7 +358,7 @@ int ewn_puct_advance(int board_size, int cube_layer, int M, int sims, float c_pu
     const float inv_tv = 1.0f / terminal_value;
     PuAdvanceBuf b = { (uint8_t *)tree, logits, value, leaf_boards, leaf_dice };
     hipStream_t s = (hipStream_t)stream;
-    const unsigned blocks = pu_blocks(M, PU_NT / 64);
+    const unsigned blocks = la_blocks(M, PU_NT / 64, PU_MAX_BLOCKS);
     return board_size == 5 ? pol_launch_kernel(k_puct_advance<5>, blocks, PU_NT, 0, 64 * 1024, POL_LDS_MAX, s, M, sims, c_puct, inv_tv, L, b)
                            : pol_launch_kernel(k_puct_advance<7>, blocks, PU_NT, 0, 64 * 1024, POL_LDS_MAX, s, M, sims, c_puct, inv_tv, L, b);
 }
@@ -393,5 +371,5 @@ int ewn_puct_result(int board_size, int cube_layer, int M, const void *tree, int
     if (!tree || !actions) return EWN_ENULL;
     if ((uintptr_t)tree & 3) return EWN_EINVAL;
     PuResultBuf b = { (uint8_t *)tree, actions, visits, q, value };
-    return pol_launch_kernel(k_puct_result, pu_blocks(M, PU_NT / 64), PU_NT, 0, 64 * 1024, POL_LDS_MAX, (hipStream_t)stream, board_size, M, b);
+    return pol_launch_kernel(k_puct_result, la_blocks(M, PU_NT / 64, PU_MAX_BLOCKS), PU_NT, 0, 64 * 1024, POL_LDS_MAX, (hipStream_t)stream, board_size, M, b);
 }

@@ -13,7 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .vec_env import _describe, _policy_input, _ptr, _require_gpu, _stream
+from .vec_env import _describe, _lookahead_shape, _policy_input, _ptr, _require_gpu, _same_gpu, _stream
 
 
 class EndgameTable:
@@ -72,19 +72,12 @@ class EndgameTable:
         table's GPU; host arrays are copied over; anything else raises ValueError before a launch."""
         who = "EndgameTable.lookup"
         S, dev = self.board_size, self.table.device
-        shp = tuple(boards.shape) if isinstance(boards, torch.Tensor) else np.asarray(boards).shape
-        if len(shp) == 2:
-            shp = (1,) + tuple(shp)
-        if len(shp) != 3 or shp[1] != shp[2]:
-            raise ValueError("%s: boards must have shape [S, S] or [M, S, S], got %s" % (who, list(shp)))
-        if shp[1] != S:
-            raise ValueError("%s: boards of shape %s, the table is for %dx%d" % (who, list(shp), S, S))
-        M = int(shp[0])
+        M, Sb, _ = _lookahead_shape(who, boards)
+        if Sb != S:
+            raise ValueError("%s: boards of shape %s, the table is for %dx%d" % (who, [M, Sb, Sb], S, S))
         b = _policy_input("boards", boards, torch.int8, (M, S, S), dev, who=who)
         d = _policy_input("dice", dice, torch.int8, (M,), dev, who=who)
-        for name, t in (("table", self.table), ("boards", b), ("dice", d)):
-            if not (t.is_cuda and t.device == dev):
-                raise ValueError("%s: %s must live on the GPU that holds the table (%s), got %s" % (who, name, dev, _describe(t)))
+        _same_gpu(who, dev, "the table", (("table", self.table), ("boards", b), ("dice", d)))
         acts = torch.zeros((M, 2), dtype=torch.int8, device=dev)
         covered = torch.zeros(M, dtype=torch.bool, device=dev)
         q = torch.zeros((M, 2, 3), dtype=torch.float32, device=dev) if return_q else None

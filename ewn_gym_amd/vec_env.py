@@ -660,21 +660,10 @@ def predict_policy(boards, dice, params, deterministic=True, key=0, obs_id=None,
     given, else from a hash of (key, obs_id[m]) -- obs_id None: m.  Tensors are read in place and must be contiguous device tensors of
     the kernel's dtype (int8 observations, float32 params / uniforms, int32 or uint32 obs_id); host arrays are copied over.  Anything
     else raises ValueError before a launch."""
+    who = "predict_policy"
     lib = _lib.load()
-    shp = tuple(boards.shape) if isinstance(boards, torch.Tensor) else np.asarray(boards).shape
-    if len(shp) == 2:
-        shp = (1,) + tuple(shp)
-    if len(shp) != 3 or shp[1] != shp[2]:
-        raise ValueError("predict_policy: boards must have shape [S, S] or [M, S, S], got %s" % (list(shp),))
-    M, S = int(shp[0]), int(shp[1])
-    P = lib.ewn_policy_param_count(S, int(cube_layer))
-    if P < 0:
-        raise ValueError("predict_policy: no policy network for %dx%d boards with cube_layer %d (served: cube_layer 3 on 5x5 and 7x7)" % (
-            S, S, cube_layer))
-    if not (isinstance(params, torch.Tensor) and params.dtype == torch.float32 and params.is_contiguous() and params.numel() == P):
-        raise ValueError("predict_policy: params must be a contiguous float32 tensor of %d elements (the %dx%d actor-critic), got %s" % (
-            P, S, S, _describe(params)))
-    dev = params.device
+    M, S, P = _lookahead_shape(who, boards, cube_layer)
+    dev = _policy_params(who, params, P, S)
     b = _policy_input("boards", boards, torch.int8, (M, S, S), dev)
     d = _policy_input("dice", dice, torch.int8, (M,), dev)
     u = None if uniforms is None else _policy_input("uniforms", uniforms, torch.float32, (M, 5), dev)
@@ -685,9 +674,7 @@ def predict_policy(boards, dice, params, deterministic=True, key=0, obs_id=None,
         if not isinstance(obs_id, torch.Tensor):
             obs_id = np.asarray(obs_id).astype(np.uint32).view(np.int32)
         ids = _policy_input("obs_id", obs_id, torch.int32, (M,), dev)
-    for name, t in (("params", params), ("boards", b), ("dice", d), ("uniforms", u), ("obs_id", ids)):
-        if t is not None and not (t.is_cuda and t.device == dev):
-            raise ValueError("predict_policy: %s must live on the GPU that holds params (%s), got %s" % (name, dev, _describe(t)))
+    _same_gpu(who, dev, "params", (("params", params), ("boards", b), ("dice", d), ("uniforms", u), ("obs_id", ids)))
     acts = torch.zeros((M, 2), dtype=torch.int8, device=dev)
     logits = torch.zeros((M, 5), dtype=torch.float32, device=dev) if return_logits else None
     value = torch.zeros(M, dtype=torch.float32, device=dev) if return_value else None
@@ -699,33 +686,48 @@ def predict_policy(boards, dice, params, deterministic=True, key=0, obs_id=None,
     return out[0] if len(out) == 1 else out
 
 
-def _lookahead_shape(who, boards, cube_layer):
-    """(M, S) of boards [S, S] or [M, S, S]; ValueError where there is no policy network for the geometry"""
+def _lookahead_shape(who, boards, cube_layer=None):
+    """(M, S, P) of boards [S, S] or [M, S, S], P the policy network's parameter count; ValueError where there is no policy network for
+    the geometry.  cube_layer None: any board size, P None"""
     shp = tuple(boards.shape) if isinstance(boards, torch.Tensor) else np.asarray(boards).shape
     if len(shp) == 2:
         shp = (1,) + tuple(shp)
     if len(shp) != 3 or shp[1] != shp[2]:
         raise ValueError("%s: boards must have shape [S, S] or [M, S, S], got %s" % (who, list(shp)))
     M, S = int(shp[0]), int(shp[1])
-    if _lib.load().ewn_policy_param_count(S, int(cube_layer)) < 0:
+    P = None if cube_layer is None else _lib.load().ewn_policy_param_count(S, int(cube_layer))
+    if P is not None and P < 0:
         raise ValueError("%s: no policy network for %dx%d boards with cube_layer %d (served: cube_layer 3 on 5x5 and 7x7)" % (
             who, S, S, cube_layer))
-    return M, S
+    return M, S, P
+
+
+def _policy_params(who, params, P, S):
+    """params is the flat fp32 vector of the SxS actor-critic, P elements -> its device, where everything else has to live"""
+    if not (isinstance(params, torch.Tensor) and params.dtype == torch.float32 and params.is_contiguous() and params.numel() == P):
+        raise ValueError("%s: params must be a contiguous float32 tensor of %d elements (the %dx%d actor-critic), got %s" % (
+            who, P, S, S, _describe(params)))
+    return params.device
+
+
+def _same_gpu(who, dev, holder, named):
+    """every tensor of named = [(name, tensor or None)] lives on dev, a GPU: the one that holds `holder`"""
+    for name, t in named:
+        if t is not None and not (t.is_cuda and t.device == dev):
+            raise ValueError("%s: %s must live on the GPU that holds %s (%s), got %s" % (who, name, holder, dev, _describe(t)))
 
 
 def _stage_inputs(who, named, cube_layer):
     """the inputs of a lookahead stage, checked as predict_lookahead checks its own: named = [(name, x, dtype, shape of (M, S))], boards
     first.  The device is the first tensor's (host arrays are copied there), and it must be a GPU."""
-    M, S = _lookahead_shape(who, named[0][1], cube_layer)
-    if M * 648 > 2 ** 31 - 1:
-        raise ValueError("%s: %d observations are %d leaf rows, more than 2^31 - 1: call in chunks" % (who, M, M * 648))
+    M, S, _ = _lookahead_shape(who, named[0][1], cube_layer)
+    if M * LA_ROWS > 2 ** 31 - 1:
+        raise ValueError("%s: %d observations are %d leaf rows, more than 2^31 - 1: call in chunks" % (who, M, M * LA_ROWS))
     first = next((x for _, x, _, _ in named if isinstance(x, torch.Tensor)), None)
     dev = first.device if first is not None else torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() \
         else torch.device("cpu")
     out = [_policy_input(name, x, dtype, shape(M, S), dev, who=who) for name, x, dtype, shape in named]
-    for (name, _, _, _), t in zip(named, out):
-        if not (t.is_cuda and t.device == dev):
-            raise ValueError("%s: %s must live on the GPU that holds %s (%s), got %s" % (who, name, named[0][0], dev, _describe(t)))
+    _same_gpu(who, dev, named[0][0], [(name, t) for (name, _, _, _), t in zip(named, out)])
     return M, S, dev, out
 
 
@@ -738,9 +740,9 @@ def lookahead_expand(boards, dice, cube_layer=3):
     argument checks."""
     M, S, dev, (b, d) = _stage_inputs("lookahead_expand", [("boards", boards, torch.int8, lambda M, S: (M, S, S)),
                                                            ("dice", dice, torch.int8, lambda M, S: (M,))], cube_layer)
-    lb = torch.empty((M, 648, S, S), dtype=torch.int8, device=dev)
-    ld = torch.empty((M, 648), dtype=torch.int8, device=dev)
-    kind = torch.empty((M, 108), dtype=torch.int8, device=dev)
+    lb = torch.empty((M, LA_ROWS, S, S), dtype=torch.int8, device=dev)
+    ld = torch.empty((M, LA_ROWS), dtype=torch.int8, device=dev)
+    kind = torch.empty((M, LA_TUPLES), dtype=torch.int8, device=dev)
     with torch.cuda.device(dev):
         check(_lib.load().ewn_lookahead_expand(S, int(cube_layer), M, _ptr(b), _ptr(d), _ptr(lb), _ptr(ld), _ptr(kind), _stream()),
               "ewn_lookahead_expand")
@@ -756,13 +758,13 @@ def lookahead_reduce(boards, dice, kind, leaf, terminal_value=1.0, return_q=Fals
     if not math.isfinite(float(terminal_value)):
         raise ValueError("%s: terminal_value must be finite, got %r" % (who, terminal_value))
     shp = tuple(leaf.shape) if isinstance(leaf, torch.Tensor) else np.asarray(leaf).shape
-    if not (len(shp) in (2, 3) and shp[1] == 648 and (len(shp) == 2 or shp[2] == 6)):
+    if not (len(shp) in (2, 3) and shp[1] == LA_ROWS and (len(shp) == 2 or shp[2] == 6)):
         raise ValueError("%s: leaf must have shape [M, 648] or [M, 648, 6], got %s" % (who, list(shp)))
     width = 6 if len(shp) == 3 else 1
     M, S, dev, (b, d, k, lf) = _stage_inputs(who, [("boards", boards, torch.int8, lambda M, S: (M, S, S)),
                                                   ("dice", dice, torch.int8, lambda M, S: (M,)),
-                                                  ("kind", kind, torch.int8, lambda M, S: (M, 108)),
-                                                  ("leaf", leaf, torch.float32, lambda M, S: (M, 648, width))], cube_layer)
+                                                  ("kind", kind, torch.int8, lambda M, S: (M, LA_TUPLES)),
+                                                  ("leaf", leaf, torch.float32, lambda M, S: (M, LA_ROWS, width))], cube_layer)
     acts = torch.zeros((M, 2), dtype=torch.int8, device=dev)
     q = torch.zeros((M, 2, 3), dtype=torch.float32, device=dev) if return_q else None
     with torch.cuda.device(dev):
@@ -787,27 +789,14 @@ def predict_lookahead(boards, dice, params, terminal_value=1.0, return_q=False, 
         raise ValueError("predict_lookahead: plies must be 1 or 2, got %r" % (plies,))
     if int(chunk) < 1:
         raise ValueError("predict_lookahead: chunk must be at least 1, got %r" % (chunk,))
-    shp = tuple(boards.shape) if isinstance(boards, torch.Tensor) else np.asarray(boards).shape
-    if len(shp) == 2:
-        shp = (1,) + tuple(shp)
-    if len(shp) != 3 or shp[1] != shp[2]:
-        raise ValueError("predict_lookahead: boards must have shape [S, S] or [M, S, S], got %s" % (list(shp),))
-    M, S = int(shp[0]), int(shp[1])
-    P = lib.ewn_policy_param_count(S, int(cube_layer))
-    if P < 0:
-        raise ValueError("predict_lookahead: no policy network for %dx%d boards with cube_layer %d (served: cube_layer 3 on 5x5 and 7x7)" % (
-            S, S, cube_layer))
-    if not (isinstance(params, torch.Tensor) and params.dtype == torch.float32 and params.is_contiguous() and params.numel() == P):
-        raise ValueError("predict_lookahead: params must be a contiguous float32 tensor of %d elements (the %dx%d actor-critic), got %s" % (
-            P, S, S, _describe(params)))
+    who = "predict_lookahead"
+    M, S, P = _lookahead_shape(who, boards, cube_layer)
+    dev = _policy_params(who, params, P, S)
     if not math.isfinite(float(terminal_value)):
         raise ValueError("predict_lookahead: terminal_value must be finite, got %r" % (terminal_value,))
-    dev = params.device
-    b = _policy_input("boards", boards, torch.int8, (M, S, S), dev, who="predict_lookahead")
-    d = _policy_input("dice", dice, torch.int8, (M,), dev, who="predict_lookahead")
-    for name, t in (("params", params), ("boards", b), ("dice", d)):
-        if not (t.is_cuda and t.device == dev):
-            raise ValueError("predict_lookahead: %s must live on the GPU that holds params (%s), got %s" % (name, dev, _describe(t)))
+    b = _policy_input("boards", boards, torch.int8, (M, S, S), dev, who=who)
+    d = _policy_input("dice", dice, torch.int8, (M,), dev, who=who)
+    _same_gpu(who, dev, "params", (("params", params), ("boards", b), ("dice", d)))
     acts = torch.zeros((M, 2), dtype=torch.int8, device=dev)
     q = torch.zeros((M, 2, 3), dtype=torch.float32, device=dev) if return_q else None
     if plies == 2:
@@ -822,12 +811,12 @@ def _predict_lookahead2(lib, S, L, M, b, d, params, tv, acts, q, chunk):
     """predict_lookahead(plies=2) on checked inputs: per chunk of c observations expand -> ewn_predict_lookahead with q on the 648 c
     leaf rows -> reduce at leaf_width 6; the scratch is one allocation per call, every row of it rewritten per chunk"""
     dev = params.device
-    c = max(1, min(chunk, M, (2 ** 31 - 1) // 648))      # a chunk's 648 c leaf rows are counted in an int
-    lb = torch.empty((c * 648, S, S), dtype=torch.int8, device=dev)
-    ld = torch.empty(c * 648, dtype=torch.int8, device=dev)
-    kind = torch.empty((c, 108), dtype=torch.int8, device=dev)
-    la = torch.empty((c * 648, 2), dtype=torch.int8, device=dev)
-    lq = torch.empty((c * 648, 6), dtype=torch.float32, device=dev)
+    c = max(1, min(chunk, M, (2 ** 31 - 1) // LA_ROWS))  # a chunk's 648 c leaf rows are counted in an int
+    lb = torch.empty((c * LA_ROWS, S, S), dtype=torch.int8, device=dev)
+    ld = torch.empty(c * LA_ROWS, dtype=torch.int8, device=dev)
+    kind = torch.empty((c, LA_TUPLES), dtype=torch.int8, device=dev)
+    la = torch.empty((c * LA_ROWS, 2), dtype=torch.int8, device=dev)
+    lq = torch.empty((c * LA_ROWS, 6), dtype=torch.float32, device=dev)
     tvf = C.c_float(tv)
     with torch.cuda.device(dev):
         st = _stream()
@@ -835,7 +824,7 @@ def _predict_lookahead2(lib, S, L, M, b, d, params, tv, acts, q, chunk):
             n = min(c, M - i)
             bi, di, ai, qi = b[i:i + n], d[i:i + n], acts[i:i + n], None if q is None else q[i:i + n]
             check(lib.ewn_lookahead_expand(S, L, n, _ptr(bi), _ptr(di), _ptr(lb), _ptr(ld), _ptr(kind), st), "ewn_lookahead_expand")
-            check(lib.ewn_predict_lookahead(S, L, 648 * n, _ptr(lb), _ptr(ld), _ptr(params), tvf, _ptr(la), _ptr(lq), st), "ewn_predict_lookahead")
+            check(lib.ewn_predict_lookahead(S, L, LA_ROWS * n, _ptr(lb), _ptr(ld), _ptr(params), tvf, _ptr(la), _ptr(lq), st), "ewn_predict_lookahead")
             check(lib.ewn_lookahead_reduce(S, L, n, _ptr(bi), _ptr(di), _ptr(kind), _ptr(lq), 6, tvf, _ptr(ai), _ptr(qi), st),
                   "ewn_lookahead_reduce")
     return acts if q is None else (acts, q)
@@ -879,17 +868,13 @@ def sup_grad(boards, dice, target_pi, target_value, params, weight=None, pi_coef
     argument checks: anything the kernels cannot read in place raises ValueError before a launch.  The step is ewn_a2c_apply."""
     who = "sup_grad"
     lib = _lib.load()
-    M, S = _lookahead_shape(who, boards, cube_layer)
+    M, S, P = _lookahead_shape(who, boards, cube_layer)
     if M < 1:
         raise ValueError("%s: needs at least one observation (a mean over nothing is undefined)" % who)
-    P = lib.ewn_policy_param_count(S, int(cube_layer))
-    if not (isinstance(params, torch.Tensor) and params.dtype == torch.float32 and params.is_contiguous() and params.numel() == P):
-        raise ValueError("%s: params must be a contiguous float32 tensor of %d elements (the %dx%d actor-critic), got %s" % (
-            who, P, S, S, _describe(params)))
+    dev = _policy_params(who, params, P, S)
     for name, v in (("pi_coef", pi_coef), ("vf_coef", vf_coef)):
         if not math.isfinite(float(v)) or float(v) < 0.0:
             raise ValueError("%s: %s must be finite and not negative, got %r" % (who, name, v))
-    dev = params.device
     named = [("boards", _policy_input("boards", boards, torch.int8, (M, S, S), dev, who=who)),
              ("dice", _policy_input("dice", dice, torch.int8, (M,), dev, who=who)),
              ("target_pi", _policy_input("target_pi", target_pi, torch.float32, (M, 5), dev, who=who)),
@@ -903,9 +888,7 @@ def sup_grad(boards, dice, target_pi, target_value, params, weight=None, pi_coef
         raise ValueError("%s: scratch must be a contiguous, 4-byte aligned uint8 tensor of at least %d elements, got %s%s" % (
             who, nscr, _describe(scratch), " at an address that is %d past a multiple of 4" % (scratch.data_ptr() % 4)
             if isinstance(scratch, torch.Tensor) and scratch.data_ptr() % 4 else ""))
-    for name, t in [("params", params)] + named + [("scratch", scratch)]:
-        if t is not None and not (t.is_cuda and t.device == dev):
-            raise ValueError("%s: %s must live on the GPU that holds params (%s), got %s" % (who, name, dev, _describe(t)))
+    _same_gpu(who, dev, "params", [("params", params)] + named + [("scratch", scratch)])
     b, d, tp, tv, w = (t for _, t in named[:5])
     grad = out if out is not None else torch.zeros(P + 8, dtype=torch.float32, device=dev)
     if scratch is None:
@@ -916,6 +899,8 @@ def sup_grad(boards, dice, target_pi, target_value, params, weight=None, pi_coef
     return grad
 
 
+LA_TUPLES = 108        # (agent move, reply) tuples per observation of the lookahead tree (csrc/ewn_lookahead.hpp)
+LA_ROWS = 648          # its leaf rows: a tuple under each of the six d2
 PUCT_LAYOUT = 1        # the version of a PUCT tree's layout (csrc/ewn_puct.hip); begin writes it into every header
 PUCT_MAX_SIMS = 4096
 
@@ -1061,18 +1046,12 @@ def predict_puct(boards, dice, params, sims=64, c_puct=1.5, terminal_value=1.0, 
     sims = _puct_numbers(who, sims, c_puct, terminal_value)
     if int(chunk) < 1:
         raise ValueError("%s: chunk must be at least 1, got %r" % (who, chunk))
-    M, S = _lookahead_shape(who, boards, cube_layer)
+    M, S, P = _lookahead_shape(who, boards, cube_layer)
     L = int(cube_layer)
-    P = lib.ewn_policy_param_count(S, L)
-    if not (isinstance(params, torch.Tensor) and params.dtype == torch.float32 and params.is_contiguous() and params.numel() == P):
-        raise ValueError("%s: params must be a contiguous float32 tensor of %d elements (the %dx%d actor-critic), got %s" % (
-            who, P, S, S, _describe(params)))
-    dev = params.device
+    dev = _policy_params(who, params, P, S)
     b = _policy_input("boards", boards, torch.int8, (M, S, S), dev, who=who)
     d = _policy_input("dice", dice, torch.int8, (M,), dev, who=who)
-    for name, t in (("params", params), ("boards", b), ("dice", d)):
-        if not (t.is_cuda and t.device == dev):
-            raise ValueError("%s: %s must live on the GPU that holds params (%s), got %s" % (who, name, dev, _describe(t)))
+    _same_gpu(who, dev, "params", (("params", params), ("boards", b), ("dice", d)))
     acts = torch.zeros((M, 2), dtype=torch.int8, device=dev)
     visits = torch.zeros((M, 2, 3), dtype=torch.int32, device=dev) if return_visits else None
     q = torch.zeros((M, 2, 3), dtype=torch.float32, device=dev) if return_q else None

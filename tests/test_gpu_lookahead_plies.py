@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 from tests.guarded_alloc import GuardedAllocator  # noqa: E402
-from tests.test_gpu_predict_lookahead import cube_moves, find_cube, tree  # noqa: E402
+from tests.test_gpu_predict_lookahead import boards_of, cube_moves, find_cube, i8, tree  # noqa: E402
 from tests.test_gpu_predict_policy import bits, pool  # noqa: E402
 
 
@@ -24,19 +24,6 @@ def ea():
         pytest.skip("no GPU")
     import ewn_gym_amd
     return ewn_gym_amd
-
-
-def boards_of(S, *specs):
-    """each spec: {(x, y): cube}"""
-    out = np.zeros((len(specs), S, S), np.int8)
-    for i, s in enumerate(specs):
-        for (x, y), v in s.items():
-            out[i, x, y] = v
-    return torch.as_tensor(out).cuda()
-
-
-def i8(*v):
-    return torch.tensor(v, dtype=torch.int8, device="cuda")
 
 
 def cubes(board, player):

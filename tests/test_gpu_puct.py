@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 from tests.guarded_alloc import GuardedAllocator  # noqa: E402
-from tests.test_gpu_predict_lookahead import cube_moves, cubes_of, find_cube  # noqa: E402
+from tests.test_gpu_predict_lookahead import boards_of, cube_moves, cubes_of, find_cube, i8  # noqa: E402
 from tests.test_gpu_predict_policy import bits, make_model, pool  # noqa: E402
 
 F = np.float32
@@ -230,19 +230,6 @@ def pool_run(ea, S, M, sims):
     p = pool(ea, S)
     off = 100 * sims                                           # other observations per budget
     return lockstep(ea, S, p["boards"][off:off + M], p["dice"][off:off + M], p["params"], sims, key=(S, M, sims))
-
-
-def boards_of(S, *specs):
-    """each spec: {(x, y): cube}"""
-    out = np.zeros((len(specs), S, S), np.int8)
-    for i, s in enumerate(specs):
-        for (x, y), v in s.items():
-            out[i, x, y] = v
-    return torch.as_tensor(out).cuda()
-
-
-def i8(*v):
-    return torch.tensor(v, dtype=torch.int8, device="cuda")
 
 
 # ---------------------------------------------------------------- 1. lock step
