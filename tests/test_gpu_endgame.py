@@ -163,8 +163,8 @@ def check_positions(ea, S, K, T, positions, what):
     assert act.shape == (M, 2) and act.dtype == torch.int8 and cov.dtype == torch.bool and q.shape == (M, 2, 3) and val.shape == (M,)
     assert bool(cov.all())
     qk, vk, a = q.cpu().numpy(), val.cpu().numpy(), act.cpu().numpy().astype(np.int64)
-    q64 = np.stack([mod.q(p, dd)[0] for p in positions for dd in range(1, 7)])
-    q32 = np.stack([mod.q(p, dd)[1] for p in positions for dd in range(1, 7)])
+    qs = [mod.q(p, dd) for p in positions for dd in range(1, 7)]
+    q64, q32 = np.stack([x[0] for x in qs]), np.stack([x[1] for x in qs])
     v64 = np.repeat([mod.E(p)[0] for p in positions], 6)
     v32 = np.repeat(np.array([mod.E(p)[1] for p in positions], F32), 6)
     tol = 7 * 2.0 ** -24 * np.repeat([phi(p, S) for p in positions], 6)
@@ -446,17 +446,24 @@ def test_save_and_load(ea, tmp_path):
         ea.EndgameTable.load(path)
 
 
-def test_endgame_agent_on_the_drop_in_env(ea):
-    """64 episodes, every ply: the agent's action is lookup's where covered and the fallback's elsewhere"""
+@pytest.mark.parametrize("S,K,T,episodes", [(5, 2, 4, 64), (7, 2, 3, 16)])
+def test_endgame_agent_on_the_drop_in_env(ea, S, K, T, episodes):
+    """every ply of every episode: the agent's action is lookup's where covered and the fallback's elsewhere.  On 7x7 random play from
+    the opening does not reach the table within the test, so every second episode starts from a sampled position the table covers:
+    the covered plies come from the inputs"""
     from classical_policies import EndgameAgent, RandomAgent
     from envs import EinsteinWuerfeltNichtEnv
-    t = table(ea, 5, 2, 4)
-    env = EinsteinWuerfeltNichtEnv(board_size=5, seed=3)
+    t = table(ea, S, K, T)
+    env = EinsteinWuerfeltNichtEnv(board_size=S, seed=3)
     fallback = RandomAgent(env)
     agent = EndgameAgent(t, fallback)
     plies = exact = 0
-    for ep in range(64):
+    rng = random.Random(S)
+    for ep in range(episodes):
         obs, _ = env.reset(seed=ep)
+        if S != 5 and ep % 2 == 0:
+            env.board[:] = board_of(sample(rng, S, K, T), S)     # in place: obs["board"] is the env's board
+            env._push_board()
         for _ in range(200):
             action, state = agent.predict(obs)
             assert state is None and isinstance(action, np.ndarray) and action.shape == (2,)
@@ -471,9 +478,14 @@ def test_endgame_agent_on_the_drop_in_env(ea):
             if terminated or truncated:
                 break
         assert terminated or truncated
-    print("EndgameAgent: %d plies, %d covered" % (plies, exact))
+    print("EndgameAgent %dx%d: %d plies, %d covered" % (S, S, plies, exact))
     assert exact > 0 and exact < plies
-    bb, dd = mixed_rows(ea, 300)
+    if S == 5:
+        bb, dd = mixed_rows(ea, 300)
+    else:
+        p = pool(ea, S)
+        bb, dd = p["boards"][:300].clone(), p["dice"][:300].clone()
+        bb[::3] = torch.as_tensor(np.stack([board_of(sample(rng, S, K, T), S) for _ in range(100)])).cuda()
     assert torch.equal(agent.policy_fn()(bb, dd, 3), agent.predict_batch(bb, dd))
 
 
@@ -497,27 +509,43 @@ def make_env(ea, N, S=5, key=77):
     return env
 
 
-def test_one_distill_update_with_the_table_is_the_public_calls_composed(ea):
+def few_cube_lanes(env, K, T, seed):
+    """every second lane of the env goes on from a sampled position that the (S, K, T) table covers, under the dice it has"""
+    rng = random.Random(seed)
+    b = env.board.clone().reshape(env.N, env.S, env.S)
+    b[::2] = torch.as_tensor(np.stack([board_of(sample(rng, env.S, K, T), env.S) for _ in range(0, env.N, 2)])).cuda()
+    env.set_obs(b, env.dice.clone())
+
+
+@pytest.mark.parametrize("S", [5, 7])
+def test_one_distill_update_with_the_table_is_the_public_calls_composed(ea, S):
+    """on 7x7 with the (7, 2, 3) table a rollout does not reach a covered position within the test: every second lane is put on one"""
     from ewn_gym_amd._lib import EwnA2cHyper, check
     from ewn_gym_amd.distill import SearchDistillTrainer
     from ewn_gym_amd.vec_env import _ptr, _stream
     N, K = 256, 5
-    t = table(ea, 5, 2, 4)
-    tr = SearchDistillTrainer(make_env(ea, N), n_steps=K, seed=5, endgame_table=t, terminal_value=0.75)
+    t = table(ea, 5, 2, 4) if S == 5 else table(ea, 7, 2, 3)
+    tr = SearchDistillTrainer(make_env(ea, N, S), n_steps=K, seed=5, endgame_table=t, terminal_value=0.75)
     params, sq = tr.params.clone(), torch.zeros_like(tr.params)
     tr.env.rollout_policy(14, params, noise_key=1)     # past the openings: a rollout from the reset holds no position with few cubes
+    if S == 7:
+        few_cube_lanes(tr.env, 2, 3, 7)
     tr.collect_and_update()
-    env = make_env(ea, N)
+    env = make_env(ea, N, S)
     env.rollout_policy(14, params, noise_key=1)
+    if S == 7:
+        few_cube_lanes(env, 2, 3, 7)
     traj = env.alloc_rollout(K, layout="record", initial_obs=True)
     env.rollout_policy(K, params, traj=traj, noise_key=tr.noise_key)
     assert torch.equal(traj["record"], tr.traj["record"])
-    b = traj["obs_board"][:K].reshape(K * N, 5, 5).contiguous()
+    b = traj["obs_board"][:K].reshape(K * N, S, S).contiguous()
     d = traj["obs_dice"][:K].reshape(K * N).contiguous()
     _, q = ea.predict_lookahead(b, d, params, terminal_value=0.75, return_q=True)
     _, cov, qe = t.lookup(b, d, return_q=True)
-    print("distill update: %d of %d rows covered" % (int(cov.sum()), K * N))
+    print("distill update %dx%d: %d of %d rows covered" % (S, S, int(cov.sum()), K * N))
     assert 0 < int(cov.sum()) < K * N
+    if S == 7:
+        assert int(cov[:N].sum()) >= N // 2                                # the lanes that were put on covered positions
     assert torch.equal(torch.isneginf(q[cov]), torch.isneginf(qe[cov]))   # -inf in the same places, by construction
     q = torch.where(cov[:, None, None], 0.75 * qe, q)
     tp, tv, w = ea.lookahead_targets(q, 0.0)

@@ -249,6 +249,12 @@ def test_lock_step(ea, S, M, sims):
 @pytest.mark.parametrize("S,M,sims", [(5, 70, 40), (7, 70, 40), (5, 33, 7), (7, 1, 1)])
 def test_result_against_the_model(ea, S, M, sims):
     tree, models, _ = pool_run(ea, S, M, sims)
+    check_result(ea, tree, models, S, sims)
+
+
+def check_result(ea, tree, models, S, sims):
+    """puct_result of lockstep's trees against the results of its models"""
+    M = len(models)
     act, visits, q, value = ea.puct_result(tree, S, sims, return_visits=True, return_q=True, return_value=True)
     assert act.shape == (M, 2) and act.dtype == torch.int8 and visits.shape == (M, 2, 3) and visits.dtype == torch.int32
     assert q.shape == (M, 2, 3) and q.dtype == torch.float32 and value.shape == (M,) and value.dtype == torch.float32
@@ -311,6 +317,12 @@ def test_what_the_buffer_held_does_not_matter(ea, S):
 @pytest.mark.parametrize("S,M,sims", [(5, 70, 40), (7, 70, 40), (5, 33, 7), (7, 33, 7), (5, 1, 1), (7, 70, 1)])
 def test_invariants(ea, S, M, sims):
     _, _, v = pool_run(ea, S, M, sims)
+    check_invariants(v, sims)
+
+
+def check_invariants(v, sims):
+    """what holds of every finished tree, whatever the model says: v the host views (host_views) of trees after sims + 1 rounds"""
+    M = v["count"].shape[0]
     live = v["degenerate"] == 0
     n, w, p, kind, cn, child, parent = (v[k] for k in ("n", "w", "p", "kind", "cn", "child", "parent"))
     assert np.array_equal(n[:, 0].sum(1)[live], np.full(int(live.sum()), sims))
@@ -549,23 +561,30 @@ def test_one_puct_update_is_the_public_calls_composed(ea):
     assert SearchDistillTrainer(make_env(ea, N), n_steps=K, seed=5).search == "lookahead"
 
 
-def test_a_puct_update_with_an_endgame_table(ea):
-    """covered rows get the exact q's targets, as the lookahead trainer's rows get them; the others the search's"""
+@pytest.mark.parametrize("S", [5, 7])
+def test_a_puct_update_with_an_endgame_table(ea, S):
+    """covered rows get the exact q's targets, as the lookahead trainer's rows get them; the others the search's.  On 7x7, with the
+    (7, 2, 3) table, every second lane is put on a covered position: a rollout does not reach one within the test"""
     from ewn_gym_amd.distill import SearchDistillTrainer, puct_targets
     from tests.test_gpu_distill_trainer import make_env
-    from tests.test_gpu_endgame import table
+    from tests.test_gpu_endgame import few_cube_lanes, table
     N, K = 256, 5
-    t = table(ea, 5, 2, 4)
-    tr = SearchDistillTrainer(make_env(ea, N), n_steps=K, seed=5, search="puct", sims=6, c_puct=1.0, endgame_table=t, terminal_value=0.75)
+    t = table(ea, 5, 2, 4) if S == 5 else table(ea, 7, 2, 3)
+    tr = SearchDistillTrainer(make_env(ea, N, S), n_steps=K, seed=5, search="puct", sims=6, c_puct=1.0, endgame_table=t, terminal_value=0.75)
     params = tr.params.clone()
     tr.env.rollout_policy(14, params, noise_key=1)     # past the openings: a rollout from the reset holds no position with few cubes
+    if S == 7:
+        few_cube_lanes(tr.env, 2, 3, 7)
     tr.collect_and_update()
     b, d = tr._boards, tr._dice
     _, visits, q, value = ea.predict_puct(b, d, params, sims=6, c_puct=1.0, terminal_value=0.75, return_visits=True, return_q=True,
                                           return_value=True)
     tp, tv, w = puct_targets(visits, q, value, 0.75)
     _, cov, qe = t.lookup(b, d, return_q=True)
+    print("puct update %dx%d: %d of %d rows covered" % (S, S, int(cov.sum()), K * N))
     assert 0 < int(cov.sum()) < K * N
+    if S == 7:
+        assert int(cov[:N].sum()) >= N // 2                                # the lanes that were put on covered positions
     ep, ev, ew = ea.lookahead_targets(0.75 * qe, 0.0)
     tp, tv, w = torch.where(cov[:, None], ep, tp), torch.where(cov, ev, tv), torch.where(cov, ew, w)
     assert bool((w[cov] == 1).all()) and float(tv[cov].abs().max()) <= 0.75
