@@ -18,6 +18,7 @@
 
 #define EG_NT 256            // threads per block of both kernels
 #define EG_MAX_BLOCKS 9      // (ka, ko) blocks of a table: K <= 3
+#define EG_MAX_GRID (1u << 22)   // workgroups per launch: a launch's grid is 32 bits of THREADS (2^24 workgroups of EG_NT), see eg_build
 
 struct EgMasks { uint8_t rank[64]; uint8_t unrank[4][20]; };   // rank[mask of cubes 1..6 >> 1]; unrank[popcount][rank]
 static constexpr EgMasks eg_make_masks()
@@ -142,6 +143,7 @@ EWN_DEV bool eg_decode(u32 i, int k, int bad, bool far_goal, u64 &occ0, u64 &occ
 
 struct EgLevel {
     int level, nblk;
+    u32 first;                                                  // the level's workgroup that this launch's blockIdx.x = 0 is
     struct { int ka, ko; u32 wg0, chunks; } b[EG_MAX_BLOCKS];   // workgroups wg0 .. : chunks per agent side index, EG_NT opposing side indices per chunk
 };
 
@@ -151,7 +153,7 @@ template <int S>
 __global__ __launch_bounds__(EG_NT) void k_endgame_level(float *tbl, EgGeo g, EgLevel L)
 {
     constexpr int C = S * S;
-    const u32 wg = blockIdx.x;
+    const u32 wg = L.first + blockIdx.x;
     int bi = 0;
     #pragma unroll 1
     for (int i = 1; i < L.nblk; i++) if (wg >= L.b[i].wg0) bi = i;
@@ -264,10 +266,17 @@ static int eg_build(int K, int T, float *table, long long entries, const EgGeo &
     if (hipMemsetAsync(table, 0, (size_t)entries * sizeof(float), s) != hipSuccess) return EWN_ELAUNCH;
     for (int level = 2; level <= 2 * T * (S - 1); level++) {     // Phi >= 2: a live position has a cube a side, neither on its corner
         const unsigned long long wg = eg_level(S, K, T, level, L);
-        if (wg == 0) continue;
-        k_endgame_level<S><<<dim3((unsigned)wg), dim3(EG_NT), 0, s>>>(table, g, L);
-        const int rc = launch_status();
-        if (rc != EWN_OK) return rc;
+        // A level goes out in launches of at most EG_MAX_GRID workgroups.  The runtime takes a grid of 2^24 workgroups of 256 threads
+        // or more without an error and runs its thread count modulo 2^32: levels 5 to 16 of (5, 3, 5) have 23 866 975 workgroups, of which
+        // one launch ran the first 7 089 759 and left blocks (3, 1), (3, 2) and 43 % of (2, 3) at the cleared 0.  The launches of a
+        // level write disjoint entries and read lower levels only, so their order on the stream is all they need.
+        for (unsigned long long first = 0; first < wg; first += EG_MAX_GRID) {
+            const unsigned long long n = wg - first < EG_MAX_GRID ? wg - first : EG_MAX_GRID;
+            L.first = (u32)first;
+            k_endgame_level<S><<<dim3((unsigned)n), dim3(EG_NT), 0, s>>>(table, g, L);
+            const int rc = launch_status();
+            if (rc != EWN_OK) return rc;
+        }
     }
     return EWN_OK;
 }

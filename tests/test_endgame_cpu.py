@@ -72,6 +72,20 @@ def test_build_refusals_and_their_order():
         assert build(table=addr) == EINVAL                         # not 4-byte aligned
 
 
+def test_build_refuses_a_level_of_more_than_2_31_workgroups():
+    """three cubes a side and six in all from 6x6 on: block (3, 3) alone has 20 * 36^3 = 933 120 side indices a side and 3 645
+    workgroups per agent side, 3.40 x 10^9 at one level.  The refusal comes before anything touches the table (16 is no address),
+    and after the checks of the pointer and the size.  (No shape that passes is built here: it would go on to the device.)"""
+    EUNSUPPORTED = -4
+    assert _lib.load().ewn_strerror(EUNSUPPORTED) != _lib.load().ewn_strerror(EINVAL)
+    assert -(-(20 * 36 ** 3) // 256) * (20 * 36 ** 3) == 3645 * 933120 > 2 ** 31 - 1
+    for S in (6, 7, 11):
+        assert build(S=S, K=3, T=6) == EUNSUPPORTED, S
+    assert build(S=6, K=3, T=6, table_bytes=formula(6, 3, 6) - 4) == EINVAL and build(S=6, K=3, T=6, table_bytes=formula(6, 3, 5)) == EINVAL
+    assert build(S=6, K=3, T=6, table=18) == EINVAL
+    assert build(S=6, K=3, T=6, table=None) == ENULL and build(S=6, K=3, T=6, table=None, table_bytes=8) == ENULL
+
+
 def test_lookup_refusals_and_their_order():
     assert lookup(M=-1) == EINVAL and lookup(M=-1, table=None) == EINVAL
     assert lookup(S=2, M=0) == EINVAL and lookup(K=0, M=0) == EINVAL and lookup(T=5, M=0) == EINVAL   # the parameters before the empty batch

@@ -357,7 +357,7 @@ def test_not_covered(ea):
     assert t3.lookup(b3, i8(1, 1, 1))[1].tolist() == [False, True, True]
 
 
-@pytest.mark.parametrize("S,K,T", [(5, 2, 4), (3, 3, 4)])
+@pytest.mark.parametrize("S,K,T", [(5, 2, 4), (3, 3, 4), (3, 3, 6)])
 def test_the_recurrence_through_the_public_calls(ea, S, K, T):
     """value recomputed in float32 from lookup's q under the six dice: the maxima summed in dice order, one multiply"""
     t = table(ea, S, K, T)
