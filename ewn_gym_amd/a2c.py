@@ -16,6 +16,7 @@ Multi-GPU: one process per GPU, each owning its own lanes; the only collective o
 training path is ONE all-reduce (RCCL under torch.distributed's "nccl" backend) of the
 flattened gradient (~13 k fp32 = 52 KB: latency-bound on xGMI, a single bucket by design).
 """
+import ctypes as C
 import math
 
 import torch
@@ -351,25 +352,23 @@ class PolicyOpponent:
         return False
 
 
-class FusedA2CTrainer(PolicyOpponent):
-    """A2C with the whole loop in the engine (BASELINE config 4): the n-step rollout is ONE kernel (ewn_step_k_policy: policy
-    network on the matrix cores, Gumbel-max sampling, shaped env step, opponent search, records), the update three more
-    (ewn_a2c_grad: value pass, policy pass, reduction; ewn_a2c_apply: global-norm clip + RMSprop) -- no torch operator on the
-    training path, one all-reduce of the flat gradient between grad and apply when there are several ranks.  Same loss and
-    optimiser as A2CTrainer (SB3's documented A2C defaults, gae_lambda = 1); the parameters live in ONE flat fp32 tensor that the
-    torch module `self.model` views (evaluation, checkpoints)."""
+class FusedTrainer(PolicyOpponent):
+    """What the trainers with the whole loop in the engine share: the parameters in ONE flat fp32 tensor that the torch module `self.model`
+    views (evaluation, checkpoints) and the kernels read and update in place, the record trajectory of ewn_step_k_policy, the flat
+    gradient and its one all-reduce, the update loop (captured as one hipGraph where the update is kernel launches only) and the
+    checkpoint.  A subclass supplies `_launch` (one rollout + update on the current stream), `stats_dict`, and its optimiser state
+    through `_state` / `_load_state`."""
 
-    algorithm = "A2C"
     best_score = -1.0
+    _use_instead = ""        # the tail of the refusal below: the torch trainer that serves such an env
+    _written_by = None       # "the fused A2C trainer": who load() says a foreign checkpoint was not written by
 
-    def __init__(self, env, n_steps=5, learning_rate=7e-4, gamma=0.99, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, seed=None,
-                 rms_alpha=0.99, rms_eps=1e-5, use_graph=True, opponent=None, opponent_update_every=100, opponent_deterministic=False):
-        import ctypes as C
+    def __init__(self, env, n_steps, seed, use_graph, opponent, opponent_update_every, opponent_deterministic):
+        import torch.distributed as dist
         from . import _lib
         if opponent is None and not env.supports_policy_rollout():
-            raise _lib.EwnError("this env configuration has no policy-driven rollout kernel (ewn_step_k_policy): use A2CTrainer")
-        self.env, self.lib, self.C = env, env.lib, C
-        self.device = env.board.device
+            raise _lib.EwnError("this env configuration has no policy-driven rollout kernel (ewn_step_k_policy)" + self._use_instead)
+        self.env, self.lib, self.device = env, env.lib, env.board.device
         if seed is not None:
             torch.manual_seed(seed)
         self.model = ActorCritic(env.S, env.cube_num).to(self.device)
@@ -379,48 +378,32 @@ class FusedA2CTrainer(PolicyOpponent):
             p.data = self.params[off:off + p.numel()].view_as(p)
             off += p.numel()
         assert off == env.policy_param_count()
-        self._sync_parameters()
+        self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        if self.world > 1:                                            # every rank starts from rank 0's parameters
+            dist.broadcast(self.params, src=0)
         self._init_opponent(opponent, opponent_update_every, opponent_deterministic, seed)
-        self.sq_avg = torch.zeros_like(self.params)
         self.grad = torch.zeros(self.params.numel() + 8, dtype=torch.float32, device=self.device)
         self.grad_norm = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.n_steps, self.num_timesteps = int(n_steps), 0
-        world = 1
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized():
-            world = dist.get_world_size()
-        self.world = world
-        self.hyper = _lib.EwnA2cHyper(float(gamma), float(vf_coef), float(ent_coef), float(max_grad_norm), float(learning_rate),
-                                      float(rms_alpha), float(rms_eps), int(world))
-        nscr = _lib.check(self.lib.ewn_a2c_scratch_bytes(C.byref(env.cfg), self.n_steps), "ewn_a2c_scratch_bytes")
-        self.scratch = torch.zeros(int(nscr), dtype=torch.uint8, device=self.device)
         self.traj = env.alloc_rollout(self.n_steps, layout="record", initial_obs=True)
         self.noise_key = (0 if seed is None else int(seed)) * 0x9E3779B97F4A7C15 & 0xFFFFFFFFFFFFFFFF
         self.gen = torch.Generator(device=self.device)                # policy_fn's sampling only (evaluation is deterministic)
         self.gen.manual_seed(0 if seed is None else int(seed))
         self.force_collective = False     # tools/nccl_selftest.py: all-reduce the gradient even in a one-rank group
-        self.use_graph = use_graph and world == 1
+        self.use_graph = use_graph and self.world == 1
         self._graph = None
         self._warm = False
 
-    _sync_parameters = A2CTrainer._sync_parameters
-
-    def _launch(self):
-        from ._lib import check
-        from .vec_env import _ptr, _stream
-        C, env = self.C, self.env
-        env.rollout_policy(self.n_steps, self.params, traj=self.traj, noise_key=self.noise_key, **self._opponent_kwargs())
-        check(self.lib.ewn_a2c_grad(C.byref(env.cfg), self.n_steps, _ptr(self.traj["record"]), _ptr(self.traj["reward"]), _ptr(self.params),
-                                    C.byref(self.hyper), _ptr(self.grad), _ptr(self.scratch), _stream()), "ewn_a2c_grad")
-        if self.world > 1 or self.force_collective:   # the one collective of the training path: the flat gradient (52 KB), summed; apply divides by the world size
+    def _all_reduce_grad(self):
+        """the one collective of the training path, between grad and apply: the flat gradient and its sums (52 KB), summed; apply
+        divides by the world size"""
+        if self.world > 1 or self.force_collective:
             import torch.distributed as dist
             dist.all_reduce(self.grad, op=dist.ReduceOp.SUM)
-        check(self.lib.ewn_a2c_apply(C.byref(env.cfg), _ptr(self.params), _ptr(self.sq_avg), _ptr(self.grad), C.byref(self.hyper),
-                                     _ptr(self.grad_norm), _stream()), "ewn_a2c_apply")
 
     def collect_and_update(self):
         if self.use_graph and self._warm:
-            if self._graph is None:       # five kernel launches, no torch operator: captured once, replayed per update
+            if self._graph is None:       # kernel launches on one stream, no torch operator: captured once, replayed per update
                 torch.cuda.synchronize()
                 self._graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(self._graph):
@@ -433,14 +416,6 @@ class FusedA2CTrainer(PolicyOpponent):
         self.num_timesteps += self.n_steps * self.env.N
         return self.grad
 
-    def stats_dict(self):
-        g = self.grad[-8:].tolist()
-        n = float(self.n_steps * self.env.N * self.world)
-        pl, vl, en = g[0] / n, g[5] / n, g[2] / n
-        return {"loss": pl + self.hyper.vf_coef * vl - self.hyper.ent_coef * en, "policy_loss": pl, "value_loss": vl, "entropy": en,
-                "mean_reward": float(self.traj["reward"].mean()), "episodes": int(self.traj["terminated"].sum()),
-                "grad_norm": float(self.grad_norm)}
-
     def learn(self, total_timesteps):
         target = self.num_timesteps + total_timesteps
         while self.num_timesteps < target:
@@ -451,16 +426,66 @@ class FusedA2CTrainer(PolicyOpponent):
         return lambda b, d, t: self.model.act(b, d, deterministic=deterministic, generator=self.gen)[0]
 
     def save(self, path):
-        torch.save({"algorithm": self.algorithm, "fused": True, "params": self.params, "sq_avg": self.sq_avg,
-                    "num_timesteps": self.num_timesteps, "best_score": float(self.best_score), **self._opponent_state()}, path)
+        torch.save({"algorithm": self.algorithm, "fused": True, "params": self.params, **self._state(), "num_timesteps": self.num_timesteps,
+                    "best_score": float(self.best_score), **self._opponent_state()}, path)
 
     def load(self, path):
         sd = torch.load(path, map_location=self.device, weights_only=True)
-        if sd.get("algorithm", "A2C") != self.algorithm or not sd.get("fused", False):
-            raise ValueError("checkpoint %s was not written by the fused A2C trainer" % path)
-        self.params.copy_(sd["params"])
-        self.sq_avg.copy_(sd["sq_avg"])
+        if sd.get("algorithm", "A2C") == self.algorithm and sd.get("fused", False):
+            self.params.copy_(sd["params"])
+            self._load_state(sd)
+        else:
+            self._load_foreign(path, sd)
         self.num_timesteps = sd["num_timesteps"]
         self.best_score = float(sd.get("best_score", -1.0))
         self._opponent_loaded(sd)
 
+    def _load_foreign(self, path, sd):
+        raise ValueError("checkpoint %s was not written by %s" % (path, self._written_by))
+
+
+class FusedA2CTrainer(FusedTrainer):
+    """A2C with the whole loop in the engine (BASELINE config 4): the n-step rollout is ONE kernel (ewn_step_k_policy: policy
+    network on the matrix cores, Gumbel-max sampling, shaped env step, opponent search, records), the update three more
+    (ewn_a2c_grad: value pass, policy pass, reduction; ewn_a2c_apply: global-norm clip + RMSprop) -- no torch operator on the
+    training path, one all-reduce of the flat gradient between grad and apply when there are several ranks.  Same loss and
+    optimiser as A2CTrainer (SB3's documented A2C defaults, gae_lambda = 1); the flat parameters and the loop are FusedTrainer's."""
+
+    algorithm = "A2C"
+    _use_instead = ": use A2CTrainer"
+    _written_by = "the fused A2C trainer"
+
+    def __init__(self, env, n_steps=5, learning_rate=7e-4, gamma=0.99, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, seed=None,
+                 rms_alpha=0.99, rms_eps=1e-5, use_graph=True, opponent=None, opponent_update_every=100, opponent_deterministic=False):
+        from . import _lib
+        super().__init__(env, n_steps, seed, use_graph, opponent, opponent_update_every, opponent_deterministic)
+        self.sq_avg = torch.zeros_like(self.params)
+        self.hyper = _lib.EwnA2cHyper(float(gamma), float(vf_coef), float(ent_coef), float(max_grad_norm), float(learning_rate),
+                                      float(rms_alpha), float(rms_eps), int(self.world))
+        nscr = _lib.check(self.lib.ewn_a2c_scratch_bytes(C.byref(env.cfg), self.n_steps), "ewn_a2c_scratch_bytes")
+        self.scratch = torch.zeros(int(nscr), dtype=torch.uint8, device=self.device)
+
+    def _launch(self):
+        from ._lib import check
+        from .vec_env import _ptr, _stream
+        env = self.env
+        env.rollout_policy(self.n_steps, self.params, traj=self.traj, noise_key=self.noise_key, **self._opponent_kwargs())
+        check(self.lib.ewn_a2c_grad(C.byref(env.cfg), self.n_steps, _ptr(self.traj["record"]), _ptr(self.traj["reward"]), _ptr(self.params),
+                                    C.byref(self.hyper), _ptr(self.grad), _ptr(self.scratch), _stream()), "ewn_a2c_grad")
+        self._all_reduce_grad()
+        check(self.lib.ewn_a2c_apply(C.byref(env.cfg), _ptr(self.params), _ptr(self.sq_avg), _ptr(self.grad), C.byref(self.hyper),
+                                     _ptr(self.grad_norm), _stream()), "ewn_a2c_apply")
+
+    def stats_dict(self):
+        g = self.grad[-8:].tolist()
+        n = float(self.n_steps * self.env.N * self.world)
+        pl, vl, en = g[0] / n, g[5] / n, g[2] / n
+        return {"loss": pl + self.hyper.vf_coef * vl - self.hyper.ent_coef * en, "policy_loss": pl, "value_loss": vl, "entropy": en,
+                "mean_reward": float(self.traj["reward"].mean()), "episodes": int(self.traj["terminated"].sum()),
+                "grad_norm": float(self.grad_norm)}
+
+    def _state(self):
+        return {"sq_avg": self.sq_avg}
+
+    def _load_state(self, sd):
+        self.sq_avg.copy_(sd["sq_avg"])

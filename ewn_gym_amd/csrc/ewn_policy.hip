@@ -146,22 +146,26 @@ static void a2c_reduce_launch(const A2cRedBuf &rb, hipStream_t s)
     else k_a2c_reduce<<<(rb.P + 8 + A2C_RED_E - 1) / A2C_RED_E, 256, 0, s>>>(rb);
 }
 
-// the bf16 x 3 kernel (ewn_a2c3.hpp): one wave per tile and SIMD, everything in registers
+// the bf16 x 3 gradient kernels (ewn_a2c3.hpp: one wave per tile and SIMD, everything in registers) launch alike: the value pass first
+// (it leaves the advantages for the policy pass), the policy pass, then the blocks' partials -> the flat gradient
+template <typename Kern, typename Cfg, typename Buf>
+static int grad3_launch(Kern kv, Kern kp, int blocks, size_t lds, const Cfg &c, const Buf &b, const A2cRedBuf &rb, hipStream_t s)
+{
+    if (hipFuncSetAttribute((const void *)kv, hipFuncAttributeMaxDynamicSharedMemorySize, POL_LDS_MAX) != hipSuccess) return EWN_ELAUNCH;
+    if (hipFuncSetAttribute((const void *)kp, hipFuncAttributeMaxDynamicSharedMemorySize, POL_LDS_MAX) != hipSuccess) return EWN_ELAUNCH;
+    kv<<<blocks, 256, lds, s>>>(c, b);
+    kp<<<blocks, 256, lds, s>>>(c, b);
+    a2c_reduce_launch(rb, s);
+    return launch_status();
+}
+
 template <int S>
-static int a2c_grad_launch(const A2cCfg &ac, A2cBuf ab, float *grad, hipStream_t s)
+static int a2c_grad_launch(const A2cCfg &ac, const A2cBuf &ab, float *grad, hipStream_t s)
 {
     constexpr size_t lds = A2c3Geo<S>::lds_bytes();
     static_assert(lds <= POL_LDS_MAX, "weight images + the gradient image must fit the CU's LDS");
-    auto kv = k_a2c_grad3<S, 1>;
-    auto kp = k_a2c_grad3<S, 0>;
-    if (hipFuncSetAttribute((const void *)kv, hipFuncAttributeMaxDynamicSharedMemorySize, POL_LDS_MAX) != hipSuccess) return EWN_ELAUNCH;
-    if (hipFuncSetAttribute((const void *)kp, hipFuncAttributeMaxDynamicSharedMemorySize, POL_LDS_MAX) != hipSuccess) return EWN_ELAUNCH;
     const int blocks = a2c_blocks(ac.N, 4);
-    kv<<<blocks, 256, lds, s>>>(ac, ab);         // value pass first: it leaves the advantages for the policy pass
-    kp<<<blocks, 256, lds, s>>>(ac, ab);
-    A2cRedBuf rb = { ab.partial, ab.stats, grad, blocks, MlpGeo<S>::P };
-    a2c_reduce_launch(rb, s);
-    return launch_status();
+    return grad3_launch(k_a2c_grad3<S, 1>, k_a2c_grad3<S, 0>, blocks, lds, ac, ab, A2cRedBuf{ ab.partial, ab.stats, grad, blocks, MlpGeo<S>::P }, s);
 }
 
 int ewn_a2c_grad(const ewn_config *cfg, int K, const uint8_t *record, const double *reward, const float *params, const ewn_a2c_hyper *hp,
@@ -262,16 +266,8 @@ static int ppo_grad_launch(const PpoCfg &c, const PpoBuf &b, float *grad, hipStr
 {
     constexpr size_t lds = Ppo3Geo<S>::lds_bytes();
     static_assert(lds <= POL_LDS_MAX, "weight images + the gradient image must fit the CU's LDS");
-    auto kv = k_ppo_grad3<S, 1>;
-    auto kp = k_ppo_grad3<S, 0>;
-    if (hipFuncSetAttribute((const void *)kv, hipFuncAttributeMaxDynamicSharedMemorySize, POL_LDS_MAX) != hipSuccess) return EWN_ELAUNCH;
-    if (hipFuncSetAttribute((const void *)kp, hipFuncAttributeMaxDynamicSharedMemorySize, POL_LDS_MAX) != hipSuccess) return EWN_ELAUNCH;
     const int blocks = a2c_blocks(c.B, 4);
-    kv<<<blocks, 256, lds, s>>>(c, b);           // value pass first: it leaves the advantage sums for the policy pass
-    kp<<<blocks, 256, lds, s>>>(c, b);
-    A2cRedBuf rb = { b.partial, b.stats, grad, blocks, MlpGeo<S>::P };
-    a2c_reduce_launch(rb, s);
-    return launch_status();
+    return grad3_launch(k_ppo_grad3<S, 1>, k_ppo_grad3<S, 0>, blocks, lds, c, b, A2cRedBuf{ b.partial, b.stats, grad, blocks, MlpGeo<S>::P }, s);
 }
 
 int ewn_ppo_grad(const ewn_config *cfg, int K, const uint8_t *record, const float *samples, const float *params, const ewn_ppo_hyper *hp,
@@ -335,18 +331,12 @@ static int sup_grad_launch(const SupCfg &c, SupBuf b, const int8_t *boards, cons
     b.stats = b.partial + (size_t)A2C_MAX_BLOCKS * P;
     uint8_t *rows = (uint8_t *)(((uintptr_t)scratch + sup_rows_offset(P) + 15) & ~(uintptr_t)15);
     b.rows = rows;
-    auto kv = k_sup_grad3<S, 1>;
+    auto kv = k_sup_grad3<S, 1>;                 // named before k_sup_rows: the unit's kernels keep their order in the code object
     auto kp = k_sup_grad3<S, 0>;
-    if (hipFuncSetAttribute((const void *)kv, hipFuncAttributeMaxDynamicSharedMemorySize, POL_LDS_MAX) != hipSuccess) return EWN_ELAUNCH;
-    if (hipFuncSetAttribute((const void *)kp, hipFuncAttributeMaxDynamicSharedMemorySize, POL_LDS_MAX) != hipSuccess) return EWN_ELAUNCH;
     const size_t words = (size_t)c.M * (RecGeo<S>::STR / 4), need = (words + 255) / 256;
     k_sup_rows<S><<<(unsigned)(need < 65536 ? need : 65536), 256, 0, s>>>(c.M, boards, dice, (u32 *)rows);
     const int blocks = a2c_blocks(c.M, 4);
-    kv<<<blocks, 256, lds, s>>>(c, b);
-    kp<<<blocks, 256, lds, s>>>(c, b);
-    A2cRedBuf rb = { b.partial, b.stats, grad, blocks, (int)P };
-    a2c_reduce_launch(rb, s);
-    return launch_status();
+    return grad3_launch(kv, kp, blocks, lds, c, b, A2cRedBuf{ b.partial, b.stats, grad, blocks, (int)P }, s);
 }
 
 int ewn_sup_grad(int board_size, int cube_layer, int M, const int8_t *boards, const int8_t *dice, const float *target_pi,

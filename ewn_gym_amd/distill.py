@@ -15,7 +15,7 @@ import ctypes as C
 
 import torch
 
-from .a2c import ActorCritic, A2CTrainer, PolicyOpponent
+from .a2c import FusedTrainer
 
 
 def puct_targets(visits, q, value, terminal_value=1.0):
@@ -36,22 +36,20 @@ def puct_targets(visits, q, value, terminal_value=1.0):
     return target_pi.contiguous(), target_value.contiguous(), live.to(torch.float32)
 
 
-class SearchDistillTrainer(PolicyOpponent):
-    """FusedA2CTrainer's surface (flat `params` viewed by `self.model`, collect_and_update, learn, stats_dict, policy_fn, save / load)
-    with the supervised search-distillation update.  The env's rewards are not read: the rollout only supplies the state
-    distribution, so the plain or the shaped env serves, against any opponent the policy rollout plays (opponent=: PolicyOpponent's
-    model opponents, "self" included)."""
+class SearchDistillTrainer(FusedTrainer):
+    """a2c.FusedTrainer (flat `params` viewed by `self.model`, collect_and_update, learn, policy_fn, save / load) with the supervised
+    search-distillation update, which runs torch operators and allocates: it stays eager, never a captured graph.  The env's rewards
+    are not read: the rollout only supplies the state distribution, so the plain or the shaped env serves, against any opponent the
+    policy rollout plays (opponent=: PolicyOpponent's model opponents, "self" included)."""
 
     algorithm = "SEARCH"
-    best_score = -1.0
+    _written_by = "the search-distillation trainer"
 
     def __init__(self, env, n_steps=5, learning_rate=7e-4, pi_coef=1.0, vf_coef=0.5, temperature=0.0, plies=1, terminal_value=1.0,
                  max_grad_norm=0.5, rms_alpha=0.99, rms_eps=1e-5, seed=None, opponent=None, opponent_update_every=100,
                  opponent_deterministic=False, endgame_table=None, search="lookahead", sims=64, c_puct=1.5):
         import math
         from . import _lib
-        if opponent is None and not env.supports_policy_rollout():
-            raise _lib.EwnError("this env configuration has no policy-driven rollout kernel (ewn_step_k_policy)")
         if search not in ("lookahead", "puct"):
             raise ValueError("SearchDistillTrainer: search must be 'lookahead' or 'puct', got %r" % (search,))
         if plies not in (1, 2):
@@ -75,48 +73,21 @@ class SearchDistillTrainer(PolicyOpponent):
                 raise ValueError("SearchDistillTrainer: the endgame table is for %dx%d boards, the env plays %dx%d" % (
                     endgame_table.board_size, endgame_table.board_size, env.S, env.S))
         self.endgame_table = endgame_table   # None: the search's q alone; else its q is replaced by the exact one on covered rows
-        self.env, self.lib = env, env.lib
-        self.device = env.board.device
-        if seed is not None:
-            torch.manual_seed(seed)
-        self.model = ActorCritic(env.S, env.cube_num).to(self.device)
-        self.params = self.model.flat_parameters()                    # the flat vector the kernels read and update in place
-        off = 0
-        for p in self.model.parameters():                             # ... and the module's parameters become views of it
-            p.data = self.params[off:off + p.numel()].view_as(p)
-            off += p.numel()
-        assert off == env.policy_param_count()
-        self._sync_parameters()
-        self._init_opponent(opponent, opponent_update_every, opponent_deterministic, seed)
+        super().__init__(env, n_steps, seed, False, opponent, opponent_update_every, opponent_deterministic)
         self.sq_avg = torch.zeros_like(self.params)
-        self.grad = torch.zeros(self.params.numel() + 8, dtype=torch.float32, device=self.device)
-        self.grad_norm = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self.n_steps, self.num_timesteps = int(n_steps), 0
         self.pi_coef, self.vf_coef, self.temperature = float(pi_coef), float(vf_coef), float(temperature)
         self.plies, self.terminal_value = int(plies), float(terminal_value)
         self.search, self.sims, self.c_puct = search, int(sims), float(c_puct)
-        world = 1
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized():
-            world = dist.get_world_size()
-        self.world = world
         # the optimiser step is ewn_a2c_apply: of this struct it reads max_grad_norm, learning_rate, rms_alpha, rms_eps, world_size
         self.hyper = _lib.EwnA2cHyper(0.0, float(vf_coef), 0.0, float(max_grad_norm), float(learning_rate), float(rms_alpha), float(rms_eps),
-                                      int(world))
+                                      int(self.world))
         M, S = self.n_steps * env.N, env.S
         nscr = _lib.check(self.lib.ewn_sup_scratch_bytes(S, env.L, M), "ewn_sup_scratch_bytes")
         self.scratch = torch.zeros(int(nscr), dtype=torch.uint8, device=self.device)
-        self.traj = env.alloc_rollout(self.n_steps, layout="record", initial_obs=True)
         self._boards = torch.zeros((M, S, S), dtype=torch.int8, device=self.device)      # rows 0 .. n_steps - 1 of the observations, packed
         self._dice = torch.zeros(M, dtype=torch.int8, device=self.device)
-        self.noise_key = (0 if seed is None else int(seed)) * 0x9E3779B97F4A7C15 & 0xFFFFFFFFFFFFFFFF
-        self.gen = torch.Generator(device=self.device)                # policy_fn's sampling only (evaluation is deterministic)
-        self.gen.manual_seed(0 if seed is None else int(seed))
-        self.force_collective = False
 
-    _sync_parameters = A2CTrainer._sync_parameters
-
-    def collect_and_update(self):
+    def _launch(self):
         from ._lib import check
         from .vec_env import _ptr, _stream, lookahead_targets, predict_lookahead, predict_puct, sup_grad
         env, K, N, S = self.env, self.n_steps, self.env.N, self.env.S
@@ -142,14 +113,9 @@ class SearchDistillTrainer(PolicyOpponent):
             target_pi, target_value, weight = lookahead_targets(q, self.temperature)
         sup_grad(self._boards, self._dice, target_pi, target_value, self.params, weight=weight, pi_coef=self.pi_coef, vf_coef=self.vf_coef,
                  cube_layer=env.L, out=self.grad, scratch=self.scratch)
-        if self.world > 1 or self.force_collective:   # the one collective: the flat gradient and its sums; apply divides by the world size
-            import torch.distributed as dist
-            dist.all_reduce(self.grad, op=dist.ReduceOp.SUM)
+        self._all_reduce_grad()
         check(self.lib.ewn_a2c_apply(C.byref(env.cfg), _ptr(self.params), _ptr(self.sq_avg), _ptr(self.grad), C.byref(self.hyper),
                                      _ptr(self.grad_norm), _stream()), "ewn_a2c_apply")
-        self._after_update()
-        self.num_timesteps += K * N
-        return self.grad
 
     def stats_dict(self):
         g = self.grad[-8:].tolist()
@@ -159,31 +125,13 @@ class SearchDistillTrainer(PolicyOpponent):
         return {"loss": self.pi_coef * pl + self.vf_coef * vl, "policy_loss": pl, "value_loss": vl, "entropy": en, "agreement": per(g[2]),
                 "grad_norm": float(self.grad_norm), "live_fraction": live / float(self.n_steps * self.env.N * self.world)}
 
-    def learn(self, total_timesteps):
-        target = self.num_timesteps + total_timesteps
-        while self.num_timesteps < target:
-            self.collect_and_update()
-        return self.stats_dict()
+    def _state(self):
+        return {"sq_avg": self.sq_avg, "terminal_value": float(self.terminal_value), "plies": int(self.plies), "search": self.search,
+                "sims": int(self.sims), "c_puct": float(self.c_puct)}
 
-    def policy_fn(self, deterministic=True):
-        return lambda b, d, t: self.model.act(b, d, deterministic=deterministic, generator=self.gen)[0]
-
-    def save(self, path):
-        torch.save({"algorithm": self.algorithm, "fused": True, "params": self.params, "sq_avg": self.sq_avg,
-                    "num_timesteps": self.num_timesteps, "best_score": float(self.best_score), "terminal_value": float(self.terminal_value),
-                    "plies": int(self.plies), "search": self.search, "sims": int(self.sims), "c_puct": float(self.c_puct),
-                    **self._opponent_state()}, path)
-
-    def load(self, path):
-        sd = torch.load(path, map_location=self.device, weights_only=True)
-        if sd.get("algorithm", "A2C") != self.algorithm or not sd.get("fused", False):
-            raise ValueError("checkpoint %s was not written by the search-distillation trainer" % path)
-        self.params.copy_(sd["params"])
+    def _load_state(self, sd):
         self.sq_avg.copy_(sd["sq_avg"])
-        self.num_timesteps = sd["num_timesteps"]
-        self.best_score = float(sd.get("best_score", -1.0))
         self.terminal_value = float(sd.get("terminal_value", self.terminal_value))
         self.plies = int(sd.get("plies", self.plies))
         self.search = sd.get("search", self.search)
         self.sims, self.c_puct = int(sd.get("sims", self.sims)), float(sd.get("c_puct", self.c_puct))
-        self._opponent_loaded(sd)

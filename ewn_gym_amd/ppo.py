@@ -19,10 +19,12 @@ per rollout here).  Multi-GPU: as in A2C, ONE flattened-gradient all-reduce per 
 Two trainers: PPOTrainer (torch forward per step + ewn_step, eager autograd per minibatch) and FusedPPOTrainer (the same arithmetic in the
 engine: ewn_step_k_policy + ewn_ppo_prepare / _shuffle / _grad / _apply, one hipGraph per update).
 """
+import ctypes as C
+
 import torch
 import torch.nn as nn
 
-from .a2c import A2CTrainer, PolicyOpponent, all_reduce_gradients, n_step_returns
+from .a2c import A2CTrainer, FusedTrainer, all_reduce_gradients, n_step_returns
 
 
 class PPOTrainer(A2CTrainer):
@@ -85,73 +87,39 @@ class PPOTrainer(A2CTrainer):
         return stats
 
 
-class FusedPPOTrainer(PolicyOpponent):
+class FusedPPOTrainer(FusedTrainer):
     """PPOTrainer's update with the whole loop in the engine: the n-step rollout is ONE kernel (ewn_step_k_policy), then
     ewn_ppo_prepare (behaviour-policy log-probabilities, values, GAE advantages and returns of every sample), ewn_ppo_shuffle (every
     epoch's minibatch order, on the device) and per minibatch ewn_ppo_grad (value pass, policy pass, reduction) + ewn_ppo_apply
     (global-norm clip + Adam) -- no torch operator on the training path; with several ranks one all-reduce of the flat gradient between
-    grad and apply per minibatch.  Same knobs, defaults and arithmetic as PPOTrainer; the parameters live in ONE flat fp32 tensor that
-    the torch module `self.model` views (evaluation, checkpoints), the Adam state in two more and the step count in a device int32 (which
-    also keys the shuffle: a replayed graph draws a new order every update)."""
+    grad and apply per minibatch.  Same knobs, defaults and arithmetic as PPOTrainer; the flat parameters and the loop are
+    a2c.FusedTrainer's, the Adam state lives in two more flat tensors and the step count in a device int32 (which also keys the shuffle:
+    a replayed graph draws a new order every update)."""
 
     algorithm = "PPO"
-    best_score = -1.0
+    _use_instead = ": use PPOTrainer"
 
     def __init__(self, env, n_steps=32, batch_size=None, n_epochs=10, learning_rate=3e-4, gamma=0.99, gae_lambda=0.95, clip_range=0.2,
                  normalize_advantage=True, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, seed=None, use_graph=True, opponent=None,
                  opponent_update_every=100, opponent_deterministic=False):
-        import ctypes as C
-        import torch.distributed as dist
         from . import _lib
-        from .a2c import ActorCritic
-        if opponent is None and not env.supports_policy_rollout():
-            raise _lib.EwnError("this env configuration has no policy-driven rollout kernel (ewn_step_k_policy): use PPOTrainer")
-        self.env, self.lib, self.C = env, env.lib, C
-        self.device = env.board.device
-        if seed is not None:
-            torch.manual_seed(seed)
-        self.model = ActorCritic(env.S, env.cube_num).to(self.device)
-        self.params = self.model.flat_parameters()
-        off = 0
-        for p in self.model.parameters():
-            p.data = self.params[off:off + p.numel()].view_as(p)
-            off += p.numel()
-        assert off == env.policy_param_count()
-        self._sync_parameters()
-        self._init_opponent(opponent, opponent_update_every, opponent_deterministic, seed)
+        super().__init__(env, n_steps, seed, use_graph, opponent, opponent_update_every, opponent_deterministic)
         self.exp_avg = torch.zeros_like(self.params)
         self.exp_avg_sq = torch.zeros_like(self.params)
         self.step = torch.zeros(1, dtype=torch.int32, device=self.device)   # Adam steps taken; also keys the shuffle
-        self.grad = torch.zeros(self.params.numel() + 8, dtype=torch.float32, device=self.device)
-        self.grad_norm = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self.n_steps, self.num_timesteps = int(n_steps), 0
         total = self.n_steps * env.N
         self.batch_size = max(1, total // 4) if batch_size is None else int(batch_size)
         if not 1 <= self.batch_size <= total:
             raise ValueError("batch_size %d outside [1, n_steps x lanes = %d]" % (self.batch_size, total))
         self.n_epochs = int(n_epochs)
         self.n_minibatches = total // self.batch_size          # whole minibatches only, as PPOTrainer
-        self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         self.hyper = _lib.EwnPpoHyper(float(gamma), float(gae_lambda), float(clip_range), float(vf_coef), float(ent_coef), float(max_grad_norm),
                                       float(learning_rate), 0.9, 0.999, 1e-5, int(bool(normalize_advantage)), int(self.world))
         nscr = _lib.check(self.lib.ewn_ppo_scratch_bytes(C.byref(env.cfg), self.n_steps, self.batch_size), "ewn_ppo_scratch_bytes")
         self.scratch = torch.zeros(int(nscr), dtype=torch.uint8, device=self.device)
         self.samples = torch.zeros((total, 4), dtype=torch.float32, device=self.device)   # {old log pi, adv, ret, old value} per sample
         self.perm = torch.zeros((self.n_epochs, total), dtype=torch.int32, device=self.device)
-        self.traj = env.alloc_rollout(self.n_steps, layout="record", initial_obs=True)
-        self.noise_key = (0 if seed is None else int(seed)) * 0x9E3779B97F4A7C15 & 0xFFFFFFFFFFFFFFFF
         self.shuffle_key = ((0 if seed is None else int(seed)) * 31 + 17) & 0xFFFFFFFFFFFFFFFF
-        self.gen = torch.Generator(device=self.device)                # policy_fn's sampling only
-        self.gen.manual_seed(0 if seed is None else int(seed))
-        self.force_collective = False
-        self.use_graph = use_graph and self.world == 1
-        self._graph = None
-        self._warm = False
-
-    def _sync_parameters(self):
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            dist.broadcast(self.params, src=0)
 
     def launches_per_update(self):
         """kernel launches of one update: rollout, prepare, shuffle, then per minibatch 3 (grad) + 1 (apply)"""
@@ -160,7 +128,7 @@ class FusedPPOTrainer(PolicyOpponent):
     def _launch(self):
         from ._lib import check
         from .vec_env import _ptr, _stream
-        C, env, lib = self.C, self.env, self.lib
+        env, lib = self.env, self.lib
         K, total, B = self.n_steps, self.n_steps * env.N, self.batch_size
         cfg, hp = C.byref(env.cfg), C.byref(self.hyper)
         rec, params, samples, grad, scratch = _ptr(self.traj["record"]), _ptr(self.params), _ptr(self.samples), _ptr(self.grad), _ptr(self.scratch)
@@ -172,26 +140,9 @@ class FusedPPOTrainer(PolicyOpponent):
             for m in range(self.n_minibatches):
                 idx = C.c_void_p(base + 4 * (e * total + m * B))
                 check(lib.ewn_ppo_grad(cfg, K, rec, samples, params, hp, idx, B, grad, scratch, _stream()), "ewn_ppo_grad")
-                if self.world > 1 or self.force_collective:   # the one collective per optimiser step: the flat gradient, summed
-                    import torch.distributed as dist
-                    dist.all_reduce(self.grad, op=dist.ReduceOp.SUM)
+                self._all_reduce_grad()                       # per optimiser step
                 check(lib.ewn_ppo_apply(cfg, params, _ptr(self.exp_avg), _ptr(self.exp_avg_sq), _ptr(self.step), grad, hp,
                                         _ptr(self.grad_norm), _stream()), "ewn_ppo_apply")
-
-    def collect_and_update(self):
-        if self.use_graph and self._warm:
-            if self._graph is None:       # one stream, no parallel branches: captured once, replayed per update
-                torch.cuda.synchronize()
-                self._graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self._graph):
-                    self._launch()
-            self._graph.replay()
-        else:
-            self._launch()
-            self._warm = True
-        self._after_update()
-        self.num_timesteps += self.n_steps * self.env.N
-        return self.grad
 
     def stats_dict(self):
         """PPOTrainer's keys (the last minibatch's losses) plus clip_fraction, approx_kl (mean of (r - 1) - log r) and grad_norm"""
@@ -202,45 +153,30 @@ class FusedPPOTrainer(PolicyOpponent):
                 "mean_reward": float(self.traj["reward"].mean()), "episodes": int(self.traj["terminated"].sum()),
                 "clip_fraction": cf, "approx_kl": kl, "grad_norm": float(self.grad_norm)}
 
-    def learn(self, total_timesteps):
-        target = self.num_timesteps + total_timesteps
-        while self.num_timesteps < target:
-            self.collect_and_update()
-        return self.stats_dict()
+    def _state(self):
+        return {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "step": self.step, "noise_key": self.noise_key,
+                "shuffle_key": self.shuffle_key}
 
-    def policy_fn(self, deterministic=True):
-        return lambda b, d, t: self.model.act(b, d, deterministic=deterministic, generator=self.gen)[0]
+    def _load_state(self, sd):
+        self.exp_avg.copy_(sd["exp_avg"])
+        self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+        self.step.copy_(sd["step"])
+        self.noise_key, self.shuffle_key = int(sd["noise_key"]), int(sd["shuffle_key"])   # the run continues with its own streams
 
-    def save(self, path):
-        torch.save({"algorithm": self.algorithm, "fused": True, "params": self.params, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq,
-                    "step": self.step, "noise_key": self.noise_key, "shuffle_key": self.shuffle_key, "num_timesteps": self.num_timesteps,
-                    "best_score": float(self.best_score), **self._opponent_state()}, path)
-
-    def load(self, path):
-        """a checkpoint of this trainer, or of PPOTrainer (its module state and Adam state mapped onto the flat vectors)"""
-        sd = torch.load(path, map_location=self.device, weights_only=True)
+    def _load_foreign(self, path, sd):
+        """a checkpoint of PPOTrainer: its module state and Adam state mapped onto the flat vectors"""
         algo = sd.get("algorithm", "A2C")
         if algo != self.algorithm:
             raise ValueError("checkpoint %s was written by the %s trainer, this is the %s trainer" % (path, algo, self.algorithm))
-        if sd.get("fused", False):
-            self.params.copy_(sd["params"])
-            self.exp_avg.copy_(sd["exp_avg"])
-            self.exp_avg_sq.copy_(sd["exp_avg_sq"])
-            self.step.copy_(sd["step"])
-            self.noise_key, self.shuffle_key = int(sd["noise_key"]), int(sd["shuffle_key"])   # the run continues with its own streams
-        else:
-            self.model.load_state_dict(sd["model"])   # copies into the views of self.params
-            state = sd["opt"]["state"]
-            off, step = 0, 0
-            for i, p in enumerate(self.model.parameters()):
-                st = state.get(i)
-                sl = slice(off, off + p.numel())
-                self.exp_avg[sl].copy_(st["exp_avg"].reshape(-1) if st else 0.0)
-                self.exp_avg_sq[sl].copy_(st["exp_avg_sq"].reshape(-1) if st else 0.0)
-                if st:
-                    step = int(st["step"])
-                off += p.numel()
-            self.step.fill_(step)
-        self.num_timesteps = sd["num_timesteps"]
-        self.best_score = float(sd.get("best_score", -1.0))
-        self._opponent_loaded(sd)
+        self.model.load_state_dict(sd["model"])   # copies into the views of self.params
+        state = sd["opt"]["state"]
+        off, step = 0, 0
+        for i, p in enumerate(self.model.parameters()):
+            st = state.get(i)
+            sl = slice(off, off + p.numel())
+            self.exp_avg[sl].copy_(st["exp_avg"].reshape(-1) if st else 0.0)
+            self.exp_avg_sq[sl].copy_(st["exp_avg_sq"].reshape(-1) if st else 0.0)
+            if st:
+                step = int(st["step"])
+            off += p.numel()
+        self.step.fill_(step)

@@ -36,6 +36,22 @@ def _describe(t):
     return "%s %s on %s%s" % (t.dtype, list(t.shape), t.device, "" if t.is_contiguous() else " (not contiguous)")
 
 
+def _is_buffer(t, dtype):
+    return isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_cuda and t.is_contiguous()
+
+
+def _check_buffer(who, name, t, dtype, lead, shape):
+    """ValueError unless t is a contiguous device tensor of `dtype` and shape [>= lead, *shape] (lead None: exactly `shape`)"""
+    if not (_is_buffer(t, dtype) and (tuple(t.shape) == shape if lead is None else
+                                      t.dim() == 1 + len(shape) and t.shape[0] >= lead and tuple(t.shape[1:]) == shape)):
+        dims = ([] if lead is None else [">= %d" % lead]) + [str(x) for x in shape]
+        raise ValueError("%s: %s must be a contiguous %s device tensor of shape [%s], got %s" % (
+            who, name, str(dtype).replace("torch.", ""), ", ".join(dims), _describe(t)))
+
+
+_TOTALS = {"return_sum": torch.float64, "n_steps": torch.int32, "n_episodes": torch.int32, "n_wins": torch.int32}
+
+
 def _no_initial_obs(traj):
     if "obs_board" in traj:
         raise ValueError("this trajectory was allocated with initial_obs=True (K + 1 record rows, the step views start at row 1): that "
@@ -135,7 +151,7 @@ class VecEWN:
 
     # -- step(actions) (envs/ewn.py:436-486 / envs/training_ewn.py:43-99)
     def step(self, actions):
-        if not (isinstance(actions, torch.Tensor) and actions.dtype == torch.int8 and actions.is_cuda and actions.is_contiguous()):
+        if not _is_buffer(actions, torch.int8):
             actions = self._actions.copy_(torch.as_tensor(actions).reshape(self.N, 2))
         assert actions.numel() == 2 * self.N
         if self._opp_model is not None:
@@ -167,10 +183,7 @@ class VecEWN:
             return
         act3 = None
         if opponent_action is not None:
-            if not (isinstance(opponent_action, torch.Tensor) and opponent_action.dtype == torch.int8 and opponent_action.is_cuda
-                    and opponent_action.is_contiguous() and tuple(opponent_action.shape) == (self.N, 3)):
-                raise ValueError("set_opponent_model: opponent_action must be a contiguous int8 device tensor of shape [%d, 3], got %s" % (
-                    self.N, _describe(opponent_action)))
+            _check_buffer("set_opponent_model", "opponent_action", opponent_action, torch.int8, None, (self.N, 3))
             act3 = opponent_action.unsqueeze(0)
         st = self._opponent_struct("set_opponent_model", 1, params, deterministic, noise_key, act3)
         if not self.supports_step_vs():
@@ -260,6 +273,38 @@ class VecEWN:
         return {"return_sum": torch.zeros(N, dtype=torch.float64, device=dev), "n_steps": torch.zeros(N, dtype=torch.int32, device=dev),
                 "n_episodes": torch.zeros(N, dtype=torch.int32, device=dev), "n_wins": torch.zeros(N, dtype=torch.int32, device=dev)}
 
+    def _check_traj(self, who, K, traj):
+        """traj as alloc_rollout() makes it (either layout, without the initial-observation row), at least K steps long"""
+        if not isinstance(traj, dict):
+            raise ValueError("%s: traj must be the dict of alloc_rollout(), got %s" % (who, type(traj).__name__))
+        _no_initial_obs(traj)
+        N, S = self.N, self.S
+        cols = {"board": (torch.int8, (N, S, S)), "dice": (torch.int8, (N,)), "action": (torch.int8, (N, 2)),
+                "reward": (torch.float64, (N,)), "terminated": (torch.uint8, (N,)), "truncated": (torch.uint8, (N,)),
+                "info": (torch.uint8, (N,)), "record": (torch.uint8, (N, (S * S + 6 + 15) & ~15))}
+        for name, t in traj.items():
+            if name not in cols:
+                raise ValueError("%s: unknown trajectory entry %r" % (who, name))
+            if "record" not in traj or name in ("record", "reward"):   # the record layout's column entries are views, not buffers
+                _check_buffer(who, "traj[%r]" % name, t, cols[name][0], K, cols[name][1])
+
+    def _check_totals(self, who, totals, required=False):
+        """totals as alloc_totals() makes it; required: all four entries, else any subset"""
+        if not isinstance(totals, dict):
+            raise ValueError("%s: totals must be the dict of alloc_totals(), got %s" % (who, type(totals).__name__))
+        for name in (_TOTALS if required else totals):
+            if name not in _TOTALS:
+                raise ValueError("%s: unknown totals entry %r" % (who, name))
+            _check_buffer(who, "totals[%r]" % name, totals.get(name), _TOTALS[name], None, (self.N,))
+
+    @staticmethod
+    def _rollout_out(traj, totals):
+        col = (lambda k: None) if "record" in traj else traj.get   # record layout: the column entries are views, not buffers
+        return EwnRolloutOut(_ptr(col("board")), _ptr(col("dice")), _ptr(col("action")), _ptr(traj.get("reward")),
+                             _ptr(col("terminated")), _ptr(col("truncated")), _ptr(col("info")),
+                             _ptr(totals.get("return_sum")), _ptr(totals.get("n_steps")), _ptr(totals.get("n_episodes")),
+                             _ptr(totals.get("n_wins")), _ptr(traj.get("record")))
+
     def rollout(self, K, agent="random", agent_max_depth=3, traj=None, totals=None, opponent_action=None):
         """Play K steps of every lane in one launch, the agent being RandomAgent ("random"), ExpectiMinimaxAgent(agent_max_depth)
         ("minimax") or env.action_space.sample() ("sample": all six actions, illegal ones included).
@@ -269,14 +314,9 @@ class VecEWN:
         traj, totals = traj or {}, totals or {}
         if opponent_action is not None and self._opp_model is None:
             raise ValueError("rollout: opponent_action needs a model opponent (set_opponent_model)")
-        _no_initial_obs(traj)
-        for v in traj.values():
-            assert v.shape[0] >= K and v.shape[1] == self.N
-        col = (lambda k: None) if "record" in traj else traj.get   # record layout: the column entries are views, not buffers
-        out = EwnRolloutOut(_ptr(col("board")), _ptr(col("dice")), _ptr(col("action")), _ptr(traj.get("reward")),
-                            _ptr(col("terminated")), _ptr(col("truncated")), _ptr(col("info")),
-                            _ptr(totals.get("return_sum")), _ptr(totals.get("n_steps")), _ptr(totals.get("n_episodes")),
-                            _ptr(totals.get("n_wins")), _ptr(traj.get("record")))
+        self._check_traj("rollout", K, traj)
+        self._check_totals("rollout", totals)
+        out = self._rollout_out(traj, totals)
         if self._opp_model is not None:
             opp = self._model_opponent("rollout", K, opponent_action)
             check(self.lib.ewn_step_k_vs(C.byref(self.cfg), C.byref(self._st), int(K), AGENT[agent], int(agent_max_depth), C.byref(opp),
@@ -293,14 +333,9 @@ class VecEWN:
         if self._opp_model is not None:
             raise _lib.EwnError("bind_rollout: a model opponent is set; use rollout() (ewn_step_k_vs)")
         traj, totals = traj or {}, totals or {}
-        _no_initial_obs(traj)
-        for v in traj.values():
-            assert v.shape[0] >= K and v.shape[1] == self.N
-        col = (lambda k: None) if "record" in traj else traj.get
-        out = EwnRolloutOut(_ptr(col("board")), _ptr(col("dice")), _ptr(col("action")), _ptr(traj.get("reward")),
-                            _ptr(col("terminated")), _ptr(col("truncated")), _ptr(col("info")),
-                            _ptr(totals.get("return_sum")), _ptr(totals.get("n_steps")), _ptr(totals.get("n_episodes")),
-                            _ptr(totals.get("n_wins")), _ptr(traj.get("record")))
+        self._check_traj("bind_rollout", K, traj)
+        self._check_totals("bind_rollout", totals)
+        out = self._rollout_out(traj, totals)
         fn, cfg, st, outp = self.lib.ewn_step_k, C.byref(self.cfg), C.byref(self._st), C.byref(out)
         k, a, d = int(K), AGENT[agent], int(agent_max_depth)
         keep = (out, traj, totals)
@@ -330,17 +365,21 @@ class VecEWN:
         return self.tables is not None and self.lib.ewn_policy_eval_vs_supported(C.byref(self.cfg)) == 1
 
     def _opponent_struct(self, what, K, opponent_params, deterministic, noise_key, action):
-        N = self.N
-        if not (isinstance(opponent_params, torch.Tensor) and opponent_params.dtype == torch.float32 and opponent_params.is_cuda
-                and opponent_params.is_contiguous() and opponent_params.dim() == 1 and opponent_params.numel() == self.policy_param_count()):
-            raise ValueError("%s: opponent_params must be a contiguous float32 device vector of %d elements, got %s" % (
-                what, self.policy_param_count(), _describe(opponent_params)))
-        if action is not None and not (isinstance(action, torch.Tensor) and action.dtype == torch.int8 and action.is_cuda
-                                       and action.is_contiguous() and action.dim() == 3 and action.shape[0] >= K
-                                       and tuple(action.shape[1:]) == (N, 3)):
-            raise ValueError("%s: opponent_action must be a contiguous int8 device tensor of shape [>= %d, %d, 3], got %s" % (
-                what, K, N, _describe(action)))
+        _check_buffer(what, "opponent_params", opponent_params, torch.float32, None, (self.policy_param_count(),))
+        if action is not None:
+            _check_buffer(what, "opponent_action", action, torch.int8, K, (self.N, 3))
         return EwnOpponentPolicy(_ptr(opponent_params), int(bool(deterministic)), int(noise_key) & 0xFFFFFFFFFFFFFFFF, _ptr(action))
+
+    def _resolve_opponent(self, what, K, opponent_params, deterministic, noise_key, action):
+        """the opponent of a policy-driven K-step call: the set model, as set_opponent_model configured it; else opponent_params; else
+        None (the env's own opponent)"""
+        if opponent_params is not None:
+            return self._opponent_struct(what, K, opponent_params, deterministic, noise_key, action)
+        if self._opp_model is not None:
+            return self._model_opponent(what, K, action)
+        if action is not None:
+            raise ValueError("%s: opponent_action needs opponent_params" % what)
+        return None
 
     def rollout_policy(self, K, params, traj=None, totals=None, deterministic=False, noise_key=0, logits=None, value=None, noise=None,
                        opponent_params=None, opponent_deterministic=False, opponent_noise_key=0, opponent_action=None):
@@ -354,18 +393,10 @@ class VecEWN:
         traj, totals = traj or {}, totals or {}
         assert params.dtype == torch.float32 and params.is_contiguous() and params.numel() == self.policy_param_count()
         N = self.N
-        if opponent_params is None and self._opp_model is not None:   # the set model plays, as set_opponent_model configured it
-            opp = self._model_opponent("rollout_policy", K, opponent_action)
-        elif opponent_params is None and opponent_action is not None:
-            raise ValueError("rollout_policy: opponent_action needs opponent_params")
-        else:
-            opp = None if opponent_params is None else self._opponent_struct("rollout_policy", K, opponent_params, opponent_deterministic,
-                                                                             opponent_noise_key, opponent_action)
+        opp = self._resolve_opponent("rollout_policy", K, opponent_params, opponent_deterministic, opponent_noise_key, opponent_action)
         for name, t, shape in (("logits", logits, (N, 5)), ("value", value, (N,)), ("noise", noise, (N, 5))):
-            if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_cuda and t.is_contiguous()
-                                      and t.dim() == 1 + len(shape) and t.shape[0] >= K and tuple(t.shape[1:]) == shape):
-                raise ValueError("rollout_policy: %s must be a contiguous float32 device tensor of shape [>= %d, %s], got %s" % (
-                    name, K, ", ".join(map(str, shape)), _describe(t)))
+            if t is not None:
+                _check_buffer("rollout_policy", name, t, torch.float32, K, shape)
         rec0 = 0
         if "record" in traj:
             rec0 = 1 if "obs_board" in traj else 0
@@ -376,11 +407,7 @@ class VecEWN:
             if t.shape[0] < K or t.shape[1] != N or ("record" not in traj and not t.is_contiguous()):
                 raise ValueError("rollout_policy: traj[%r] must have shape [>= %d, %d, ...]%s, got %s" % (
                     name, K, N, "" if "record" in traj else " and be contiguous", _describe(t)))
-        col = (lambda k: None) if "record" in traj else traj.get
-        out = EwnRolloutOut(_ptr(col("board")), _ptr(col("dice")), _ptr(col("action")), _ptr(traj.get("reward")),
-                            _ptr(col("terminated")), _ptr(col("truncated")), _ptr(col("info")),
-                            _ptr(totals.get("return_sum")), _ptr(totals.get("n_steps")), _ptr(totals.get("n_episodes")),
-                            _ptr(totals.get("n_wins")), _ptr(traj.get("record")))
+        out = self._rollout_out(traj, totals)
         pol = EwnPolicy(_ptr(params), int(bool(deterministic)), rec0, int(noise_key) & 0xFFFFFFFFFFFFFFFF, _ptr(logits), _ptr(value), _ptr(noise))
         if opp is not None:
             check(self.lib.ewn_step_k_selfplay(C.byref(self.cfg), C.byref(self._st), int(K), C.byref(pol), C.byref(opp), C.byref(out),
@@ -408,32 +435,12 @@ class VecEWN:
         opponent_params: a second parameter vector that plays the opponent instead of the env's own (ewn_policy_eval_vs; its argmax
         unless opponent_deterministic=False); opponent_action: optional int8 [>= K, N, 3], the opponent's {dice, flag, dir} of the steps a
         lane plays ({0, 0, 0}: it did not move)."""
-        N = self.N
-        if opponent_params is None and self._opp_model is not None:   # the set model plays, as set_opponent_model configured it
-            opp = self._model_opponent("eval_policy", K, opponent_action)
-        elif opponent_params is None and opponent_action is not None:
-            raise ValueError("eval_policy: opponent_action needs opponent_params")
-        else:
-            opp = None if opponent_params is None else self._opponent_struct("eval_policy", K, opponent_params, opponent_deterministic,
-                                                                             opponent_noise_key, opponent_action)
-        if not (isinstance(params, torch.Tensor) and params.dtype == torch.float32 and params.is_cuda and params.is_contiguous()
-                and params.dim() == 1 and params.numel() == self.policy_param_count()):
-            raise ValueError("eval_policy: params must be a contiguous float32 device vector of %d elements, got %s" % (
-                self.policy_param_count(), _describe(params)))
-        if not isinstance(totals, dict):
-            raise ValueError("eval_policy: totals must be the dict of alloc_totals(), got %s" % type(totals).__name__)
-        for name, dt in (("return_sum", torch.float64), ("n_steps", torch.int32), ("n_episodes", torch.int32), ("n_wins", torch.int32)):
-            t = totals.get(name)
-            if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (N,)):
-                raise ValueError("eval_policy: totals[%r] must be a contiguous %s device tensor of shape [%d], got %s" % (
-                    name, str(dt).replace("torch.", ""), N, _describe(t)))
-        if action is not None and not (isinstance(action, torch.Tensor) and action.dtype == torch.int8 and action.is_cuda
-                                       and action.is_contiguous() and action.dim() == 3 and action.shape[0] >= K
-                                       and tuple(action.shape[1:]) == (N, 2)):
-            raise ValueError("eval_policy: action must be a contiguous int8 device tensor of shape [>= %d, %d, 2], got %s" % (
-                K, N, _describe(action)))
-        out = EwnRolloutOut(None, None, _ptr(action), None, None, None, None, _ptr(totals["return_sum"]), _ptr(totals["n_steps"]),
-                            _ptr(totals["n_episodes"]), _ptr(totals["n_wins"]), None)
+        opp = self._resolve_opponent("eval_policy", K, opponent_params, opponent_deterministic, opponent_noise_key, opponent_action)
+        _check_buffer("eval_policy", "params", params, torch.float32, None, (self.policy_param_count(),))
+        self._check_totals("eval_policy", totals, required=True)
+        if action is not None:
+            _check_buffer("eval_policy", "action", action, torch.int8, K, (self.N, 2))
+        out = self._rollout_out({"action": action}, totals)
         if opp is not None:
             check(self.lib.ewn_policy_eval_vs(C.byref(self.cfg), C.byref(self._st), int(K), _ptr(params), C.byref(opp), C.byref(out),
                                               _stream()), "ewn_policy_eval_vs")
@@ -482,37 +489,9 @@ class VecEWN:
         if a is None:
             raise ValueError("agent_rollout: agent must be {\"kind\": \"mcts\"|\"minimax\", ...} with a known heuristic, got %r" % (agent,))
         traj, totals = traj or {}, totals or {}
-        if not isinstance(traj, dict) or not isinstance(totals, dict):
-            raise ValueError("agent_rollout: traj / totals must be the dicts of alloc_rollout() / alloc_totals()")
-        _no_initial_obs(traj)
-        N, S = self.N, self.S
-        stride = (S * S + 6 + 15) & ~15
-        cols = {"board": (torch.int8, (N, S, S)), "dice": (torch.int8, (N,)), "action": (torch.int8, (N, 2)),
-                "reward": (torch.float64, (N,)), "terminated": (torch.uint8, (N,)), "truncated": (torch.uint8, (N,)),
-                "info": (torch.uint8, (N,)), "record": (torch.uint8, (N, stride))}
-        record = "record" in traj
-        for name, t in traj.items():
-            if name not in cols:
-                raise ValueError("agent_rollout: unknown trajectory entry %r" % name)
-            if record and name not in ("record", "reward"):
-                continue            # the record layout's column entries are views into the records, not buffers of their own
-            dt, shape = cols[name]
-            if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_cuda and t.is_contiguous() and t.dim() == 1 + len(shape)
-                    and t.shape[0] >= K and tuple(t.shape[1:]) == shape):
-                raise ValueError("agent_rollout: traj[%r] must be a contiguous %s device tensor of shape [>= %d, %s], got %s" % (
-                    name, str(dt).replace("torch.", ""), K, ", ".join(str(x) for x in shape), _describe(t)))
-        for name, t in totals.items():
-            dt = {"return_sum": torch.float64, "n_steps": torch.int32, "n_episodes": torch.int32, "n_wins": torch.int32}.get(name)
-            if dt is None:
-                raise ValueError("agent_rollout: unknown totals entry %r" % name)
-            if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (N,)):
-                raise ValueError("agent_rollout: totals[%r] must be a contiguous %s device tensor of shape [%d], got %s" % (
-                    name, str(dt).replace("torch.", ""), N, _describe(t)))
-        col = (lambda k: None) if record else traj.get
-        out = EwnRolloutOut(_ptr(col("board")), _ptr(col("dice")), _ptr(col("action")), _ptr(traj.get("reward")),
-                            _ptr(col("terminated")), _ptr(col("truncated")), _ptr(col("info")),
-                            _ptr(totals.get("return_sum")), _ptr(totals.get("n_steps")), _ptr(totals.get("n_episodes")),
-                            _ptr(totals.get("n_wins")), _ptr(traj.get("record")))
+        self._check_traj("agent_rollout", K, traj)
+        self._check_totals("agent_rollout", totals)
+        out = self._rollout_out(traj, totals)
         check(self.lib.ewn_step_k_agent(C.byref(self.cfg), C.byref(self._st), int(K), C.byref(a), C.byref(out), _stream()),
               "ewn_step_k_agent")
         return self.board, self.dice
