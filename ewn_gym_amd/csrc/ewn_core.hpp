@@ -265,6 +265,10 @@ EWN_DEV void legal_nth(const Geom &g, const GState<NW> &s, int dice, int n, int 
     for_each_legal<SIDE, NW>(g, s, dice, [&](int fl, int kk, int dr) { if (i == n) { flag = fl; k = kk; dir = dr; } i++; return i <= n; });
 }
 
+// an action (flag, dir) as one 16-bit word: how the int8 [.][2] action arrays are read and written, one access per lane
+EWN_DEV uint16_t pack_action(int flag, int dir) { return (uint16_t)((uint8_t)flag | ((uint16_t)(uint8_t)dir << 8)); }
+EWN_DEV void unpack_action(uint16_t a2, int &flag, int &dir) { flag = (int8_t)(a2 & 0xff); dir = (int8_t)(a2 >> 8); }
+
 // ---------------------------------------------------------------- heuristics
 
 // min over a side's cubes of max(S-1-row, S-1-col): BOTH sides are measured to the

@@ -123,17 +123,18 @@ static inline void fill_trajectory(Buf &b, const ewn_rollout_out *out)
 // bytes per game of the LDS staging area of the one-thread-per-game K-step kernels: a record of ewn_rollout_out.record (or a board)
 static inline int traj_record_stride(const Geom &g) { return EWN_TRAJ_RECORD_STRIDE(g.S); }
 
+// SV = the board size of a table-driven kernel instance as a compile-time constant, in the style of BY_NW.  Serves the sizes with a
+// table image, 5 .. 8: every caller has established fast_tables_bytes(S, L) > 0 first, so the last case takes what is left.
+#define BY_S(S, X) do { switch (S) { case 5: { constexpr int SV = 5; X; } break; case 6: { constexpr int SV = 6; X; } break; \
+                                     case 7: { constexpr int SV = 7; X; } break; default: { constexpr int SV = 8; X; } break; } } while (0)
+
 // specialised depth-3 tables exist for cube_layer 3 and board sizes whose distinct leaf values fit 10-bit ranks
 static inline int64_t fast_tables_bytes(int S, int L)
 {
-    if (L != 3) return 0;
-    switch (S) {
-    case 5: return (int64_t)FAST_TAB_BYTES(5);
-    case 6: return (int64_t)FAST_TAB_BYTES(6);
-    case 7: return (int64_t)FAST_TAB_BYTES(7);
-    case 8: return (int64_t)FAST_TAB_BYTES(8);
-    default: return 0;
-    }
+    if (L != 3 || S < 5 || S > 8) return 0;
+    int64_t bytes = 0;
+    BY_S(S, bytes = (int64_t)FAST_TAB_BYTES(SV));
+    return bytes;
 }
 
 // table image of a search with the given heuristic and max_depth: max_depth 4 and 6 read the image's second variant (leaves
@@ -188,12 +189,50 @@ static inline int rollout_threads_per_game(int n_games)
     return 2;
 }
 
-// ewn_step_d3.hip: the lean table-driven step kernel (one launch = one env step)
+// The MT19937-compat windows of an auto-resetting lane are rebuilt BETWEEN launches (ewn_core.hpp): ewn_step queues refills for
+// them, and a launch that plays several episodes of a lane (every K-step kernel) cannot use the kind -- it is refused there.
+// Without auto-reset (one episode per lane: evaluation) the kind is fine everywhere.
+static inline bool mt_autoreset(const ewn_config *cfg) { return cfg->rng_kind == EWN_RNG_MT19937 && cfg->autoreset; }
+
+// What ewn_step launches for a configuration: the ONE place that decides it.  ewn_step, ewn_step_scratch_bytes (which path needs
+// which scratch), ewn_lanes_per_game(cfg, 0) (what the tests assert kernel families through) and the lean kernel's launcher
+// (ewn_step_d3_tu.inc) all read it.
+//   STEP_SPLIT        the opponent's policy runs as kernels of its own between two half steps (MCTS, minimax 'sim_winrate')
+//   STEP_LEAN_TABLES  k_step_d3, T lanes per game, table-driven search (the 'two_min_dist' image: ewn_step_d3_h2.hip's instances)
+//   STEP_LEAN_RANDOM  k_step_d3 against RandomAgent, one lane per game
+//   STEP_TABLES       k_step<1, 0, S>: one thread per game, the search from a table image (EWN_D3_T=0)
+//   STEP_GENERIC      k_step<NW, 0, 0>: any geometry, RandomAgent or the template-recursive search
+// have_tables: the caller's state carries the table images (ewn_state.tables); a query without a state assumes it does.
+enum StepPath { STEP_SPLIT, STEP_LEAN_TABLES, STEP_LEAN_RANDOM, STEP_TABLES, STEP_GENERIC };
+struct StepPlan { StepPath path; int T; };   // T: lanes per game of the lean kernel, 0 on the other paths
+
+static inline StepPlan step_plan(const ewn_config *cfg, const Geom &g, const KCfg &k, bool have_tables)
+{
+    if (cfg->opponent_kind == EWN_OPP_MCTS || (cfg->opponent_kind == EWN_OPP_MINIMAX && cfg->heuristic == EWN_H_SIM_WINRATE)) return { STEP_SPLIT, 0 };
+    const bool tab = have_tables && fast_tables_bytes(g.S, g.L) > 0;
+    // the one-thread-per-game kernel searches any table image; the lean kernel only those with instances of it (fast_heur_step)
+    const bool fast = tab && cfg->opponent_kind == EWN_OPP_MINIMAX && cfg->max_depth <= 6 && fast_heur_image(cfg->heuristic) >= 0;
+    const int T3 = d3_threads_per_game(k.N);
+    if (T3 > 0 && tab && cfg->opponent_kind == EWN_OPP_RANDOM) return { STEP_LEAN_RANDOM, 1 };
+    if (T3 > 0 && fast && fast_heur_step(cfg->heuristic)) {
+        // leaves are shared among lanes at depth 3-4; depth 5-6 splits its inner dice over two lanes while the chip is not full
+        const int T = cfg->max_depth < 3 ? 1 : (cfg->max_depth > 4 ? (k.N <= 131072 && T3 != 1 ? 2 : 1) : T3);
+        return { STEP_LEAN_TABLES, T };
+    }
+    return { fast ? STEP_TABLES : STEP_GENERIC, 0 };
+}
+
+// what every entry point that plays games needs of the caller's state; with the table images; the shaped-reward columns
+static inline bool state_ok(const ewn_state *st) { return st && st->board && st->dice && st->done && st->rng; }
+static inline bool state_tables_ok(const ewn_state *st) { return state_ok(st) && st->tables; }
+static inline bool shaped_ok(const ewn_config *cfg, const ewn_state *st) { return !cfg->shaped || (st->prev_score && st->tolerance); }
+
+// ewn_step_d3.hip: the lean table-driven step kernel (one launch = one env step); plan: step_plan's STEP_LEAN_* answer
 int ewn_launch_step_d3(const ewn_config *cfg, const Geom &g, const KCfg &k, const ewn_state *st, const void *tables, const int8_t *actions,
-                       const ewn_step_out *out, void *scratch, bool lean_random, bool fused_refill, hipStream_t s);
+                       const ewn_step_out *out, void *scratch, const StepPlan &plan, bool fused_refill, hipStream_t s);
 // ewn_step_d3_h2.hip: the same for the 'two_min_dist' table image
 int ewn_launch_step_d3_h2(const ewn_config *cfg, const Geom &g, const KCfg &k, const ewn_state *st, const void *tables, const int8_t *actions,
-                          const ewn_step_out *out, void *scratch, bool lean_random, bool fused_refill, hipStream_t s);
+                          const ewn_step_out *out, void *scratch, const StepPlan &plan, bool fused_refill, hipStream_t s);
 
 // ewn_rollout_s<S>.hip: K env steps per launch (ewn_rollout.hpp), one unit per board size
 struct RollCfg;

@@ -61,16 +61,53 @@ __device__ void policy_minimax(const Geom &g, const GState<NW> &s, int dice, int
     if (value) *value = v;
 }
 
+// DV = a search depth 1 .. 6 as a compile-time constant, in the style of BY_NW (device and host code).  Any other depth takes the
+// last case, the depth-6 instance: a site that refuses such a depth does so before it dispatches.
+#define BY_DEPTH(depth, X) do { switch (depth) { case 1: { constexpr int DV = 1; X; } break; case 2: { constexpr int DV = 2; X; } break; \
+                                                 case 3: { constexpr int DV = 3; X; } break; case 4: { constexpr int DV = 4; X; } break; \
+                                                 case 5: { constexpr int DV = 5; X; } break; default: { constexpr int DV = 6; X; } break; } } while (0)
+
 template <int NW>
 __device__ void policy_minimax_rt(const Geom &g, const GState<NW> &s, int dice, int depth, int heur, int &oflag, int &odir)
 {
-    switch (depth) {
-    case 1: policy_minimax<NW, 1>(g, s, dice, heur, oflag, odir, nullptr); break;
-    case 2: policy_minimax<NW, 2>(g, s, dice, heur, oflag, odir, nullptr); break;
-    case 3: policy_minimax<NW, 3>(g, s, dice, heur, oflag, odir, nullptr); break;
-    case 4: policy_minimax<NW, 4>(g, s, dice, heur, oflag, odir, nullptr); break;
-    case 5: policy_minimax<NW, 5>(g, s, dice, heur, oflag, odir, nullptr); break;
-    default: policy_minimax<NW, 6>(g, s, dice, heur, oflag, odir, nullptr); break;
+    BY_DEPTH(depth, (policy_minimax<NW, DV>(g, s, dice, heur, oflag, odir, nullptr)));
+}
+
+// One uniformly random legal move of SIDE (classical_policies/mcts.py:29-35): dice, legal list in the reference's
+// order as a 6-bit mask (larger-neighbour cube's dirs, then smaller-neighbour cube's), uniform pick, apply.
+template <int SIDE, int NW>
+EWN_DEV void rollout_ply(const Geom &g, GState<NW> &s, PlayoutRng &ps)
+{
+    u32 d0, frac;
+    ps.draw(d0, frac);
+    const int d = 1 + (int)d0; // random.randint(1, 6), mcts.py:29
+    const CubeSel cs = select_cubes(alive_of<SIDE>(s), d);
+    const bool have0 = cs.exact || cs.has_up, have1 = !cs.exact && cs.has_down;
+    const int k0 = cs.exact ? cs.k_exact : cs.k_up, k1 = cs.k_down;
+    const int p0 = pos_of<SIDE>(s, have0 ? k0 : 0), p1 = pos_of<SIDE>(s, have1 ? k1 : 0);
+    u32 okm = 0;
+    #pragma unroll
+    for (int dir = 0; dir < 3; dir++) {
+        okm |= ((have0 && dir_ok<SIDE>(g, p0, dir)) ? 1u : 0u) << dir;
+        okm |= ((have1 && dir_ok<SIDE>(g, p1, dir)) ? 1u : 0u) << (3 + dir);
+    }
+    const int n = __popc(okm);
+    const int pick = (int)PlayoutRng::pick(frac, (u32)n);
+    u32 m = okm;
+    for (int i = 0; i < pick; i++) m &= m - 1;
+    const int slot = __ffs((int)m) - 1;
+    if (n > 0) apply_move<SIDE, NW>(g, s, slot < 3 ? k0 : k1, slot < 3 ? slot : slot - 3);
+}
+
+// A uniformly random playout to the end (mcts.py:29-41, minimax_ewn.py:222-232): the sides alternate, `first` (0 TOP_LEFT,
+// 1 BOTTOM_RIGHT) moving first; at most 1024 plies.  SimLeaf below keeps its own loop: its side to move is a chain across playouts.
+template <int NW>
+EWN_DEV void playout_to_end(const Geom &g, GState<NW> &s, PlayoutRng &ps, int first)
+{
+    int cur = first;
+    for (int ply = 0; ply < 1024 && !is_win<NW>(g, s); ply++) {
+        if (cur == 0) rollout_ply<0, NW>(g, s, ps); else rollout_ply<1, NW>(g, s, ps);
+        cur ^= 1;
     }
 }
 
@@ -153,8 +190,8 @@ __global__ __launch_bounds__(BS) void k_step(Geom g, KCfg c, KState st, const in
         hdr = *rng_hdr_ptr(st.rng, lane);
         dice = st.dice[lane];
         frozen = st.done[lane] != 0;
-        if (PHASE != 2) { const uint16_t a2 = ((const uint16_t *)actions)[lane]; aflag = (int8_t)(a2 & 0xff); adir = (int8_t)(a2 >> 8); }
-        else { pending = sc.phase[lane] != 0; const uint16_t a2 = ((const uint16_t *)sc.act)[lane]; aflag = (int8_t)(a2 & 0xff); adir = (int8_t)(a2 >> 8); }
+        if (PHASE == 2) pending = sc.phase[lane] != 0;
+        unpack_action(((const uint16_t *)(PHASE != 2 ? actions : sc.act))[lane], aflag, adir);
     }
     block_copy_in(lds, st.board + (size_t)lane0 * g.cells, nl * g.cells);
     if (PHASE == 2 && out.tboard) block_copy_in(lds_t, out.tboard + (size_t)lane0 * g.cells, nl * g.cells);
@@ -175,7 +212,7 @@ __global__ __launch_bounds__(BS) void k_step(Geom g, KCfg c, KState st, const in
                 }
                 if (out.tboard) for (int i = 0; i < g.cells; i++) mine_t[i] = mine[i];
                 if (out.tdice) out.tdice[lane] = (int8_t)dice;
-                if (out.ract) ((uint16_t *)out.ract)[lane] = 0;
+                if (out.ract) ((uint16_t *)out.ract)[lane] = pack_action(0, 0);
             } else {
                 LaneRng r; r.load(c.rng_kind, hdr, rng_win_ptr(st.rng, c.N, c.W, lane, RNGF_CUR(hdr.w)), c.W, c.key);
                 if (PHASE != 2) r.begin_kernel();
@@ -196,7 +233,7 @@ __global__ __launch_bounds__(BS) void k_step(Geom g, KCfg c, KState st, const in
                         sc.cdice[lane] = (int8_t)dice;
                         sc.obs_id[lane] = r.seed_mix() * 0x9E3779B1u + r.draws();
                         settled = false;
-                        if (c.opp == EWN_OPP_MCTS) n_root = for_each_legal<0, NW>(g, cst, dice, [](int, int, int) { return true; });
+                        if (c.opp == EWN_OPP_MCTS) n_root = legal_count<0, NW>(g, cst, dice);
                     }
                     // flat Monte-Carlo opponent: the win counters of the root moves start here (0 = a move to play out, -1 = no
                     // such move / no reply pending) -- what k_mcts_init does for the stateless policy, without its launch
@@ -204,13 +241,12 @@ __global__ __launch_bounds__(BS) void k_step(Geom g, KCfg c, KState st, const in
                 } else if (reply) {
                     if (PHASE == 2 && c.opp == EWN_OPP_MCTS) {
                         // MctsAgent's choice, classical_policies/mcts.py:68: np.argmax over the root moves' wins (first maximum),
-                        // then that entry of the legal list of the canonical observation -- k_mcts_pick without its launch
-                        int best = 0, bw = -1;
-                        for (int i = 0; i < 6; i++) { const int w = sc.wins[(size_t)lane * 6 + i]; if (w > bw) { bw = w; best = i; } }
-                        const GState<NW> cst = canonicalize<NW>(g, s);
-                        int j = 0;
+                        // then that entry of the legal list of the canonical observation -- k_mcts_pick without its launch.  A reply is
+                        // pending only after an agent move that did not win, so the row holds a root move and argmax_wins' -1 (no
+                        // move) cannot come up here: starting the maximum at entry 0 or at "none" is the same thing.
+                        int k;
                         oflag = 0; odir = 0;
-                        for_each_legal<0, NW>(g, cst, dice, [&](int flag, int, int dir) { if (j == best) { oflag = flag; odir = dir; } j++; return j <= best; });
+                        legal_nth<0, NW>(g, canonicalize<NW>(g, s), dice, argmax_wins(sc.wins + (size_t)lane * 6), oflag, k, odir);
                     }
                     if constexpr (FAST != 0) {
                         const GState<1> cst = canonicalize<1>(g, s);
@@ -236,16 +272,12 @@ __global__ __launch_bounds__(BS) void k_step(Geom g, KCfg c, KState st, const in
                 encode_board<NW>(g, s, mine);
                 st.dice[lane] = (int8_t)dice;
                 if (settled && out.ract) { // RandomAgent.predict on the post-step observation
-                    int f = 0, d = 0;
+                    int f = 0, d = 0, k;
                     if (!(o.term && !c.autoreset)) {
-                        const int n = for_each_legal<0, NW>(g, s, dice, [](int, int, int) { return true; });
-                        if (n > 0) {
-                            const int pick = (int)__umulhi(agent_hash(r.seed_mix(), r.draws(), (u32)(c.lane_offset + lane), c.key), (u32)n);
-                            int i = 0;
-                            for_each_legal<0, NW>(g, s, dice, [&](int flag, int, int dir) { if (i == pick) { f = flag; d = dir; } i++; return i <= pick; });
-                        }
+                        const int n = legal_count<0, NW>(g, s, dice);
+                        if (n > 0) legal_nth<0, NW>(g, s, dice, (int)__umulhi(agent_hash(r.seed_mix(), r.draws(), (u32)(c.lane_offset + lane), c.key), (u32)n), f, k, d);
                     }
-                    ((uint16_t *)out.ract)[lane] = (uint16_t)((uint8_t)f | ((uint16_t)(uint8_t)d << 8));
+                    ((uint16_t *)out.ract)[lane] = pack_action(f, d);
                 }
             }
             if (settled) {
@@ -289,8 +321,6 @@ __global__ __launch_bounds__(BS) void k_legal(Geom g, int M, const int8_t *board
     if (n_acts) n_acts[m] = (int8_t)n;
 }
 
-template <int SIDE, int NW> EWN_DEV void rollout_ply(const Geom &g, GState<NW> &s, PlayoutRng &ps);
-
 template <int NW>
 __global__ __launch_bounds__(BS) void k_apply_action(Geom g, int M, const int8_t *boards, const int8_t *dice, int player,
                                                      const int8_t *actions, int8_t *new_boards, uint8_t *valid)
@@ -323,11 +353,7 @@ __global__ __launch_bounds__(BS) void k_playout_wins(Geom g, int M, int n_sims, 
     decode_board<NW>(g, boards + (size_t)m * g.cells, s);
     PlayoutRng ps;
     ps.seed(PlayoutRng::obs_word((u32)m, 0x53494D55u, key), (u32)r);
-    int cur = first_player == 1 ? 0 : 1;
-    for (int ply = 0; ply < 1024 && !is_win<NW>(g, s); ply++) {
-        if (cur == 0) rollout_ply<0, NW>(g, s, ps); else rollout_ply<1, NW>(g, s, ps);
-        cur ^= 1;
-    }
+    playout_to_end<NW>(g, s, ps, first_player == 1 ? 0 : 1);
     if (top_left_won<NW>(g, s)) atomicAdd(&wins[m], 1);
 }
 
@@ -427,16 +453,14 @@ __global__ __launch_bounds__(BS) void k_predict_random(Geom g, int M, const int8
     if (m >= M) return;
     GState<NW> s;
     decode_board<NW>(g, lds + threadIdx.x * g.cells, s);
-    int f = 0, dr = 0;
+    int f = 0, dr = 0, k;
     if (s.aliveP != 0 && d >= 1 && d <= g.CN) {
-        const int n = for_each_legal<0, NW>(g, s, d, [](int, int, int) { return true; });
         u32 o[4];
         philox4x32_10(step, (u32)(lane_offset + m), 0x41474E54u, 0u, (u32)key, (u32)(key >> 32), o);
-        const int pick = (int)__umulhi(o[0], (u32)n);
-        int i = 0;
-        for_each_legal<0, NW>(g, s, d, [&](int flag, int, int dir) { if (i == pick) { f = flag; dr = dir; } i++; return i <= pick; });
+        // an empty list: entry 0 of nothing, (0, 0) stays
+        legal_nth<0, NW>(g, s, d, (int)__umulhi(o[0], (u32)legal_count<0, NW>(g, s, d)), f, k, dr);
     }
-    ((uint16_t *)actions)[m] = (uint16_t)((uint8_t)f | ((uint16_t)(uint8_t)dr << 8));
+    ((uint16_t *)actions)[m] = pack_action(f, dr);
 }
 
 // ---------------------------------------------------------------- flat Monte-Carlo ("MCTS")
@@ -453,35 +477,9 @@ __global__ __launch_bounds__(BS) void k_mcts_init(Geom g, int M, const int8_t *b
         decode_board<NW>(g, boards + (size_t)m * g.cells, s);
         const int d = dice[m];
         if (s.aliveP != 0 && d >= 1 && d <= g.CN && !is_win<NW>(g, s))
-            n = for_each_legal<0, NW>(g, s, d, [](int, int, int) { return true; });
+            n = legal_count<0, NW>(g, s, d);
     }
     for (int i = 0; i < 6; i++) wins[(size_t)m * 6 + i] = i < n ? 0 : -1;
-}
-
-// One uniformly random legal move of SIDE (classical_policies/mcts.py:29-35): dice, legal list in the reference's
-// order as a 6-bit mask (larger-neighbour cube's dirs, then smaller-neighbour cube's), uniform pick, apply.
-template <int SIDE, int NW>
-EWN_DEV void rollout_ply(const Geom &g, GState<NW> &s, PlayoutRng &ps)
-{
-    u32 d0, frac;
-    ps.draw(d0, frac);
-    const int d = 1 + (int)d0; // random.randint(1, 6), mcts.py:29
-    const CubeSel cs = select_cubes(alive_of<SIDE>(s), d);
-    const bool have0 = cs.exact || cs.has_up, have1 = !cs.exact && cs.has_down;
-    const int k0 = cs.exact ? cs.k_exact : cs.k_up, k1 = cs.k_down;
-    const int p0 = pos_of<SIDE>(s, have0 ? k0 : 0), p1 = pos_of<SIDE>(s, have1 ? k1 : 0);
-    u32 okm = 0;
-    #pragma unroll
-    for (int dir = 0; dir < 3; dir++) {
-        okm |= ((have0 && dir_ok<SIDE>(g, p0, dir)) ? 1u : 0u) << dir;
-        okm |= ((have1 && dir_ok<SIDE>(g, p1, dir)) ? 1u : 0u) << (3 + dir);
-    }
-    const int n = __popc(okm);
-    const int pick = (int)PlayoutRng::pick(frac, (u32)n);
-    u32 m = okm;
-    for (int i = 0; i < pick; i++) m &= m - 1;
-    const int slot = __ffs((int)m) - 1;
-    if (n > 0) apply_move<SIDE, NW>(g, s, slot < 3 ? k0 : k1, slot < 3 ? slot : slot - 3);
 }
 
 // The 'sim_winrate' heuristic as a search leaf: MinimaxEnv.simulate (envs/minimax_ewn.py:215-238) -- num_simulations = 100
@@ -551,18 +549,12 @@ __global__ __launch_bounds__(BS) void k_mcts_rollout(Geom g, int M, int total, c
     if (wins[(size_t)m * 6 + i] < 0) return; // no such root move (or inactive lane); set by k_mcts_init, never by this kernel
     GState<NW> s;
     decode_board<NW>(g, boards + (size_t)m * g.cells, s);
-    {
-        int j = 0, mk = 0, md = 0;
-        for_each_legal<0, NW>(g, s, dice[m], [&](int, int k, int dir) { if (j == i) { mk = k; md = dir; } j++; return j <= i; });
-        apply_move<0, NW>(g, s, mk, md);
-    }
+    int mf = 0, mk = 0, md = 0;
+    legal_nth<0, NW>(g, s, dice[m], i, mf, mk, md);
+    apply_move<0, NW>(g, s, mk, md);
     PlayoutRng ps;
     ps.seed(PlayoutRng::obs_word(obs_id ? obs_id[m] : (u32)m, 0x4D435453u, key), (u32)(i * total + r));
-    int cur = 1; // BOTTOM_RIGHT replies first, mcts.py:26
-    for (int ply = 0; ply < 1024 && !is_win<NW>(g, s); ply++) {
-        if (cur == 0) rollout_ply<0, NW>(g, s, ps); else rollout_ply<1, NW>(g, s, ps);
-        cur ^= 1;
-    }
+    playout_to_end<NW>(g, s, ps, 1); // BOTTOM_RIGHT replies first, mcts.py:26
     if (top_left_won<NW>(g, s)) atomicAdd(&wins[(size_t)m * 6 + i], 1); // mcts.py:39-41
 }
 
@@ -698,14 +690,12 @@ __global__ __launch_bounds__(BS) void k_mcts_pick(Geom g, int M, const int8_t *b
 {
     const int m = blockIdx.x * BS + threadIdx.x;
     if (m >= M) return;
-    int best = -1, bw = -1;
-    for (int i = 0; i < 6; i++) { const int w = wins[(size_t)m * 6 + i]; if (w > bw) { bw = w; best = i; } } // np.argmax: first max
-    int f = 0, dr = 0;
-    if (best >= 0) {
+    const int best = argmax_wins(wins + (size_t)m * 6);
+    int f = 0, dr = 0, k;
+    if (best >= 0) { // else a finished observation or an inactive lane: (0, 0)
         GState<NW> s;
         decode_board<NW>(g, boards + (size_t)m * g.cells, s);
-        int j = 0;
-        for_each_legal<0, NW>(g, s, dice[m], [&](int flag, int, int dir) { if (j == best) { f = flag; dr = dir; } j++; return j <= best; });
+        legal_nth<0, NW>(g, s, dice[m], best, f, k, dr);
     }
     actions[2 * m] = (int8_t)f; actions[2 * m + 1] = (int8_t)dr;
 }
@@ -721,32 +711,18 @@ template <int NW>
 static void launch_minimax(const Geom &g, int M, const int8_t *boards, const int8_t *dice, int depth, int heur, int8_t *actions,
                            double *values, hipStream_t s)
 {
-    switch (depth) {
-    case 1: k_predict_minimax<NW, 1><<<GRID(M), BS, 0, s>>>(g, M, boards, dice, heur, actions, values); break;
-    case 2: k_predict_minimax<NW, 2><<<GRID(M), BS, 0, s>>>(g, M, boards, dice, heur, actions, values); break;
-    case 3: k_predict_minimax<NW, 3><<<GRID(M), BS, 0, s>>>(g, M, boards, dice, heur, actions, values); break;
-    case 4: k_predict_minimax<NW, 4><<<GRID(M), BS, 0, s>>>(g, M, boards, dice, heur, actions, values); break;
-    case 5: k_predict_minimax<NW, 5><<<GRID(M), BS, 0, s>>>(g, M, boards, dice, heur, actions, values); break;
-    default: k_predict_minimax<NW, 6><<<GRID(M), BS, 0, s>>>(g, M, boards, dice, heur, actions, values); break;
-    }
+    BY_DEPTH(depth, (k_predict_minimax<NW, DV><<<GRID(M), BS, 0, s>>>(g, M, boards, dice, heur, actions, values)));
 }
 
 template <int NW>
 static int launch_minimax_sim(const Geom &g, int M, const int8_t *boards, const int8_t *dice, const uint8_t *active, const u32 *obs_id,
                               u64 key, int depth, int8_t *actions, double *values, hipStream_t s)
 {
+    if (depth < 1 || depth > 6) return EWN_EUNSUPPORTED;
     const dim3 grid((unsigned)((M + 63) / 64));
-    switch (depth) {
-    case 1: k_predict_minimax_sim<NW, 1><<<grid, 64, 0, s>>>(g, M, boards, dice, active, obs_id, key, EWN_SIM_WINRATE_PLAYOUTS, actions, values); break;
-    case 2: k_predict_minimax_sim<NW, 2><<<grid, 64, 0, s>>>(g, M, boards, dice, active, obs_id, key, EWN_SIM_WINRATE_PLAYOUTS, actions, values); break;
-    case 3: k_predict_minimax_sim<NW, 3><<<grid, 64, 0, s>>>(g, M, boards, dice, active, obs_id, key, EWN_SIM_WINRATE_PLAYOUTS, actions, values); break;
-    case 4: k_predict_minimax_sim<NW, 4><<<grid, 64, 0, s>>>(g, M, boards, dice, active, obs_id, key, EWN_SIM_WINRATE_PLAYOUTS, actions, values); break;
     // max_depth 5 / 6: thousands of leaves x 100 playouts per observation, one thread each -- seconds per launch (the reference: minutes
     // per move); served because the reference has no such limit (classical_policies/minimax.py:19-73 with envs/minimax_ewn.py:36-37)
-    case 5: k_predict_minimax_sim<NW, 5><<<grid, 64, 0, s>>>(g, M, boards, dice, active, obs_id, key, EWN_SIM_WINRATE_PLAYOUTS, actions, values); break;
-    case 6: k_predict_minimax_sim<NW, 6><<<grid, 64, 0, s>>>(g, M, boards, dice, active, obs_id, key, EWN_SIM_WINRATE_PLAYOUTS, actions, values); break;
-    default: return EWN_EUNSUPPORTED;
-    }
+    BY_DEPTH(depth, (k_predict_minimax_sim<NW, DV><<<grid, 64, 0, s>>>(g, M, boards, dice, active, obs_id, key, EWN_SIM_WINRATE_PLAYOUTS, actions, values)));
     return launch_status();
 }
 
@@ -783,13 +759,7 @@ int ewn_build_tables(int board_size, int cube_layer, void *host_out)
     for (int hi = 0; hi < FAST_HEUR_IMAGES; hi++)
         for (int variant = 0; variant < 2; variant++) {
             void *dst = (int8_t *)host_out + (size_t)(hi * 2 + variant) * fast_tables_bytes(board_size, cube_layer);
-            switch (board_size) {
-            case 5: rc |= build_fast_tables<5>((FastTab<5> *)dst, variant, heur_of_image[hi]); break;
-            case 6: rc |= build_fast_tables<6>((FastTab<6> *)dst, variant, heur_of_image[hi]); break;
-            case 7: rc |= build_fast_tables<7>((FastTab<7> *)dst, variant, heur_of_image[hi]); break;
-            case 8: rc |= build_fast_tables<8>((FastTab<8> *)dst, variant, heur_of_image[hi]); break;
-            default: rc = -1;
-            }
+            BY_S(board_size, rc |= build_fast_tables<SV>((FastTab<SV> *)dst, variant, heur_of_image[hi]));   // 5 .. 8: ewn_tables_bytes > 0 above
         }
     return rc == 0 ? EWN_OK : EWN_EUNSUPPORTED;
 }
@@ -814,9 +784,8 @@ int64_t ewn_step_scratch_bytes(const ewn_config *cfg)
     const int rc = check_cfg(cfg, g, k);
     if (rc) return rc;
     const int64_t N = k.N;
-    const bool split = cfg->opponent_kind == EWN_OPP_MCTS || (cfg->opponent_kind == EWN_OPP_MINIMAX && cfg->heuristic == EWN_H_SIM_WINRATE);
-    if (!split)   // MT kind with auto-reset: the refill queue of the lean step kernel (ewn_step_d3.hpp)
-        return (cfg->rng_kind == EWN_RNG_MT19937 && cfg->autoreset) ? mtq_bytes(k.N) : 0;
+    if (step_plan(cfg, g, k, true).path != STEP_SPLIT)   // MT kind with auto-reset: the refill queue of the lean step kernel (ewn_step_d3.hpp)
+        return mt_autoreset(cfg) ? mtq_bytes(k.N) : 0;
     // phase u8 | cdice i8 | act i8x2 | (pad to 8) | obs_id u32 | wins i32x6 | cboard i8[cells]
     return ((N * 4 + 7) / 8) * 8 + N * 4 + N * 24 + N * g.cells;
 }
@@ -846,7 +815,7 @@ int ewn_init_aux(const ewn_config *cfg, const ewn_state *st, void *stream)
     int rc = check_cfg(cfg, g, k);
     if (rc) return rc;
     if (!st || !st->done || !st->rng) return EWN_ENULL;
-    if (cfg->shaped && (!st->prev_score || !st->tolerance)) return EWN_ENULL;
+    if (!shaped_ok(cfg, st)) return EWN_ENULL;
     hipStream_t s = (hipStream_t)stream;
     BY_NW(g, (k_init_aux<NWV><<<GRID(k.N), BS, 0, s>>>(g, k, kstate(st), cfg->illegal_move_tolerance)));
     return launch_status();
@@ -857,7 +826,7 @@ int ewn_reset(const ewn_config *cfg, const ewn_state *st, const uint32_t *seeds,
     Geom g; KCfg k;
     int rc = check_cfg(cfg, g, k);
     if (rc) return rc;
-    if (!st || !st->board || !st->dice || !st->done || !st->rng) return EWN_ENULL;
+    if (!state_ok(st)) return EWN_ENULL;
     hipStream_t s = (hipStream_t)stream;
     const size_t lds = (size_t)BS * g.cells;
     BY_NW(g, (k_reset<NWV><<<GRID(k.N), BS, lds, s>>>(g, k, kstate(st), seeds, lane_mask)));
@@ -899,51 +868,42 @@ int ewn_step(const ewn_config *cfg, const ewn_state *st, const int8_t *actions, 
     Geom g; KCfg k;
     int rc = check_cfg(cfg, g, k);
     if (rc) return rc;
-    if (!st || !st->board || !st->dice || !st->done || !st->rng || !actions || !out) return EWN_ENULL;
+    if (!state_ok(st) || !actions || !out) return EWN_ENULL;
     if (!out->reward || !out->terminated || !out->truncated || !out->info) return EWN_ENULL;
-    if (cfg->shaped && (!st->prev_score || !st->tolerance)) return EWN_ENULL;
+    if (!shaped_ok(cfg, st)) return EWN_ENULL;
     hipStream_t s = (hipStream_t)stream;
     KOut ko = { out->reward, out->terminated, out->truncated, out->info, out->terminal_board, out->terminal_dice, out->random_action };
     KState ks = kstate(st);
     if (!cfg->shaped) { ks.prev_score = nullptr; ks.tolerance = nullptr; }
     KScratch sc = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
     // MT kind with auto-reset: the step kernel flags the lanes whose spare window it consumed; k_mt_refill rebuilds them right after
-    const bool refill = cfg->rng_kind == EWN_RNG_MT19937 && cfg->autoreset;
-    const bool sim_opp = cfg->opponent_kind == EWN_OPP_MINIMAX && cfg->heuristic == EWN_H_SIM_WINRATE;
-    const bool split = cfg->opponent_kind == EWN_OPP_MCTS || sim_opp; // the opponent's policy runs as kernels of its own between two half steps
-    if (split) {
-        if (!scratch) return EWN_ENULL;
-        carve_scratch(g, k, scratch, sc);
-    }
+    const bool refill = mt_autoreset(cfg);
+    const StepPlan plan = step_plan(cfg, g, k, st->tables != nullptr);
     const size_t lds = (size_t)2 * BS * g.cells;
-    if (!split) {
-        const bool fast = st->tables && fast_tables_bytes(g.S, g.L) > 0 && cfg->opponent_kind == EWN_OPP_MINIMAX &&
-                          cfg->max_depth <= 6 && fast_heur_image(cfg->heuristic) >= 0;
-        const bool lean_random = st->tables && fast_tables_bytes(g.S, g.L) > 0 && cfg->opponent_kind == EWN_OPP_RANDOM;
-        if (fast) ks.tables = fast_image(st->tables, g.S, g.L, cfg->max_depth, cfg->heuristic); // the image of this heuristic and depth class
-        if (((fast && fast_heur_step(cfg->heuristic)) || lean_random) && d3_threads_per_game(k.N) > 0) {
+    if (plan.path != STEP_SPLIT) {
+        if (plan.path == STEP_LEAN_TABLES || plan.path == STEP_TABLES)
+            ks.tables = fast_image(st->tables, g.S, g.L, cfg->max_depth, cfg->heuristic); // the image of this heuristic and depth class
+        if (plan.path == STEP_LEAN_TABLES || plan.path == STEP_LEAN_RANDOM) {
             // the lean fused kernel: canonical ring space end to end, T lanes per game (ewn_step_d3.hpp / ewn_step_d3.hip).
             // MT kind with auto-reset: window refills are extra blocks of the same launch (needs the caller's scratch).
             const bool fused_refill = refill && scratch != nullptr;
-            if (fast && cfg->heuristic == EWN_H_TWO_MIN_DIST) rc = ewn_launch_step_d3_h2(cfg, g, k, st, ks.tables, actions, out, scratch, false, fused_refill, s);
-            else rc = ewn_launch_step_d3(cfg, g, k, st, ks.tables, actions, out, scratch, lean_random, fused_refill, s);
+            if (plan.path == STEP_LEAN_TABLES && cfg->heuristic == EWN_H_TWO_MIN_DIST) rc = ewn_launch_step_d3_h2(cfg, g, k, st, ks.tables, actions, out, scratch, plan, fused_refill, s);
+            else rc = ewn_launch_step_d3(cfg, g, k, st, ks.tables, actions, out, scratch, plan, fused_refill, s);
             if (rc || fused_refill) return rc;
-        } else if (fast) {
+        } else if (plan.path == STEP_TABLES) {
             const size_t base = (lds + 15) & ~(size_t)15;
-            switch (g.S) {
-            case 5: k_step<1, 0, 5><<<GRID(k.N), BS, base + FAST_TAB_BYTES(5), s>>>(g, k, ks, actions, ko, sc); break;
-            case 6: k_step<1, 0, 6><<<GRID(k.N), BS, base + FAST_TAB_BYTES(6), s>>>(g, k, ks, actions, ko, sc); break;
-            case 7: k_step<1, 0, 7><<<GRID(k.N), BS, base + FAST_TAB_BYTES(7), s>>>(g, k, ks, actions, ko, sc); break;
-            default: k_step<1, 0, 8><<<GRID(k.N), BS, base + FAST_TAB_BYTES(8), s>>>(g, k, ks, actions, ko, sc); break;
-            }
+            BY_S(g.S, (k_step<1, 0, SV><<<GRID(k.N), BS, base + FAST_TAB_BYTES(SV), s>>>(g, k, ks, actions, ko, sc)));
         } else {
             BY_NW(g, (k_step<NWV, 0, 0><<<GRID(k.N), BS, lds, s>>>(g, k, ks, actions, ko, sc)));
         }
     } else {
+        // the opponent's policy runs as kernels of its own between two half steps, its inputs and its answer in the caller's scratch
+        if (!scratch) return EWN_ENULL;
+        carve_scratch(g, k, scratch, sc);
         BY_NW(g, (k_step<NWV, 1, 0><<<GRID(k.N), BS, lds, s>>>(g, k, ks, actions, ko, sc)));
         rc = launch_status();
         if (rc) return rc;
-        if (sim_opp) {
+        if (cfg->opponent_kind == EWN_OPP_MINIMAX) {   // 'sim_winrate'
             BY_NW(g, rc = launch_minimax_sim<NWV>(g, k.N, sc.cboard, sc.cdice, sc.phase, sc.obs_id, k.key, k.depth, sc.act, nullptr, s));
         } else rc = mcts_launch(g, k.N, sc.cboard, sc.cdice, sc.phase, k.nsim_total, k.key, sc.obs_id, sc.act, sc.wins, s, false);
         if (rc) return rc;
@@ -958,6 +918,36 @@ int ewn_step(const ewn_config *cfg, const ewn_state *st, const int8_t *actions, 
     return rc;
 }
 
+
+// The two clauses every K-step plan of ewn_step_k shares.  Its kernels play a stand-in agent (RandomAgent / action_space.sample());
+// minimax is an agent the ABI knows and these kernels do not serve, any other kind is malformed.  And mt_autoreset (ewn_host.hpp) is
+// refused: a launch that plays several episodes of a lane cannot use windows that are rebuilt between launches.
+static int stand_in_agent_only(int agent_kind)
+{
+    if (agent_kind == EWN_AGENT_RANDOM || agent_kind == EWN_AGENT_SAMPLE) return EWN_OK;
+    return agent_kind == EWN_AGENT_MINIMAX ? EWN_EUNSUPPORTED : EWN_EINVAL;
+}
+
+// games per block of the K-step kernels with playouts (rollout_mcts_body): 8, or 4 for an instance with a search, doubled while
+// that leaves about 2 048 blocks, up to MR_GPB (measured, us per step: 65 536 lanes MCTS(10 x 5) 473 / 426 / 449 / 485 at 16 / 32 / 64 /
+// 128 games per block; 32 768 lanes 7x7 400 playouts 1 822 / 2 020 / 2 303 / 3 587) -- fewer, larger blocks starve the SIMDs of waves,
+// smaller ones leave too few cells per barrier to balance.  With a search the searching lanes diverge: fewer per wave and twice the
+// blocks at small N measured 11-13 % faster at 1 024 lanes.
+static int mcts_games_per_block(int N, bool search)
+{
+    int gpb = search ? 4 : 8;
+    while (gpb < MR_GPB && (long long)N / (2 * gpb) >= 2048) gpb *= 2;
+    return gpb;
+}
+
+// a zeroed RollBuf with every column of the caller's `out`
+static RollBuf rollbuf_of(const ewn_rollout_out *out)
+{
+    RollBuf rb;
+    memset(&rb, 0, sizeof(rb));
+    fill_trajectory(rb, out);
+    return rb;
+}
 
 // which k_rollout_d3 instantiation serves (cfg, agent): EWN_OK and the template selectors, or why not
 static int rollout_plan(const ewn_config *cfg, const Geom &g, const KCfg &k, int agent_kind, int agent_max_depth, int &T, int &opp, int &agent)
@@ -974,9 +964,7 @@ static int rollout_plan(const ewn_config *cfg, const Geom &g, const KCfg &k, int
         if (agent_max_depth > EWN_MAX_DEPTH) return EWN_EUNSUPPORTED;
         agent = agent_max_depth > 4 ? 2 : 1;
     } else return EWN_EINVAL;
-    // the MT19937-compat windows of an auto-resetting lane are rebuilt BETWEEN launches (ewn_core.hpp): a launch that plays
-    // several episodes of a lane cannot use them.  Without auto-reset (one episode per lane: evaluation) the kind is fine.
-    if (cfg->rng_kind == EWN_RNG_MT19937 && cfg->autoreset) return EWN_EUNSUPPORTED;
+    if (mt_autoreset(cfg)) return EWN_EUNSUPPORTED;
     const bool mt = cfg->rng_kind == EWN_RNG_MT19937;
     if (agent != 0) T = 2;
     else if (opp == 1) T = 1;
@@ -992,9 +980,8 @@ static int generic_rollout_plan(const ewn_config *cfg, const Geom &g, int agent_
     if (fast_tables_bytes(g.S, g.L) > 0 || cfg->shaped) return EWN_EUNSUPPORTED;
     if (cfg->opponent_kind == EWN_OPP_MINIMAX) { if (cfg->heuristic == EWN_H_SIM_WINRATE) return EWN_EUNSUPPORTED; }
     else if (cfg->opponent_kind != EWN_OPP_RANDOM) return EWN_EUNSUPPORTED;
-    if (agent_kind != EWN_AGENT_RANDOM && agent_kind != EWN_AGENT_SAMPLE) return agent_kind == EWN_AGENT_MINIMAX ? EWN_EUNSUPPORTED : EWN_EINVAL;
-    if (cfg->rng_kind == EWN_RNG_MT19937 && cfg->autoreset) return EWN_EUNSUPPORTED;
-    return EWN_OK;
+    if (const int rc = stand_in_agent_only(agent_kind)) return rc;
+    return mt_autoreset(cfg) ? EWN_EUNSUPPORTED : EWN_OK;
 }
 
 // the flat Monte-Carlo opponent inside ewn_step_k (k_rollout_mcts): byte-per-cube playouts (cube_layer <= 3, boards <= 8x8), un-shaped,
@@ -1002,9 +989,8 @@ static int generic_rollout_plan(const ewn_config *cfg, const Geom &g, int agent_
 static int mcts_rollout_plan(const ewn_config *cfg, const Geom &g, int agent_kind)
 {
     if (cfg->opponent_kind != EWN_OPP_MCTS || cfg->shaped || g.CN > 6 || g.S > 8) return EWN_EUNSUPPORTED;
-    if (agent_kind != EWN_AGENT_RANDOM && agent_kind != EWN_AGENT_SAMPLE) return agent_kind == EWN_AGENT_MINIMAX ? EWN_EUNSUPPORTED : EWN_EINVAL;
-    if (cfg->rng_kind == EWN_RNG_MT19937 && cfg->autoreset) return EWN_EUNSUPPORTED;
-    return EWN_OK;
+    if (const int rc = stand_in_agent_only(agent_kind)) return rc;
+    return mt_autoreset(cfg) ? EWN_EUNSUPPORTED : EWN_OK;
 }
 
 int ewn_lanes_per_game(const ewn_config *cfg, int entry)
@@ -1018,13 +1004,7 @@ int ewn_lanes_per_game(const ewn_config *cfg, int entry)
         return rc == EWN_OK ? T : 0;
     }
     if (entry != 0) return EWN_EINVAL;
-    const bool tab = fast_tables_bytes(g.S, g.L) > 0;
-    const bool fast = tab && cfg->opponent_kind == EWN_OPP_MINIMAX && cfg->max_depth <= 6 && fast_heur_step(cfg->heuristic);
-    const bool lean_random = tab && cfg->opponent_kind == EWN_OPP_RANDOM;
-    if (!(fast || lean_random) || d3_threads_per_game(k.N) <= 0) return 0;
-    if (lean_random || cfg->max_depth < 3) return 1;
-    if (cfg->max_depth > 4) return (k.N <= 131072 && d3_threads_per_game(k.N) != 1) ? 2 : 1;
-    return d3_threads_per_game(k.N);
+    return step_plan(cfg, g, k, true).T;   // no state here: the table images are taken to be there
 }
 
 int ewn_step_k_supported(const ewn_config *cfg, int agent_kind, int agent_max_depth)
@@ -1048,28 +1028,19 @@ int ewn_step_k(const ewn_config *cfg, const ewn_state *st, int K, int agent_kind
     if (rc) return rc;
     if (K < 1) return EWN_EINVAL;
     if (cfg->opponent_kind == EWN_OPP_MCTS) {
-        if (!st || !st->board || !st->dice || !st->done || !st->rng) return EWN_ENULL;
+        if (!state_ok(st)) return EWN_ENULL;
         rc = mcts_rollout_plan(cfg, g, agent_kind);
         if (rc) return rc;
-        RollBuf rb;
-        memset(&rb, 0, sizeof(rb));
-        fill_trajectory(rb, out);
-        // games per block: about 2 048 blocks (measured, us per step: 65 536 lanes MCTS(10 x 5) 473 / 426 / 449 / 485 at 16 / 32 / 64 / 128 games
-        // per block; 32 768 lanes 7x7 400 playouts 1 822 / 2 020 / 2 303 / 3 587) -- fewer, larger blocks starve the SIMDs of waves, smaller
-        // ones leave too few cells per barrier to balance.  EWN_MCTS_GPB overrides (tuning).
+        // EWN_MCTS_GPB overrides the games per block (tuning)
         static const int gpb_env = [] { const char *e = getenv("EWN_MCTS_GPB"); const int v = e ? atoi(e) : 0; return v >= 8 && v <= MR_GPB ? v : 0; }();
-        int gpb = 8;
-        while (gpb < MR_GPB && (long long)k.N / (2 * gpb) >= 2048) gpb *= 2;
-        if (gpb_env) gpb = gpb_env;
+        const int gpb = gpb_env ? gpb_env : mcts_games_per_block(k.N, false);
         MctsRoll mr = { K, k.nsim_total, playout_group_log2(k.nsim_total), agent_kind == EWN_AGENT_SAMPLE ? 1 : 0, traj_record_stride(g), gpb };
-        k_rollout_mcts<<<dim3((unsigned)((k.N + mr.gpb - 1) / mr.gpb)), BS, (size_t)mr.gpb * mr.strd, (hipStream_t)stream>>>(g, k, kstate(st), mr, rb);
+        k_rollout_mcts<<<dim3((unsigned)((k.N + mr.gpb - 1) / mr.gpb)), BS, (size_t)mr.gpb * mr.strd, (hipStream_t)stream>>>(g, k, kstate(st), mr, rollbuf_of(out));
         return launch_status();
     }
     if (generic_rollout_plan(cfg, g, agent_kind) == EWN_OK) {
-        if (!st || !st->board || !st->dice || !st->done || !st->rng) return EWN_ENULL;
-        RollBuf rb;
-        memset(&rb, 0, sizeof(rb));
-        fill_trajectory(rb, out);
+        if (!state_ok(st)) return EWN_ENULL;
+        const RollBuf rb = rollbuf_of(out);
         GenRoll gr = { K, agent_kind == EWN_AGENT_SAMPLE ? 1 : 0, traj_record_stride(g) };
         const KState ks = kstate(st);
         const size_t lds = (size_t)BS * gr.strd;
@@ -1077,17 +1048,15 @@ int ewn_step_k(const ewn_config *cfg, const ewn_state *st, int K, int agent_kind
         BY_NW(g, (k_rollout_generic<NWV><<<GRID(k.N), BS, lds, s>>>(g, k, ks, gr, rb)));
         return launch_status();
     }
-    if (!st || !st->board || !st->dice || !st->done || !st->rng || !st->tables) return EWN_ENULL;
+    if (!state_tables_ok(st)) return EWN_ENULL;
     int T, opp, agent;
     rc = rollout_plan(cfg, g, k, agent_kind, agent_max_depth, T, opp, agent);
     if (rc) return rc;
     RollCfg rcf = { k.N, k.autoreset, k.lane_offset, k.depth, agent_max_depth, K, agent_kind == EWN_AGENT_SAMPLE ? 1 : 0, k.seed_stride, k.W, k.reward, k.key };
-    RollBuf rb;
-    memset(&rb, 0, sizeof(rb));
+    RollBuf rb = rollbuf_of(out);
     rb.board = st->board; rb.dice = st->dice; rb.done = st->done; rb.rng = st->rng;
     rb.tables = opp == 1 ? st->tables : fast_image(st->tables, g.S, g.L, cfg->max_depth, cfg->heuristic);
     rb.agent_tables = agent == 0 ? rb.tables : fast_image(st->tables, g.S, g.L, agent_max_depth, EWN_H_HYBRID);
-    fill_trajectory(rb, out);
     hipStream_t s = (hipStream_t)stream;
     const bool h2 = opp != 1 && cfg->heuristic == EWN_H_TWO_MIN_DIST;
     switch (g.S) {
@@ -1116,7 +1085,7 @@ static int agent_rollout_plan(const ewn_config *cfg, const Geom &g, const ewn_ag
     } else if (a->kind == EWN_AGENT_RANDOM || a->kind == EWN_AGENT_SAMPLE || a->kind == EWN_AGENT_MLP) return EWN_EUNSUPPORTED;
     else return EWN_EINVAL;
     if (cfg->shaped || g.CN != 6 || g.S > 8) return EWN_EUNSUPPORTED;
-    if (cfg->rng_kind == EWN_RNG_MT19937 && cfg->autoreset) return EWN_EUNSUPPORTED;
+    if (mt_autoreset(cfg)) return EWN_EUNSUPPORTED;
     opp_mcts = cfg->opponent_kind == EWN_OPP_MCTS;
     return EWN_OK;
 }
@@ -1138,22 +1107,17 @@ int ewn_step_k_agent(const ewn_config *cfg, const ewn_state *st, int K, const ew
     int rc = check_cfg(cfg, g, k);
     if (rc) return rc;
     if (K < 1) return EWN_EINVAL;
-    if (!agent || !st || !st->board || !st->dice || !st->done || !st->rng) return EWN_ENULL;
+    if (!agent || !state_ok(st)) return EWN_ENULL;
     int ag; bool om;
     rc = agent_rollout_plan(cfg, g, agent, ag, om);
     if (rc) return rc;
     // the minimax side (the agent of AG 1, the opponent of AG 2 against minimax) searches from its table image
     const bool tab = ag == 1 || cfg->opponent_kind == EWN_OPP_MINIMAX;
     if (tab && !st->tables) return EWN_ENULL;
-    RollBuf rb;
-    memset(&rb, 0, sizeof(rb));
+    RollBuf rb = rollbuf_of(out);
     if (tab) rb.tables = ag == 1 ? fast_image(st->tables, g.S, g.L, agent->max_depth, agent->heuristic)
                                  : fast_image(st->tables, g.S, g.L, cfg->max_depth, cfg->heuristic);
-    fill_trajectory(rb, out);
-    // games per block: ewn_step_k's rule for the MCTS opponent (8 .. MR_GPB, about 2 048 blocks), from 4 for the instances with a search:
-    // its searching lanes diverge, fewer per wave and twice the blocks at small N measured 11-13 % faster at 1 024 lanes
-    int gpb = tab ? 4 : 8;
-    while (gpb < MR_GPB && (long long)k.N / (2 * gpb) >= 2048) gpb *= 2;
+    const int gpb = mcts_games_per_block(k.N, tab);
     const int atotal = ag == 2 ? agent->num_simulations * agent->num_env_copies : 0;
     MctsRoll mr = { K, k.nsim_total, om ? playout_group_log2(k.nsim_total) : 3, 0, traj_record_stride(g), gpb };
     AgentRoll ar = { agent->max_depth, agent->heuristic, atotal, ag == 2 ? playout_group_log2(atotal) : 3, agent->step_base, agent->key };
@@ -1168,12 +1132,7 @@ int ewn_step_k_agent(const ewn_config *cfg, const ewn_state *st, int K, const ew
 #define AGL(SS) do { auto kern = ag == 1 ? k_rollout_mcts_agent<1, 2, SS> : k_rollout_mcts_agent<2, 1, SS>; \
                      if (lds > 64 * 1024 && hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return EWN_ELAUNCH; \
                      kern<<<grid, BS, lds, s>>>(g, k, kstate(st), mr, rb, ar); } while (0)
-    switch (g.S) {
-    case 5: AGL(5); break;
-    case 6: AGL(6); break;
-    case 7: AGL(7); break;
-    default: AGL(8); break;
-    }
+    BY_S(g.S, AGL(SV));
 #undef AGL
     return launch_status();
 }
@@ -1274,12 +1233,7 @@ int ewn_predict_minimax(int board_size, int cube_layer, int M, const int8_t *boa
         tables = fast_image(tables, g.S, g.L, max_depth, heuristic);
 #define PMF(SS) do { if (heuristic == EWN_H_TWO_MIN_DIST) k_predict_minimax_fast<SS, true><<<GRID(M), BS, FAST_TAB_BYTES(SS), s>>>(g, M, boards, dice, max_depth, actions, values, tables); \
                     else k_predict_minimax_fast<SS, false><<<GRID(M), BS, FAST_TAB_BYTES(SS), s>>>(g, M, boards, dice, max_depth, actions, values, tables); } while (0)
-        switch (g.S) {
-        case 5: PMF(5); break;
-        case 6: PMF(6); break;
-        case 7: PMF(7); break;
-        default: PMF(8); break;
-        }
+        BY_S(g.S, PMF(SV));
 #undef PMF
         return launch_status();
     }

@@ -74,11 +74,10 @@ EWN_DEV void step_opponent(const Geom &g, const KCfg &c, GState<NW> &s, int &dic
 template <int NW>
 EWN_DEV void policy_random(const Geom &g, const GState<NW> &s, int dice, LaneRng &r, int &oflag, int &odir)
 {
-    const int n = for_each_legal<1, NW>(g, s, dice, [](int, int, int) { return true; });
-    const int pick = r.randint(0, n);
-    int i = 0;
+    const int pick = r.randint(0, legal_count<1, NW>(g, s, dice));   // drawn for an empty list too
+    int k;
     oflag = 0; odir = 0;
-    for_each_legal<1, NW>(g, s, dice, [&](int flag, int, int dir) { if (i == pick) { oflag = flag; odir = dir; } i++; return i <= pick; });
+    legal_nth<1, NW>(g, s, dice, pick, oflag, k, odir);
 }
 
 // The stand-in agent of ewn_step_k: RandomAgent.predict (the hash pick of ewn_step_out.random_action) or, with agent_sample,
@@ -106,7 +105,7 @@ struct LaneTotals {
 // One lane's entries of a trajectory row, index = step * N + lane: the columns of ewn_rollout_out that the caller asked for
 EWN_DEV void traj_columns_store(const RollBuf &B, size_t index, int aflag, int adir, int dice, const StepRes &o)
 {
-    if (B.t_action) ((uint16_t *)B.t_action)[index] = (uint16_t)((uint8_t)aflag | ((uint16_t)(uint8_t)adir << 8));
+    if (B.t_action) ((uint16_t *)B.t_action)[index] = pack_action(aflag, adir);
     if (B.t_dice) B.t_dice[index] = (int8_t)dice;
     if (B.t_reward) B.t_reward[index] = o.reward;
     if (B.t_term) B.t_term[index] = (uint8_t)o.term;
@@ -219,7 +218,18 @@ EWN_DEV void mcts_playout_phase(const Geom &g, const PlayTab *T, const PState *p
     __syncthreads();
 }
 
-// np.argmax over the root moves' wins (first maximum), then that entry of the legal list of the observation (mcts.py:68)
+// np.argmax over the six win counters of an observation's root moves (first maximum, mcts.py:68); -1 for a row of six -1: no root
+// move (a finished observation, an inactive lane), where the stateless policy answers (0, 0)
+EWN_DEV int argmax_wins(const int *w6)
+{
+    int best = -1, bw = -1;
+    #pragma unroll
+    for (int i = 0; i < 6; i++) { const int w = w6[i]; if (w > bw) { bw = w; best = i; } }
+    return best;
+}
+
+// MctsAgent's choice inside the K-step loop: that entry of the legal list of the observation.  Its owner has a root move, so it starts
+// the maximum at entry 0; kept as its own loop because rebasing it on argmax_wins changes the code of the kernels around it.
 EWN_DEV void mcts_pick(const Geom &g, const GState<1> &obs, int dice, const int *w6, int &flag, int &dir)
 {
     int best = 0, bw = -1;

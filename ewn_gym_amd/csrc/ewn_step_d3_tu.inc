@@ -18,10 +18,10 @@ static int d3_launch_one(dim3 grid, size_t lds, hipStream_t s, const D3Cfg &dc, 
 }
 
 int D3_LAUNCHER(const ewn_config *cfg, const Geom &g, const KCfg &k, const ewn_state *st, const void *tables, const int8_t *actions,
-                       const ewn_step_out *out, void *scratch, bool lean_random, bool fused_refill, hipStream_t s)
+                       const ewn_step_out *out, void *scratch, const StepPlan &plan, bool fused_refill, hipStream_t s)
 {
-    // leaves are shared among lanes at depth 3-4; depth 5-6 splits its inner dice over two lanes while the chip is not full
-    const int T = (lean_random || cfg->max_depth < 3) ? 1 : (cfg->max_depth > 4 ? (k.N <= 131072 && d3_threads_per_game(k.N) != 1 ? 2 : 1) : d3_threads_per_game(k.N));
+    const bool lean_random = plan.path == STEP_LEAN_RANDOM;
+    const int T = plan.T;   // lanes per game: step_plan (ewn_host.hpp)
     const int gpb = D3_BS / T, step_blocks = (k.N + gpb - 1) / gpb;
     // MT kind with auto-reset: window refills are extra blocks of the same launch (needs the caller's scratch).
     // One refill block (one wave) per step block: a lane of it rebuilds at most one window, ~29 k cycles, well inside the
@@ -49,12 +49,7 @@ int D3_LAUNCHER(const ewn_config *cfg, const Geom &g, const KCfg &k, const ewn_s
 #endif
 #define D3_BY_T(SS) do { if (lean_random) { if (D3_H2) lrc = EWN_EUNSUPPORTED; else D3_LAUNCH_R(SS); } else if (cfg->max_depth > 4) { if (T == 2) D3_LAUNCH(SS, 2, 2); else D3_LAUNCH(SS, 1, 2); } else if (T == 1) D3_LAUNCH(SS, 1, 0); else D3_LAUNCH(SS, 2, 0); } while (0)
     int lrc = EWN_OK;
-    switch (g.S) {
-    case 5: D3_BY_T(5); break;
-    case 6: D3_BY_T(6); break;
-    case 7: D3_BY_T(7); break;
-    default: D3_BY_T(8); break;
-    }
+    BY_S(g.S, D3_BY_T(SV));
     int rc = lrc != EWN_OK ? lrc : launch_status();
     if (rc == EWN_OK && fused_refill) {
         k_mtq_flip<<<1, 64, 0, s>>>((u32 *)scratch);
