@@ -64,25 +64,42 @@ class ModelAgent(PolicyBase):
         return lambda b, d, t: self.predict_batch(b, d, key=(self.key + 0x9E3779B97F4A7C15 * (t + 1)) & 0xFFFFFFFFFFFFFFFF)
 
 
+def _leaf_table(who, table, board_size):
+    """endgame_table= of a searching agent: None, an EndgameTable, or the path of a saved one (loaded once), for the agent's boards"""
+    from ewn_gym_amd.endgame import EndgameTable
+    if table is None:
+        return None
+    if isinstance(table, (str, os.PathLike)):
+        table = EndgameTable.load(table)
+    if not isinstance(table, EndgameTable):
+        raise ValueError("%s: endgame_table must be an EndgameTable or the path of a saved one, got %s" % (who, type(table).__name__))
+    if table.board_size != board_size:
+        raise ValueError("%s: the table is for %dx%d boards, the agent plays %dx%d" % (who, table.board_size, table.board_size, board_size,
+                                                                                       board_size))
+    return table
+
+
 class ValueSearchAgent(ModelAgent):
     """The trained actor-critic searching one move ahead with its own value net (ewn_predict_lookahead): one agent move,
     the opponent's best reply under every dice, the critic at the next agent-to-move state -- plain expectiminimax, no pruning.  This
     project's counterpart of the reference's AlphaZeroMinimaxAgent (classical_policies/minimax.py:96-223: expectiminimax whose leaf
     is a network's value), on the network the trainers here produce.  Always deterministic: the first maximum of Q.  plies=2: two
-    moves ahead (agent, reply, agent, reply, critic)."""
+    moves ahead (agent, reply, agent, reply, critic).  endgame_table (an ewn_gym_amd.EndgameTable or the path of a
+    saved one): a leaf that the table covers is worth its exact value instead of the critic's."""
 
-    def __init__(self, model_or_path, board_size=5, cube_layer=3, terminal_value=1.0, plies=1):
+    def __init__(self, model_or_path, board_size=5, cube_layer=3, terminal_value=1.0, plies=1, endgame_table=None):
         if plies not in (1, 2):
             raise ValueError("ValueSearchAgent: plies must be 1 or 2, got %r" % (plies,))
         super().__init__(model_or_path, board_size=board_size, cube_layer=cube_layer, deterministic=True)
         self.terminal_value = float(terminal_value)
         self.plies = int(plies)
+        self.endgame_table = _leaf_table("ValueSearchAgent", endgame_table, board_size)
 
     def predict_batch(self, boards, dice, return_q=False):
         """boards (M,S,S), dice (M,) device or host arrays -> int8 (M,2) device tensor (and the float32 (M,2,3) Q if asked for)"""
         b, d = self._on_device(boards, dice)
         return self._ea.predict_lookahead(b, d, self.params, terminal_value=self.terminal_value, return_q=return_q,
-                                          cube_layer=self.cube_layer, plies=self.plies)
+                                          cube_layer=self.cube_layer, plies=self.plies, endgame_table=self.endgame_table)
 
     def policy_fn(self):
         """(board, dice, t) -> actions, the callable tournament.evaluate takes"""
@@ -93,13 +110,16 @@ class PuctAgent(ModelAgent):
     """The trained actor-critic behind a PUCT search of `sims` simulations (ewn_gym_amd.predict_puct): the policy head
     says where to look, the value head what a leaf is worth, chance nodes take the dice in a fixed stratified order.  This project's
     counterpart of the reference's AlphaZeroMCTSAgent (classical_policies/alpha_zero/MCTS.py), on the network the trainers here
-    produce.  Always deterministic: a win on the board, else the most visited move.  sims=0 plays the first legal move unless one wins."""
+    produce.  Always deterministic: a win on the board, else the most visited move.  sims=0 plays the first legal move unless one wins.
+    endgame_table (an ewn_gym_amd.EndgameTable or the path of a saved one): a leaf that the table covers is worth its exact value
+    instead of the value head's."""
 
-    def __init__(self, model_or_path, board_size=5, cube_layer=3, sims=64, c_puct=1.5, terminal_value=1.0):
+    def __init__(self, model_or_path, board_size=5, cube_layer=3, sims=64, c_puct=1.5, terminal_value=1.0, endgame_table=None):
         from ewn_gym_amd.vec_env import _puct_numbers
         self.sims = _puct_numbers("PuctAgent", sims, c_puct, terminal_value)
         self.c_puct, self.terminal_value = float(c_puct), float(terminal_value)
         super().__init__(model_or_path, board_size=board_size, cube_layer=cube_layer, deterministic=True)
+        self.endgame_table = _leaf_table("PuctAgent", endgame_table, board_size)
 
     def predict_batch(self, boards, dice, return_visits=False, return_q=False, return_value=False):
         """boards (M,S,S), dice (M,) device or host arrays -> int8 (M,2) device tensor (and the int32 (M,2,3) root visits, the float32
@@ -107,7 +127,7 @@ class PuctAgent(ModelAgent):
         b, d = self._on_device(boards, dice)
         return self._ea.predict_puct(b, d, self.params, sims=self.sims, c_puct=self.c_puct, terminal_value=self.terminal_value,
                                      return_visits=return_visits, return_q=return_q, return_value=return_value,
-                                     cube_layer=self.cube_layer)
+                                     cube_layer=self.cube_layer, endgame_table=self.endgame_table)
 
     def policy_fn(self):
         """(board, dice, t) -> actions, the callable tournament.evaluate takes"""

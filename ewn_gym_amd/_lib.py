@@ -32,7 +32,7 @@ EXPORTS = ["ewn_abi_version", "ewn_strerror", "ewn_rng_words", "ewn_step_scratch
            "ewn_step_vs_supported", "ewn_step_vs", "ewn_step_k_vs_supported", "ewn_step_k_vs", "ewn_predict_policy",
            "ewn_predict_lookahead", "ewn_lookahead_expand", "ewn_lookahead_reduce",
            "ewn_sup_scratch_bytes", "ewn_sup_grad", "ewn_lookahead_targets",
-           "ewn_endgame_table_bytes", "ewn_endgame_build", "ewn_endgame_lookup",
+           "ewn_endgame_table_bytes", "ewn_endgame_build", "ewn_endgame_lookup", "ewn_predict_lookahead_eg",
            "ewn_puct_tree_bytes", "ewn_puct_begin", "ewn_puct_advance", "ewn_puct_result"]
 AGENT = {"random": 0, "minimax": 1, "sample": 2, "mlp": 3}   # "mlp": the trained policy, through ewn_step_k_policy   # "sample": env.action_space.sample(), all six actions (EWN_AGENT_SAMPLE)
 AGENT_MCTS = 4   # ewn_agent.kind of the MCTS agent (ewn_step_k_agent only; ewn_step_k does not take it)
@@ -177,6 +177,7 @@ def load():
         "ewn_endgame_table_bytes": (C.c_int64, [i32, i32, i32]),
         "ewn_endgame_build": (i32, [i32, i32, i32, vp, C.c_int64, vp]),
         "ewn_endgame_lookup": (i32, [i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "ewn_predict_lookahead_eg": (i32, [i32, i32, i32, vp, vp, vp, C.c_float, i32, i32, vp, vp, vp, vp, vp]),
         "ewn_puct_tree_bytes": (C.c_int64, [i32, i32, i32]),
         "ewn_puct_begin": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
         "ewn_puct_advance": (i32, [i32, i32, i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp]),

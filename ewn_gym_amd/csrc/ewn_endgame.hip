@@ -14,52 +14,12 @@
 // side = rank of the 6-bit presence mask among the masks of its popcount (ascending) * C^k + the cells in cube-number order as a
 // base-C number, lowest cube number most significant.  Slots of positions that are not live (cubes sharing a cell, an agent cube on
 // C - 1, an opposing cube on 0) are never read; the build writes 0 there (the whole table is cleared first).
-#include "ewn_lookahead.hpp"
+#define EG_MASKS_LINKAGE    // EG_MASKS is this unit's own symbol; every other unit's copy is static
+#include "ewn_endgame.hpp"
 
 #define EG_NT 256            // threads per block of both kernels
 #define EG_MAX_BLOCKS 9      // (ka, ko) blocks of a table: K <= 3
 #define EG_MAX_GRID (1u << 22)   // workgroups per launch: a launch's grid is 32 bits of THREADS (2^24 workgroups of EG_NT), see eg_build
-
-struct EgMasks { uint8_t rank[64]; uint8_t unrank[4][20]; };   // rank[mask of cubes 1..6 >> 1]; unrank[popcount][rank]
-static constexpr EgMasks eg_make_masks()
-{
-    EgMasks t{};
-    int cnt[7] = {0, 0, 0, 0, 0, 0, 0};
-    for (int m = 0; m < 64; m++) {
-        const int k = __builtin_popcount((unsigned)m);
-        t.rank[m] = (uint8_t)cnt[k];
-        if (k <= 3) t.unrank[k][cnt[k]] = (uint8_t)m;
-        cnt[k]++;
-    }
-    return t;
-}
-__constant__ EgMasks EG_MASKS = eg_make_masks();
-
-struct EgGeo { int K, T; long long off[4][4]; };             // off[ka][ko]: the block's first entry (in floats); -1: not in the table
-
-template <int S> struct EgDim {
-    static constexpr int C = S * S;
-    static constexpr u32 pw(int k) { return k == 0 ? 1u : k == 1 ? (u32)C : k == 2 ? (u32)C * C : (u32)C * C * C; }
-    static constexpr u32 n(int k) { return (k == 1 ? 6u : k == 2 ? 15u : 20u) * pw(k); }
-};
-template <int S> EWN_DEV u32 eg_pw(int k) { return k == 1 ? EgDim<S>::pw(1) : k == 2 ? EgDim<S>::pw(2) : EgDim<S>::pw(3); }
-template <int S> EWN_DEV u32 eg_n(int k) { return k == 1 ? EgDim<S>::n(1) : k == 2 ? EgDim<S>::n(2) : EgDim<S>::n(3); }
-
-// a side as registers: M the presence mask (bit k: cube k, k = 1 .. 6), pos the cell of cube k in byte k - 1 (read only where M has k)
-EWN_DEV int eg_cell(u64 pos, int k) { return (int)((pos >> (8 * (k - 1))) & 0xFFull); }
-
-// the side's index; turned: as flip() shows it to the other side (cell c -> C - 1 - c)
-template <int S>
-EWN_DEV u32 eg_side(int M, u64 pos, bool turned)
-{
-    constexpr int C = S * S;
-    u32 v = EG_MASKS.rank[(M >> 1) & 63];
-    for (int m = M; m; m &= m - 1) {
-        const int c = eg_cell(pos, __builtin_ctz(m));
-        v = v * (u32)C + (u32)(turned ? C - 1 - c : c);
-    }
-    return v;
-}
 
 // G of the agent's cube `cube` (in Ma) in direction r; -inf where the move leaves the board.  Every index it forms is inside the table:
 // a move never adds a cube and never empties the mover's side, so 1 <= popcounts <= K, their sum <= T, and each side index < n_k.
@@ -218,27 +178,6 @@ __global__ __launch_bounds__(EG_NT) void k_endgame_lookup(int M, EgGeo g, EgLook
 }
 
 // ---------------------------------------------------------------- host
-static inline bool eg_params_ok(int S, int K, int T) { return S >= 3 && S <= 11 && K >= 1 && K <= 3 && T >= 2 && T <= 2 * K; }
-
-static inline long long eg_n_host(int S, int k)
-{
-    long long n = k == 1 ? 6 : k == 2 ? 15 : 20;
-    for (int i = 0; i < k; i++) n *= S * S;
-    return n;
-}
-
-// the block offsets, ka-major; returns the table's entries
-static long long eg_geo(int S, int K, int T, EgGeo &g)
-{
-    g.K = K; g.T = T;
-    long long total = 0;
-    for (int a = 0; a < 4; a++) for (int o = 0; o < 4; o++) g.off[a][o] = -1;
-    for (int a = 1; a <= K; a++)
-        for (int o = 1; o <= K; o++)
-            if (a + o <= T) { g.off[a][o] = total; total += eg_n_host(S, a) * eg_n_host(S, o); }
-    return total;
-}
-
 // the active (ka, ko) blocks of a level and its grid: EG_NT entries a workgroup, rounded up per agent side.  0: nothing at this level
 static unsigned long long eg_level(int S, int K, int T, int level, EgLevel &L)
 {

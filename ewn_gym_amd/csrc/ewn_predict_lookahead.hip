@@ -12,12 +12,15 @@
 // b2, each evaluated under six d2: at most 648 columns of the value net, 21 MFMA tiles.  The leaf arithmetic is ewn_predict_policy's
 // (mlp3_pack_fwd's image of net 1, pol_obs_operand on a zero-padded slot, mlp3_forward<S, 1>).  The observation in LDS, the roots
 // and the fold of W into Q and the action are ewn_lookahead.hpp's helpers, the ones ewn_lookahead_stages.hip calls.
-#include "ewn_lookahead.hpp"
+// ewn_predict_lookahead_eg is the same tree with W = terminal_value * E(b2) wherever an endgame table covers b2: the
+// second instance of the one kernel below, k_predict_lookahead<S, true>.
+#include "ewn_endgame.hpp"
 
 #define LA_NT 256            // threads per block: four waves, one observation each per trip
 #define LA_MAX_BLOCKS 256    // one block per CU (PRED_MAX_BLOCKS' reasoning); more observations than that are walked grid-stride
 #define LA_NONE (-1)         // a tuple's meta byte: no such reply (or a root that is not searched) ...
 #define LA_LOST (-2)         // ... a reply that wins for the opponent; >= 0: the b2's leaf slot
+#define LA_EXACT (-3)        // k_predict_lookahead<S, true> only: a b2 the endgame table covers -- no leaf slot, no columns, W from the table
 
 // LDS of k_predict_lookahead<S>: the value net's image | per wave: the observation as a slot | cube positions | tuple meta | W | R | Q |
 // V [648] | 108 leaf slots of RecGeo<S>::STR bytes
@@ -38,13 +41,23 @@ template <int S> struct LaGeo {
 };
 
 struct LaBuf { const int8_t *boards; const int8_t *dice; const float *params; int8_t *actions; float *q; };
+// a kernel's buffers: the plain instance's are LaBuf and nothing else; the instance with a table adds the table (layout 1), its
+// max_cubes and max_total, and leaf_counts [M][2] or NULL: {leaves valued by the table, by the critic}
+template <bool EG> struct LaArgs : LaBuf {};
+template <> struct LaArgs<true> : LaBuf { int K, T; const float *table; int16_t *counts; };
 
 // Everything is per wave; nothing after the pack crosses a wave, so there is no block barrier in the loop.  Phases per observation:
 // (a) lanes enumerate the 108 tuples (two per lane) and write each distinct non-terminal b2 into the next free leaf slot (ballot
 // ranks); (b) the value net over tiles of 32 columns, column = 6 slot + d2 - 1; (c) W per tuple, then la_fold: R per (root, d1), Q per
 // root, the pick, the stores.
-template <int S>
-__global__ __launch_bounds__(LA_NT, 1) void k_predict_lookahead(int M, float tv, LaBuf B)
+// EG: in (a) the lane of a tuple whose b2 the table covers -- 1 .. K cubes a side, at most T in all; a leaf never has an
+// agent cube on C - 1 (that root wins, or the row is over) nor an opposing cube on 0 (that reply is LA_LOST, or the row is over) --
+// forms the table index from its registers and the 16-byte position table and issues the gather; it takes no leaf slot, so the ranks
+// and ncol count the critic's leaves only, and (c) consumes the loaded E behind (b)'s tiles.  Every index lies inside the table: a
+// move never adds a cube and the coverage test comes first (eg_move's argument).  A root with a cube number twice on a side, or a
+// cell outside -6 .. 6, is no position of the table's: its cells outnumber its presence masks, and every leaf goes to the critic.
+template <int S, bool EG>
+__global__ __launch_bounds__(LA_NT, 1) void k_predict_lookahead(int M, float tv, LaArgs<EG> B)
 {
     using P = LaGeo<S>;
     using Q3 = Mlp3Geo<S>;
@@ -67,8 +80,18 @@ __global__ __launch_bounds__(LA_NT, 1) void k_predict_lookahead(int M, float tv,
         int PA, PO;
         const int d = la_dice((int)B.dice[m]);
         const bool live = la_observation<S, STR>(B.boards + m * CELLS, lane, base, pos, PA, PO);
-        if (!live) { la_row_over(B.actions, B.q, m, lane); continue; }
+        if (!live) {
+            if constexpr (EG) { if (B.counts && lane < 2) B.counts[m * 2 + lane] = 0; }
+            la_row_over(B.actions, B.q, m, lane);
+            continue;
+        }
         const int c0 = la_find(0, d, PA), c1 = la_find(1, d, PA);
+        bool eg_row = false;                                   // wave-uniform
+        float ev[2] = {0.0f, 0.0f};                            // E(b2) of this lane's covered tuples: loaded in (a), read in (c)
+        if constexpr (EG) {
+            const int ncell = __builtin_popcountll(__builtin_amdgcn_ballot_w64(lane < CELLS && base[lane < CELLS ? lane : 0] != 0));
+            eg_row = ncell == __builtin_popcount((unsigned)PA) + __builtin_popcount((unsigned)PO);
+        }
 
         // ---- (a) tuple t = lane + 64 half: the reply of cube k in direction e to root `root`
         int mt[2];
@@ -87,12 +110,30 @@ __global__ __launch_bounds__(LA_NT, 1) void k_predict_lookahead(int M, float tv,
                         const int PA2 = R.PA1 & ~(v1 > 0 ? 1 << (v1 & 7) : 0);
                         mt[half] = (t1 == 0 || PA2 == 0) ? LA_LOST : 0;
                         src0[half] = R.src; dst0[half] = R.dst; cub0[half] = R.cube; src1[half] = s1; dst1[half] = t1; cub1[half] = -k;
+                        if constexpr (EG) {
+                            const int PO2 = R.PO1 & ~(v1 < 0 ? 1 << (-v1 & 7) : 0);   // a reply captures its own side's cubes too
+                            const int na = __builtin_popcount((unsigned)PA2), no = __builtin_popcount((unsigned)PO2);   // both >= 1 on a leaf
+                            if (eg_row && mt[half] == 0 && na <= B.K && no <= B.K && na + no <= B.T) {
+                                // cube k's cell in byte k - 1 (eg_cell): pos[1 .. 6] and pos[9 .. 14], the two moved cubes at their targets
+                                const int sa = 8 * (R.cube - 1), so = 8 * (k - 1);
+                                const u64 pa = ((*(const u64 *)pos >> 8) & ~(0xFFull << sa)) | ((u64)R.dst << sa);
+                                const u64 po = ((*(const u64 *)(pos + 8) >> 8) & ~(0xFFull << so)) | ((u64)t1 << so);
+                                // no load but the gather itself (eg_rank, eg_off): nothing waits on it before (c)
+                                ev[half] = B.table[eg_off<S>(B.K, B.T, na, no) + (long long)eg_side_of<S>(eg_rank(PA2), PA2, pa, false) * (long long)eg_n<S>(no)
+                                                   + (long long)eg_side_of<S>(eg_rank(PO2), PO2, po, false)];
+                                mt[half] = LA_EXACT;
+                            }
+                        }
                     }
                 }
             }
         }
         const u64 leaf0 = __builtin_amdgcn_ballot_w64(mt[0] == 0), leaf1 = __builtin_amdgcn_ballot_w64(mt[1] == 0);
         const int n0 = __builtin_popcountll(leaf0), nleaf = n0 + __builtin_popcountll(leaf1);   // <= 108
+        if constexpr (EG) {
+            const int nex = __builtin_popcountll(__builtin_amdgcn_ballot_w64(mt[0] == LA_EXACT)) + __builtin_popcountll(__builtin_amdgcn_ballot_w64(mt[1] == LA_EXACT));
+            if (B.counts && lane < 2) B.counts[m * 2 + lane] = (int16_t)(lane == 0 ? nex : nleaf);
+        }
         #pragma unroll
         for (int half = 0; half < 2; half++) {
             const u64 bal = half ? leaf1 : leaf0;
@@ -137,6 +178,7 @@ __global__ __launch_bounds__(LA_NT, 1) void k_predict_lookahead(int M, float tv,
                     const float *v = Vt + 6 * mm;
                     w = (((((v[0] + v[1]) + v[2]) + v[3]) + v[4]) + v[5]) * (1.0f / 6.0f);
                 }
+                if constexpr (EG) { if (mm == LA_EXACT) w = tv * ev[half]; }
                 Wt[t] = w;
             }
         }
@@ -150,7 +192,15 @@ static int la_launch(int M, float tv, const LaBuf &lb, hipStream_t s)
 {
     constexpr size_t lds = LaGeo<S>::lds_bytes();
     static_assert(lds <= POL_LDS_MAX, "the value net's image + four waves' slots and tables must fit the CU's LDS");
-    return pol_launch_kernel(k_predict_lookahead<S>, la_blocks(M, LaGeo<S>::NW, LA_MAX_BLOCKS), LA_NT, lds, 64 * 1024, POL_LDS_MAX, s, M, tv, lb);
+    return pol_launch_kernel(k_predict_lookahead<S, false>, la_blocks(M, LaGeo<S>::NW, LA_MAX_BLOCKS), LA_NT, lds, 64 * 1024, POL_LDS_MAX, s, M, tv,
+                             LaArgs<false>{lb});
+}
+
+template <int S>
+static int la_launch_eg(int M, float tv, const LaArgs<true> &a, hipStream_t s)
+{
+    return pol_launch_kernel(k_predict_lookahead<S, true>, la_blocks(M, LaGeo<S>::NW, LA_MAX_BLOCKS), LA_NT, LaGeo<S>::lds_bytes(), 64 * 1024, POL_LDS_MAX,
+                             s, M, tv, a);
 }
 
 // ewn_predict_policy's order of refusals: arguments, geometry, the empty batch, pointers; then the terminal value -- all before the launch
@@ -165,4 +215,21 @@ int ewn_predict_lookahead(int board_size, int cube_layer, int M, const int8_t *b
     LaBuf lb = { boards, dice, params, actions, q };
     hipStream_t s = (hipStream_t)stream;
     return board_size == 5 ? la_launch<5>(M, terminal_value, lb, s) : la_launch<7>(M, terminal_value, lb, s);
+}
+
+// ewn_predict_lookahead's order with the table's parameters after the geometry (ewn_endgame_table_bytes' refusal)
+int ewn_predict_lookahead_eg(int board_size, int cube_layer, int M, const int8_t *boards, const int8_t *dice, const float *params,
+                             float terminal_value, int max_cubes, int max_total, const float *table, int8_t *actions, float *q,
+                             int16_t *leaf_counts, void *stream)
+{
+    if (M < 0) return EWN_EINVAL;
+    if (ewn_policy_param_count(board_size, cube_layer) < 0) return EWN_EUNSUPPORTED;
+    if (!eg_params_ok(board_size, max_cubes, max_total)) return EWN_EINVAL;
+    if (M == 0) return EWN_OK;
+    if (!boards || !dice || !params || !table || !actions) return EWN_ENULL;
+    if (!std::isfinite(terminal_value)) return EWN_EINVAL;
+    LaBuf lb = { boards, dice, params, actions, q };
+    LaArgs<true> a = { lb, max_cubes, max_total, table, leaf_counts };
+    hipStream_t s = (hipStream_t)stream;
+    return board_size == 5 ? la_launch_eg<5>(M, terminal_value, a, s) : la_launch_eg<7>(M, terminal_value, a, s);
 }

@@ -5,7 +5,8 @@ search is ewn_predict_lookahead (one or two moves ahead on the value net, DESIGN
 search's action, the critic toward the search's value, which bootstraps from the real terminal values (+-terminal_value) through
 its own leaves.  One update:
     rollout with the current policy (ewn_step_k_policy: only the visited observations are used, not the rewards)
-    -> predict_lookahead on the n_steps x lanes observations [-> the exact q where an endgame table covers the position, 4n]
+    -> predict_lookahead on the n_steps x lanes observations [with the table's exact values at the leaves it covers, 4p]
+       [-> the exact q where an endgame table covers the position, 4n]
     -> ewn_lookahead_targets -> ewn_sup_grad
     -> [all-reduce of the flat gradient] -> ewn_a2c_apply (global-norm clip + RMSprop).
 search="puct"  puts predict_puct in the search's place and AlphaZero's target in the target's: the policy heads are
@@ -47,7 +48,7 @@ class SearchDistillTrainer(FusedTrainer):
 
     def __init__(self, env, n_steps=5, learning_rate=7e-4, pi_coef=1.0, vf_coef=0.5, temperature=0.0, plies=1, terminal_value=1.0,
                  max_grad_norm=0.5, rms_alpha=0.99, rms_eps=1e-5, seed=None, opponent=None, opponent_update_every=100,
-                 opponent_deterministic=False, endgame_table=None, search="lookahead", sims=64, c_puct=1.5):
+                 opponent_deterministic=False, endgame_table=None, search="lookahead", sims=64, c_puct=1.5, endgame_leaves=False):
         import math
         from . import _lib
         if search not in ("lookahead", "puct"):
@@ -62,6 +63,8 @@ class SearchDistillTrainer(FusedTrainer):
                 raise ValueError("SearchDistillTrainer: %s must be finite and not negative, got %r" % (name, v))
         if not math.isfinite(float(terminal_value)):
             raise ValueError("SearchDistillTrainer: terminal_value must be finite, got %r" % (terminal_value,))
+        if endgame_leaves and endgame_table is None:
+            raise ValueError("SearchDistillTrainer: endgame_leaves=True needs an endgame_table")
         if endgame_table is not None:
             from .endgame import EndgameTable
             if not float(terminal_value) > 0.0:
@@ -73,6 +76,7 @@ class SearchDistillTrainer(FusedTrainer):
                 raise ValueError("SearchDistillTrainer: the endgame table is for %dx%d boards, the env plays %dx%d" % (
                     endgame_table.board_size, endgame_table.board_size, env.S, env.S))
         self.endgame_table = endgame_table   # None: the search's q alone; else its q is replaced by the exact one on covered rows
+        self.endgame_leaves = bool(endgame_leaves)   # the search itself takes the table: exact values at the leaves it covers (4p)
         super().__init__(env, n_steps, seed, False, opponent, opponent_update_every, opponent_deterministic)
         self.sq_avg = torch.zeros_like(self.params)
         self.pi_coef, self.vf_coef, self.temperature = float(pi_coef), float(vf_coef), float(temperature)
@@ -91,13 +95,14 @@ class SearchDistillTrainer(FusedTrainer):
         from ._lib import check
         from .vec_env import _ptr, _stream, lookahead_targets, predict_lookahead, predict_puct, sup_grad
         env, K, N, S = self.env, self.n_steps, self.env.N, self.env.S
+        leaves = {"endgame_table": self.endgame_table} if self.endgame_leaves else {}   # nothing: the calls as they were
         env.rollout_policy(K, self.params, traj=self.traj, noise_key=self.noise_key, **self._opponent_kwargs())
         self._boards.view(K, N, S, S).copy_(self.traj["obs_board"][:K])
         self._dice.view(K, N).copy_(self.traj["obs_dice"][:K])
         if self.search == "puct":
             _, visits, q, value = predict_puct(self._boards, self._dice, self.params, sims=self.sims, c_puct=self.c_puct,
                                                terminal_value=self.terminal_value, return_visits=True, return_q=True, return_value=True,
-                                               cube_layer=env.L)
+                                               cube_layer=env.L, **leaves)
             target_pi, target_value, weight = puct_targets(visits, q, value, self.terminal_value)
             if self.endgame_table is not None:     # covered rows: the exact q's targets, as the lookahead's rows get them
                 _, covered, q_exact = self.endgame_table.lookup(self._boards, self._dice, return_q=True)
@@ -106,7 +111,7 @@ class SearchDistillTrainer(FusedTrainer):
                 target_value, weight = torch.where(covered, e_value, target_value), torch.where(covered, e_weight, weight)
         else:
             _, q = predict_lookahead(self._boards, self._dice, self.params, terminal_value=self.terminal_value, return_q=True,
-                                     cube_layer=env.L, plies=self.plies)
+                                     cube_layer=env.L, plies=self.plies, **leaves)
             if self.endgame_table is not None:     # the exact rows have -inf where the search's have: the same moves leave the board
                 _, covered, q_exact = self.endgame_table.lookup(self._boards, self._dice, return_q=True)
                 q = torch.where(covered[:, None, None], self.terminal_value * q_exact, q)

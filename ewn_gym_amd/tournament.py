@@ -53,12 +53,14 @@ def _policy(spec, cube_layer, key):
         from classical_policies.model import ValueSearchAgent
         model = spec["model"]
         return ValueSearchAgent(model, board_size=getattr(model, "S", spec.get("board_size", 5)), cube_layer=cube_layer,
-                                terminal_value=spec.get("terminal_value", 1.0), plies=spec.get("plies", 1)).policy_fn()
+                                terminal_value=spec.get("terminal_value", 1.0), plies=spec.get("plies", 1),
+                                endgame_table=spec.get("endgame_table")).policy_fn()   # a table or its path: exact leaves
     if kind == "mlp_puct":      # the model's PUCT search on both of its heads (predict_puct), ply by ply through ewn_step
         from classical_policies.model import PuctAgent
         model = spec["model"]
         return PuctAgent(model, board_size=getattr(model, "S", spec.get("board_size", 5)), cube_layer=cube_layer, sims=spec.get("sims", 64),
-                         c_puct=spec.get("c_puct", 1.5), terminal_value=spec.get("terminal_value", 1.0)).policy_fn()
+                         c_puct=spec.get("c_puct", 1.5), terminal_value=spec.get("terminal_value", 1.0),
+                         endgame_table=spec.get("endgame_table")).policy_fn()
     if kind == "endgame":       # the exact move where the endgame table covers the position, the "fallback" spec's policy elsewhere
         from classical_policies.model import EndgameAgent
         if "table" not in spec or "fallback" not in spec:
@@ -336,13 +338,22 @@ def load_policy(path, board_size=5, cube_layer=3, device="cuda"):
 
 
 def evaluate_model(model, names=("random", "minimax"), num=1024, max_depth=5, num_simulations=10, num_env_copies=5, board_size=5,
-                   cube_layer=3, heuristic="hybrid", rng="mt19937", lookahead=False, endgame_table=None, puct=None):
+                   cube_layer=3, heuristic="hybrid", rng="mt19937", lookahead=False, endgame_table=None, puct=None,
+                   endgame_leaves=False):
     """eval_A2C.py's loop: the model's deterministic policy against every listed opponent; lookahead (1 / True, or 2): and, beside
     each, its lookahead policy of that many moves ({"kind": "mlp_lookahead", "plies": ...}) on the same episodes.  endgame_table (an
     EndgameTable or its path): every agent plays the exact move where the table covers the position ({"kind": "endgame"}, ply by ply).
-    puct (a number of simulations): and its PUCT search of that budget ({"kind": "mlp_puct", "sims": ...}), rows "puct(SIMS) vs ..." """
+    puct (a number of simulations): and its PUCT search of that budget ({"kind": "mlp_puct", "sims": ...}), rows "puct(SIMS) vs ..."
+    endgame_leaves (with lookahead and endgame_table): the table is not laid over the agents' moves; beside the lookahead's row
+    stands the same lookahead with the table's exact values at the leaves it covers, "lookahead + exact leaves vs ..." """
     table = {}
-    if endgame_table is not None:
+    leaf_table = None
+    if endgame_leaves:
+        if endgame_table is None or not lookahead:
+            raise ValueError("evaluate_model: endgame_leaves goes with lookahead and an endgame_table")
+        from .endgame import EndgameTable
+        leaf_table = endgame_table if isinstance(endgame_table, EndgameTable) else EndgameTable.load(endgame_table)
+    elif endgame_table is not None:
         return _evaluate_model_endgame(model, names, num, max_depth, num_simulations, num_env_copies, board_size, cube_layer, heuristic,
                                        rng, lookahead, endgame_table)
     for o in names:
@@ -354,6 +365,11 @@ def evaluate_model(model, names=("random", "minimax"), num=1024, max_depth=5, nu
             r = evaluate({"kind": "mlp_lookahead", "model": model, "plies": plies}, opp, num=num, board_size=board_size, cube_layer=cube_layer,
                          rng=rng)
             table[("lookahead(2) vs %s" if plies == 2 else "lookahead vs %s") % o] = {k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}
+            if leaf_table is not None:
+                r = evaluate({"kind": "mlp_lookahead", "model": model, "plies": plies, "endgame_table": leaf_table}, opp, num=num,
+                             board_size=board_size, cube_layer=cube_layer, rng=rng)
+                table[("lookahead(2) + exact leaves vs %s" if plies == 2 else "lookahead + exact leaves vs %s") % o] = {
+                    k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}
         if puct is not None:
             r = evaluate({"kind": "mlp_puct", "model": model, "sims": int(puct)}, opp, num=num, board_size=board_size, cube_layer=cube_layer,
                          rng=rng)
@@ -395,6 +411,9 @@ def _parser():
     ap.add_argument("--endgame_table", default=None,
                     help="with --model: a saved EndgameTable; the model (and its --lookahead) plays the exact move wherever the table "
                          "covers the position")
+    ap.add_argument("--endgame_leaves", action="store_true",
+                    help="with --lookahead and --endgame_table: the table is not laid over the moves; beside the lookahead's row, the "
+                         "same lookahead with the table's exact values at the leaves it covers (\"lookahead + exact leaves vs ...\")")
     ap.add_argument("--num", type=int, default=1024)
     ap.add_argument("--max_depth", type=int, default=5)
     ap.add_argument("--heuristic", default="hybrid")
@@ -417,6 +436,8 @@ def main():
         ap.error("--puct takes 0..4096 simulations")
     if a.endgame_table and (a.model is None or a.opponent_model is not None):
         ap.error("--endgame_table goes with --model and the classical opponents of --agents")
+    if a.endgame_leaves and not (a.endgame_table and a.lookahead):
+        ap.error("--endgame_leaves goes with --lookahead and --endgame_table")
     if a.opponent_model is not None and a.model is None:
         t = evaluate_agents_vs_model(load_policy(a.opponent_model, a.board_size, a.cube_layer), a.agents, a.num, a.max_depth,
                                      a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer, a.heuristic, a.rng)
@@ -428,7 +449,8 @@ def main():
     elif a.model is not None:
         model = load_policy(a.model, a.board_size, a.cube_layer)
         t = evaluate_model(model, a.agents, a.num, a.max_depth, a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer,
-                           a.heuristic, a.rng, lookahead=a.lookahead or False, endgame_table=a.endgame_table, puct=a.puct)
+                           a.heuristic, a.rng, lookahead=a.lookahead or False, endgame_table=a.endgame_table, puct=a.puct,
+                           endgame_leaves=a.endgame_leaves)
     else:
         t = tournament(a.agents, a.num, a.max_depth, a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer,
                        a.heuristic, a.rng)

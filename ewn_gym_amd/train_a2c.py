@@ -36,6 +36,8 @@ def _parser():
     ap.add_argument("--terminal_value", type=float, default=1.0, help="SEARCH: the value of a won (+) or lost (-) position in the lookahead")
     ap.add_argument("--endgame_table", default=None,
                     help="SEARCH: a saved EndgameTable; the search's q is replaced by the exact one wherever the table covers the position")
+    ap.add_argument("--endgame_leaves", action="store_true",
+                    help="SEARCH with --endgame_table: the search also values every leaf that the table covers by the table (DESIGN.md 4p)")
     ap.add_argument("--batch_size", "-b", type=int, default=None,
                     help="PPO: minibatch size in samples of the n_steps x lanes rollout buffer (default: a quarter of it; train.py:178-183)")
     ap.add_argument("--n_epochs", type=int, default=10, help="PPO: passes over the rollout buffer per update (SB3 default)")
@@ -87,6 +89,8 @@ def main():
         raise SystemExit("--search is read by SEARCH only")
     if a.endgame_table is not None and a.algorithm != "SEARCH":
         raise SystemExit("--endgame_table is read by SEARCH only")
+    if a.endgame_leaves and (a.algorithm != "SEARCH" or a.endgame_table is None):
+        raise SystemExit("--endgame_leaves goes with SEARCH and --endgame_table")
     lo, hi = lane_range(a.num_envs * world, world, rank)
     if a.reference_quirks and a.opponent_policy not in ("random", "minimax", "mcts"):
         raise SystemExit("--reference_quirks drops the opponent (MinimaxEnv plays RandomAgent whatever it is given): it cannot be combined "
@@ -114,7 +118,7 @@ def main():
         from .distill import SearchDistillTrainer
         trainer = SearchDistillTrainer(env, n_steps=a.n_steps, learning_rate=a.learning_rate, temperature=a.temperature, plies=a.plies,
                                        terminal_value=a.terminal_value, seed=mseed, endgame_table=a.endgame_table, search=a.search,
-                                       sims=a.sims, c_puct=a.c_puct, **okw)
+                                       sims=a.sims, c_puct=a.c_puct, endgame_leaves=a.endgame_leaves, **okw)
     elif a.trainer == "fused" or model_opp is not None or (a.trainer == "auto" and env.supports_policy_rollout()):
         trainer = FusedA2CTrainer(env, n_steps=a.n_steps, learning_rate=a.learning_rate, seed=mseed, **okw)
     else:

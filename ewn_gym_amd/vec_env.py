@@ -752,7 +752,21 @@ def lookahead_reduce(boards, dice, kind, leaf, terminal_value=1.0, return_q=Fals
     return (acts, q) if return_q else acts
 
 
-def predict_lookahead(boards, dice, params, terminal_value=1.0, return_q=False, cube_layer=3, plies=1, chunk=1024):
+def _leaf_table(who, table, M, S):
+    """endgame_table= of a search on M SxS boards: None, or an EndgameTable for that size, else ValueError (EndgameTable.lookup's
+    texts); that it lives on the GPU of the rest is the caller's _same_gpu"""
+    from .endgame import EndgameTable
+    if table is None:
+        return None
+    if not isinstance(table, EndgameTable):
+        raise ValueError("%s: endgame_table must be an EndgameTable, got %s" % (who, type(table).__name__))
+    if table.board_size != S:
+        raise ValueError("%s: boards of shape %s, the table is for %dx%d" % (who, [M, S, S], table.board_size, table.board_size))
+    return table
+
+
+def predict_lookahead(boards, dice, params, terminal_value=1.0, return_q=False, cube_layer=3, plies=1, chunk=1024, endgame_table=None,
+                      return_leaf_counts=False):
     """What the trained actor-critic plays when it looks one move ahead with its own value net (ewn_predict_lookahead):
     per observation and env action (f, r), Q = -inf for a move that leaves the board, +terminal_value for one that wins, otherwise the
     mean over the opponent's dice of its best (minimal) reply, a reply being worth -terminal_value if it wins for the opponent and
@@ -762,33 +776,51 @@ def predict_lookahead(boards, dice, params, terminal_value=1.0, return_q=False, 
     argument checks as predict_policy: anything the kernel cannot read in place raises ValueError before a launch.
     plies=2 looks two moves ahead: the same tree with each leaf V(b2, d2) replaced by the maximum of the one-move Q at
     (b2, d2) -- lookahead_expand, ewn_predict_lookahead on the 648 leaf rows per observation, lookahead_reduce -- `chunk` observations
-    at a time on scratch allocated once per call (about 49 KB per observation of the chunk at 7x7)."""
+    at a time on scratch allocated once per call (about 49 KB per observation of the chunk at 7x7).
+    endgame_table (an EndgameTable of the boards' size on the same GPU): a leaf b2 that the table covers is worth
+    terminal_value * E(b2), exactly, instead of the critic's mean there (ewn_predict_lookahead_eg); with plies=2 the table goes to the
+    inner call on the 648 leaf rows.  return_leaf_counts (plies=1 with a table): the int16 [M, 2] counts of leaf tuples valued by the
+    table and by the critic are returned last."""
     lib = _lib.load()
     if plies not in (1, 2):
         raise ValueError("predict_lookahead: plies must be 1 or 2, got %r" % (plies,))
     if int(chunk) < 1:
         raise ValueError("predict_lookahead: chunk must be at least 1, got %r" % (chunk,))
+    if return_leaf_counts and plies != 1:
+        raise ValueError("predict_lookahead: return_leaf_counts is the one-move call's (plies=1), got plies=%r" % (plies,))
+    if return_leaf_counts and endgame_table is None:
+        raise ValueError("predict_lookahead: return_leaf_counts needs an endgame_table")
     who = "predict_lookahead"
     M, S, P = _lookahead_shape(who, boards, cube_layer)
+    table = _leaf_table(who, endgame_table, M, S)
     dev = _policy_params(who, params, P, S)
     if not math.isfinite(float(terminal_value)):
         raise ValueError("predict_lookahead: terminal_value must be finite, got %r" % (terminal_value,))
     b = _policy_input("boards", boards, torch.int8, (M, S, S), dev, who=who)
     d = _policy_input("dice", dice, torch.int8, (M,), dev, who=who)
-    _same_gpu(who, dev, "params", (("params", params), ("boards", b), ("dice", d)))
+    _same_gpu(who, dev, "params", (("params", params), ("boards", b), ("dice", d), ("the table", None if table is None else table.table)))
     acts = torch.zeros((M, 2), dtype=torch.int8, device=dev)
     q = torch.zeros((M, 2, 3), dtype=torch.float32, device=dev) if return_q else None
     if plies == 2:
-        return _predict_lookahead2(lib, S, int(cube_layer), M, b, d, params, float(terminal_value), acts, q, int(chunk))
+        return _predict_lookahead2(lib, S, int(cube_layer), M, b, d, params, float(terminal_value), acts, q, int(chunk), table)
+    if table is None:
+        with torch.cuda.device(dev):
+            check(lib.ewn_predict_lookahead(S, int(cube_layer), M, _ptr(b), _ptr(d), _ptr(params), C.c_float(float(terminal_value)),
+                                            _ptr(acts), _ptr(q), _stream()), "ewn_predict_lookahead")
+        return (acts, q) if return_q else acts
+    counts = torch.zeros((M, 2), dtype=torch.int16, device=dev) if return_leaf_counts else None
     with torch.cuda.device(dev):
-        check(lib.ewn_predict_lookahead(S, int(cube_layer), M, _ptr(b), _ptr(d), _ptr(params), C.c_float(float(terminal_value)), _ptr(acts),
-                                        _ptr(q), _stream()), "ewn_predict_lookahead")
-    return (acts, q) if return_q else acts
+        check(lib.ewn_predict_lookahead_eg(S, int(cube_layer), M, _ptr(b), _ptr(d), _ptr(params), C.c_float(float(terminal_value)),
+                                           table.max_cubes, table.max_total, _ptr(table.table), _ptr(acts), _ptr(q), _ptr(counts),
+                                           _stream()), "ewn_predict_lookahead_eg")
+    out = (acts,) + tuple(t for t in (q, counts) if t is not None)
+    return out[0] if len(out) == 1 else out
 
 
-def _predict_lookahead2(lib, S, L, M, b, d, params, tv, acts, q, chunk):
+def _predict_lookahead2(lib, S, L, M, b, d, params, tv, acts, q, chunk, table=None):
     """predict_lookahead(plies=2) on checked inputs: per chunk of c observations expand -> ewn_predict_lookahead with q on the 648 c
-    leaf rows -> reduce at leaf_width 6; the scratch is one allocation per call, every row of it rewritten per chunk"""
+    leaf rows (ewn_predict_lookahead_eg where there is a table) -> reduce at leaf_width 6; the scratch is one allocation per call,
+    every row of it rewritten per chunk"""
     dev = params.device
     c = max(1, min(chunk, M, (2 ** 31 - 1) // LA_ROWS))  # a chunk's 648 c leaf rows are counted in an int
     lb = torch.empty((c * LA_ROWS, S, S), dtype=torch.int8, device=dev)
@@ -803,7 +835,11 @@ def _predict_lookahead2(lib, S, L, M, b, d, params, tv, acts, q, chunk):
             n = min(c, M - i)
             bi, di, ai, qi = b[i:i + n], d[i:i + n], acts[i:i + n], None if q is None else q[i:i + n]
             check(lib.ewn_lookahead_expand(S, L, n, _ptr(bi), _ptr(di), _ptr(lb), _ptr(ld), _ptr(kind), st), "ewn_lookahead_expand")
-            check(lib.ewn_predict_lookahead(S, L, LA_ROWS * n, _ptr(lb), _ptr(ld), _ptr(params), tvf, _ptr(la), _ptr(lq), st), "ewn_predict_lookahead")
+            if table is None:
+                check(lib.ewn_predict_lookahead(S, L, LA_ROWS * n, _ptr(lb), _ptr(ld), _ptr(params), tvf, _ptr(la), _ptr(lq), st), "ewn_predict_lookahead")
+            else:
+                check(lib.ewn_predict_lookahead_eg(S, L, LA_ROWS * n, _ptr(lb), _ptr(ld), _ptr(params), tvf, table.max_cubes, table.max_total,
+                                                   _ptr(table.table), _ptr(la), _ptr(lq), None, st), "ewn_predict_lookahead_eg")
             check(lib.ewn_lookahead_reduce(S, L, n, _ptr(bi), _ptr(di), _ptr(kind), _ptr(lq), 6, tvf, _ptr(ai), _ptr(qi), st),
                   "ewn_lookahead_reduce")
     return acts if q is None else (acts, q)
@@ -1011,7 +1047,7 @@ def puct_result(tree, board_size, sims, return_visits=False, return_q=False, ret
 
 
 def predict_puct(boards, dice, params, sims=64, c_puct=1.5, terminal_value=1.0, return_visits=False, return_q=False, return_value=False,
-                 cube_layer=3, chunk=1024):
+                 cube_layer=3, chunk=1024, endgame_table=None):
     """What the trained actor-critic plays after a PUCT search of `sims` simulations on its own two heads: the policy
     head says where to look, the value head what a leaf is worth, a move that wins on the board is worth +1 and is played; the
     opponent's and the agent's later dice are chance nodes sampled in a fixed stratified order, so the search is deterministic.
@@ -1019,18 +1055,21 @@ def predict_puct(boards, dice, params, sims=64, c_puct=1.5, terminal_value=1.0, 
     tuple (actions, visits int32 [M, 2, 3], q float32 [M, 2, 3], value float32 [M]) of what was asked for, as puct_result returns
     them.  sims=0: no search, zero visits, the first legal move unless one wins.  The stages are puct_begin, then sims + 1 rounds of
     ewn_predict_policy on the leaf rows and puct_advance, then puct_result, `chunk` observations at a time on scratch allocated once
-    per call (a tree is 256 bytes per simulation at 5x5, 280 at 7x7).  predict_lookahead's argument checks."""
+    per call (a tree is 256 bytes per simulation at 5x5, 280 at 7x7).  predict_lookahead's argument checks.
+    endgame_table (an EndgameTable of the boards' size on the same GPU): a pending leaf that the table covers is worth
+    terminal_value * max_a q_exact(leaf board, leaf dice) instead of the value head's output; the logits are the policy head's."""
     who = "predict_puct"
     lib = _lib.load()
     sims = _puct_numbers(who, sims, c_puct, terminal_value)
     if int(chunk) < 1:
         raise ValueError("%s: chunk must be at least 1, got %r" % (who, chunk))
     M, S, P = _lookahead_shape(who, boards, cube_layer)
+    table = _leaf_table(who, endgame_table, M, S)
     L = int(cube_layer)
     dev = _policy_params(who, params, P, S)
     b = _policy_input("boards", boards, torch.int8, (M, S, S), dev, who=who)
     d = _policy_input("dice", dice, torch.int8, (M,), dev, who=who)
-    _same_gpu(who, dev, "params", (("params", params), ("boards", b), ("dice", d)))
+    _same_gpu(who, dev, "params", (("params", params), ("boards", b), ("dice", d), ("the table", None if table is None else table.table)))
     acts = torch.zeros((M, 2), dtype=torch.int8, device=dev)
     visits = torch.zeros((M, 2, 3), dtype=torch.int32, device=dev) if return_visits else None
     q = torch.zeros((M, 2, 3), dtype=torch.float32, device=dev) if return_q else None
@@ -1053,6 +1092,9 @@ def predict_puct(boards, dice, params, sims=64, c_puct=1.5, terminal_value=1.0, 
             for _ in range(sims + 1):
                 check(lib.ewn_predict_policy(S, L, n, _ptr(lb), _ptr(ld), _ptr(params), 1, C.c_uint64(0), None, None, _ptr(la), _ptr(lg),
                                              _ptr(lv), st), "ewn_predict_policy")
+                if table is not None:                          # a tree without a pending leaf shows a zero board: not covered
+                    _, covered, q_exact = table.lookup(lb[:n], ld[:n], return_q=True)
+                    lv[:n] = torch.where(covered, float(terminal_value) * q_exact.reshape(n, 6).max(1).values, lv[:n])
                 check(lib.ewn_puct_advance(S, L, n, sims, cp, tv, _ptr(tree), _ptr(lg), _ptr(lv), _ptr(lb), _ptr(ld), st), "ewn_puct_advance")
             check(lib.ewn_puct_result(S, L, n, _ptr(tree), _ptr(acts[sl]), _ptr(None if visits is None else visits[sl]),
                                       _ptr(None if q is None else q[sl]), _ptr(None if val is None else val[sl]), st), "ewn_puct_result")

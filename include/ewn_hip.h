@@ -658,6 +658,21 @@ int ewn_endgame_lookup(int board_size, int max_cubes, int max_total, const float
                        const int8_t *dice, int8_t *actions /* [M][2] */, float *q /* [M][6], optional */,
                        float *value /* [M], optional */, uint8_t *covered /* [M], optional */, void *stream);
 
+/* ewn_predict_lookahead with exact leaves: everything as there, except that W of a reply whose b2 the table (of
+ * ewn_endgame_build for board_size, max_cubes, max_total) covers is fl(terminal_value * E(b2)), E(b2) the table's entry for b2 with
+ * the agent to move, instead of the mean of the six critic values.  b2 is covered exactly where ewn_endgame_lookup would cover it.
+ * An observation with a cube number twice on a side, or a cell outside -6..6, is no position of the table's: all its leaves go to
+ * the critic and its row is ewn_predict_lookahead's, bit for bit.  q [M][6] may be NULL; leaf_counts [M][2] (int16) may be NULL:
+ * the number of leaf tuples valued by the table, then by the critic ((0, 0) on a row that is not searched).  Refusals in this order:
+ * EWN_EINVAL for M < 0, EWN_EUNSUPPORTED where ewn_policy_param_count() is negative, EWN_EINVAL for table parameters that
+ * ewn_endgame_table_bytes refuses, EWN_OK without a launch for M == 0, EWN_ENULL for a missing boards, dice, params, table or
+ * actions, EWN_EINVAL for a non-finite terminal_value.  One kernel launch on `stream`, no allocation, no synchronisation.  Reads
+ * exactly boards[0 .. M*S*S), dice[0 .. M) and the table entries of covered leaves; writes exactly the M rows of the outputs given. */
+int ewn_predict_lookahead_eg(int board_size, int cube_layer, int M, const int8_t *boards, const int8_t *dice,
+                             const float *params, float terminal_value, int max_cubes, int max_total, const float *table,
+                             int8_t *actions /* [M][2] */, float *q /* [M][6], optional */,
+                             int16_t *leaf_counts /* [M][2], optional */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

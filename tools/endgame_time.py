@@ -11,8 +11,12 @@ agent-to-move observations of a 64-step rollout of each model's own policy on 4 
 ones the critic's |V / terminal_value - max q_exact|, the one-move and the two-move lookahead's |Q / terminal_value - q_exact| over the
 moves that stay on the board (mean and maximum), and how often the argmax policy, the critic-free lookaheads' actions are exact-optimal
 (their q_exact equals the row's maximum).
+With the (5, 3, 5) table built (not --skip_big, and at least 32 GiB of device memory free), also DESIGN.md section 4p's figure: on
+the rows that (5, 3, 5) covers and (5, 2, 4) does not, the one-move and two-move |Q / terminal_value - q_exact| against the large
+table's q_exact, with the critic alone at the leaves and with the (5, 2, 4) table's exact values at the leaves it covers.
 Part (d): over `--episodes` episodes (seeds 0 .. n-1, MT19937-compat dice) the wins of EndgameAgent(table, fallback=ValueSearchAgent)
-beside the bare ValueSearchAgent, against RandomAgent and minimax(5), Wilson 95 % intervals.
+and of ValueSearchAgent(endgame_table=table), the lookahead with exact leaves (4p), beside the bare ValueSearchAgent, against
+RandomAgent and minimax(5), Wilson 95 % intervals.
 One JSON line per row.  No pass bar: nothing here was measured before."""
 import argparse
 import json
@@ -94,12 +98,37 @@ def against_the_table(name, tr, tv, tables):
         row["lookahead(%d)_abs_err_mean_max" % plies] = [round(float(e.mean()), 4), round(float(e.max()), 4)]
         row["lookahead(%d)_optimal" % plies] = optimal(a)
     print(json.dumps(row), flush=True)
+    if len(tables) > 1:
+        exact_leaves(name, tr, tv, tables[0], tables[1], traj, K * N)
+
+
+def exact_leaves(name, tr, tv, small, big, traj, M):
+    """the positions the exact leaves are for: covered by `big`, not by `small`; Q with the critic at every leaf and with `small`'s
+    exact values at the leaves it covers, against `big`'s q_exact"""
+    S = small.board_size
+    b = traj["obs_board"][:-1].reshape(M, S, S).contiguous()
+    d = traj["obs_dice"][:-1].reshape(M).contiguous()
+    _, cov_big, qe = big.lookup(b, d, return_q=True)
+    rows = cov_big & ~small.lookup(b, d)[1]
+    b, d, qe = b[rows].contiguous(), d[rows].contiguous(), qe[rows].reshape(-1, 6)
+    on, best = torch.isfinite(qe), qe.max(1).values
+    counts = ea.predict_lookahead(b, d, tr.params, terminal_value=tv, endgame_table=small, return_leaf_counts=True)[1].sum(0).tolist()
+    row = {"trained": name, "rows covered by %s and not by %s" % ((big.board_size, big.max_cubes, big.max_total), (S, small.max_cubes, small.max_total)):
+           int(rows.sum()), "leaf_tuples_by_table_by_critic": counts}
+    for plies in (1, 2):
+        for label, t in (("critic leaves", None), ("exact leaves", small)):
+            a, q = ea.predict_lookahead(b, d, tr.params, terminal_value=tv, return_q=True, plies=plies, endgame_table=t)
+            e = (q.reshape(-1, 6) / tv - qe).abs()[on]
+            opt = (qe.gather(1, (a[:, 0].long() * 3 + a[:, 1].long())[:, None])[:, 0] == best).float().mean()
+            row["lookahead(%d) %s: abs_err_mean_max, optimal" % (plies, label)] = [round(float(e.mean()), 4), round(float(e.max()), 4), round(float(opt), 4)]
+    print(json.dumps(row), flush=True)
 
 
 def strength(name, tr, tv, t, episodes):
     for opp in ({"kind": "random"}, {"kind": "minimax", "max_depth": 5}):
         bare = {"kind": "mlp_lookahead", "model": tr.model, "terminal_value": tv}
-        for pol, agent in (("lookahead", bare), ("endgame+lookahead", {"kind": "endgame", "table": t, "fallback": bare})):
+        for pol, agent in (("lookahead", bare), ("endgame+lookahead", {"kind": "endgame", "table": t, "fallback": bare}),
+                           ("lookahead+exact leaves", dict(bare, endgame_table=t))):
             r = evaluate(agent, opp, num=episodes, board_size=5)
             print(json.dumps({"trained": name, "policy": pol, "opponent": opp["kind"] + ("(5)" if opp["kind"] == "minimax" else ""),
                               "episodes": r["episodes"], "wins": r["wins"], "win_rate": round(r["win_rate"], 4),
@@ -116,6 +145,9 @@ def main():
     a = ap.parse_args()
     tables = [build_ms(5, 2, 4, a.runs)]
     part_b(tables[0], a.runs)
+    if not a.skip_big and torch.cuda.mem_get_info()[0] < 32 << 30:
+        print(json.dumps({"skipped": "(7, 2, 4) and (5, 3, 5): less than 32 GiB of device memory free"}), flush=True)
+        a.skip_big = True
     if not a.skip_big:
         t7 = build_ms(7, 2, 4, 1)
         del t7

@@ -15,7 +15,13 @@ Prints one JSON line per row.  No pass bar: nothing here was measured before.
 
 --plies 2 (section 4l): part 1 becomes predict_lookahead(plies=2) beside predict_lookahead(plies=1) at M = 1 and 1 024, alternated in the
 same process, with the two stage calls (lookahead_expand, lookahead_reduce at leaf_width 6) timed alone; part 2 gains a lookahead(2) row
-per opponent: the same model, seeds, dice and terminal_value."""
+per opponent: the same model, seeds, dice and terminal_value.
+
+--endgame_table PATH (section 4p; a table written by EndgameTable.save): instead of the parts above, per batch (M = 1, 1 024, 65 536)
+on the table's board predict_lookahead(endgame_table=) beside the plain predict_lookahead on the same observations, alternated in the
+same process, actions only.  The observations are every observation of a `--rollout_steps`-step random-agent rollout of 4 096 games with
+auto-reset, long enough that games reach their endgames (the step count is printed), repeated up to M; with them the share of leaf
+tuples that the table values, from leaf_counts."""
 import argparse
 import json
 import os
@@ -67,13 +73,44 @@ def leaf_columns(board, d):
     return 6 * n
 
 
+def exact_leaves(t, steps, runs):
+    S, N = t.board_size, 4096
+    torch.manual_seed(9)
+    params = ActorCritic(S, 6).cuda().flat_parameters()
+    env = ea.VecEWN(N, board_size=S, opponent_policy="random", rng="philox", autoreset=True, seed_stride=N, philox_key=7)
+    env.reset(seeds=(np.arange(N, dtype=np.uint64) + 9487).astype(np.uint32))
+    traj = env.alloc_rollout(steps)
+    env.rollout(steps, agent="random", traj=traj)
+    for M in (1, 1024, 65536):
+        idx = (torch.arange(M, device="cuda") * 7919) % (steps * N)       # spread over the steps, so that a small M sees every stage of a game
+        b, d = traj["board"].reshape(-1, S, S)[idx].contiguous(), traj["dice"].reshape(-1)[idx].contiguous()
+        counts = ea.predict_lookahead(b, d, params, endgame_table=t, return_leaf_counts=True)[1].sum(0).tolist()
+        fns = {"predict_lookahead endgame_table": lambda: ea.predict_lookahead(b, d, params, endgame_table=t),
+               "predict_lookahead": lambda: ea.predict_lookahead(b, d, params)}
+        launches = 200 if M <= 1024 else 20
+        for fn in fns.values():                                           # warm-up
+            for _ in range(5):
+                fn()
+        rows = {}
+        for _ in range(2):                                                # alternate the two, keep the later pass
+            for name, fn in fns.items():
+                rows[name] = timed(fn, launches, runs)
+        print(json.dumps({"board": S, "M": M, "table": [S, t.max_cubes, t.max_total], "rollout_steps": steps, "us_per_call_median_min_max": rows,
+                          "covered_roots_share": round(float(t.lookup(b, d)[1].float().mean()), 4), "leaf_tuples_by_table_by_critic": counts,
+                          "share_of_leaf_tuples_by_table": round(counts[0] / max(1, counts[0] + counts[1]), 4)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--updates", type=int, default=600)
     ap.add_argument("--episodes", type=int, default=1024)
     ap.add_argument("--plies", type=int, default=1, choices=(1, 2))
+    ap.add_argument("--endgame_table", default=None)
+    ap.add_argument("--rollout_steps", type=int, default=64)
     a = ap.parse_args()
+    if a.endgame_table is not None:
+        return exact_leaves(ea.EndgameTable.load(a.endgame_table), a.rollout_steps, a.runs)
     for S in (5, 7) if a.plies == 2 else ():
         torch.manual_seed(9)
         params = ActorCritic(S, 6).cuda().flat_parameters()
