@@ -363,10 +363,11 @@ class FusedTrainer(PolicyOpponent):
     _use_instead = ""        # the tail of the refusal below: the torch trainer that serves such an env
     _written_by = None       # "the fused A2C trainer": who load() says a foreign checkpoint was not written by
 
-    def __init__(self, env, n_steps, seed, use_graph, opponent, opponent_update_every, opponent_deterministic):
+    def __init__(self, env, n_steps, seed, use_graph, opponent, opponent_update_every, opponent_deterministic, policy_rollout=True):
         import torch.distributed as dist
         from . import _lib
-        if opponent is None and not env.supports_policy_rollout():
+        # policy_rollout False: a trainer that collects without ewn_step_k_policy (PuctSelfPlayTrainer) needs neither the kernel nor its records
+        if policy_rollout and opponent is None and not env.supports_policy_rollout():
             raise _lib.EwnError("this env configuration has no policy-driven rollout kernel (ewn_step_k_policy)" + self._use_instead)
         self.env, self.lib, self.device = env, env.lib, env.board.device
         if seed is not None:
@@ -385,7 +386,7 @@ class FusedTrainer(PolicyOpponent):
         self.grad = torch.zeros(self.params.numel() + 8, dtype=torch.float32, device=self.device)
         self.grad_norm = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.n_steps, self.num_timesteps = int(n_steps), 0
-        self.traj = env.alloc_rollout(self.n_steps, layout="record", initial_obs=True)
+        self.traj = env.alloc_rollout(self.n_steps, layout="record", initial_obs=True) if policy_rollout else None
         self.noise_key = (0 if seed is None else int(seed)) * 0x9E3779B97F4A7C15 & 0xFFFFFFFFFFFFFFFF
         self.gen = torch.Generator(device=self.device)                # policy_fn's sampling only (evaluation is deterministic)
         self.gen.manual_seed(0 if seed is None else int(seed))

@@ -3,6 +3,8 @@
 // observations, the caller evaluates a row per tree with ewn_predict_policy, advance folds that evaluation into the tree (priors,
 // backup) and walks one more simulation down to the next observation to evaluate, result reads the root.  No network runs here and
 // no random number enters: the chance nodes are a stratified sample of the dice (the least visited dice first).
+// Self-play on these trees (ewn_puct_advance_noise, ewn_puct_play): a second instance of advance mixes the caller's
+// weights into the root's priors, and play takes a game's move off its finished tree -- the only kernel here that draws (Philox).
 //
 // A wave per tree.  Per-edge state (N, W, P, kind, child[.][d'], cn[.][d']) of edge a is read and written by lane a alone, in every
 // kernel: a tree's values never travel between lanes through global memory, only through LDS and cross-lane reads.  The node's board
@@ -100,6 +102,14 @@ EWN_DEV void pu_backup(const PuTree &T, int j, float v, int lane, int nodes)
 struct PuBeginBuf { const int8_t *boards; const int8_t *dice; uint8_t *tree; int8_t *leaf_boards; int8_t *leaf_dice; };
 struct PuAdvanceBuf { uint8_t *tree; const float *logits; const float *value; int8_t *leaf_boards; int8_t *leaf_dice; };
 struct PuResultBuf { uint8_t *tree; int8_t *actions; int *visits; float *q; float *value; };
+// the noise instance's buffers: PuAdvanceBuf first, so that the plain instance's kernel arguments are what they were
+struct PuNoiseBuf : PuAdvanceBuf { const float *noise; float eps, keep; };   // noise [M][6]; keep = 1 - eps, formed once on the host
+template <bool NOISE> struct PuAdvanceArg { typedef PuAdvanceBuf type; };
+template <> struct PuAdvanceArg<true> { typedef PuNoiseBuf type; };
+struct PuPlayBuf {
+    const uint8_t *tree; int8_t *boards; int8_t *dice; int *game;
+    int8_t *rec_board; int8_t *rec_dice; int *rec_visits; float *rec_value; int8_t *rec_action; int8_t *rec_live;
+};
 
 // A block per tree: every byte of the tree (zeros, child -1), then wave 0 writes the header, the root and the leaf row
 template <int S>
@@ -139,8 +149,10 @@ __global__ __launch_bounds__(PU_NT) void k_puct_begin(int M, int sims, PuLayout 
     }
 }
 
-template <int S>
-__global__ __launch_bounds__(PU_NT) void k_puct_advance(int M, int sims, float c_puct, float inv_tv, PuLayout L, PuAdvanceBuf B)
+// NOISE (ewn_puct_advance_noise): when the node evaluated is the root, its priors are mixed with the caller's
+// weights, normalised over the legal edges, before the backup and before the first simulation selects on them
+template <int S, bool NOISE>
+__global__ __launch_bounds__(PU_NT) void k_puct_advance(int M, int sims, float c_puct, float inv_tv, PuLayout L, typename PuAdvanceArg<NOISE>::type B)
 {
     constexpr int CELLS = S * S;
     __shared__ __attribute__((aligned(16))) int8_t lds[(PU_NT / 64) * PU_WAVE];
@@ -178,7 +190,25 @@ __global__ __launch_bounds__(PU_NT) void k_puct_advance(int M, int sims, float c
                     if (lane < 8) sc[lane] = raw;
                     __builtin_amdgcn_wave_barrier();
                     const float sum = ((((sc[0] + sc[1]) + sc[2]) + sc[3]) + sc[4]) + sc[5];
-                    if (lane < 6) {
+                    if constexpr (NOISE) {
+                        float prior = E.kind == 0 ? 0.0f : raw / sum;
+                        if (pending == 0) {
+                            float eta = 0.0f;
+                            if (lane < 6 && E.kind != 0) {
+                                const float x = B.noise[m * 6 + lane];
+                                eta = x > 0.0f && x < __builtin_inff() ? x : 0.0f;   // NaN, inf, zero and negative numbers: no weight
+                            }
+                            __builtin_amdgcn_wave_barrier();   // the raw priors are read
+                            if (lane < 8) sc[lane] = eta;
+                            __builtin_amdgcn_wave_barrier();
+                            const float es = ((((sc[0] + sc[1]) + sc[2]) + sc[3]) + sc[4]) + sc[5];
+                            if (es > 0.0f && E.kind != 0) prior = B.keep * prior + B.eps * (eta / es);
+                        }
+                        if (lane < 6) {
+                            T.kind[6 * pending + lane] = (int8_t)E.kind;
+                            T.p[6 * pending + lane] = prior;
+                        }
+                    } else if (lane < 6) {
                         T.kind[6 * pending + lane] = (int8_t)E.kind;
                         T.p[6 * pending + lane] = E.kind == 0 ? 0.0f : raw / sum;
                     }
@@ -316,6 +346,115 @@ __global__ __launch_bounds__(PU_NT) void k_puct_result(int S, int M, PuResultBuf
     }
 }
 
+// The move of a self-play game off a finished tree (ewn_puct_play): a wave per game, the position played is the tree's
+// root.  The edge is the first winning one, else drawn in proportion to the root's visits while ply < temp_plies (integer
+// arithmetic on a Philox word), else k_puct_result's first maximum; the record row, the board after the move seen from the other
+// side, the next dice (a second Philox word) and the game's state are written.  The budget is read from the first tree's header
+template <int S>
+__global__ __launch_bounds__(PU_NT) void k_puct_play(int M, int temp_plies, u32 k0, u32 k1, long long game_offset, PuPlayBuf B)
+{
+    constexpr int CELLS = S * S;
+    __shared__ __attribute__((aligned(16))) int8_t lds[(PU_NT / 64) * PU_WAVE];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int8_t *base = lds + wave * PU_WAVE;
+    uint8_t *pos = (uint8_t *)(base + PU_O_POS);
+    float *sw = (float *)(base + PU_O_OWN);
+    int *sn = (int *)(base + PU_O_OWN) + 8;
+    const int sims = ((const int *)B.tree)[4];
+    const bool known = sims >= 0 && sims <= PU_MAX_SIMS && ((const int *)B.tree)[5] == PU_LAYOUT;
+    const PuLayout L = pu_layout(S, known ? sims : 0);
+
+    #pragma unroll 1
+    for (int m0 = (int)blockIdx.x * (PU_NT / 64) + wave; m0 < M; m0 += (int)gridDim.x * (PU_NT / 64)) {   // wave-uniform
+        const size_t m = (size_t)m0;
+        int *g = B.game + m * 4;
+        const int ply = g[0], over = g[1];
+        const PuTree T = pu_tree((uint8_t *)B.tree, m, L);     // read only
+        bool tree = false, live = false;
+        int kd = 0, nn = 0, PA = 0, PO = 0;
+        float ww = 0.0f;
+        PuEdge E = { 0, 0, 0, 0, false };
+        if (known) {
+            const int count = T.hdr[0], pending = T.hdr[2];
+            tree = T.hdr[4] == sims && T.hdr[5] == PU_LAYOUT && count >= 1 && count <= L.nodes && pending < count;
+        }
+        if (tree && over == 0 && T.hdr[3] == 0) {
+            __builtin_amdgcn_wave_barrier();                   // what was there is read
+            if (la_observation<S, 64>(T.board, lane, base, pos, PA, PO)) {
+                E = pu_edge<S>(base, pos, PA, PO, la_dice((int)T.dice[0]), lane);
+                if (lane < 6) {
+                    kd = T.kind[lane]; nn = T.n[lane]; ww = T.w[lane];
+                    kd = kd == E.kind ? kd : 0;                // an edge the rules do not know is no edge
+                }
+            }
+        }
+        if (lane < 8) { sw[lane] = ww; sn[lane] = nn; }
+        const u32 wins = (u32)__builtin_amdgcn_ballot_w64(kd == 1) & 0x3Fu, searched = (u32)__builtin_amdgcn_ballot_w64(kd == 2) & 0x3Fu;
+        __builtin_amdgcn_wave_barrier();
+        live = (wins | searched) != 0;
+        if (!live) {                                           // over, degenerate, without a move, or no tree: nothing is played
+            if (lane < CELLS && B.rec_board) B.rec_board[m * CELLS + lane] = 0;
+            if (lane < 6 && B.rec_visits) B.rec_visits[m * 6 + lane] = 0;
+            if (lane < 2 && B.rec_action) B.rec_action[m * 2 + lane] = 0;
+            if (lane == 0) {
+                if (B.rec_dice) B.rec_dice[m] = 0;
+                if (B.rec_value) B.rec_value[m] = 0.0f;
+                if (B.rec_live) B.rec_live[m] = 0;
+                if (tree && over == 0) g[1] = 1;               // a game that cannot go on is over, without a winner
+            }
+        } else {
+            u32 o[4];
+            const unsigned long long gid = (unsigned long long)game_offset + (unsigned long long)m;
+            philox4x32_10((u32)ply, (u32)gid, (u32)(gid >> 32), 0x50555350u, k0, k1, o);
+            const int tn = sn[0] + sn[1] + sn[2] + sn[3] + sn[4] + sn[5];
+            int best;
+            if (wins) best = __builtin_ctz(wins);              // a win on the board is played
+            else {
+                u32 ts = 0;                                    // the visits of the searched edges
+                #pragma unroll
+                for (int i = 0; i < 6; i++) ts += ((searched >> i) & 1u) ? (u32)sn[i] : 0u;
+                best = __builtin_ctz(searched);
+                if (ply < temp_plies && ts > 0) {              // in proportion to the visits: the first edge whose running sum passes r
+                    const u32 r = __umulhi(o[0], ts);
+                    u32 run = 0;
+                    bool found = false;
+                    #pragma unroll
+                    for (int i = 0; i < 6; i++) {
+                        run += ((searched >> i) & 1u) ? (u32)sn[i] : 0u;
+                        if (!found && ((searched >> i) & 1u) && run > r) { best = i; found = true; }
+                    }
+                } else {
+                    int nb = sn[best];
+                    #pragma unroll
+                    for (int i = 1; i < 6; i++) if (((searched >> i) & 1u) && sn[i] > nb) { nb = sn[i]; best = i; }
+                }
+            }
+            const int bk = (wins >> best) & 1u ? 1 : 2;
+            const int bsrc = __shfl(E.src, best), bdst = __shfl(E.dst, best), bcube = __shfl(E.cube, best);
+            if (lane < CELLS) {
+                if (B.rec_board) B.rec_board[m * CELLS + lane] = base[lane];
+                const int rc = CELLS - 1 - lane;               // flip(b1)
+                int v = base[rc];
+                v = rc == bsrc ? 0 : v;
+                v = rc == bdst ? bcube : v;
+                B.boards[m * CELLS + lane] = (int8_t)(-v);
+            }
+            if (lane < 6 && B.rec_visits) B.rec_visits[m * 6 + lane] = nn;
+            if (lane == 0) {
+                const float tw = ((((sw[0] + sw[1]) + sw[2]) + sw[3]) + sw[4]) + sw[5];
+                if (B.rec_dice) B.rec_dice[m] = T.dice[0];
+                if (B.rec_value) B.rec_value[m] = tn > 0 ? tw / (float)tn : 0.0f;
+                if (B.rec_action) { B.rec_action[m * 2] = (int8_t)(best / 3); B.rec_action[m * 2 + 1] = (int8_t)(best % 3); }
+                if (B.rec_live) B.rec_live[m] = 1;
+                B.dice[m] = (int8_t)(1 + (int)__umulhi(o[1], 6u));
+                g[0] = ply + 1;
+                if (bk == 1) { g[1] = 1; g[2] = (ply & 1) ? -1 : 1; }
+            }
+        }
+        __builtin_amdgcn_wave_barrier();                       // this trip's LDS is read: the next may overwrite it
+    }
+}
+
 // ewn_lookahead_expand's order of refusals: arguments, geometry, the empty batch, pointers; then the values -- all before the launch
 static inline int pu_refuse(int board_size, int cube_layer, int M)
 {
@@ -346,21 +485,40 @@ int ewn_puct_begin(int board_size, int cube_layer, int M, int sims, const int8_t
                            : pol_launch_kernel(k_puct_begin<7>, blocks, PU_NT, 0, 64 * 1024, POL_LDS_MAX, s, M, sims, L, b);
 }
 
-int ewn_puct_advance(int board_size, int cube_layer, int M, int sims, float c_puct, float terminal_value, void *tree,
-                     const float *logits, const float *value, int8_t *leaf_boards, int8_t *leaf_dice, void *stream)
+// both advance entry points: the refusals in one order, `missing` says whether a pointer of the caller's own is NULL
+template <bool NOISE>
+static int pu_advance(int board_size, int cube_layer, int M, int sims, float c_puct, float terminal_value, bool missing, float noise_eps,
+                      typename PuAdvanceArg<NOISE>::type b, void *stream)
 {
     const int rc = pu_refuse(board_size, cube_layer, M);
     if (rc != EWN_OK || M == 0) return rc;
-    if (!tree || !logits || !value || !leaf_boards || !leaf_dice) return EWN_ENULL;
-    if (sims < 0 || sims > PU_MAX_SIMS || ((uintptr_t)tree & 3)) return EWN_EINVAL;
+    if (missing || !b.tree || !b.logits || !b.value || !b.leaf_boards || !b.leaf_dice) return EWN_ENULL;
+    if (sims < 0 || sims > PU_MAX_SIMS || ((uintptr_t)b.tree & 3)) return EWN_EINVAL;
     if (!std::isfinite(terminal_value) || !(terminal_value > 0.0f) || !std::isfinite(c_puct) || c_puct < 0.0f) return EWN_EINVAL;
+    if (!(noise_eps >= 0.0f && noise_eps <= 1.0f)) return EWN_EINVAL;   // NaN is refused here as well
     const PuLayout L = pu_layout(board_size, sims);
     const float inv_tv = 1.0f / terminal_value;
-    PuAdvanceBuf b = { (uint8_t *)tree, logits, value, leaf_boards, leaf_dice };
     hipStream_t s = (hipStream_t)stream;
     const unsigned blocks = la_blocks(M, PU_NT / 64, PU_MAX_BLOCKS);
-    return board_size == 5 ? pol_launch_kernel(k_puct_advance<5>, blocks, PU_NT, 0, 64 * 1024, POL_LDS_MAX, s, M, sims, c_puct, inv_tv, L, b)
-                           : pol_launch_kernel(k_puct_advance<7>, blocks, PU_NT, 0, 64 * 1024, POL_LDS_MAX, s, M, sims, c_puct, inv_tv, L, b);
+    return board_size == 5 ? pol_launch_kernel(k_puct_advance<5, NOISE>, blocks, PU_NT, 0, 64 * 1024, POL_LDS_MAX, s, M, sims, c_puct, inv_tv, L, b)
+                           : pol_launch_kernel(k_puct_advance<7, NOISE>, blocks, PU_NT, 0, 64 * 1024, POL_LDS_MAX, s, M, sims, c_puct, inv_tv, L, b);
+}
+
+int ewn_puct_advance(int board_size, int cube_layer, int M, int sims, float c_puct, float terminal_value, void *tree,
+                     const float *logits, const float *value, int8_t *leaf_boards, int8_t *leaf_dice, void *stream)
+{
+    PuAdvanceBuf b = { (uint8_t *)tree, logits, value, leaf_boards, leaf_dice };
+    return pu_advance<false>(board_size, cube_layer, M, sims, c_puct, terminal_value, false, 0.0f, b, stream);
+}
+
+int ewn_puct_advance_noise(int board_size, int cube_layer, int M, int sims, float c_puct, float terminal_value, void *tree,
+                           const float *logits, const float *value, const float *root_noise, float noise_eps,
+                           int8_t *leaf_boards, int8_t *leaf_dice, void *stream)
+{
+    PuNoiseBuf b;
+    b.tree = (uint8_t *)tree; b.logits = logits; b.value = value; b.leaf_boards = leaf_boards; b.leaf_dice = leaf_dice;
+    b.noise = root_noise; b.eps = noise_eps; b.keep = 1.0f - noise_eps;
+    return pu_advance<true>(board_size, cube_layer, M, sims, c_puct, terminal_value, root_noise == nullptr, noise_eps, b, stream);
 }
 
 int ewn_puct_result(int board_size, int cube_layer, int M, const void *tree, int8_t *actions, int32_t *visits, float *q, float *value,
@@ -372,4 +530,21 @@ int ewn_puct_result(int board_size, int cube_layer, int M, const void *tree, int
     if ((uintptr_t)tree & 3) return EWN_EINVAL;
     PuResultBuf b = { (uint8_t *)tree, actions, visits, q, value };
     return pol_launch_kernel(k_puct_result, la_blocks(M, PU_NT / 64, PU_MAX_BLOCKS), PU_NT, 0, 64 * 1024, POL_LDS_MAX, (hipStream_t)stream, board_size, M, b);
+}
+
+int ewn_puct_play(int board_size, int cube_layer, int M, const void *tree, int8_t *boards, int8_t *dice, int32_t *game,
+                  int temp_plies, uint64_t key, int64_t game_offset,
+                  int8_t *rec_board, int8_t *rec_dice, int32_t *rec_visits, float *rec_value, int8_t *rec_action, int8_t *rec_live,
+                  void *stream)
+{
+    const int rc = pu_refuse(board_size, cube_layer, M);
+    if (rc != EWN_OK || M == 0) return rc;
+    if (!tree || !boards || !dice || !game) return EWN_ENULL;
+    if (temp_plies < 0 || ((uintptr_t)tree & 3) || ((uintptr_t)game & 3)) return EWN_EINVAL;
+    PuPlayBuf b = { (const uint8_t *)tree, boards, dice, (int *)game, rec_board, rec_dice, (int *)rec_visits, rec_value, rec_action, rec_live };
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned blocks = la_blocks(M, PU_NT / 64, PU_MAX_BLOCKS);
+    const u32 k0 = (u32)key, k1 = (u32)(key >> 32);
+    return board_size == 5 ? pol_launch_kernel(k_puct_play<5>, blocks, PU_NT, 0, 64 * 1024, POL_LDS_MAX, s, M, temp_plies, k0, k1, (long long)game_offset, b)
+                           : pol_launch_kernel(k_puct_play<7>, blocks, PU_NT, 0, 64 * 1024, POL_LDS_MAX, s, M, temp_plies, k0, k1, (long long)game_offset, b);
 }

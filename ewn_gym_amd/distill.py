@@ -17,20 +17,24 @@ import ctypes as C
 import torch
 
 from .a2c import FusedTrainer
+from .sharding import all_reduce_counters
 
 
-def puct_targets(visits, q, value, terminal_value=1.0):
+def puct_targets(visits, q, value, terminal_value=1.0, one_cube=None):
     """predict_puct's visits, q and value as training targets (plain torch, six numbers per row): visits [M, 2, 3], q float32
     [M, 2, 3], value float32 [M] -> (target_pi float32 [M, 5], target_value float32 [M], weight float32 [M]).  The flag head's target
     is sum_r visits / sum, the direction head's sum_f visits / sum; where both flags name one cube (flag 1 has no action of its own:
     its q row is all -inf) the flag head gets (0.5, 0.5), lookahead_targets' convention.  target_value = terminal_value * value.
-    A row without visits (degenerate, or sims=0) gets zeros and weight 0."""
+    A row without visits (degenerate, or sims=0) gets zeros and weight 0.  q None (self-play records hold no q): one_cube bool [M]
+    says where both flags name one cube (both_flags_one_cube)."""
+    if q is None and one_cube is None:
+        raise ValueError("puct_targets: without q, one_cube must say where both flags name one cube (both_flags_one_cube(boards, dice))")
     v = visits.reshape(-1, 2, 3).to(torch.float32)
     tot = v.sum((1, 2))
     live = tot > 0
     den = torch.where(live, tot, torch.ones_like(tot))[:, None]
     flag, direction = v.sum(2) / den, v.sum(1) / den
-    same = live & (q.reshape(-1, 2, 3)[:, 1] == float("-inf")).all(1)
+    same = live & ((q.reshape(-1, 2, 3)[:, 1] == float("-inf")).all(1) if q is not None else one_cube.reshape(-1))
     flag = torch.where(same[:, None], torch.full_like(flag, 0.5), flag)
     target_pi = torch.cat([flag, direction], 1) * live[:, None]
     target_value = torch.where(live, float(terminal_value) * value.reshape(-1), torch.zeros_like(tot))
@@ -140,3 +144,133 @@ class SearchDistillTrainer(FusedTrainer):
         self.plies = int(sd.get("plies", self.plies))
         self.search = sd.get("search", self.search)
         self.sims, self.c_puct = int(sd.get("sims", self.sims)), float(sd.get("c_puct", self.c_puct))
+
+
+def both_flags_one_cube(boards, dice):
+    """bool [M]: find_cube_to_move names one cube under both flags (plain torch): the dice's cube is on the board, or the mover's
+    cubes all lie on one side of the dice.  boards int8 [M, S, S] seen from the mover, dice [M] (outside 1..6: clamped)."""
+    flat = boards.reshape(boards.shape[0], -1)
+    d = dice.reshape(-1).clamp(1, 6).to(torch.int64)
+    present = torch.stack([(flat == k).any(1) for k in range(1, 7)], 1)
+    k = torch.arange(1, 7, device=boards.device)[None, :]
+    return present.gather(1, d[:, None] - 1)[:, 0] | ~(present & (k > d[:, None])).any(1) | ~(present & (k < d[:, None])).any(1)
+
+
+class PuctSelfPlayTrainer(FusedTrainer):
+    """AlphaZero's loop on the PUCT search: the search plays itself from fresh openings on the env's lanes
+    (selfplay_puct: root noise, moves drawn from the visits for the first temp_plies plies), the policy heads are trained toward the
+    roots' visit distributions and the critic toward terminal_value times the result of the game seen from the side to move.  Rows
+    past a game's end and rows of games that did not end within max_plies weigh nothing.  One update is one sup_grad over all
+    max_plies x lanes record rows and one ewn_a2c_apply; it runs torch operators and stays eager, like the distiller.  The env's
+    opponent and rewards are not used: the env supplies the lanes' opening positions."""
+
+    algorithm = "SELFPLAY"
+    _written_by = "the PUCT self-play trainer"
+
+    def __init__(self, env, sims=64, c_puct=1.5, terminal_value=1.0, noise_eps=0.25, noise_alpha=1.0, temp_plies=8, max_plies=None,
+                 learning_rate=7e-4, pi_coef=1.0, vf_coef=0.5, max_grad_norm=0.5, rms_alpha=0.99, rms_eps=1e-5, seed=None,
+                 endgame_table=None, chunk=1024):
+        import math
+        from . import _lib
+        from .vec_env import SELFPLAY_MAX_PLIES, _noise_eps, _play_numbers, _puct_numbers
+        who = "PuctSelfPlayTrainer"
+        _puct_numbers(who, sims, c_puct, terminal_value)
+        _noise_eps(who, noise_eps)
+        _play_numbers(who, temp_plies, 0, 0)
+        if not (math.isfinite(float(noise_alpha)) and float(noise_alpha) > 0.0):
+            raise ValueError("%s: noise_alpha must be finite and positive, got %r" % (who, noise_alpha))
+        for name, v in (("pi_coef", pi_coef), ("vf_coef", vf_coef)):
+            if not math.isfinite(float(v)) or float(v) < 0.0:
+                raise ValueError("%s: %s must be finite and not negative, got %r" % (who, name, v))
+        if max_plies is not None and not (isinstance(max_plies, int) and max_plies >= 1):
+            raise ValueError("%s: max_plies must be a positive integer or None, got %r" % (who, max_plies))
+        if endgame_table is not None:
+            from .endgame import EndgameTable
+            if not isinstance(endgame_table, EndgameTable):
+                endgame_table = EndgameTable.load(endgame_table, device=env.board.device)
+            if endgame_table.board_size != env.S:
+                raise ValueError("%s: the endgame table is for %dx%d boards, the env plays %dx%d" % (
+                    who, endgame_table.board_size, endgame_table.board_size, env.S, env.S))
+        self.endgame_table = endgame_table       # exact values at the leaves the table covers (4p), nothing else
+        super().__init__(env, 1, seed, False, None, 100, False, policy_rollout=False)
+        self.sq_avg = torch.zeros_like(self.params)
+        self.sims, self.c_puct, self.terminal_value = int(sims), float(c_puct), float(terminal_value)
+        self.noise_eps, self.noise_alpha, self.temp_plies = float(noise_eps), float(noise_alpha), int(temp_plies)
+        self.max_plies = SELFPLAY_MAX_PLIES[env.S] if max_plies is None else int(max_plies)
+        self.pi_coef, self.vf_coef, self.chunk = float(pi_coef), float(vf_coef), int(chunk)
+        self.seed_base, self.seed_counter = (0 if seed is None else int(seed)), 0   # the counter: one per update, saved and resumed
+        self.hyper = _lib.EwnA2cHyper(0.0, float(vf_coef), 0.0, float(max_grad_norm), float(learning_rate), float(rms_alpha), float(rms_eps),
+                                      int(self.world))
+        nscr = _lib.check(self.lib.ewn_sup_scratch_bytes(env.S, env.L, self.max_plies * env.N), "ewn_sup_scratch_bytes")
+        self.scratch = torch.zeros(int(nscr), dtype=torch.uint8, device=self.device)
+        self.records = None                      # the last update's games (selfplay_puct's dict)
+        self._games = [0.0, 0.0, 0.0, 0.0]       # live rows, mean plies, share of finished games, the first mover's share of them
+
+    def fresh_positions(self):
+        """the lanes reset on seeds no rank and no earlier update has used: counter x all lanes + the global lane id -> (board, dice,
+        the first lane's global game number)"""
+        import numpy as np
+        env = self.env
+        first = self.seed_counter * env.N * self.world + int(env.cfg.lane_offset)
+        seeds = (self.seed_base + first + np.arange(env.N, dtype=np.uint64)) & np.uint64(0xFFFFFFFF)
+        self.seed_counter += 1
+        board, dice = env.reset(seeds=seeds.astype(np.uint32))
+        return board, dice, first
+
+    def _launch(self):
+        from ._lib import check
+        from .vec_env import _ptr, _stream, selfplay_puct, sup_grad
+        env = self.env
+        board, dice, first = self.fresh_positions()
+        rec = selfplay_puct(board, dice, self.params, sims=self.sims, max_plies=self.max_plies, c_puct=self.c_puct,
+                            terminal_value=self.terminal_value, noise_eps=self.noise_eps, noise_alpha=self.noise_alpha,
+                            temp_plies=self.temp_plies, key=self.noise_key, game_offset=first, chunk=self.chunk,
+                            endgame_table=self.endgame_table, cube_layer=env.L)
+        self.records = rec
+        R, S = self.max_plies * env.N, env.S
+        b, d = rec["board"].reshape(R, S, S), rec["dice"].reshape(R).clamp(min=1)         # rows past a game's end hold dice 0
+        target_pi, _, _ = puct_targets(rec["visits"].reshape(R, 2, 3), None, rec["value"].reshape(R), self.terminal_value,
+                                       one_cube=both_flags_one_cube(b, d))
+        target_value = (self.terminal_value * rec["z"]).reshape(R).contiguous()
+        sup_grad(b, d, target_pi, target_value, self.params, weight=rec["weight"].reshape(R), pi_coef=self.pi_coef, vf_coef=self.vf_coef,
+                 cube_layer=env.L, out=self.grad, scratch=self.scratch)
+        self._all_reduce_grad()
+        check(self.lib.ewn_a2c_apply(C.byref(env.cfg), _ptr(self.params), _ptr(self.sq_avg), _ptr(self.grad), C.byref(self.hyper),
+                                     _ptr(self.grad_norm), _stream()), "ewn_a2c_apply")
+
+    def collect_and_update(self):
+        self._launch()
+        self._after_update()
+        rec = self.records
+        # Games differ in length from rank to rank, and learn() loops on num_timesteps: the counts are summed over the ranks, so that
+        # every rank adds the same number and leaves the loop after the same update (a rank alone in the gradient's all-reduce hangs)
+        counts = all_reduce_counters(torch.stack([rec["live"].sum(), rec["plies"].sum(), (rec["winner"] != 0).sum(),
+                                                  (rec["winner"] == 1).sum()]).to(torch.int64)).tolist()   # the update's one host read
+        games = self.env.N * self.world
+        self._games = [counts[0], counts[1] / games, counts[2] / games, counts[3] / max(1, counts[2])]
+        self.num_timesteps += counts[0] // self.world                                    # recorded positions, this rank's share
+        return self.grad
+
+    def stats_dict(self):
+        g = self.grad[-8:].tolist()
+        live = g[3]
+        per = (lambda x: x / live) if live > 0 else (lambda x: 0.0)
+        pl, vl, en = per(g[0]), per(g[4]), per(g[1])
+        return {"loss": self.pi_coef * pl + self.vf_coef * vl, "policy_loss": pl, "value_loss": vl, "entropy": en, "agreement": per(g[2]),
+                "grad_norm": float(self.grad_norm), "live_fraction": live / float(self.max_plies * self.env.N * self.world),
+                "mean_game_length": self._games[1], "finished_fraction": self._games[2], "first_mover_win_fraction": self._games[3]}
+
+    def _state(self):
+        return {"sq_avg": self.sq_avg, "terminal_value": float(self.terminal_value), "sims": int(self.sims), "c_puct": float(self.c_puct),
+                "noise_eps": float(self.noise_eps), "noise_alpha": float(self.noise_alpha), "temp_plies": int(self.temp_plies),
+                "max_plies": int(self.max_plies), "seed_counter": int(self.seed_counter)}
+
+    def _load_state(self, sd):
+        self.sq_avg.copy_(sd["sq_avg"])
+        self.terminal_value = float(sd.get("terminal_value", self.terminal_value))
+        self.sims, self.c_puct = int(sd.get("sims", self.sims)), float(sd.get("c_puct", self.c_puct))
+        self.noise_eps, self.noise_alpha = float(sd.get("noise_eps", self.noise_eps)), float(sd.get("noise_alpha", self.noise_alpha))
+        self.temp_plies, self.seed_counter = int(sd.get("temp_plies", self.temp_plies)), int(sd.get("seed_counter", self.seed_counter))
+        if int(sd.get("max_plies", self.max_plies)) != self.max_plies:
+            raise ValueError("the checkpoint's games have at most %d plies, this trainer's %d: the update's scratch is sized by it" % (
+                int(sd["max_plies"]), self.max_plies))

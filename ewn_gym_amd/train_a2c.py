@@ -1,6 +1,6 @@
 """Command-line counterpart of the reference's train.py (argument names follow train.py:162-259
 where they apply): A2C (or PPO: `python -m ewn_gym_amd.train_a2c PPO ...`; or SEARCH: distillation of the lookahead search,
-ewn_gym_amd/distill.py) on VecEWN lanes instead of SubprocVecEnv workers, per-epoch evaluation
+ewn_gym_amd/distill.py; or SELFPLAY: the PUCT search playing itself, PuctSelfPlayTrainer) on VecEWN lanes instead of SubprocVecEnv workers, per-epoch evaluation
 against minimax on the un-shaped env (train.py:66-117), best-model checkpointing.
 
   python -m ewn_gym_amd.train_a2c --num_envs 4096 --epoch_num 10 --timesteps_per_epoch 200000
@@ -23,17 +23,26 @@ from .vec_env import VecEWN
 def _parser():
     ap = argparse.ArgumentParser(description="Trainer for EWN on VecEWN lanes (counterpart of the reference's train.py)")
     # train.py:174-184 selects the algorithm with a sub-command; A2C is the one built here
-    ap.add_argument("algorithm", nargs="?", default="A2C", choices=["A2C", "PPO", "SEARCH"],
-                    help="train.py:174-184's sub-command; SEARCH: train toward the lookahead on the model's own critic (SearchDistillTrainer)")
+    ap.add_argument("algorithm", nargs="?", default="A2C", choices=["A2C", "PPO", "SEARCH", "SELFPLAY"],
+                    help="train.py:174-184's sub-command; SEARCH: train toward the lookahead on the model's own critic (SearchDistillTrainer); "
+                         "SELFPLAY: games of the PUCT search against itself, policy target the root visits, value target the result "
+                         "(PuctSelfPlayTrainer, DESIGN.md 4q)")
     ap.add_argument("--search", default="lookahead", choices=["lookahead", "puct"],
                     help="SEARCH: the expert: the lookahead on the critic, or a PUCT search on both heads whose root visit distribution "
                          "is the policy target (predict_puct)")
-    ap.add_argument("--sims", type=int, default=64, help="SEARCH --search puct: simulations per observation (0..4096)")
-    ap.add_argument("--c_puct", type=float, default=1.5, help="SEARCH --search puct: the exploration constant")
+    ap.add_argument("--sims", type=int, default=64, help="SEARCH --search puct, SELFPLAY: simulations per observation (0..4096)")
+    ap.add_argument("--c_puct", type=float, default=1.5, help="SEARCH --search puct, SELFPLAY: the exploration constant")
+    ap.add_argument("--noise_eps", type=float, default=0.25, help="SELFPLAY: the weight of the Dirichlet noise in the root's priors (0: none)")
+    ap.add_argument("--noise_alpha", type=float, default=1.0,
+                    help="SELFPLAY: the Dirichlet parameter (about 10 / the number of moves, AlphaZero's rule of thumb: a choice, not a measurement)")
+    ap.add_argument("--temp_plies", type=int, default=8,
+                    help="SELFPLAY: a game's first plies whose move is drawn in proportion to the root's visits; later ones play the most visited move")
+    ap.add_argument("--max_plies", type=int, default=None,
+                    help="SELFPLAY: record rows per game (default 80 on 5x5, 128 on 7x7: above the longest possible game)")
     ap.add_argument("--plies", type=int, default=1, choices=[1, 2], help="SEARCH: moves the lookahead looks ahead")
     ap.add_argument("--temperature", type=float, default=0.0,
                     help="SEARCH: 0 trains toward the search's action, > 0 toward the softmax of its Q / temperature")
-    ap.add_argument("--terminal_value", type=float, default=1.0, help="SEARCH: the value of a won (+) or lost (-) position in the lookahead")
+    ap.add_argument("--terminal_value", type=float, default=1.0, help="SEARCH, SELFPLAY: the value of a won (+) or lost (-) position in the search")
     ap.add_argument("--endgame_table", default=None,
                     help="SEARCH: a saved EndgameTable; the search's q is replaced by the exact one wherever the table covers the position")
     ap.add_argument("--endgame_leaves", action="store_true",
@@ -75,7 +84,8 @@ def _parser():
 
 
 def main():
-    a = _parser().parse_args()
+    ap = _parser()
+    a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     if world > 1:
@@ -85,12 +95,24 @@ def main():
     if a.algorithm == "SEARCH" and (a.trainer == "torch" or a.batch_size is not None):
         raise SystemExit("SEARCH has one trainer, SearchDistillTrainer, whose update is one full batch in the engine: --trainer torch and "
                          "--batch_size do not apply to it (--n_epochs is PPO's and is not read)")
+    if a.algorithm == "SELFPLAY":
+        if a.trainer == "torch" or a.batch_size is not None or a.opponent_policy != "random":
+            raise SystemExit("SELFPLAY has one trainer, PuctSelfPlayTrainer: the search plays itself and the update is one full batch in the "
+                             "engine, so --trainer torch, --batch_size and --opponent_policy do not apply to it")
+        unread = [name for name in ("n_steps", "opponent_update_every", "max_depth", "goal_reward", "illegal_move_reward",
+                                    "illegal_move_tolerance", "reference_quirks") if getattr(a, name) != ap.get_default(name)]
+        if unread:
+            raise SystemExit("SELFPLAY plays whole games of the search against itself and trains on their results: it reads no rollout "
+                             "length, opponent or reward, so --%s do(es) not apply to it" % ", --".join(unread))
+        if (a.endgame_table is None) != (not a.endgame_leaves):
+            raise SystemExit("SELFPLAY trains toward visits and results: a table serves it at the search's leaves only, "
+                             "--endgame_table PATH --endgame_leaves")
     if a.search != "lookahead" and a.algorithm != "SEARCH":
         raise SystemExit("--search is read by SEARCH only")
-    if a.endgame_table is not None and a.algorithm != "SEARCH":
-        raise SystemExit("--endgame_table is read by SEARCH only")
-    if a.endgame_leaves and (a.algorithm != "SEARCH" or a.endgame_table is None):
-        raise SystemExit("--endgame_leaves goes with SEARCH and --endgame_table")
+    if a.endgame_table is not None and a.algorithm not in ("SEARCH", "SELFPLAY"):
+        raise SystemExit("--endgame_table is read by SEARCH and SELFPLAY only")
+    if a.endgame_leaves and (a.algorithm not in ("SEARCH", "SELFPLAY") or a.endgame_table is None):
+        raise SystemExit("--endgame_leaves goes with SEARCH or SELFPLAY and --endgame_table")
     lo, hi = lane_range(a.num_envs * world, world, rank)
     if a.reference_quirks and a.opponent_policy not in ("random", "minimax", "mcts"):
         raise SystemExit("--reference_quirks drops the opponent (MinimaxEnv plays RandomAgent whatever it is given): it cannot be combined "
@@ -119,6 +141,11 @@ def main():
         trainer = SearchDistillTrainer(env, n_steps=a.n_steps, learning_rate=a.learning_rate, temperature=a.temperature, plies=a.plies,
                                        terminal_value=a.terminal_value, seed=mseed, endgame_table=a.endgame_table, search=a.search,
                                        sims=a.sims, c_puct=a.c_puct, endgame_leaves=a.endgame_leaves, **okw)
+    elif a.algorithm == "SELFPLAY":
+        from .distill import PuctSelfPlayTrainer
+        trainer = PuctSelfPlayTrainer(env, sims=a.sims, c_puct=a.c_puct, terminal_value=a.terminal_value, noise_eps=a.noise_eps,
+                                      noise_alpha=a.noise_alpha, temp_plies=a.temp_plies, max_plies=a.max_plies,
+                                      learning_rate=a.learning_rate, seed=mseed, endgame_table=a.endgame_table)
     elif a.trainer == "fused" or model_opp is not None or (a.trainer == "auto" and env.supports_policy_rollout()):
         trainer = FusedA2CTrainer(env, n_steps=a.n_steps, learning_rate=a.learning_rate, seed=mseed, **okw)
     else:

@@ -996,14 +996,25 @@ def puct_begin(boards, dice, sims, cube_layer=3):
     return tree, lb, ld
 
 
-def puct_advance(tree, logits, value, leaf_boards, leaf_dice, sims, c_puct=1.5, terminal_value=1.0, board_size=None, cube_layer=3):
+def _noise_eps(who, noise_eps):
+    if not (math.isfinite(float(noise_eps)) and 0.0 <= float(noise_eps) <= 1.0):
+        raise ValueError("%s: noise_eps must be a finite number in [0, 1], got %r" % (who, noise_eps))
+    return float(noise_eps)
+
+
+def puct_advance(tree, logits, value, leaf_boards, leaf_dice, sims, c_puct=1.5, terminal_value=1.0, board_size=None, cube_layer=3,
+                 root_noise=None, noise_eps=0.25):
     """One round of the search (ewn_puct_advance): logits float32 [M, 5] and value float32 [M] are predict_policy's on
     the leaf rows.  Per tree the pending leaf is evaluated (priors from the logits, v = value / terminal_value clamped to [-1, 1])
     and backed up; then, while fewer than `sims` simulations have begun, one more walks down to a new leaf, or ends at once on a
     winning move.  tree, leaf_boards and leaf_dice are updated in place (a tree without a pending leaf: a zero board with dice 1) and
-    returned.  board_size: taken from leaf_boards [M, S, S] when None.  sims + 1 rounds after puct_begin complete the search."""
+    returned.  board_size: taken from leaf_boards [M, S, S] when None.  sims + 1 rounds after puct_begin complete the search.
+    root_noise (float32 [M, 2, 3] or [M, 6], un-normalised weights, e.g. Gamma variates): ewn_puct_advance_noise
+    instead -- where the leaf evaluated is the root, its priors become (1 - noise_eps) P + noise_eps eta / sum(eta) over the legal
+    edges with a finite positive weight.  None: exactly the plain call, noise_eps is not looked at."""
     who = "puct_advance"
     sims = _puct_numbers(who, sims, c_puct, terminal_value)
+    eps = None if root_noise is None else _noise_eps(who, noise_eps)
     for name, t in (("tree", tree), ("leaf_boards", leaf_boards), ("leaf_dice", leaf_dice)):
         if not isinstance(t, torch.Tensor):
             raise ValueError("%s: %s is updated in place and must be a tensor, got %s" % (who, name, _describe(t)))
@@ -1016,6 +1027,14 @@ def puct_advance(tree, logits, value, leaf_boards, leaf_dice, sims, c_puct=1.5, 
     Mt, _ = _puct_tree(who, tree, S, sims, cube_layer)
     if Mt != M or not (tree.is_cuda and tree.device == dev):
         raise ValueError("%s: tree must hold %d trees on %s, got %s" % (who, M, dev, _describe(tree)))
+    if root_noise is not None:
+        rn = _policy_input("root_noise", root_noise, torch.float32, (M, 6), dev, who=who)
+        _same_gpu(who, dev, "leaf_boards", (("root_noise", rn),))
+        with torch.cuda.device(dev):
+            check(_lib.load().ewn_puct_advance_noise(S, int(cube_layer), M, sims, C.c_float(float(c_puct)), C.c_float(float(terminal_value)),
+                                                     _ptr(tree), _ptr(lg), _ptr(v), _ptr(rn), C.c_float(eps), _ptr(lb), _ptr(ld), _stream()),
+                  "ewn_puct_advance_noise")
+        return tree, leaf_boards, leaf_dice
     with torch.cuda.device(dev):
         check(_lib.load().ewn_puct_advance(S, int(cube_layer), M, sims, C.c_float(float(c_puct)), C.c_float(float(terminal_value)), _ptr(tree),
                                            _ptr(lg), _ptr(v), _ptr(lb), _ptr(ld), _stream()), "ewn_puct_advance")
@@ -1044,6 +1063,24 @@ def puct_result(tree, board_size, sims, return_visits=False, return_q=False, ret
               "ewn_puct_result")
     out = (acts,) + tuple(t for t in (visits, q, val) if t is not None)
     return out[0] if len(out) == 1 else out
+
+
+def _puct_search(lib, S, L, n, sims, b, d, params, cp, tv, table, scratch, st, noise=None, eps=0.0):
+    """predict_puct's and selfplay_puct's search of n observations on the caller's scratch: begin, then sims + 1 rounds of
+    ewn_predict_policy and advance.  noise (float32 [n, 6]): the first round, which evaluates the roots, is the noise instance's"""
+    tree, lb, ld, la, lg, lv = scratch
+    check(lib.ewn_puct_begin(S, L, n, sims, _ptr(b), _ptr(d), _ptr(tree), _ptr(lb), _ptr(ld), st), "ewn_puct_begin")
+    for rnd in range(sims + 1):
+        check(lib.ewn_predict_policy(S, L, n, _ptr(lb), _ptr(ld), _ptr(params), 1, C.c_uint64(0), None, None, _ptr(la), _ptr(lg),
+                                     _ptr(lv), st), "ewn_predict_policy")
+        if table is not None:                                  # a tree without a pending leaf shows a zero board: not covered
+            _, covered, q_exact = table.lookup(lb[:n], ld[:n], return_q=True)
+            lv[:n] = torch.where(covered, tv.value * q_exact.reshape(n, 6).max(1).values, lv[:n])
+        if rnd == 0 and noise is not None:
+            check(lib.ewn_puct_advance_noise(S, L, n, sims, cp, tv, _ptr(tree), _ptr(lg), _ptr(lv), _ptr(noise), C.c_float(eps), _ptr(lb),
+                                             _ptr(ld), st), "ewn_puct_advance_noise")
+        else:
+            check(lib.ewn_puct_advance(S, L, n, sims, cp, tv, _ptr(tree), _ptr(lg), _ptr(lv), _ptr(lb), _ptr(ld), st), "ewn_puct_advance")
 
 
 def predict_puct(boards, dice, params, sims=64, c_puct=1.5, terminal_value=1.0, return_visits=False, return_q=False, return_value=False,
@@ -1088,15 +1125,152 @@ def predict_puct(boards, dice, params, sims=64, c_puct=1.5, terminal_value=1.0, 
         for i in range(0, M, c):
             n = min(c, M - i)
             sl = slice(i, i + n)
-            check(lib.ewn_puct_begin(S, L, n, sims, _ptr(b[sl]), _ptr(d[sl]), _ptr(tree), _ptr(lb), _ptr(ld), st), "ewn_puct_begin")
-            for _ in range(sims + 1):
-                check(lib.ewn_predict_policy(S, L, n, _ptr(lb), _ptr(ld), _ptr(params), 1, C.c_uint64(0), None, None, _ptr(la), _ptr(lg),
-                                             _ptr(lv), st), "ewn_predict_policy")
-                if table is not None:                          # a tree without a pending leaf shows a zero board: not covered
-                    _, covered, q_exact = table.lookup(lb[:n], ld[:n], return_q=True)
-                    lv[:n] = torch.where(covered, float(terminal_value) * q_exact.reshape(n, 6).max(1).values, lv[:n])
-                check(lib.ewn_puct_advance(S, L, n, sims, cp, tv, _ptr(tree), _ptr(lg), _ptr(lv), _ptr(lb), _ptr(ld), st), "ewn_puct_advance")
+            _puct_search(lib, S, L, n, sims, b[sl], d[sl], params, cp, tv, table, (tree, lb, ld, la, lg, lv), st)
             check(lib.ewn_puct_result(S, L, n, _ptr(tree), _ptr(acts[sl]), _ptr(None if visits is None else visits[sl]),
                                       _ptr(None if q is None else q[sl]), _ptr(None if val is None else val[sl]), st), "ewn_puct_result")
     out = (acts,) + tuple(t for t in (visits, q, val) if t is not None)
     return out[0] if len(out) == 1 else out
+
+
+SELFPLAY_MAX_PLIES = {5: 80, 7: 128}   # above the rules' bound on a game's length: 69 / 117 plies
+_PLAY_ROWS = (("board", torch.int8, lambda S: (S, S)), ("dice", torch.int8, lambda S: ()), ("visits", torch.int32, lambda S: (2, 3)),
+              ("value", torch.float32, lambda S: ()), ("action", torch.int8, lambda S: (2,)), ("live", torch.int8, lambda S: ()))
+
+
+def _play_numbers(who, temp_plies, key, game_offset):
+    if not (isinstance(temp_plies, (int, np.integer)) and 0 <= int(temp_plies) <= 2 ** 31 - 1):
+        raise ValueError("%s: temp_plies must be an integer that is not negative, got %r" % (who, temp_plies))
+    if not (isinstance(key, (int, np.integer)) and isinstance(game_offset, (int, np.integer)) and -2 ** 63 <= int(game_offset) < 2 ** 63):
+        raise ValueError("%s: key and game_offset must be integers, game_offset within 64 bits, got %r and %r" % (who, key, game_offset))
+    return int(temp_plies), int(key) & 0xFFFFFFFFFFFFFFFF, int(game_offset)
+
+
+def puct_play(tree, boards, dice, game, board_size, sims, temp_plies=0, key=0, game_offset=0, out=None, cube_layer=3):
+    """One ply of M self-play games off their searched trees (ewn_puct_play; puct_result's checks of the tree).  boards
+    int8 [M, S, S], dice int8 [M] and game int32 [M, 4] = (ply, over, winner, 0) are updated in place: the move is the first root
+    move that wins, else drawn in proportion to the root's visits while ply < temp_plies (a Philox word of key, game_offset + m and
+    ply), else the first maximum of the visits; the next dice is a second word of the same block.  The position played and recorded
+    is the tree's root.  A game that is over, or whose tree is degenerate, is left as it is (the latter is then over, without a
+    winner).  out: None -> a new record row {board int8 [M, S, S], dice int8 [M], visits int32 [M, 2, 3], value float32 [M], action
+    int8 [M, 2], live int8 [M]} is returned; a dict -> the tensors it holds under those names are written (a missing name or None:
+    not written) and it is returned."""
+    who = "puct_play"
+    sims = _puct_numbers(who, sims)
+    temp_plies, key, game_offset = _play_numbers(who, temp_plies, key, game_offset)
+    S = int(board_size)
+    M, _ = _puct_tree(who, tree, S, sims, cube_layer)
+    for name, t, dtype, shape in (("boards", boards, torch.int8, (M, S, S)), ("dice", dice, torch.int8, (M,)), ("game", game, torch.int32, (M, 4))):
+        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous()):
+            raise ValueError("%s: %s is updated in place and must be a contiguous %s tensor of shape %s, got %s" % (
+                who, name, str(dtype).replace("torch.", ""), list(shape), _describe(t)))
+    if out is not None and (not isinstance(out, dict) or set(out) - {name for name, _, _ in _PLAY_ROWS}):
+        raise ValueError("%s: out must be a dict with keys among board, dice, visits, value, action, live, got %r" % (
+            who, sorted(out) if isinstance(out, dict) else type(out).__name__))
+    if not tree.is_cuda:
+        raise ValueError("%s: tree must live on the GPU, got %s" % (who, _describe(tree)))
+    dev = tree.device
+    _same_gpu(who, dev, "tree", (("boards", boards), ("dice", dice), ("game", game)))
+    if out is None:
+        out = {name: torch.zeros((M,) + shape(S), dtype=dt, device=dev) for name, dt, shape in _PLAY_ROWS}
+    rows = []
+    for name, dt, shape in _PLAY_ROWS:
+        t = out.get(name)
+        if t is not None:
+            if isinstance(t, torch.Tensor) and t.dtype == torch.bool and dt == torch.int8:
+                t = t.view(torch.int8)
+            if not (_is_buffer(t, dt) and t.numel() == M * math.prod(shape(S))):
+                raise ValueError("%s: out[%r] must be a contiguous %s device tensor of %s elements, got %s" % (
+                    who, name, str(dt).replace("torch.", ""), " x ".join(map(str, (M,) + shape(S))), _describe(t)))
+            _same_gpu(who, dev, "tree", ((("out[%r]" % name), t),))
+        rows.append(t)
+    with torch.cuda.device(dev):
+        check(_lib.load().ewn_puct_play(S, int(cube_layer), M, _ptr(tree), _ptr(boards), _ptr(dice), _ptr(game), temp_plies, C.c_uint64(key),
+                                        C.c_int64(game_offset), *[_ptr(t) for t in rows], _stream()), "ewn_puct_play")
+    return out
+
+
+def selfplay_outcomes(winner, live):
+    """The value targets of self-play records whose games all start at ply 0 in row 0 (plain torch): winner [M] (0 none, +1 the side
+    that moves at even plies, -1 the other), live bool [T, M] -> (z float32 [T, M], weight float32 [T, M]).  z[t, m] is the result
+    seen from the side to move in row t: winner[m] at even t, -winner[m] at odd t, on live rows; weight is 1 on the live rows of
+    finished games.  Everything else is 0."""
+    live = live.to(torch.bool)
+    w = winner.to(torch.float32)[None, :]
+    sign = 1.0 - 2.0 * (torch.arange(live.shape[0], device=live.device) % 2).to(torch.float32)
+    counts = live & (w != 0)
+    z = torch.where(counts, w * sign[:, None], torch.zeros((), device=live.device))
+    return z.contiguous(), counts.to(torch.float32).contiguous()
+
+
+def selfplay_noise(M, noise_alpha, key, game_offset, ply, device="cuda"):
+    """selfplay_puct's root noise of one ply: float32 [M, 6] Gamma(noise_alpha) variates (torch._standard_gamma) on a generator seeded
+    from key, game_offset and the ply.  Normalised over the legal edges by the kernel they are Dirichlet(noise_alpha) noise."""
+    gen = torch.Generator(device=device)
+    gen.manual_seed((int(key) * 0x9E3779B97F4A7C15 + int(game_offset) * 0xD1B54A32D192ED03 + int(ply) * 0x2545F4914F6CDD1D) & (2 ** 63 - 1))
+    return torch._standard_gamma(torch.full((int(M), 6), float(noise_alpha), dtype=torch.float32, device=device), generator=gen)
+
+
+def selfplay_puct(boards, dice, params, sims=64, max_plies=None, c_puct=1.5, terminal_value=1.0, noise_eps=0.25, noise_alpha=1.0,
+                  temp_plies=8, key=0, game_offset=0, chunk=1024, check_every=8, endgame_table=None, cube_layer=3):
+    """M games of the PUCT search against itself, from the given positions to the end: per ply puct_begin, sims + 1
+    rounds of ewn_predict_policy and advance -- the first with Dirichlet(noise_alpha) noise of weight noise_eps on the root's priors
+    (ewn_puct_advance_noise) -- then ewn_puct_play into row t: the move is drawn in proportion to the visits for the first
+    temp_plies plies of a game and is the most visited one after that.  boards [S, S] or [M, S, S], dice [M], params as
+    predict_policy takes them; they are not changed.  `chunk` games are played at a time, each chunk to its end; every check_every
+    plies one host read ends a chunk whose games are all over.  max_plies None: 80 on 5x5, 128 on 7x7 -- a move lowers the mover's
+    summed distance to its corner by at least one, so a game lasts at most 69 / 117 plies.  noise_alpha = 1.0 is a choice (about 10
+    over the number of moves, AlphaZero's rule of thumb), not a measurement.  endgame_table: predict_puct's, at the leaves.
+    The noise is torch._standard_gamma on a generator seeded from key, game_offset and the ply, drawn once per ply for all M games
+    and read by each chunk's rows: a call repeats itself bit for bit, whatever the chunk.  Returns a dict: board int8 [T, M, S, S], dice int8
+    [T, M], visits int32 [T, M, 2, 3], value float32 [T, M], action int8 [T, M, 2], live bool [T, M] (T = max_plies; rows past a
+    game's end are zero), z and weight float32 [T, M] (selfplay_outcomes), winner int32 [M], plies int32 [M]."""
+    who = "selfplay_puct"
+    lib = _lib.load()
+    sims = _puct_numbers(who, sims, c_puct, terminal_value)
+    eps = _noise_eps(who, noise_eps)
+    temp_plies, key, game_offset = _play_numbers(who, temp_plies, key, game_offset)
+    if not (math.isfinite(float(noise_alpha)) and float(noise_alpha) > 0.0):
+        raise ValueError("%s: noise_alpha must be finite and positive, got %r" % (who, noise_alpha))
+    if int(chunk) < 1 or int(check_every) < 1:
+        raise ValueError("%s: chunk and check_every must be at least 1, got %r and %r" % (who, chunk, check_every))
+    M, S, P = _lookahead_shape(who, boards, cube_layer)
+    T = SELFPLAY_MAX_PLIES[S] if max_plies is None else max_plies
+    if not (isinstance(T, (int, np.integer)) and int(T) >= 1):
+        raise ValueError("%s: max_plies must be a positive integer or None, got %r" % (who, max_plies))
+    T = int(T)
+    table = _leaf_table(who, endgame_table, M, S)
+    L = int(cube_layer)
+    dev = _policy_params(who, params, P, S)
+    b = _policy_input("boards", boards, torch.int8, (M, S, S), dev, who=who)
+    d = _policy_input("dice", dice, torch.int8, (M,), dev, who=who)
+    _same_gpu(who, dev, "params", (("params", params), ("boards", b), ("dice", d), ("the table", None if table is None else table.table)))
+    rec = {name: torch.zeros((T, M) + shape(S), dtype=dt, device=dev) for name, dt, shape in _PLAY_ROWS}
+    game = torch.zeros((M, 4), dtype=torch.int32, device=dev)
+    c = max(1, min(int(chunk), M))
+    nb = int(lib.ewn_puct_tree_bytes(S, L, sims))
+    scratch = (torch.empty((c, nb), dtype=torch.uint8, device=dev), torch.empty((c, S, S), dtype=torch.int8, device=dev),
+               torch.empty(c, dtype=torch.int8, device=dev), torch.empty((c, 2), dtype=torch.int8, device=dev),
+               torch.empty((c, 5), dtype=torch.float32, device=dev), torch.empty(c, dtype=torch.float32, device=dev))
+    cp, tv = C.c_float(float(c_puct)), C.c_float(float(terminal_value))
+    with torch.cuda.device(dev):
+        st = _stream()
+        drawn = []
+        for i in range(0, M, c):
+            n = min(c, M - i)
+            cb, cd, cg = b[i:i + n].clone(), d[i:i + n].clone(), game[i:i + n]
+            for t in range(T):
+                noise = None
+                if eps > 0.0:
+                    if t == len(drawn):                        # a ply's noise is drawn once, for all M games: later chunks read their rows
+                        drawn.append(selfplay_noise(M, noise_alpha, key, game_offset, t, dev))
+                    noise = drawn[t][i:i + n]
+                _puct_search(lib, S, L, n, sims, cb, cd, params, cp, tv, table, scratch, st, noise, eps)
+                check(lib.ewn_puct_play(S, L, n, _ptr(scratch[0]), _ptr(cb), _ptr(cd), _ptr(cg), temp_plies, C.c_uint64(key),
+                                        C.c_int64(game_offset + i), *[_ptr(rec[name][t, i:i + n]) for name, _, _ in _PLAY_ROWS], st),
+                      "ewn_puct_play")
+                if (t + 1) % int(check_every) == 0 and bool(cg[:, 1].all()):
+                    break
+    rec["live"] = rec["live"].view(torch.bool)
+    rec["winner"], rec["plies"] = game[:, 2].contiguous(), game[:, 0].contiguous()
+    rec["z"], rec["weight"] = selfplay_outcomes(rec["winner"], rec["live"])
+    return rec

@@ -594,6 +594,43 @@ int ewn_puct_result(int board_size, int cube_layer, int M, const void *tree, int
                     int32_t *visits /* [M][6], optional */, float *q /* [M][6], optional */, float *value /* [M], optional */,
                     void *stream);
 
+/* ---- PUCT self-play: exploration at the root and the move of a game, on the trees above ----
+ * ewn_puct_advance_noise is ewn_puct_advance in every respect but one: when the node it evaluates is node 0, the root's priors are
+ * mixed with the caller's weights before the backup and before the first simulation selects on them (that simulation begins in
+ * the same launch, so the mixing cannot be a later kernel).  With eta[a] = root_noise[m][a] where edge a has kind 1 or 2 and the
+ * number is finite and positive, 0 otherwise, and es the fp32 sum of eta in ascending a:
+ *   es > 0:  P[a] = fl(fl(keep * P[a]) + fl(noise_eps * fl(eta[a] / es)))  on the edges of kind 1 or 2,  keep = fl(1 - noise_eps),
+ *   es == 0: the priors stay as they are.
+ * The weights are un-normalised (Gamma(alpha) variates give Dirichlet(alpha) noise over the legal edges); their sum must not overflow.
+ * Refusals in ewn_puct_advance's order, with root_noise == NULL among the pointers (EWN_ENULL) and, last, a noise_eps that is not
+ * finite or outside [0, 1] (EWN_EINVAL).  With noise_eps == 0 every written byte equals ewn_puct_advance's.
+ *
+ * ewn_puct_play plays one ply of M games off their searched trees.  game [M][4] int32, 4-byte aligned: {ply, over (0 / 1), winner, 0};
+ * winner 0 none, +1 the side that moves at even plies, -1 the other.  The position played is the tree's root board and dice (the
+ * budget is read from the first tree's header).  rec_* address this ply's row of the caller's record; each may be NULL.  Per game:
+ *  1. not live -- over != 0, or the tree is degenerate, or the root has no edge of kind 1 or 2, or the buffer is no tree of this
+ *     layout (ewn_puct_advance's checks): rec_live 0 and the other record rows zero; boards, dice and ply are not touched; a tree
+ *     (degenerate or without a move) whose game was not over sets over = 1 and leaves winner 0.
+ *  2. o = philox4x32_10(ctr = {ply, lo32(g), hi32(g), 0x50555350}, key = {lo32(key), hi32(key)}), g = game_offset + m.
+ *  3. the edge: the first root edge of kind 1; else, with tn the sum of N over the edges of kind 2: if ply < temp_plies and tn > 0,
+ *     r = (uint64(o[0]) * tn) >> 32 and the edge is the first of kind 2 in ascending a whose running sum of N exceeds r (integers
+ *     only, proportional to the visits, an edge with N == 0 is never drawn); else ewn_puct_result's first maximum of N (strict >).
+ *  4. the record: rec_board [M][S*S] and rec_dice [M] the root's, rec_visits [M][6] = N, rec_value [M] = sum W / sum N or 0 (as
+ *     ewn_puct_result's value), rec_action [M][2] = (a / 3, a % 3), rec_live [M] = 1.
+ *  5. the move: boards[m] = flip(b1), b1 the board after the edge's move (captures as in the search); dice[m] = 1 +
+ *     ((uint64(o[1]) * 6) >> 32), whose bias is below 2^-30 (6 does not divide 2^32: no face's probability is off by more than
+ *     2^-32); ply += 1; an edge of kind 1 also sets over = 1 and winner = +1 if the ply just played was even, -1 otherwise.
+ * Refusals in this order: ewn_puct_result's for M and the geometry, EWN_OK without a launch for M == 0, EWN_ENULL for a missing
+ * tree, boards, dice or game, then EWN_EINVAL for temp_plies < 0 or a tree or game that is not 4-byte aligned.  One kernel launch
+ * each on `stream`, vector stores only, no atomics, no allocation, no synchronisation: the same inputs give the same bits. */
+int ewn_puct_advance_noise(int board_size, int cube_layer, int M, int sims, float c_puct, float terminal_value, void *tree,
+                           const float *logits /* [M][5] */, const float *value /* [M] */, const float *root_noise /* [M][6] */,
+                           float noise_eps, int8_t *leaf_boards, int8_t *leaf_dice, void *stream);
+int ewn_puct_play(int board_size, int cube_layer, int M, const void *tree, int8_t *boards, int8_t *dice, int32_t *game /* [M][4] */,
+                  int temp_plies, uint64_t key, int64_t game_offset,
+                  int8_t *rec_board, int8_t *rec_dice, int32_t *rec_visits, float *rec_value, int8_t *rec_action, int8_t *rec_live,
+                  void *stream);
+
 /* ---- the supervised update on M given observations: targets from outside (a search: expert iteration) ----
  * loss = (1/M) sum_m w_m (pi_coef CE_m + vf_coef (V_m - v*_m)^2),  CE_m = -sum_i p_i logsoftmax_head(i)(logits_m)_i, with
  * p = target_pi[m][0..4] (entries 0-1 the flag head, 2-4 the direction head; the caller makes each head's mass 1, or 0 to mask the
