@@ -6,7 +6,8 @@ the GPU's bits as test_gpu_puct's lock step does.  NOISE_TOL = P_TOL + 16 * 2^-2
 keep <= 1 does not enlarge that), and the mixing adds ten fp32 roundings on values of at most 1 -- five additions in es, the division
 eta / es, the product with eps, keep = 1 - eps itself, the product keep * P and the final sum -- each of at most 2^-24 absolute;
 ten is rounded up to sixteen as test_gpu_puct rounds its count up.  Derived, not tuned.  3. ewn_puct_play against the model, bit for
-bit.  4. the driver is the stages, and its records obey the rules of the game.  5. guard zones.  6. the trainer."""
+bit.  4. the driver is the stages, and its records obey the rules of the game; with endgame_table= it is the stages with the table's
+exact values written over the covered leaves' (DESIGN.md 4p).  5. guard zones.  6. the trainer, without and with a table."""
 import ctypes as C
 
 import numpy as np
@@ -356,8 +357,10 @@ def reset_positions(ea, S, n=33):
     return b.clone(), d.clone()
 
 
-def by_hand(ea, S, b, d, params, sims, T, key, off, eps=0.25, alpha=1.0, temp_plies=8):
-    """selfplay_puct written out in the public calls, without the early exit"""
+def by_hand(ea, S, b, d, params, sims, T, key, off, eps=0.25, alpha=1.0, temp_plies=8, table=None, terminal_value=1.0):
+    """selfplay_puct written out in the public calls, without the early exit.  table (an EndgameTable): a pending leaf that it covers is
+    worth terminal_value * max_a q_exact instead of the value head's output, the substitution that
+    test_gpu_lookahead_endgame.py::test_predict_puct_with_a_table_is_the_public_calls_composed writes out"""
     M = b.shape[0]
     cb, cd = b.clone(), d.clone()
     game = torch.zeros((M, 4), dtype=torch.int32, device="cuda")
@@ -369,7 +372,11 @@ def by_hand(ea, S, b, d, params, sims, T, key, off, eps=0.25, alpha=1.0, temp_pl
         tree, lb, ld = ea.puct_begin(cb, cd, sims)
         for rnd in range(sims + 1):
             _, logits, value = ea.predict_policy(lb, ld, params, return_logits=True, return_value=True)
-            ea.puct_advance(tree, logits, value, lb, ld, sims, root_noise=noise if rnd == 0 else None, noise_eps=eps)
+            if table is not None:
+                _, covered, q_exact = table.lookup(lb, ld, return_q=True)
+                value = torch.where(covered, terminal_value * q_exact.reshape(M, 6).max(1).values, value)
+            ea.puct_advance(tree, logits, value, lb, ld, sims, terminal_value=terminal_value, root_noise=noise if rnd == 0 else None,
+                            noise_eps=eps)
         ea.puct_play(tree, cb, cd, game, S, sims, temp_plies=temp_plies, key=key, game_offset=off, out={k: rec[k][t] for k in rec})
     rec["live"] = rec["live"].view(torch.bool)
     rec["winner"], rec["plies"] = game[:, 2].contiguous(), game[:, 0].contiguous()
@@ -430,6 +437,58 @@ def test_the_driver_is_the_stages(ea, S, T):
         assert got["board"].data_ptr() != b.data_ptr() and torch.equal(b, reset_positions(ea, S)[0])   # the inputs are not changed
 
 
+def table_openings(ea):
+    """the (5, 2, 4) table, and 64 openings: the 33 of reset_positions, then 31 sampled positions with one or two cubes a side, neither
+    side already won, under varied dice, which the table covers from ply 0"""
+    import random
+    from tests.test_gpu_endgame import board_of, sample
+    from tests.test_gpu_lookahead_endgame import tab
+    t, rng = tab(ea, 5), random.Random(64)
+    b, d = reset_positions(ea, 5)
+    fb = torch.as_tensor(np.stack([board_of(sample(rng, 5, t.max_cubes, t.max_total), 5) for _ in range(31)])).cuda()
+    fd = torch.tensor([1 + i % 6 for i in range(31)], dtype=torch.int8, device="cuda")
+    assert bool(t.lookup(fb, fd)[1].all()) and not bool(t.lookup(b, d)[1].any())
+    assert len({int((x != 0).sum()) for x in fb}) > 1              # two, three and four cubes in all
+    return t, torch.cat([b, fb]).contiguous(), torch.cat([d, fd]).contiguous()
+
+
+def covered_roots(t, rec):
+    """bool [T, M]: the recorded roots that the table covers (rows past a game's end are zero boards: not covered)"""
+    T, M, S = rec["board"].shape[:3]
+    cov = t.lookup(rec["board"].reshape(T * M, S, S), rec["dice"].reshape(T * M).clamp(min=1))[1].reshape(T, M)
+    assert not bool((cov & ~rec["live"]).any())
+    return cov
+
+
+@pytest.mark.parametrize("tv", [1.0, 0.75])
+def test_the_driver_with_a_table_is_the_stages(ea, tv):
+    """selfplay_puct(endgame_table=) is by_hand(table=): late in a game most leaves are covered, and the overwritten leaf values meet
+    the noise round and ewn_puct_play.  That the table is read is checked on the host: recorded roots that lookup covers"""
+    S, T = 5, 80
+    params = pool(ea, S)["params"]
+    t, b, d = table_openings(ea)
+    # key 15: of the keys 11 .. 20 the one whose by-hand games reach the most covered roots under both terminal values (key 11, the
+    # plain test's, reaches 11 of them at terminal_value 1 and none at 0.75)
+    kw = dict(sims=8, max_plies=T, key=15, game_offset=2 ** 32 + 5, terminal_value=tv)
+    got = ea.selfplay_puct(b, d, params, endgame_table=t, **kw)
+    want = by_hand(ea, S, b, d, params, 8, T, 15, 2 ** 32 + 5, table=t, terminal_value=tv)
+    cov = covered_roots(t, want)                                         # counted on the by-hand run, before it is compared
+    n_reset, n_few = int(cov[:, :33].sum()), int(cov[:, 33:].sum())
+    print("tv=%g: %d recorded roots of the 33 reset games are covered (in %d of the games), %d of the 31 few-cube games; %d roots in all" % (
+        tv, n_reset, int(cov[:, :33].any(0).sum()), n_few, int(want["live"].sum())))
+    assert bool(cov[0, 33:].all()) and not bool(cov[0, :33].any())
+    assert n_reset > 0                                                   # among the reset games' later plies
+    same_records(got, want)
+    check_rules(got, S, T)
+    plain = ea.selfplay_puct(b, d, params, **kw)
+    check_rules(plain, S, T)
+    assert any(not torch.equal(plain[k], got[k]) for k in ("visits", "value", "action"))   # the table is read: other searches
+    if tv == 1.0:                                                        # chunks of 16 and a host read every ply: the same bytes
+        same_records(got, ea.selfplay_puct(b, d, params, endgame_table=t, chunk=16, **kw))
+        same_records(got, ea.selfplay_puct(b, d, params, endgame_table=t, check_every=1, **kw))
+        same_records(got, ea.selfplay_puct(b, d, params, endgame_table=t, chunk=16, check_every=1, **kw))
+
+
 # ---------------------------------------------------------------- 5. guard zones
 
 @pytest.mark.parametrize("S", [5, 7])
@@ -474,6 +533,50 @@ def selfplay_trainer(ea, **kw):
     return PuctSelfPlayTrainer(make_env(ea, 64), **dict(dict(sims=6, seed=5, temp_plies=4, max_plies=16), **kw))
 
 
+def targets_by_hand(rec, terminal_value=1.0):
+    """the trainer's target arithmetic on selfplay_puct's records, written out -> (boards [R, S, S], dice [R], target_pi [R, 5],
+    target_value [R], weight [R], one bool [R]: a recorded root whose two flags name one cube), R = T * M"""
+    T, M, S = rec["board"].shape[:3]
+    R = T * M
+    b, d = rec["board"].reshape(R, S, S), rec["dice"].reshape(R).clamp(min=1)
+    vis = rec["visits"].reshape(R, 2, 3).float()
+    tot = vis.sum((1, 2))
+    den = torch.where(tot > 0, tot, torch.ones_like(tot))[:, None]
+    flag, direction = vis.sum(2) / den, vis.sum(1) / den
+    hb, hd = b.cpu().numpy(), d.cpu().numpy()
+    one = torch.tensor([bool(tot[i] > 0) and find_cube(cubes_of(hb[i], 1), int(hd[i]), False) == find_cube(cubes_of(hb[i], 1), int(hd[i]), True)
+                        for i in range(R)], device="cuda")
+    flag = torch.where(one[:, None], torch.full_like(flag, 0.5), flag)
+    tp = (torch.cat([flag, direction], 1) * (tot > 0)[:, None]).contiguous()
+    tv = (terminal_value * rec["z"]).reshape(R).contiguous()
+    return b, d, tp, tv, rec["weight"].reshape(R).contiguous(), one
+
+
+def test_one_update_with_a_table_is_the_public_calls_composed(ea, monkeypatch):
+    """test_one_update_is_the_public_calls_composed with endgame_table=: the records are selfplay_puct's with the table, the gradient
+    sup_grad's on them; the parts that the table does not change (the apply, the counters, the statistics) are tested there"""
+    from tests.test_gpu_distill_trainer import make_env
+    from tests.test_gpu_lookahead_endgame import tab
+    N, T, t = 64, 16, tab(ea, 5)
+    tr = selfplay_trainer(ea, endgame_table=t)
+    assert tr.endgame_table is t and selfplay_trainer(ea).endgame_table is None
+    params = tr.params.clone()
+    lookups, lookup = [], t.lookup
+    monkeypatch.setattr(t, "lookup", lambda *a, **kw: (lookups.append(a[0].shape[0]), lookup(*a, **kw))[1])
+    tr.collect_and_update()
+    monkeypatch.undo()
+    assert lookups and len(lookups) % 7 == 0 and set(lookups) == {N}     # the search asked the table: sims + 1 rounds per ply, 64 leaf rows
+    env = make_env(ea, N)
+    b0, d0 = env.reset(seeds=(5 + np.arange(N, dtype=np.uint64)).astype(np.uint32))
+    rec = ea.selfplay_puct(b0, d0, params, sims=6, max_plies=T, temp_plies=4, key=tr.noise_key, game_offset=0, endgame_table=t)
+    same_records(rec, tr.records)
+    b, d, tp, tv, w, one = targets_by_hand(rec)
+    assert bool(one.any()) and 0 < float(w.sum()) < T * N
+    grad = ea.sup_grad(b, d, tp, tv, params, weight=w, pi_coef=1.0, vf_coef=0.5)
+    assert torch.equal(bits(grad), bits(tr.grad))
+    assert tr.num_timesteps == int(rec["live"].sum()) and tr.seed_counter == 1
+
+
 def test_one_update_is_the_public_calls_composed(ea):
     from ewn_gym_amd._lib import EwnA2cHyper, check
     from ewn_gym_amd.vec_env import _ptr, _stream
@@ -489,19 +592,7 @@ def test_one_update_is_the_public_calls_composed(ea):
     rec = ea.selfplay_puct(b0, d0, params, sims=6, max_plies=T, temp_plies=4, key=tr.noise_key, game_offset=0)
     same_records(rec, tr.records)
     R = T * N
-    b, d = rec["board"].reshape(R, 5, 5), rec["dice"].reshape(R).clamp(min=1)
-    # the target arithmetic, written out
-    vis = rec["visits"].reshape(R, 2, 3).float()
-    tot = vis.sum((1, 2))
-    den = torch.where(tot > 0, tot, torch.ones_like(tot))[:, None]
-    flag, direction = vis.sum(2) / den, vis.sum(1) / den
-    hb, hd = b.cpu().numpy(), d.cpu().numpy()
-    one = torch.tensor([bool(tot[i] > 0) and find_cube(cubes_of(hb[i], 1), int(hd[i]), False) == find_cube(cubes_of(hb[i], 1), int(hd[i]), True)
-                        for i in range(R)], device="cuda")
-    flag = torch.where(one[:, None], torch.full_like(flag, 0.5), flag)
-    tp = (torch.cat([flag, direction], 1) * (tot > 0)[:, None]).contiguous()
-    tv = (1.0 * rec["z"]).reshape(R).contiguous()
-    w = rec["weight"].reshape(R).contiguous()
+    b, d, tp, tv, w, one = targets_by_hand(rec)
     live = rec["live"].reshape(R)
     unfinished = live & (w == 0)
     assert bool(one.any()) and bool(unfinished.any()) and 0 < float(w.sum()) < float(live.sum()) < R

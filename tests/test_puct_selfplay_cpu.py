@@ -239,6 +239,21 @@ def test_the_trainer_refuses_bad_numbers_before_it_looks_at_the_env():
     assert PuctSelfPlayTrainer.algorithm == "SELFPLAY"
 
 
+def test_the_trainer_refuses_a_table_of_another_board_size():
+    torch = pytest.importorskip("torch")
+    from ewn_gym_amd.distill import PuctSelfPlayTrainer
+    from ewn_gym_amd.endgame import EndgameTable
+
+    class Env:                             # only its board size is looked at
+        S = 5
+
+    t = EndgameTable(7, 1, 2, torch.zeros(EndgameTable.table_bytes(7, 1, 2) // 4))   # wraps a buffer: nothing is built or launched
+    with pytest.raises(ValueError, match="PuctSelfPlayTrainer: the endgame table is for 7x7 boards, the env plays 5x5"):
+        PuctSelfPlayTrainer(Env(), endgame_table=t)
+    with pytest.raises(ValueError, match="PuctSelfPlayTrainer: sims"):     # the numbers are still looked at first
+        PuctSelfPlayTrainer(Env(), sims=-1, endgame_table=t)
+
+
 def test_targets_without_q_need_the_mask():
     torch = pytest.importorskip("torch")
     from ewn_gym_amd.distill import puct_targets
