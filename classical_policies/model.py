@@ -112,11 +112,14 @@ class PuctAgent(ModelAgent):
     counterpart of the reference's AlphaZeroMCTSAgent (classical_policies/alpha_zero/MCTS.py), on the network the trainers here
     produce.  Always deterministic: a win on the board, else the most visited move.  sims=0 plays the first legal move unless one wins.
     endgame_table (an ewn_gym_amd.EndgameTable or the path of a saved one): a leaf that the table covers is worth its exact value
-    instead of the value head's."""
+    instead of the value head's.  fused=True: the search of a batch is one kernel launch (ewn_puct_search, DESIGN.md
+    4r) instead of 2 sims + 3: the same moves; not together with endgame_table."""
 
-    def __init__(self, model_or_path, board_size=5, cube_layer=3, sims=64, c_puct=1.5, terminal_value=1.0, endgame_table=None):
-        from ewn_gym_amd.vec_env import _puct_numbers
+    def __init__(self, model_or_path, board_size=5, cube_layer=3, sims=64, c_puct=1.5, terminal_value=1.0, endgame_table=None, fused=False):
+        from ewn_gym_amd.vec_env import _fused_table, _puct_numbers
         self.sims = _puct_numbers("PuctAgent", sims, c_puct, terminal_value)
+        _fused_table("PuctAgent", fused, endgame_table)
+        self.fused = bool(fused)
         self.c_puct, self.terminal_value = float(c_puct), float(terminal_value)
         super().__init__(model_or_path, board_size=board_size, cube_layer=cube_layer, deterministic=True)
         self.endgame_table = _leaf_table("PuctAgent", endgame_table, board_size)
@@ -127,7 +130,7 @@ class PuctAgent(ModelAgent):
         b, d = self._on_device(boards, dice)
         return self._ea.predict_puct(b, d, self.params, sims=self.sims, c_puct=self.c_puct, terminal_value=self.terminal_value,
                                      return_visits=return_visits, return_q=return_q, return_value=return_value,
-                                     cube_layer=self.cube_layer, endgame_table=self.endgame_table)
+                                     cube_layer=self.cube_layer, endgame_table=self.endgame_table, fused=self.fused)
 
     def policy_fn(self):
         """(board, dice, t) -> actions, the callable tournament.evaluate takes"""

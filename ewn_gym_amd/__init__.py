@@ -7,10 +7,10 @@ from ._lib import EwnError, INFO_MESSAGES, LIB_PATH  # noqa: F401
 from .vec_env import (VecEWN, apply_action, evaluate, legal_actions, lookahead_expand, lookahead_reduce, lookahead_targets,  # noqa: F401
                       playout_wins, predict_mcts, predict_lookahead, predict_minimax, predict_policy, predict_random, sup_grad,
                       predict_puct, puct_advance, puct_begin, puct_result, puct_tree_views, puct_play, selfplay_noise, selfplay_outcomes,
-                      selfplay_puct)
+                      selfplay_puct, puct_search)
 from .endgame import EndgameTable  # noqa: F401
 
 __all__ = ["VecEWN", "EwnError", "INFO_MESSAGES", "legal_actions", "apply_action", "playout_wins", "evaluate", "predict_minimax", "predict_random",
            "predict_mcts", "predict_policy", "predict_lookahead", "lookahead_expand", "lookahead_reduce", "lookahead_targets", "sup_grad", "EndgameTable",
            "predict_puct", "puct_begin", "puct_advance", "puct_result", "puct_tree_views",
-           "puct_play", "selfplay_noise", "selfplay_outcomes", "selfplay_puct"]
+           "puct_play", "selfplay_noise", "selfplay_outcomes", "selfplay_puct", "puct_search"]

@@ -20,7 +20,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
 FILE_FLAGS = {"ewn_policy.hip": ["-fno-slp-vectorize"], "ewn_policy_eval.hip": ["-fno-slp-vectorize"],
               "ewn_policy_eval_mcts.hip": ["-fno-slp-vectorize"], "ewn_selfplay.hip": ["-fno-slp-vectorize"],
               "ewn_step_vs.hip": ["-fno-slp-vectorize"], "ewn_predict_policy.hip": ["-fno-slp-vectorize"],
-              "ewn_predict_lookahead.hip": ["-fno-slp-vectorize"], "ewn_lookahead_stages.hip": ["-fno-slp-vectorize"]}
+              "ewn_predict_lookahead.hip": ["-fno-slp-vectorize"], "ewn_lookahead_stages.hip": ["-fno-slp-vectorize"],
+              "ewn_puct_fused.hip": ["-fno-slp-vectorize"]}
 
 
 def stale():

@@ -1,0 +1,305 @@
+// ewn_puct.hpp -- the one copy of the PUCT tree's device code: the layout, a node's edges, the backup, the
+// root written by begin, the evaluation of a pending node and one simulation's walk.  ewn_puct.hip (the staged kernels: the
+// network's outputs come and the leaf rows go through global memory, a launch per step) and ewn_puct_fused.hip (the whole search in
+// one launch: both come and go through LDS) call the same functions, so the two paths agree byte for byte by construction.
+//
+// A wave per tree.  Per-edge state (N, W, P, kind, child[.][d'], cn[.][d']) of edge a is read and written by lane a alone, in every
+// kernel.  What one lane writes and ANOTHER reads through global memory -- a node's dice and parent triple and the header (lane 0
+// writes, every lane reads), begin's fill (any lane writes a word that another lane's root or edge lies in) -- is handed over in one
+// of two ways, and a kernel that calls these functions must provide one of them:
+//   staged:  the write and the read are in different launches (boards, dice and parent triples are written one launch before they
+//            are read);
+//   fused:   a tree stays on ONE wave from the fill to the end of the search, and between the write and the read lies a block
+//            barrier (__syncthreads: a workgroup-scope release / acquire), the barriers of the round structure.
+// Within one call of pu_round nothing is read that another lane wrote in the same call: a board cell is read by the lane that wrote
+// it, the nodes of a backup chain and of a walk were created in earlier rounds, and the node created now is not entered again.
+// The node's board goes to LDS by ewn_lookahead.hpp's la_observation, so that la_find and la_root apply unchanged.
+#pragma once
+#include "ewn_lookahead.hpp"
+#include <climits>
+
+#define PU_MAX_SIMS 4096
+#define PU_LAYOUT 1          // hdr[5]: the version of the layout below (ewn_gym_amd.vec_env.PUCT_LAYOUT)
+
+// per wave: the node's board (64 bytes, zero past the board) | cube positions [16] | 16 words of the kernel's own
+#define PU_O_POS 64
+#define PU_O_OWN 80
+#define PU_WAVE (PU_O_OWN + 16 * 4)
+
+// One tree, sections of structure-of-arrays inside one 4-byte aligned buffer; `nodes` = sims + 1.  Offsets in bytes:
+//   hdr    int32 [8]            node count | simulations begun | pending node (-1: none) | degenerate | sims | PU_LAYOUT | 0 | 0
+//   n      int32 [nodes][6]     visits per edge a = 3 f + r
+//   w      float [nodes][6]     sum of the values backed up through the edge
+//   p      float [nodes][6]     prior
+//   child  int16 [nodes][6][6]  the node under (edge, dice d' - 1), -1 for none
+//   cn     int16 [nodes][6][6]  its visits
+//   parent int16 [nodes][4]     node, edge, dice d', 0; the root: -1, 0, 0, 0
+//   kind   int8  [nodes][6]     0 not an action | 1 wins | 2 searched (written when the node is evaluated)
+//   dice   int8  [nodes]
+//   board  int8  [nodes][S*S]   seen from the node's side to move
+// kind, dice and board are each padded to a multiple of 4 bytes.
+struct PuLayout { int nodes; u32 n, w, p, child, cn, parent, kind, dice, board; long long bytes; };
+
+__host__ __device__ static inline PuLayout pu_layout(int S, int sims)
+{
+    PuLayout L;
+    const u32 N = (u32)sims + 1u, C = (u32)(S * S);
+    u32 o = 32;
+    L.nodes = (int)N;
+    L.n = o; o += 24 * N;
+    L.w = o; o += 24 * N;
+    L.p = o; o += 24 * N;
+    L.child = o; o += 72 * N;
+    L.cn = o; o += 72 * N;
+    L.parent = o; o += 8 * N;
+    L.kind = o; o += (6 * N + 3) & ~3u;
+    L.dice = o; o += (N + 3) & ~3u;
+    L.board = o; o += (N * C + 3) & ~3u;
+    L.bytes = (long long)o;
+    return L;
+}
+
+struct PuTree { int *hdr; int *n; float *w; float *p; int16_t *child, *cn, *parent; int8_t *kind, *dice, *board; };
+
+EWN_DEV PuTree pu_tree(uint8_t *trees, size_t m, const PuLayout &L)
+{
+    uint8_t *t = trees + m * (size_t)L.bytes;                  // 64-bit byte offsets
+    PuTree T;
+    T.hdr = (int *)t; T.n = (int *)(t + L.n); T.w = (float *)(t + L.w); T.p = (float *)(t + L.p);
+    T.child = (int16_t *)(t + L.child); T.cn = (int16_t *)(t + L.cn); T.parent = (int16_t *)(t + L.parent);
+    T.kind = (int8_t *)(t + L.kind); T.dice = (int8_t *)(t + L.dice); T.board = (int8_t *)(t + L.board);
+    return T;
+}
+
+// lane a's edge of the node in LDS under dice d: kind and the move (lanes 6 .. 63: kind 0)
+struct PuEdge { int kind, src, dst, cube; bool one; };         // one: both flags name one cube
+
+template <int S>
+EWN_DEV PuEdge pu_edge(const int8_t *base, const uint8_t *pos, int PA, int PO, int d, int lane)
+{
+    const int c0 = la_find(0, d, PA), c1 = la_find(1, d, PA);
+    const LaRoot R = la_root<S>(base, pos, PA, PO, c0, c1, lane < 6 ? lane : 0);
+    PuEdge E;
+    E.one = c1 == c0;
+    E.kind = lane >= 6 || (lane >= 3 && E.one) ? 0 : R.code;
+    E.src = R.src; E.dst = R.dst; E.cube = R.cube;
+    return E;
+}
+
+// Backup of v from node j: every lane walks the parent chain, lane a adds to edge a
+EWN_DEV void pu_backup(const PuTree &T, int j, float v, int lane, int nodes)
+{
+    #pragma unroll 1
+    for (int guard = 0; guard < nodes; guard++) {
+        const int p = T.parent[4 * j], a = T.parent[4 * j + 1], d = T.parent[4 * j + 2];
+        if (p < 0 || p >= j || a < 0 || a > 5 || d < 1 || d > 6) break;   // the root (or a buffer that is no tree)
+        v = -v;
+        if (lane == a) {
+            T.w[6 * p + a] += v;
+            T.n[6 * p + a] += 1;
+            T.cn[36 * p + 6 * a + d - 1] += 1;
+        }
+        j = p;
+    }
+}
+
+// The root of a tree whose every byte is filled (zeros, child -1), by one wave: the header, node 0 and the leaf row -- the root's
+// observation, or a zero board with dice 1 where the observation is over or a side has no cube (a degenerate tree).  `lds` is the
+// wave's PU_WAVE bytes; leaf_row [CELLS] and leaf_dice [1] may lie in global memory or in LDS
+template <int S>
+EWN_DEV void pu_root(const PuTree &T, const int8_t *row, const int8_t *dice, int sims, int8_t *leaf_row, int8_t *leaf_dice, int lane, int8_t *lds)
+{
+    constexpr int CELLS = S * S;
+    uint8_t *pos = (uint8_t *)(lds + PU_O_POS);
+    int PA, PO;
+    __builtin_amdgcn_wave_barrier();                           // what was there is read
+    const bool live = la_observation<S, 64>(row, lane, lds, pos, PA, PO);
+    const int d = la_dice((int)dice[0]);
+    if (lane < CELLS) {
+        T.board[lane] = lds[lane];
+        leaf_row[lane] = live ? lds[lane] : (int8_t)0;
+    }
+    if (lane == 0) {
+        T.hdr[0] = 1; T.hdr[1] = 0; T.hdr[2] = live ? 0 : -1; T.hdr[3] = live ? 0 : 1; T.hdr[4] = sims; T.hdr[5] = PU_LAYOUT;
+        T.dice[0] = (int8_t)d;
+        T.parent[0] = -1;
+        leaf_dice[0] = (int8_t)(live ? d : 1);
+    }
+}
+
+// the noise instance's own (ewn_puct_advance_noise): the tree's six weights, eps and keep = 1 - eps formed once on the host
+struct PuNoise { const float *row; float eps, keep; };
+
+// The evaluation of the pending node: priors from the five logits at lg (softmax over the flags times softmax over the directions,
+// normalised over the legal edges), kind, then the backup of v = *vp * inv_tv clamped to [-1, 1].  NOISE: when the node is the root,
+// its priors are mixed with the caller's weights, normalised over the legal edges, before the backup and before the first
+// simulation selects on them.  lg and vp may lie in global memory or in LDS
+template <int S, bool NOISE>
+EWN_DEV void pu_evaluate(const PuTree &T, int pending, const float *lg, const float *vp, float inv_tv, const PuNoise &Z, int nodes, int lane,
+                         int8_t *base)
+{
+    constexpr int CELLS = S * S;
+    uint8_t *pos = (uint8_t *)(base + PU_O_POS);
+    float *sc = (float *)(base + PU_O_OWN);
+    int PA, PO;
+    __builtin_amdgcn_wave_barrier();                           // what was there is read
+    la_observation<S, 64>(T.board + (size_t)pending * CELLS, lane, base, pos, PA, PO);
+    if (PA != 0 && PO != 0) {
+        const PuEdge E = pu_edge<S>(base, pos, PA, PO, (int)T.dice[pending], lane);
+        const float l0 = lg[0], l1 = lg[1], l2 = lg[2], l3 = lg[3], l4 = lg[4];
+        const float mf = l1 > l0 ? l1 : l0;
+        const float f0 = expf(l0 - mf), f1 = expf(l1 - mf), sf = f0 + f1;
+        float mr = l3 > l2 ? l3 : l2;
+        mr = l4 > mr ? l4 : mr;
+        const float r0 = expf(l2 - mr), r1 = expf(l3 - mr), r2 = expf(l4 - mr), sr = (r0 + r1) + r2;
+        const int f = lane >= 3, r = lane - 3 * f;
+        const float pf = (f ? f1 : f0) / sf, pr = (r == 0 ? r0 : r == 1 ? r1 : r2) / sr;
+        const float raw = E.kind == 0 ? 0.0f : E.one ? pr : pf * pr;
+        if (lane < 8) sc[lane] = raw;
+        __builtin_amdgcn_wave_barrier();
+        const float sum = ((((sc[0] + sc[1]) + sc[2]) + sc[3]) + sc[4]) + sc[5];
+        if constexpr (NOISE) {
+            float prior = E.kind == 0 ? 0.0f : raw / sum;
+            if (pending == 0) {
+                float eta = 0.0f;
+                if (lane < 6 && E.kind != 0) {
+                    const float x = Z.row[lane];
+                    eta = x > 0.0f && x < __builtin_inff() ? x : 0.0f;   // NaN, inf, zero and negative numbers: no weight
+                }
+                __builtin_amdgcn_wave_barrier();               // the raw priors are read
+                if (lane < 8) sc[lane] = eta;
+                __builtin_amdgcn_wave_barrier();
+                const float es = ((((sc[0] + sc[1]) + sc[2]) + sc[3]) + sc[4]) + sc[5];
+                if (es > 0.0f && E.kind != 0) prior = Z.keep * prior + Z.eps * (eta / es);
+            }
+            if (lane < 6) {
+                T.kind[6 * pending + lane] = (int8_t)E.kind;
+                T.p[6 * pending + lane] = prior;
+            }
+        } else if (lane < 6) {
+            T.kind[6 * pending + lane] = (int8_t)E.kind;
+            T.p[6 * pending + lane] = E.kind == 0 ? 0.0f : raw / sum;
+        }
+        float v = vp[0] * inv_tv;
+        v = v > -1.0f ? v : -1.0f;
+        v = v < 1.0f ? v : 1.0f;
+        pu_backup(T, pending, v, lane, nodes);
+    }
+}
+
+// One simulation from the root: down to a new node, which becomes the pending leaf (its observation goes to leaf_row / leaf_dice,
+// global memory or LDS; returns true), or to a winning edge, which is backed up at once.  count: the tree's nodes, one more with a leaf
+template <int S>
+EWN_DEV bool pu_walk(const PuTree &T, int &count, int &pending, int nodes, float c_puct, int8_t *leaf_row, int8_t *leaf_dice, int lane,
+                     int8_t *base)
+{
+    constexpr int CELLS = S * S;
+    uint8_t *pos = (uint8_t *)(base + PU_O_POS);
+    float *sc = (float *)(base + PU_O_OWN);
+    int *isc = (int *)(base + PU_O_OWN) + 8;
+    int j = 0;
+    #pragma unroll 1
+    for (int step = 0; step < nodes; step++) {                 // a path holds at most `count` nodes
+        int PA, PO;
+        __builtin_amdgcn_wave_barrier();                       // what was there is read
+        la_observation<S, 64>(T.board + (size_t)j * CELLS, lane, base, pos, PA, PO);
+        if (PA == 0 || PO == 0) break;
+        const PuEdge E = pu_edge<S>(base, pos, PA, PO, (int)T.dice[j], lane);
+        const int nn = lane < 6 ? T.n[6 * j + lane] : 0;
+        const float ww = lane < 6 ? T.w[6 * j + lane] : 0.0f, pp = lane < 6 ? T.p[6 * j + lane] : 0.0f;
+        if (lane < 8) isc[lane] = nn;
+        __builtin_amdgcn_wave_barrier();
+        const int Ns = isc[0] + isc[1] + isc[2] + isc[3] + isc[4] + isc[5];
+        const float rs = (float)sqrt((double)(Ns + 1));        // the correctly rounded fp32 root of an integer
+        const float qa = nn > 0 ? ww / (float)nn : 0.0f;
+        const float score = qa + ((c_puct * pp) * rs) / (float)(1 + nn);
+        if (lane < 8) sc[lane] = score;
+        const u32 valid = (u32)__builtin_amdgcn_ballot_w64(E.kind != 0) & 0x3Fu;
+        __builtin_amdgcn_wave_barrier();
+        int best = -1;
+        float sb = 0.0f;
+        #pragma unroll
+        for (int i = 0; i < 6; i++) {
+            const float si = sc[i];
+            if (((valid >> i) & 1u) && (best < 0 || si > sb)) { best = i; sb = si; }
+        }
+        if (best < 0) break;
+        const int bk = __shfl(E.kind, best), bsrc = __shfl(E.src, best), bdst = __shfl(E.dst, best), bcube = __shfl(E.cube, best);
+        if (bk == 1) {                                         // the move wins: +1 from this node, no network call
+            if (lane == best) { T.w[6 * j + best] += 1.0f; T.n[6 * j + best] += 1; }
+            pu_backup(T, j, 1.0f, lane, nodes);
+            break;
+        }
+        int dsel = 1, c = -1;                                  // chance: the least visited dice, the first of them
+        if (lane == best) {
+            const int16_t *cn = T.cn + 36 * j + 6 * best;
+            int mn = cn[0];
+            #pragma unroll
+            for (int i = 1; i < 6; i++) { const int x = cn[i]; if (x < mn) { mn = x; dsel = i + 1; } }
+            c = T.child[36 * j + 6 * best + dsel - 1];
+        }
+        dsel = __shfl(dsel, best); c = __shfl(c, best);
+        if (c >= 0) {
+            if (c >= count || c <= j) break;                   // no tree
+            j = c;
+            continue;
+        }
+        if (count >= nodes) break;
+        const int idx = count++;                               // a new node: flip(b1) under dsel, the pending leaf
+        if (lane == best) T.child[36 * j + 6 * best + dsel - 1] = (int16_t)idx;
+        if (lane < CELLS) {
+            const int rc = CELLS - 1 - lane;
+            int v = base[rc];
+            v = rc == bsrc ? 0 : v;
+            v = rc == bdst ? bcube : v;
+            const int8_t nb = (int8_t)(-v);
+            T.board[(size_t)idx * CELLS + lane] = nb;
+            leaf_row[lane] = nb;
+        }
+        if (lane == 0) {
+            T.dice[idx] = (int8_t)dsel;
+            T.parent[4 * idx] = (int16_t)j; T.parent[4 * idx + 1] = (int16_t)best; T.parent[4 * idx + 2] = (int16_t)dsel;
+            leaf_dice[0] = (int8_t)dsel;
+        }
+        pending = idx;
+        return true;
+    }
+    return false;
+}
+
+// One round of one tree, by one wave (ewn_puct_advance's definition): the pending node is evaluated and backed up; while fewer than
+// `sims` simulations have begun, one more walks down; the header; the leaf row of a tree without a new leaf is a zero board with
+// dice 1.  A tree of another budget or layout, or no tree at all, is left alone.  base: the wave's PU_WAVE bytes of LDS
+template <int S, bool NOISE>
+EWN_DEV void pu_round(const PuTree &T, int sims, float c_puct, float inv_tv, int nodes, const float *lg, const float *vp, const PuNoise &Z,
+                      int8_t *leaf_row, int8_t *leaf_dice, int lane, int8_t *base)
+{
+    constexpr int CELLS = S * S;
+    int count = T.hdr[0], done = T.hdr[1], pending = T.hdr[2];
+    const bool ok = T.hdr[3] == 0 && T.hdr[4] == sims && T.hdr[5] == PU_LAYOUT && count >= 1 && count <= nodes && pending < count;
+    bool leaf = false;                                         // a new node's observation went to the leaf row
+    if (ok) {
+        if (pending >= 0) {                                    // ---- evaluation: priors from the logits, then backup of v
+            pu_evaluate<S, NOISE>(T, pending, lg, vp, inv_tv, Z, nodes, lane, base);
+            pending = -1;
+        }
+        if (done < sims) {                                     // ---- one simulation: down to a new node or a winning edge
+            done++;
+            leaf = pu_walk<S>(T, count, pending, nodes, c_puct, leaf_row, leaf_dice, lane, base);
+        }
+        if (lane == 0) { T.hdr[0] = count; T.hdr[1] = done; T.hdr[2] = pending; }
+    }
+    if (!leaf) {
+        if (lane < CELLS) leaf_row[lane] = 0;
+        if (lane == 0) leaf_dice[0] = 1;
+    }
+    __builtin_amdgcn_wave_barrier();                           // this trip's LDS is read: the next may overwrite it
+}
+
+// ewn_lookahead_expand's order of refusals: arguments, geometry, the empty batch, pointers; then the values -- all before the launch
+static inline int pu_refuse(int board_size, int cube_layer, int M)
+{
+    if (M < 0 || M > INT_MAX / 64) return EWN_EINVAL;          // rows of at most 64 cells are counted in 32 bits
+    if (ewn_policy_param_count(board_size, cube_layer) < 0) return EWN_EUNSUPPORTED;
+    return EWN_OK;
+}

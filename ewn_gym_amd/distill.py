@@ -52,7 +52,7 @@ class SearchDistillTrainer(FusedTrainer):
 
     def __init__(self, env, n_steps=5, learning_rate=7e-4, pi_coef=1.0, vf_coef=0.5, temperature=0.0, plies=1, terminal_value=1.0,
                  max_grad_norm=0.5, rms_alpha=0.99, rms_eps=1e-5, seed=None, opponent=None, opponent_update_every=100,
-                 opponent_deterministic=False, endgame_table=None, search="lookahead", sims=64, c_puct=1.5, endgame_leaves=False):
+                 opponent_deterministic=False, endgame_table=None, search="lookahead", sims=64, c_puct=1.5, endgame_leaves=False, fused=False):
         import math
         from . import _lib
         if search not in ("lookahead", "puct"):
@@ -69,6 +69,10 @@ class SearchDistillTrainer(FusedTrainer):
             raise ValueError("SearchDistillTrainer: terminal_value must be finite, got %r" % (terminal_value,))
         if endgame_leaves and endgame_table is None:
             raise ValueError("SearchDistillTrainer: endgame_leaves=True needs an endgame_table")
+        if fused and search != "puct":
+            raise ValueError("SearchDistillTrainer: fused=True is the PUCT search in one launch: it needs search='puct'")
+        if fused and endgame_leaves:
+            raise ValueError("SearchDistillTrainer: fused=True does not take endgame_leaves=True: the exact leaves are the staged path's")
         if endgame_table is not None:
             from .endgame import EndgameTable
             if not float(terminal_value) > 0.0:
@@ -86,6 +90,7 @@ class SearchDistillTrainer(FusedTrainer):
         self.pi_coef, self.vf_coef, self.temperature = float(pi_coef), float(vf_coef), float(temperature)
         self.plies, self.terminal_value = int(plies), float(terminal_value)
         self.search, self.sims, self.c_puct = search, int(sims), float(c_puct)
+        self.fused = bool(fused)             # the PUCT search as the one launch of ewn_puct_search (4r): the same targets bit for bit
         # the optimiser step is ewn_a2c_apply: of this struct it reads max_grad_norm, learning_rate, rms_alpha, rms_eps, world_size
         self.hyper = _lib.EwnA2cHyper(0.0, float(vf_coef), 0.0, float(max_grad_norm), float(learning_rate), float(rms_alpha), float(rms_eps),
                                       int(self.world))
@@ -106,7 +111,7 @@ class SearchDistillTrainer(FusedTrainer):
         if self.search == "puct":
             _, visits, q, value = predict_puct(self._boards, self._dice, self.params, sims=self.sims, c_puct=self.c_puct,
                                                terminal_value=self.terminal_value, return_visits=True, return_q=True, return_value=True,
-                                               cube_layer=env.L, **leaves)
+                                               cube_layer=env.L, fused=self.fused, **leaves)
             target_pi, target_value, weight = puct_targets(visits, q, value, self.terminal_value)
             if self.endgame_table is not None:     # covered rows: the exact q's targets, as the lookahead's rows get them
                 _, covered, q_exact = self.endgame_table.lookup(self._boards, self._dice, return_q=True)
@@ -136,7 +141,7 @@ class SearchDistillTrainer(FusedTrainer):
 
     def _state(self):
         return {"sq_avg": self.sq_avg, "terminal_value": float(self.terminal_value), "plies": int(self.plies), "search": self.search,
-                "sims": int(self.sims), "c_puct": float(self.c_puct)}
+                "sims": int(self.sims), "c_puct": float(self.c_puct), "fused_search": bool(self.fused)}
 
     def _load_state(self, sd):
         self.sq_avg.copy_(sd["sq_avg"])
@@ -144,6 +149,7 @@ class SearchDistillTrainer(FusedTrainer):
         self.plies = int(sd.get("plies", self.plies))
         self.search = sd.get("search", self.search)
         self.sims, self.c_puct = int(sd.get("sims", self.sims)), float(sd.get("c_puct", self.c_puct))
+        self.fused = bool(sd.get("fused_search", self.fused)) and self.search == "puct" and not self.endgame_leaves
 
 
 def both_flags_one_cube(boards, dice):
@@ -169,7 +175,7 @@ class PuctSelfPlayTrainer(FusedTrainer):
 
     def __init__(self, env, sims=64, c_puct=1.5, terminal_value=1.0, noise_eps=0.25, noise_alpha=1.0, temp_plies=8, max_plies=None,
                  learning_rate=7e-4, pi_coef=1.0, vf_coef=0.5, max_grad_norm=0.5, rms_alpha=0.99, rms_eps=1e-5, seed=None,
-                 endgame_table=None, chunk=1024):
+                 endgame_table=None, chunk=1024, fused=False):
         import math
         from . import _lib
         from .vec_env import SELFPLAY_MAX_PLIES, _noise_eps, _play_numbers, _puct_numbers
@@ -184,6 +190,8 @@ class PuctSelfPlayTrainer(FusedTrainer):
                 raise ValueError("%s: %s must be finite and not negative, got %r" % (who, name, v))
         if max_plies is not None and not (isinstance(max_plies, int) and max_plies >= 1):
             raise ValueError("%s: max_plies must be a positive integer or None, got %r" % (who, max_plies))
+        if fused and endgame_table is not None:
+            raise ValueError("%s: fused=True does not take an endgame_table: the exact-leaf substitution is the staged path's" % who)
         if endgame_table is not None:
             from .endgame import EndgameTable
             if not isinstance(endgame_table, EndgameTable):
@@ -198,6 +206,7 @@ class PuctSelfPlayTrainer(FusedTrainer):
         self.noise_eps, self.noise_alpha, self.temp_plies = float(noise_eps), float(noise_alpha), int(temp_plies)
         self.max_plies = SELFPLAY_MAX_PLIES[env.S] if max_plies is None else int(max_plies)
         self.pi_coef, self.vf_coef, self.chunk = float(pi_coef), float(vf_coef), int(chunk)
+        self.fused = bool(fused)                 # a ply's search as the one launch of ewn_puct_search (4r): the same records bit for bit
         self.seed_base, self.seed_counter = (0 if seed is None else int(seed)), 0   # the counter: one per update, saved and resumed
         self.hyper = _lib.EwnA2cHyper(0.0, float(vf_coef), 0.0, float(max_grad_norm), float(learning_rate), float(rms_alpha), float(rms_eps),
                                       int(self.world))
@@ -225,7 +234,7 @@ class PuctSelfPlayTrainer(FusedTrainer):
         rec = selfplay_puct(board, dice, self.params, sims=self.sims, max_plies=self.max_plies, c_puct=self.c_puct,
                             terminal_value=self.terminal_value, noise_eps=self.noise_eps, noise_alpha=self.noise_alpha,
                             temp_plies=self.temp_plies, key=self.noise_key, game_offset=first, chunk=self.chunk,
-                            endgame_table=self.endgame_table, cube_layer=env.L)
+                            endgame_table=self.endgame_table, cube_layer=env.L, fused=self.fused)
         self.records = rec
         R, S = self.max_plies * env.N, env.S
         b, d = rec["board"].reshape(R, S, S), rec["dice"].reshape(R).clamp(min=1)         # rows past a game's end hold dice 0
@@ -263,7 +272,7 @@ class PuctSelfPlayTrainer(FusedTrainer):
     def _state(self):
         return {"sq_avg": self.sq_avg, "terminal_value": float(self.terminal_value), "sims": int(self.sims), "c_puct": float(self.c_puct),
                 "noise_eps": float(self.noise_eps), "noise_alpha": float(self.noise_alpha), "temp_plies": int(self.temp_plies),
-                "max_plies": int(self.max_plies), "seed_counter": int(self.seed_counter)}
+                "max_plies": int(self.max_plies), "seed_counter": int(self.seed_counter), "fused_search": bool(self.fused)}
 
     def _load_state(self, sd):
         self.sq_avg.copy_(sd["sq_avg"])
@@ -271,6 +280,7 @@ class PuctSelfPlayTrainer(FusedTrainer):
         self.sims, self.c_puct = int(sd.get("sims", self.sims)), float(sd.get("c_puct", self.c_puct))
         self.noise_eps, self.noise_alpha = float(sd.get("noise_eps", self.noise_eps)), float(sd.get("noise_alpha", self.noise_alpha))
         self.temp_plies, self.seed_counter = int(sd.get("temp_plies", self.temp_plies)), int(sd.get("seed_counter", self.seed_counter))
+        self.fused = bool(sd.get("fused_search", self.fused)) and self.endgame_table is None
         if int(sd.get("max_plies", self.max_plies)) != self.max_plies:
             raise ValueError("the checkpoint's games have at most %d plies, this trainer's %d: the update's scratch is sized by it" % (
                 int(sd["max_plies"]), self.max_plies))

@@ -60,7 +60,7 @@ def _policy(spec, cube_layer, key):
         model = spec["model"]
         return PuctAgent(model, board_size=getattr(model, "S", spec.get("board_size", 5)), cube_layer=cube_layer, sims=spec.get("sims", 64),
                          c_puct=spec.get("c_puct", 1.5), terminal_value=spec.get("terminal_value", 1.0),
-                         endgame_table=spec.get("endgame_table")).policy_fn()
+                         endgame_table=spec.get("endgame_table"), fused=spec.get("fused", False)).policy_fn()   # fused: one launch (4r)
     if kind == "endgame":       # the exact move where the endgame table covers the position, the "fallback" spec's policy elsewhere
         from classical_policies.model import EndgameAgent
         if "table" not in spec or "fallback" not in spec:
@@ -339,11 +339,12 @@ def load_policy(path, board_size=5, cube_layer=3, device="cuda"):
 
 def evaluate_model(model, names=("random", "minimax"), num=1024, max_depth=5, num_simulations=10, num_env_copies=5, board_size=5,
                    cube_layer=3, heuristic="hybrid", rng="mt19937", lookahead=False, endgame_table=None, puct=None,
-                   endgame_leaves=False):
+                   endgame_leaves=False, fused=False):
     """eval_A2C.py's loop: the model's deterministic policy against every listed opponent; lookahead (1 / True, or 2): and, beside
     each, its lookahead policy of that many moves ({"kind": "mlp_lookahead", "plies": ...}) on the same episodes.  endgame_table (an
     EndgameTable or its path): every agent plays the exact move where the table covers the position ({"kind": "endgame"}, ply by ply).
     puct (a number of simulations): and its PUCT search of that budget ({"kind": "mlp_puct", "sims": ...}), rows "puct(SIMS) vs ..."
+    fused (with puct): that search as one launch per move (ewn_puct_search): the same moves, so the same rows.
     endgame_leaves (with lookahead and endgame_table): the table is not laid over the agents' moves; beside the lookahead's row
     stands the same lookahead with the table's exact values at the leaves it covers, "lookahead + exact leaves vs ..." """
     table = {}
@@ -371,7 +372,7 @@ def evaluate_model(model, names=("random", "minimax"), num=1024, max_depth=5, nu
                 table[("lookahead(2) + exact leaves vs %s" if plies == 2 else "lookahead + exact leaves vs %s") % o] = {
                     k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}
         if puct is not None:
-            r = evaluate({"kind": "mlp_puct", "model": model, "sims": int(puct)}, opp, num=num, board_size=board_size, cube_layer=cube_layer,
+            r = evaluate({"kind": "mlp_puct", "model": model, "sims": int(puct), "fused": bool(fused)}, opp, num=num, board_size=board_size, cube_layer=cube_layer,
                          rng=rng)
             table["puct(%d) vs %s" % (int(puct), o)] = {k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}
     return table
@@ -408,6 +409,9 @@ def _parser():
     ap.add_argument("--puct", default=None, type=int, metavar="SIMS",
                     help="with --model: beside the raw policy, its PUCT search of SIMS simulations (predict_puct) against the same "
                          "opponents, rows \"puct(SIMS) vs ...\"")
+    ap.add_argument("--fused", action="store_true",
+                    help="with --puct: the search of a move in one kernel launch (ewn_puct_search) instead of the staged launches; the "
+                         "same moves")
     ap.add_argument("--endgame_table", default=None,
                     help="with --model: a saved EndgameTable; the model (and its --lookahead) plays the exact move wherever the table "
                          "covers the position")
@@ -434,6 +438,8 @@ def main():
         ap.error("--puct goes with --model and the classical opponents of --agents, without --endgame_table")
     if a.puct is not None and not 0 <= a.puct <= 4096:
         ap.error("--puct takes 0..4096 simulations")
+    if a.fused and a.puct is None:
+        ap.error("--fused goes with --puct")
     if a.endgame_table and (a.model is None or a.opponent_model is not None):
         ap.error("--endgame_table goes with --model and the classical opponents of --agents")
     if a.endgame_leaves and not (a.endgame_table and a.lookahead):
@@ -450,7 +456,7 @@ def main():
         model = load_policy(a.model, a.board_size, a.cube_layer)
         t = evaluate_model(model, a.agents, a.num, a.max_depth, a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer,
                            a.heuristic, a.rng, lookahead=a.lookahead or False, endgame_table=a.endgame_table, puct=a.puct,
-                           endgame_leaves=a.endgame_leaves)
+                           endgame_leaves=a.endgame_leaves, fused=a.fused)
     else:
         t = tournament(a.agents, a.num, a.max_depth, a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer,
                        a.heuristic, a.rng)

@@ -32,6 +32,9 @@ def _parser():
                          "is the policy target (predict_puct)")
     ap.add_argument("--sims", type=int, default=64, help="SEARCH --search puct, SELFPLAY: simulations per observation (0..4096)")
     ap.add_argument("--c_puct", type=float, default=1.5, help="SEARCH --search puct, SELFPLAY: the exploration constant")
+    ap.add_argument("--fused", action="store_true",
+                    help="SEARCH --search puct, SELFPLAY: the PUCT search in one kernel launch (ewn_puct_search, DESIGN.md 4r) instead of the "
+                         "staged launches: the same targets bit for bit; not with --endgame_leaves")
     ap.add_argument("--noise_eps", type=float, default=0.25, help="SELFPLAY: the weight of the Dirichlet noise in the root's priors (0: none)")
     ap.add_argument("--noise_alpha", type=float, default=1.0,
                     help="SELFPLAY: the Dirichlet parameter (about 10 / the number of moves, AlphaZero's rule of thumb: a choice, not a measurement)")
@@ -109,6 +112,10 @@ def main():
                              "--endgame_table PATH --endgame_leaves")
     if a.search != "lookahead" and a.algorithm != "SEARCH":
         raise SystemExit("--search is read by SEARCH only")
+    if a.fused and not (a.algorithm == "SELFPLAY" or (a.algorithm == "SEARCH" and a.search == "puct")):
+        raise SystemExit("--fused is read by SEARCH --search puct and by SELFPLAY only")
+    if a.fused and a.endgame_leaves:
+        raise SystemExit("--fused does not go with --endgame_leaves: the exact-leaf substitution is the staged search's")
     if a.endgame_table is not None and a.algorithm not in ("SEARCH", "SELFPLAY"):
         raise SystemExit("--endgame_table is read by SEARCH and SELFPLAY only")
     if a.endgame_leaves and (a.algorithm not in ("SEARCH", "SELFPLAY") or a.endgame_table is None):
@@ -140,12 +147,12 @@ def main():
         from .distill import SearchDistillTrainer
         trainer = SearchDistillTrainer(env, n_steps=a.n_steps, learning_rate=a.learning_rate, temperature=a.temperature, plies=a.plies,
                                        terminal_value=a.terminal_value, seed=mseed, endgame_table=a.endgame_table, search=a.search,
-                                       sims=a.sims, c_puct=a.c_puct, endgame_leaves=a.endgame_leaves, **okw)
+                                       sims=a.sims, c_puct=a.c_puct, endgame_leaves=a.endgame_leaves, fused=a.fused, **okw)
     elif a.algorithm == "SELFPLAY":
         from .distill import PuctSelfPlayTrainer
         trainer = PuctSelfPlayTrainer(env, sims=a.sims, c_puct=a.c_puct, terminal_value=a.terminal_value, noise_eps=a.noise_eps,
                                       noise_alpha=a.noise_alpha, temp_plies=a.temp_plies, max_plies=a.max_plies,
-                                      learning_rate=a.learning_rate, seed=mseed, endgame_table=a.endgame_table)
+                                      learning_rate=a.learning_rate, seed=mseed, endgame_table=a.endgame_table, fused=a.fused)
     elif a.trainer == "fused" or model_opp is not None or (a.trainer == "auto" and env.supports_policy_rollout()):
         trainer = FusedA2CTrainer(env, n_steps=a.n_steps, learning_rate=a.learning_rate, seed=mseed, **okw)
     else:

@@ -918,6 +918,8 @@ LA_TUPLES = 108        # (agent move, reply) tuples per observation of the looka
 LA_ROWS = 648          # its leaf rows: a tuple under each of the six d2
 PUCT_LAYOUT = 1        # the version of a PUCT tree's layout (csrc/ewn_puct.hip); begin writes it into every header
 PUCT_MAX_SIMS = 4096
+PUCT_FUSED_TILE = 32          # the most trees a block of ewn_puct_search holds at a time (csrc/ewn_puct_fused.hip) ...
+PUCT_FUSED_MAX_BLOCKS = 256   # ... and its grid's cap: more tiles are walked grid-stride
 
 
 def _puct_sections(S, sims):
@@ -1065,10 +1067,64 @@ def puct_result(tree, board_size, sims, return_visits=False, return_q=False, ret
     return out[0] if len(out) == 1 else out
 
 
-def _puct_search(lib, S, L, n, sims, b, d, params, cp, tv, table, scratch, st, noise=None, eps=0.0):
+def _fused_table(who, fused, endgame_table):
+    if fused and endgame_table is not None:
+        raise ValueError("%s: fused=True does not take an endgame_table: the exact-leaf substitution is the staged path's (fused=False)" % who)
+
+
+def _puct_scratch(c, nb, S, dev, fused):
+    """a search's scratch for c observations: (tree, leaf boards, leaf dice, leaf actions, logits, value); fused: the tree alone"""
+    tree = torch.empty((c, nb), dtype=torch.uint8, device=dev)
+    if fused:
+        return (tree, None, None, None, None, None)
+    return (tree, torch.empty((c, S, S), dtype=torch.int8, device=dev), torch.empty(c, dtype=torch.int8, device=dev),
+            torch.empty((c, 2), dtype=torch.int8, device=dev), torch.empty((c, 5), dtype=torch.float32, device=dev),
+            torch.empty(c, dtype=torch.float32, device=dev))
+
+
+def puct_search(boards, dice, params, sims, c_puct=1.5, terminal_value=1.0, root_noise=None, noise_eps=0.25, rounds=None, cube_layer=3,
+                out=None):
+    """The whole PUCT search of M observations in one launch (ewn_puct_search) -> tree uint8 [M, tree_bytes]: byte for
+    byte what puct_begin and then `rounds` rounds of predict_policy on the leaf rows and puct_advance leave (the first round with
+    root_noise and noise_eps when root_noise is given: float32 [M, 2, 3] or [M, 6], puct_advance's).  rounds None: all sims + 1;
+    an integer: min(rounds, sims + 1), 0 is puct_begin alone.  puct_result, puct_play and puct_tree_views read the tree.  out: a
+    contiguous, 4-byte aligned uint8 tensor [M, tree_bytes] to write into (what it held does not matter).  predict_puct's argument
+    checks."""
+    who = "puct_search"
+    lib = _lib.load()
+    sims = _puct_numbers(who, sims, c_puct, terminal_value)
+    eps = 0.0 if root_noise is None else _noise_eps(who, noise_eps)
+    if rounds is not None and not (isinstance(rounds, (int, np.integer)) and int(rounds) >= 0):
+        raise ValueError("%s: rounds must be None or an integer that is not negative, got %r" % (who, rounds))
+    M, S, P = _lookahead_shape(who, boards, cube_layer)
+    L = int(cube_layer)
+    dev = _policy_params(who, params, P, S)
+    b = _policy_input("boards", boards, torch.int8, (M, S, S), dev, who=who)
+    d = _policy_input("dice", dice, torch.int8, (M,), dev, who=who)
+    rn = None if root_noise is None else _policy_input("root_noise", root_noise, torch.float32, (M, 6), dev, who=who)
+    _same_gpu(who, dev, "params", (("params", params), ("boards", b), ("dice", d), ("root_noise", rn)))
+    if out is None:
+        out = torch.empty((M, int(lib.ewn_puct_tree_bytes(S, L, sims))), dtype=torch.uint8, device=dev)
+    else:
+        Mt, _ = _puct_tree(who, out, S, sims, cube_layer)
+        if Mt != M or not (out.is_cuda and out.device == dev):
+            raise ValueError("%s: out must hold %d trees on %s, got %s" % (who, M, dev, _describe(out)))
+    with torch.cuda.device(dev):
+        check(lib.ewn_puct_search(S, L, M, sims, -1 if rounds is None else min(int(rounds), sims + 1), C.c_float(float(c_puct)),
+                                  C.c_float(float(terminal_value)), _ptr(b), _ptr(d), _ptr(params), _ptr(rn), C.c_float(eps), _ptr(out),
+                                  _stream()), "ewn_puct_search")
+    return out
+
+
+def _puct_search(lib, S, L, n, sims, b, d, params, cp, tv, table, scratch, st, noise=None, eps=0.0, fused=False):
     """predict_puct's and selfplay_puct's search of n observations on the caller's scratch: begin, then sims + 1 rounds of
-    ewn_predict_policy and advance.  noise (float32 [n, 6]): the first round, which evaluates the roots, is the noise instance's"""
+    ewn_predict_policy and advance.  noise (float32 [n, 6]): the first round, which evaluates the roots, is the noise instance's.
+    fused: the one launch of ewn_puct_search instead -- the same bytes in the tree; of the scratch only the tree is used"""
     tree, lb, ld, la, lg, lv = scratch
+    if fused:
+        check(lib.ewn_puct_search(S, L, n, sims, -1, cp, tv, _ptr(b), _ptr(d), _ptr(params), _ptr(noise), C.c_float(eps), _ptr(tree), st),
+              "ewn_puct_search")
+        return
     check(lib.ewn_puct_begin(S, L, n, sims, _ptr(b), _ptr(d), _ptr(tree), _ptr(lb), _ptr(ld), st), "ewn_puct_begin")
     for rnd in range(sims + 1):
         check(lib.ewn_predict_policy(S, L, n, _ptr(lb), _ptr(ld), _ptr(params), 1, C.c_uint64(0), None, None, _ptr(la), _ptr(lg),
@@ -1084,7 +1140,7 @@ def _puct_search(lib, S, L, n, sims, b, d, params, cp, tv, table, scratch, st, n
 
 
 def predict_puct(boards, dice, params, sims=64, c_puct=1.5, terminal_value=1.0, return_visits=False, return_q=False, return_value=False,
-                 cube_layer=3, chunk=1024, endgame_table=None):
+                 cube_layer=3, chunk=1024, endgame_table=None, fused=False):
     """What the trained actor-critic plays after a PUCT search of `sims` simulations on its own two heads: the policy
     head says where to look, the value head what a leaf is worth, a move that wins on the board is worth +1 and is played; the
     opponent's and the agent's later dice are chance nodes sampled in a fixed stratified order, so the search is deterministic.
@@ -1094,10 +1150,13 @@ def predict_puct(boards, dice, params, sims=64, c_puct=1.5, terminal_value=1.0, 
     ewn_predict_policy on the leaf rows and puct_advance, then puct_result, `chunk` observations at a time on scratch allocated once
     per call (a tree is 256 bytes per simulation at 5x5, 280 at 7x7).  predict_lookahead's argument checks.
     endgame_table (an EndgameTable of the boards' size on the same GPU): a pending leaf that the table covers is worth
-    terminal_value * max_a q_exact(leaf board, leaf dice) instead of the value head's output; the logits are the policy head's."""
+    terminal_value * max_a q_exact(leaf board, leaf dice) instead of the value head's output; the logits are the policy head's.
+    fused=True: each chunk's search is the one launch of ewn_puct_search -- the same trees byte for byte, so the same
+    results bit for bit, and no leaf-row scratch; not together with endgame_table (the exact leaves stay on the staged path)."""
     who = "predict_puct"
     lib = _lib.load()
     sims = _puct_numbers(who, sims, c_puct, terminal_value)
+    _fused_table(who, fused, endgame_table)
     if int(chunk) < 1:
         raise ValueError("%s: chunk must be at least 1, got %r" % (who, chunk))
     M, S, P = _lookahead_shape(who, boards, cube_layer)
@@ -1113,19 +1172,15 @@ def predict_puct(boards, dice, params, sims=64, c_puct=1.5, terminal_value=1.0, 
     val = torch.zeros(M, dtype=torch.float32, device=dev) if return_value else None
     c = max(1, min(int(chunk), M))
     nb = int(lib.ewn_puct_tree_bytes(S, L, sims))
-    tree = torch.empty((c, nb), dtype=torch.uint8, device=dev)
-    lb = torch.empty((c, S, S), dtype=torch.int8, device=dev)
-    ld = torch.empty(c, dtype=torch.int8, device=dev)
-    la = torch.empty((c, 2), dtype=torch.int8, device=dev)
-    lg = torch.empty((c, 5), dtype=torch.float32, device=dev)
-    lv = torch.empty(c, dtype=torch.float32, device=dev)
+    scratch = _puct_scratch(c, nb, S, dev, fused)
+    tree = scratch[0]
     cp, tv = C.c_float(float(c_puct)), C.c_float(float(terminal_value))
     with torch.cuda.device(dev):
         st = _stream()
         for i in range(0, M, c):
             n = min(c, M - i)
             sl = slice(i, i + n)
-            _puct_search(lib, S, L, n, sims, b[sl], d[sl], params, cp, tv, table, (tree, lb, ld, la, lg, lv), st)
+            _puct_search(lib, S, L, n, sims, b[sl], d[sl], params, cp, tv, table, scratch, st, fused=fused)
             check(lib.ewn_puct_result(S, L, n, _ptr(tree), _ptr(acts[sl]), _ptr(None if visits is None else visits[sl]),
                                       _ptr(None if q is None else q[sl]), _ptr(None if val is None else val[sl]), st), "ewn_puct_result")
     out = (acts,) + tuple(t for t in (visits, q, val) if t is not None)
@@ -1211,7 +1266,7 @@ def selfplay_noise(M, noise_alpha, key, game_offset, ply, device="cuda"):
 
 
 def selfplay_puct(boards, dice, params, sims=64, max_plies=None, c_puct=1.5, terminal_value=1.0, noise_eps=0.25, noise_alpha=1.0,
-                  temp_plies=8, key=0, game_offset=0, chunk=1024, check_every=8, endgame_table=None, cube_layer=3):
+                  temp_plies=8, key=0, game_offset=0, chunk=1024, check_every=8, endgame_table=None, cube_layer=3, fused=False):
     """M games of the PUCT search against itself, from the given positions to the end: per ply puct_begin, sims + 1
     rounds of ewn_predict_policy and advance -- the first with Dirichlet(noise_alpha) noise of weight noise_eps on the root's priors
     (ewn_puct_advance_noise) -- then ewn_puct_play into row t: the move is drawn in proportion to the visits for the first
@@ -1220,6 +1275,8 @@ def selfplay_puct(boards, dice, params, sims=64, max_plies=None, c_puct=1.5, ter
     plies one host read ends a chunk whose games are all over.  max_plies None: 80 on 5x5, 128 on 7x7 -- a move lowers the mover's
     summed distance to its corner by at least one, so a game lasts at most 69 / 117 plies.  noise_alpha = 1.0 is a choice (about 10
     over the number of moves, AlphaZero's rule of thumb), not a measurement.  endgame_table: predict_puct's, at the leaves.
+    fused=True: a ply's search is the one launch of ewn_puct_search, the records are the same bit for bit; not
+    together with endgame_table.
     The noise is torch._standard_gamma on a generator seeded from key, game_offset and the ply, drawn once per ply for all M games
     and read by each chunk's rows: a call repeats itself bit for bit, whatever the chunk.  Returns a dict: board int8 [T, M, S, S], dice int8
     [T, M], visits int32 [T, M, 2, 3], value float32 [T, M], action int8 [T, M, 2], live bool [T, M] (T = max_plies; rows past a
@@ -1227,6 +1284,7 @@ def selfplay_puct(boards, dice, params, sims=64, max_plies=None, c_puct=1.5, ter
     who = "selfplay_puct"
     lib = _lib.load()
     sims = _puct_numbers(who, sims, c_puct, terminal_value)
+    _fused_table(who, fused, endgame_table)
     eps = _noise_eps(who, noise_eps)
     temp_plies, key, game_offset = _play_numbers(who, temp_plies, key, game_offset)
     if not (math.isfinite(float(noise_alpha)) and float(noise_alpha) > 0.0):
@@ -1248,9 +1306,7 @@ def selfplay_puct(boards, dice, params, sims=64, max_plies=None, c_puct=1.5, ter
     game = torch.zeros((M, 4), dtype=torch.int32, device=dev)
     c = max(1, min(int(chunk), M))
     nb = int(lib.ewn_puct_tree_bytes(S, L, sims))
-    scratch = (torch.empty((c, nb), dtype=torch.uint8, device=dev), torch.empty((c, S, S), dtype=torch.int8, device=dev),
-               torch.empty(c, dtype=torch.int8, device=dev), torch.empty((c, 2), dtype=torch.int8, device=dev),
-               torch.empty((c, 5), dtype=torch.float32, device=dev), torch.empty(c, dtype=torch.float32, device=dev))
+    scratch = _puct_scratch(c, nb, S, dev, fused)
     cp, tv = C.c_float(float(c_puct)), C.c_float(float(terminal_value))
     with torch.cuda.device(dev):
         st = _stream()
@@ -1264,7 +1320,7 @@ def selfplay_puct(boards, dice, params, sims=64, max_plies=None, c_puct=1.5, ter
                     if t == len(drawn):                        # a ply's noise is drawn once, for all M games: later chunks read their rows
                         drawn.append(selfplay_noise(M, noise_alpha, key, game_offset, t, dev))
                     noise = drawn[t][i:i + n]
-                _puct_search(lib, S, L, n, sims, cb, cd, params, cp, tv, table, scratch, st, noise, eps)
+                _puct_search(lib, S, L, n, sims, cb, cd, params, cp, tv, table, scratch, st, noise, eps, fused)
                 check(lib.ewn_puct_play(S, L, n, _ptr(scratch[0]), _ptr(cb), _ptr(cd), _ptr(cg), temp_plies, C.c_uint64(key),
                                         C.c_int64(game_offset + i), *[_ptr(rec[name][t, i:i + n]) for name, _, _ in _PLAY_ROWS], st),
                       "ewn_puct_play")

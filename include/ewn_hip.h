@@ -631,6 +631,23 @@ int ewn_puct_play(int board_size, int cube_layer, int M, const void *tree, int8_
                   int8_t *rec_board, int8_t *rec_dice, int32_t *rec_visits, float *rec_value, int8_t *rec_action, int8_t *rec_live,
                   void *stream);
 
+/* ---- the PUCT search in one launch: the network inside the tree kernel ----
+ * When ewn_puct_search finishes, every byte of `tree` (M trees of ewn_puct_tree_bytes(S, L, sims) bytes, the layout above) equals
+ * what this sequence leaves there: ewn_puct_begin; then R rounds of ewn_predict_policy(deterministic = 1, logits, value) on the
+ * leaf rows, each followed by ewn_puct_advance -- round 0 by ewn_puct_advance_noise with these root_noise and noise_eps when
+ * root_noise != NULL.  R = sims + 1 when rounds < 0, min(rounds, sims + 1) otherwise; rounds == 0 is ewn_puct_begin alone.  No
+ * leaf row leaves the kernel; ewn_puct_result and ewn_puct_play read the finished tree as they read a staged one.  What `tree`
+ * held before the call does not matter.
+ * Refusals in ewn_puct_advance_noise's order, all before the launch: EWN_EINVAL for M < 0 or M > INT_MAX / 64; EWN_EUNSUPPORTED by
+ * geometry; EWN_OK without a launch for M == 0; EWN_ENULL for a missing boards, dice, params or tree; then EWN_EINVAL for sims
+ * outside 0 .. 4096, a tree that is not 4-byte aligned, a terminal_value that is not finite and positive, a c_puct that is not
+ * finite and non-negative and, only when root_noise is given, a noise_eps that is not finite or outside [0, 1].
+ * One kernel launch on `stream`, vector stores only, no atomics, no allocation, no synchronisation; byte offsets into `tree` are
+ * 64-bit.  How many trees share a block (EWN_PUCT_TILE = 1 .. 32 overrides the choice) changes no byte of the result. */
+int ewn_puct_search(int board_size, int cube_layer, int M, int sims, int rounds, float c_puct, float terminal_value,
+                    const int8_t *boards, const int8_t *dice, const float *params,
+                    const float *root_noise /* [M][6] or NULL */, float noise_eps, void *tree, void *stream);
+
 /* ---- the supervised update on M given observations: targets from outside (a search: expert iteration) ----
  * loss = (1/M) sum_m w_m (pi_coef CE_m + vf_coef (V_m - v*_m)^2),  CE_m = -sum_i p_i logsoftmax_head(i)(logits_m)_i, with
  * p = target_pi[m][0..4] (entries 0-1 the flag head, 2-4 the direction head; the caller makes each head's mass 1, or 0 to mask the
