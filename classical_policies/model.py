@@ -8,6 +8,17 @@ import numpy as np
 from classical_policies.base import PolicyBase, obs_arrays
 
 
+def _on_device(boards, dice, S, dev, other_size):
+    """boards (M,S,S), dice (M,) device or host arrays -> int8 tensors [M, S, S] and [M] on dev; other_size: the agent's sentence about
+    boards of another size, their shape left open"""
+    import torch
+    b = torch.as_tensor(np.asarray(boards) if not isinstance(boards, torch.Tensor) else boards)
+    d = torch.as_tensor(np.asarray(dice) if not isinstance(dice, torch.Tensor) else dice)
+    if b.numel() % (S * S) != 0 or b.shape[-1] != S:
+        raise ValueError(other_size % list(b.shape))
+    return b.to(dev).to(torch.int8).reshape(-1, S, S).contiguous(), d.to(dev).to(torch.int8).reshape(-1).contiguous()
+
+
 class ModelAgent(PolicyBase):
     def __init__(self, model_or_path, board_size=5, cube_layer=3, deterministic=True, key=0):
         """model_or_path: an a2c.ActorCritic, its flat fp32 parameter vector (ActorCritic.flat_parameters() order), or the path of a
@@ -35,14 +46,8 @@ class ModelAgent(PolicyBase):
         self.params = params.to("cuda").contiguous()
 
     def _on_device(self, boards, dice):
-        import torch
         S = self.board_size
-        b = torch.as_tensor(np.asarray(boards) if not isinstance(boards, torch.Tensor) else boards)
-        d = torch.as_tensor(np.asarray(dice) if not isinstance(dice, torch.Tensor) else dice)
-        if b.numel() % (S * S) != 0 or b.shape[-1] != S:
-            raise ValueError("ModelAgent: boards of shape %s, the model plays %dx%d" % (list(b.shape), S, S))
-        dev = self.params.device
-        return b.to(dev).to(torch.int8).reshape(-1, S, S).contiguous(), d.to(dev).to(torch.int8).reshape(-1).contiguous()
+        return _on_device(boards, dice, S, self.params.device, "ModelAgent: boards of shape %%s, the model plays %dx%d" % (S, S))
 
     def predict_batch(self, boards, dice, key=None, obs_id=None, return_logits=False, return_value=False):
         """boards (M,S,S), dice (M,) device or host arrays -> int8 (M,2) device tensor (with the logits / values if asked for).  A
@@ -66,17 +71,11 @@ class ModelAgent(PolicyBase):
 
 def _leaf_table(who, table, board_size):
     """endgame_table= of a searching agent: None, an EndgameTable, or the path of a saved one (loaded once), for the agent's boards"""
-    from ewn_gym_amd.endgame import EndgameTable
+    from ewn_gym_amd.endgame import EndgameTable, _accept_table
     if table is None:
         return None
-    if isinstance(table, (str, os.PathLike)):
-        table = EndgameTable.load(table)
-    if not isinstance(table, EndgameTable):
-        raise ValueError("%s: endgame_table must be an EndgameTable or the path of a saved one, got %s" % (who, type(table).__name__))
-    if table.board_size != board_size:
-        raise ValueError("%s: the table is for %dx%d boards, the agent plays %dx%d" % (who, table.board_size, table.board_size, board_size,
-                                                                                       board_size))
-    return table
+    return _accept_table(who, table, board_size, "the table is for %%dx%%d boards, the agent plays %dx%d" % (board_size, board_size),
+                         load=EndgameTable.load)
 
 
 class ValueSearchAgent(ModelAgent):
@@ -116,7 +115,7 @@ class PuctAgent(ModelAgent):
     4r) instead of 2 sims + 3: the same moves; not together with endgame_table."""
 
     def __init__(self, model_or_path, board_size=5, cube_layer=3, sims=64, c_puct=1.5, terminal_value=1.0, endgame_table=None, fused=False):
-        from ewn_gym_amd.vec_env import _fused_table, _puct_numbers
+        from ewn_gym_amd.search import _fused_table, _puct_numbers
         self.sims = _puct_numbers("PuctAgent", sims, c_puct, terminal_value)
         _fused_table("PuctAgent", fused, endgame_table)
         self.fused = bool(fused)
@@ -146,11 +145,8 @@ class EndgameAgent(PolicyBase):
 
     def __init__(self, table, fallback):
         import ewn_gym_amd
-        from ewn_gym_amd.endgame import EndgameTable
-        if isinstance(table, (str, os.PathLike)):
-            table = EndgameTable.load(table)
-        if not isinstance(table, EndgameTable):
-            raise ValueError("EndgameAgent: table must be an EndgameTable or the path of a saved one, got %s" % type(table).__name__)
+        from ewn_gym_amd.endgame import EndgameTable, _accept_table
+        table = _accept_table("EndgameAgent", table, None, None, name="table", load=EndgameTable.load)
         if not callable(getattr(fallback, "predict_batch", None)):
             raise ValueError("EndgameAgent: fallback must offer predict_batch(boards, dice), got %s" % type(fallback).__name__)
         fs = getattr(fallback, "board_size", table.board_size)
@@ -163,12 +159,8 @@ class EndgameAgent(PolicyBase):
     def predict_batch(self, boards, dice, return_covered=False):
         """boards (M,S,S), dice (M,) device or host arrays -> int8 (M,2) device tensor (and the bool (M,) covered mask if asked for)"""
         import torch
-        S, dev = self.board_size, self.table.table.device
-        b = torch.as_tensor(np.asarray(boards) if not isinstance(boards, torch.Tensor) else boards)
-        d = torch.as_tensor(np.asarray(dice) if not isinstance(dice, torch.Tensor) else dice)
-        if b.numel() % (S * S) != 0 or b.shape[-1] != S:
-            raise ValueError("EndgameAgent: boards of shape %s, the table is for %dx%d" % (list(b.shape), S, S))
-        b, d = b.to(dev).to(torch.int8).reshape(-1, S, S).contiguous(), d.to(dev).to(torch.int8).reshape(-1).contiguous()
+        S = self.board_size
+        b, d = _on_device(boards, dice, S, self.table.table.device, "EndgameAgent: boards of shape %%s, the table is for %dx%d" % (S, S))
         exact, covered = self.table.lookup(b, d)
         acts = torch.where(covered[:, None], exact, self.fallback.predict_batch(b, d).to(torch.int8))
         return (acts, covered) if return_covered else acts

@@ -4,10 +4,10 @@ Only what the hot path needs: csrc/ (HIP kernels + C ABI), the ctypes binding, a
 VecEWN (the batched engine the drop-in `envs` / `classical_policies` packages wrap).
 """
 from ._lib import EwnError, INFO_MESSAGES, LIB_PATH  # noqa: F401
-from .vec_env import (VecEWN, apply_action, evaluate, legal_actions, lookahead_expand, lookahead_reduce, lookahead_targets,  # noqa: F401
-                      playout_wins, predict_mcts, predict_lookahead, predict_minimax, predict_policy, predict_random, sup_grad,
-                      predict_puct, puct_advance, puct_begin, puct_result, puct_tree_views, puct_play, selfplay_noise, selfplay_outcomes,
-                      selfplay_puct, puct_search)
+from .vec_env import VecEWN, apply_action, evaluate, legal_actions, playout_wins, predict_mcts, predict_minimax, predict_random  # noqa: F401
+from .search import (lookahead_expand, lookahead_reduce, lookahead_targets, predict_lookahead, predict_policy, sup_grad,  # noqa: F401
+                     predict_puct, puct_advance, puct_begin, puct_result, puct_tree_views, puct_play, selfplay_noise, selfplay_outcomes,
+                     selfplay_puct, puct_search)
 from .endgame import EndgameTable  # noqa: F401
 
 __all__ = ["VecEWN", "EwnError", "INFO_MESSAGES", "legal_actions", "apply_action", "playout_wins", "evaluate", "predict_minimax", "predict_random",

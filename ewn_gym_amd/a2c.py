@@ -22,6 +22,8 @@ import math
 import torch
 import torch.nn as nn
 
+from ._args import _ptr, _stream
+
 
 class _SplitKLinearFn(torch.autograd.Function):
     """y = x W^T + b whose weight gradient dW = dy^T x is computed as P partial products over slices of the batch.
@@ -468,7 +470,6 @@ class FusedA2CTrainer(FusedTrainer):
 
     def _launch(self):
         from ._lib import check
-        from .vec_env import _ptr, _stream
         env = self.env
         env.rollout_policy(self.n_steps, self.params, traj=self.traj, noise_key=self.noise_key, **self._opponent_kwargs())
         check(self.lib.ewn_a2c_grad(C.byref(env.cfg), self.n_steps, _ptr(self.traj["record"]), _ptr(self.traj["reward"]), _ptr(self.params),

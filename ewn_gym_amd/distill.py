@@ -14,9 +14,16 @@ trained toward the root's visit distribution (puct_targets), the critic toward t
 """
 import ctypes as C
 
+import numpy as np
 import torch
 
+from . import _lib
+from ._args import _finite, _not_negative, _positive, _ptr, _stream
+from ._lib import check
 from .a2c import FusedTrainer
+from .endgame import EndgameTable, _accept_table
+from .search import (SELFPLAY_MAX_PLIES, _noise_eps, _play_numbers, _puct_numbers, lookahead_targets, predict_lookahead, predict_puct,
+                     selfplay_puct, sup_grad)
 from .sharding import all_reduce_counters
 
 
@@ -41,7 +48,64 @@ def puct_targets(visits, q, value, terminal_value=1.0, one_cube=None):
     return target_pi.contiguous(), target_value.contiguous(), live.to(torch.float32)
 
 
-class SearchDistillTrainer(FusedTrainer):
+class _SupervisedTrainer(FusedTrainer):
+    """What the trainers on ewn_sup_grad share: the checks of the loss coefficients and of the endgame table, the optimiser's state
+    and the gradient's scratch, the update on given rows and targets, and the statistics and checkpoint keys that both have.  A
+    subclass's `_launch` collects its rows and targets and ends in `_update`."""
+
+    def __init__(self, who, env, *, sims, c_puct, terminal_value, fused, pi_coef, vf_coef, endgame_table, learning_rate, max_grad_norm,
+                 rms_alpha, rms_eps, **trainer):
+        """who: the subclass, as its errors name it; an endgame_table that is not an EndgameTable is the path of one and is loaded
+        onto the env's GPU; trainer: FusedTrainer's arguments after env.  The subclass then calls _size_scratch"""
+        self.pi_coef, self.vf_coef = _not_negative(who, "pi_coef", pi_coef), _not_negative(who, "vf_coef", vf_coef)
+        if endgame_table is not None:
+            if not isinstance(endgame_table, EndgameTable):
+                endgame_table = EndgameTable.load(endgame_table, device=env.board.device)
+            _accept_table(who, endgame_table, env.S, "the endgame table is for %%dx%%d boards, the env plays %dx%d" % (env.S, env.S))
+        self.endgame_table = endgame_table
+        super().__init__(env, **trainer)
+        self.sq_avg = torch.zeros_like(self.params)
+        self.sims, self.c_puct, self.terminal_value, self.fused = int(sims), float(c_puct), float(terminal_value), bool(fused)
+        # the optimiser step is ewn_a2c_apply: of this struct it reads max_grad_norm, learning_rate, rms_alpha, rms_eps, world_size
+        self.hyper = _lib.EwnA2cHyper(0.0, float(vf_coef), 0.0, float(max_grad_norm), float(learning_rate), float(rms_alpha), float(rms_eps),
+                                      int(self.world))
+
+    def _size_scratch(self, rows):
+        """rows: the observations per lane of one update; they size ewn_sup_grad's scratch and are live_fraction's denominator"""
+        self._rows = rows
+        nscr = check(self.lib.ewn_sup_scratch_bytes(self.env.S, self.env.L, rows * self.env.N), "ewn_sup_scratch_bytes")
+        self.scratch = torch.zeros(int(nscr), dtype=torch.uint8, device=self.device)
+
+    def _update(self, boards, dice, target_pi, target_value, weight):
+        """ewn_sup_grad on the rows -> [all-reduce of the flat gradient] -> ewn_a2c_apply"""
+        env = self.env
+        sup_grad(boards, dice, target_pi, target_value, self.params, weight=weight, pi_coef=self.pi_coef, vf_coef=self.vf_coef,
+                 cube_layer=env.L, out=self.grad, scratch=self.scratch)
+        self._all_reduce_grad()
+        check(self.lib.ewn_a2c_apply(C.byref(env.cfg), _ptr(self.params), _ptr(self.sq_avg), _ptr(self.grad), C.byref(self.hyper),
+                                     _ptr(self.grad_norm), _stream()), "ewn_a2c_apply")
+
+    def stats_dict(self):
+        g = self.grad[-8:].tolist()
+        live = g[3]
+        per = (lambda x: x / live) if live > 0 else (lambda x: 0.0)
+        pl, vl, en = per(g[0]), per(g[4]), per(g[1])
+        return {"loss": self.pi_coef * pl + self.vf_coef * vl, "policy_loss": pl, "value_loss": vl, "entropy": en, "agreement": per(g[2]),
+                "grad_norm": float(self.grad_norm), "live_fraction": live / float(self._rows * self.env.N * self.world)}
+
+    def _state(self):
+        return {"sq_avg": self.sq_avg, "terminal_value": float(self.terminal_value), "sims": int(self.sims), "c_puct": float(self.c_puct),
+                "fused_search": bool(self.fused)}
+
+    def _load_state(self, sd):
+        """the keys of _state; a subclass then withdraws `fused` where what it was built with does not allow it"""
+        self.sq_avg.copy_(sd["sq_avg"])
+        self.terminal_value = float(sd.get("terminal_value", self.terminal_value))
+        self.sims, self.c_puct = int(sd.get("sims", self.sims)), float(sd.get("c_puct", self.c_puct))
+        self.fused = bool(sd.get("fused_search", self.fused))
+
+
+class SearchDistillTrainer(_SupervisedTrainer):
     """a2c.FusedTrainer (flat `params` viewed by `self.model`, collect_and_update, learn, policy_fn, save / load) with the supervised
     search-distillation update, which runs torch operators and allocates: it stays eager, never a captured graph.  The env's rewards
     are not read: the rollout only supplies the state distribution, so the plain or the shaped env serves, against any opponent the
@@ -53,56 +117,38 @@ class SearchDistillTrainer(FusedTrainer):
     def __init__(self, env, n_steps=5, learning_rate=7e-4, pi_coef=1.0, vf_coef=0.5, temperature=0.0, plies=1, terminal_value=1.0,
                  max_grad_norm=0.5, rms_alpha=0.99, rms_eps=1e-5, seed=None, opponent=None, opponent_update_every=100,
                  opponent_deterministic=False, endgame_table=None, search="lookahead", sims=64, c_puct=1.5, endgame_leaves=False, fused=False):
-        import math
-        from . import _lib
+        who = "SearchDistillTrainer"
         if search not in ("lookahead", "puct"):
             raise ValueError("SearchDistillTrainer: search must be 'lookahead' or 'puct', got %r" % (search,))
         if plies not in (1, 2):
             raise ValueError("SearchDistillTrainer: plies must be 1 or 2, got %r" % (plies,))
         if search == "puct":
-            from .vec_env import _puct_numbers
-            _puct_numbers("SearchDistillTrainer", sims, c_puct, terminal_value)
-        for name, v in (("pi_coef", pi_coef), ("vf_coef", vf_coef), ("temperature", temperature)):
-            if not math.isfinite(float(v)) or float(v) < 0.0:
-                raise ValueError("SearchDistillTrainer: %s must be finite and not negative, got %r" % (name, v))
-        if not math.isfinite(float(terminal_value)):
-            raise ValueError("SearchDistillTrainer: terminal_value must be finite, got %r" % (terminal_value,))
+            _puct_numbers(who, sims, c_puct, terminal_value)
+        self.temperature = _not_negative(who, "temperature", temperature)
+        _finite(who, "terminal_value", terminal_value)
         if endgame_leaves and endgame_table is None:
             raise ValueError("SearchDistillTrainer: endgame_leaves=True needs an endgame_table")
         if fused and search != "puct":
             raise ValueError("SearchDistillTrainer: fused=True is the PUCT search in one launch: it needs search='puct'")
         if fused and endgame_leaves:
             raise ValueError("SearchDistillTrainer: fused=True does not take endgame_leaves=True: the exact leaves are the staged path's")
-        if endgame_table is not None:
-            from .endgame import EndgameTable
-            if not float(terminal_value) > 0.0:
-                raise ValueError("SearchDistillTrainer: with an endgame table terminal_value must be positive (it scales the exact q), "
-                                 "got %r" % (terminal_value,))
-            if not isinstance(endgame_table, EndgameTable):
-                endgame_table = EndgameTable.load(endgame_table, device=env.board.device)
-            if endgame_table.board_size != env.S:
-                raise ValueError("SearchDistillTrainer: the endgame table is for %dx%d boards, the env plays %dx%d" % (
-                    endgame_table.board_size, endgame_table.board_size, env.S, env.S))
-        self.endgame_table = endgame_table   # None: the search's q alone; else its q is replaced by the exact one on covered rows
+        if endgame_table is not None and not float(terminal_value) > 0.0:
+            raise ValueError("SearchDistillTrainer: with an endgame table terminal_value must be positive (it scales the exact q), "
+                             "got %r" % (terminal_value,))
+        # endgame_table None: the search's q alone; else its q is replaced by the exact one on covered rows
+        # fused: the PUCT search as the one launch of ewn_puct_search (4r): the same targets bit for bit
+        super().__init__(who, env, sims=sims, c_puct=c_puct, terminal_value=terminal_value, fused=fused, pi_coef=pi_coef, vf_coef=vf_coef,
+                         endgame_table=endgame_table, learning_rate=learning_rate, max_grad_norm=max_grad_norm, rms_alpha=rms_alpha,
+                         rms_eps=rms_eps, n_steps=n_steps, seed=seed, use_graph=False, opponent=opponent,
+                         opponent_update_every=opponent_update_every, opponent_deterministic=opponent_deterministic)
+        self._size_scratch(self.n_steps)
         self.endgame_leaves = bool(endgame_leaves)   # the search itself takes the table: exact values at the leaves it covers (4p)
-        super().__init__(env, n_steps, seed, False, opponent, opponent_update_every, opponent_deterministic)
-        self.sq_avg = torch.zeros_like(self.params)
-        self.pi_coef, self.vf_coef, self.temperature = float(pi_coef), float(vf_coef), float(temperature)
-        self.plies, self.terminal_value = int(plies), float(terminal_value)
-        self.search, self.sims, self.c_puct = search, int(sims), float(c_puct)
-        self.fused = bool(fused)             # the PUCT search as the one launch of ewn_puct_search (4r): the same targets bit for bit
-        # the optimiser step is ewn_a2c_apply: of this struct it reads max_grad_norm, learning_rate, rms_alpha, rms_eps, world_size
-        self.hyper = _lib.EwnA2cHyper(0.0, float(vf_coef), 0.0, float(max_grad_norm), float(learning_rate), float(rms_alpha), float(rms_eps),
-                                      int(self.world))
+        self.plies, self.search = int(plies), search
         M, S = self.n_steps * env.N, env.S
-        nscr = _lib.check(self.lib.ewn_sup_scratch_bytes(S, env.L, M), "ewn_sup_scratch_bytes")
-        self.scratch = torch.zeros(int(nscr), dtype=torch.uint8, device=self.device)
         self._boards = torch.zeros((M, S, S), dtype=torch.int8, device=self.device)      # rows 0 .. n_steps - 1 of the observations, packed
         self._dice = torch.zeros(M, dtype=torch.int8, device=self.device)
 
     def _launch(self):
-        from ._lib import check
-        from .vec_env import _ptr, _stream, lookahead_targets, predict_lookahead, predict_puct, sup_grad
         env, K, N, S = self.env, self.n_steps, self.env.N, self.env.S
         leaves = {"endgame_table": self.endgame_table} if self.endgame_leaves else {}   # nothing: the calls as they were
         env.rollout_policy(K, self.params, traj=self.traj, noise_key=self.noise_key, **self._opponent_kwargs())
@@ -125,31 +171,16 @@ class SearchDistillTrainer(FusedTrainer):
                 _, covered, q_exact = self.endgame_table.lookup(self._boards, self._dice, return_q=True)
                 q = torch.where(covered[:, None, None], self.terminal_value * q_exact, q)
             target_pi, target_value, weight = lookahead_targets(q, self.temperature)
-        sup_grad(self._boards, self._dice, target_pi, target_value, self.params, weight=weight, pi_coef=self.pi_coef, vf_coef=self.vf_coef,
-                 cube_layer=env.L, out=self.grad, scratch=self.scratch)
-        self._all_reduce_grad()
-        check(self.lib.ewn_a2c_apply(C.byref(env.cfg), _ptr(self.params), _ptr(self.sq_avg), _ptr(self.grad), C.byref(self.hyper),
-                                     _ptr(self.grad_norm), _stream()), "ewn_a2c_apply")
-
-    def stats_dict(self):
-        g = self.grad[-8:].tolist()
-        live = g[3]
-        per = (lambda x: x / live) if live > 0 else (lambda x: 0.0)
-        pl, vl, en = per(g[0]), per(g[4]), per(g[1])
-        return {"loss": self.pi_coef * pl + self.vf_coef * vl, "policy_loss": pl, "value_loss": vl, "entropy": en, "agreement": per(g[2]),
-                "grad_norm": float(self.grad_norm), "live_fraction": live / float(self.n_steps * self.env.N * self.world)}
+        self._update(self._boards, self._dice, target_pi, target_value, weight)
 
     def _state(self):
-        return {"sq_avg": self.sq_avg, "terminal_value": float(self.terminal_value), "plies": int(self.plies), "search": self.search,
-                "sims": int(self.sims), "c_puct": float(self.c_puct), "fused_search": bool(self.fused)}
+        return {**super()._state(), "plies": int(self.plies), "search": self.search}
 
     def _load_state(self, sd):
-        self.sq_avg.copy_(sd["sq_avg"])
-        self.terminal_value = float(sd.get("terminal_value", self.terminal_value))
+        super()._load_state(sd)
         self.plies = int(sd.get("plies", self.plies))
         self.search = sd.get("search", self.search)
-        self.sims, self.c_puct = int(sd.get("sims", self.sims)), float(sd.get("c_puct", self.c_puct))
-        self.fused = bool(sd.get("fused_search", self.fused)) and self.search == "puct" and not self.endgame_leaves
+        self.fused = self.fused and self.search == "puct" and not self.endgame_leaves
 
 
 def both_flags_one_cube(boards, dice):
@@ -162,7 +193,7 @@ def both_flags_one_cube(boards, dice):
     return present.gather(1, d[:, None] - 1)[:, 0] | ~(present & (k > d[:, None])).any(1) | ~(present & (k < d[:, None])).any(1)
 
 
-class PuctSelfPlayTrainer(FusedTrainer):
+class PuctSelfPlayTrainer(_SupervisedTrainer):
     """AlphaZero's loop on the PUCT search: the search plays itself from fresh openings on the env's lanes
     (selfplay_puct: root noise, moves drawn from the visits for the first temp_plies plies), the policy heads are trained toward the
     roots' visit distributions and the critic toward terminal_value times the result of the game seen from the side to move.  Rows
@@ -176,49 +207,32 @@ class PuctSelfPlayTrainer(FusedTrainer):
     def __init__(self, env, sims=64, c_puct=1.5, terminal_value=1.0, noise_eps=0.25, noise_alpha=1.0, temp_plies=8, max_plies=None,
                  learning_rate=7e-4, pi_coef=1.0, vf_coef=0.5, max_grad_norm=0.5, rms_alpha=0.99, rms_eps=1e-5, seed=None,
                  endgame_table=None, chunk=1024, fused=False):
-        import math
-        from . import _lib
-        from .vec_env import SELFPLAY_MAX_PLIES, _noise_eps, _play_numbers, _puct_numbers
         who = "PuctSelfPlayTrainer"
         _puct_numbers(who, sims, c_puct, terminal_value)
         _noise_eps(who, noise_eps)
         _play_numbers(who, temp_plies, 0, 0)
-        if not (math.isfinite(float(noise_alpha)) and float(noise_alpha) > 0.0):
-            raise ValueError("%s: noise_alpha must be finite and positive, got %r" % (who, noise_alpha))
-        for name, v in (("pi_coef", pi_coef), ("vf_coef", vf_coef)):
-            if not math.isfinite(float(v)) or float(v) < 0.0:
-                raise ValueError("%s: %s must be finite and not negative, got %r" % (who, name, v))
+        _positive(who, "noise_alpha", noise_alpha)
         if max_plies is not None and not (isinstance(max_plies, int) and max_plies >= 1):
             raise ValueError("%s: max_plies must be a positive integer or None, got %r" % (who, max_plies))
         if fused and endgame_table is not None:
             raise ValueError("%s: fused=True does not take an endgame_table: the exact-leaf substitution is the staged path's" % who)
-        if endgame_table is not None:
-            from .endgame import EndgameTable
-            if not isinstance(endgame_table, EndgameTable):
-                endgame_table = EndgameTable.load(endgame_table, device=env.board.device)
-            if endgame_table.board_size != env.S:
-                raise ValueError("%s: the endgame table is for %dx%d boards, the env plays %dx%d" % (
-                    who, endgame_table.board_size, endgame_table.board_size, env.S, env.S))
-        self.endgame_table = endgame_table       # exact values at the leaves the table covers (4p), nothing else
-        super().__init__(env, 1, seed, False, None, 100, False, policy_rollout=False)
-        self.sq_avg = torch.zeros_like(self.params)
-        self.sims, self.c_puct, self.terminal_value = int(sims), float(c_puct), float(terminal_value)
-        self.noise_eps, self.noise_alpha, self.temp_plies = float(noise_eps), float(noise_alpha), int(temp_plies)
+        # endgame_table: exact values at the leaves the table covers (4p), nothing else
+        # fused: a ply's search as the one launch of ewn_puct_search (4r): the same records bit for bit
+        super().__init__(who, env, sims=sims, c_puct=c_puct, terminal_value=terminal_value, fused=fused, pi_coef=pi_coef, vf_coef=vf_coef,
+                         endgame_table=endgame_table, learning_rate=learning_rate, max_grad_norm=max_grad_norm, rms_alpha=rms_alpha,
+                         rms_eps=rms_eps, n_steps=1, seed=seed, use_graph=False, opponent=None, opponent_update_every=100,
+                         opponent_deterministic=False, policy_rollout=False)
         self.max_plies = SELFPLAY_MAX_PLIES[env.S] if max_plies is None else int(max_plies)
-        self.pi_coef, self.vf_coef, self.chunk = float(pi_coef), float(vf_coef), int(chunk)
-        self.fused = bool(fused)                 # a ply's search as the one launch of ewn_puct_search (4r): the same records bit for bit
+        self._size_scratch(self.max_plies)
+        self.noise_eps, self.noise_alpha, self.temp_plies = float(noise_eps), float(noise_alpha), int(temp_plies)
+        self.chunk = int(chunk)
         self.seed_base, self.seed_counter = (0 if seed is None else int(seed)), 0   # the counter: one per update, saved and resumed
-        self.hyper = _lib.EwnA2cHyper(0.0, float(vf_coef), 0.0, float(max_grad_norm), float(learning_rate), float(rms_alpha), float(rms_eps),
-                                      int(self.world))
-        nscr = _lib.check(self.lib.ewn_sup_scratch_bytes(env.S, env.L, self.max_plies * env.N), "ewn_sup_scratch_bytes")
-        self.scratch = torch.zeros(int(nscr), dtype=torch.uint8, device=self.device)
         self.records = None                      # the last update's games (selfplay_puct's dict)
         self._games = [0.0, 0.0, 0.0, 0.0]       # live rows, mean plies, share of finished games, the first mover's share of them
 
     def fresh_positions(self):
         """the lanes reset on seeds no rank and no earlier update has used: counter x all lanes + the global lane id -> (board, dice,
         the first lane's global game number)"""
-        import numpy as np
         env = self.env
         first = self.seed_counter * env.N * self.world + int(env.cfg.lane_offset)
         seeds = (self.seed_base + first + np.arange(env.N, dtype=np.uint64)) & np.uint64(0xFFFFFFFF)
@@ -227,8 +241,6 @@ class PuctSelfPlayTrainer(FusedTrainer):
         return board, dice, first
 
     def _launch(self):
-        from ._lib import check
-        from .vec_env import _ptr, _stream, selfplay_puct, sup_grad
         env = self.env
         board, dice, first = self.fresh_positions()
         rec = selfplay_puct(board, dice, self.params, sims=self.sims, max_plies=self.max_plies, c_puct=self.c_puct,
@@ -241,11 +253,7 @@ class PuctSelfPlayTrainer(FusedTrainer):
         target_pi, _, _ = puct_targets(rec["visits"].reshape(R, 2, 3), None, rec["value"].reshape(R), self.terminal_value,
                                        one_cube=both_flags_one_cube(b, d))
         target_value = (self.terminal_value * rec["z"]).reshape(R).contiguous()
-        sup_grad(b, d, target_pi, target_value, self.params, weight=rec["weight"].reshape(R), pi_coef=self.pi_coef, vf_coef=self.vf_coef,
-                 cube_layer=env.L, out=self.grad, scratch=self.scratch)
-        self._all_reduce_grad()
-        check(self.lib.ewn_a2c_apply(C.byref(env.cfg), _ptr(self.params), _ptr(self.sq_avg), _ptr(self.grad), C.byref(self.hyper),
-                                     _ptr(self.grad_norm), _stream()), "ewn_a2c_apply")
+        self._update(b, d, target_pi, target_value, rec["weight"].reshape(R))
 
     def collect_and_update(self):
         self._launch()
@@ -261,26 +269,18 @@ class PuctSelfPlayTrainer(FusedTrainer):
         return self.grad
 
     def stats_dict(self):
-        g = self.grad[-8:].tolist()
-        live = g[3]
-        per = (lambda x: x / live) if live > 0 else (lambda x: 0.0)
-        pl, vl, en = per(g[0]), per(g[4]), per(g[1])
-        return {"loss": self.pi_coef * pl + self.vf_coef * vl, "policy_loss": pl, "value_loss": vl, "entropy": en, "agreement": per(g[2]),
-                "grad_norm": float(self.grad_norm), "live_fraction": live / float(self.max_plies * self.env.N * self.world),
-                "mean_game_length": self._games[1], "finished_fraction": self._games[2], "first_mover_win_fraction": self._games[3]}
+        return {**super().stats_dict(), "mean_game_length": self._games[1], "finished_fraction": self._games[2],
+                "first_mover_win_fraction": self._games[3]}
 
     def _state(self):
-        return {"sq_avg": self.sq_avg, "terminal_value": float(self.terminal_value), "sims": int(self.sims), "c_puct": float(self.c_puct),
-                "noise_eps": float(self.noise_eps), "noise_alpha": float(self.noise_alpha), "temp_plies": int(self.temp_plies),
-                "max_plies": int(self.max_plies), "seed_counter": int(self.seed_counter), "fused_search": bool(self.fused)}
+        return {**super()._state(), "noise_eps": float(self.noise_eps), "noise_alpha": float(self.noise_alpha),
+                "temp_plies": int(self.temp_plies), "max_plies": int(self.max_plies), "seed_counter": int(self.seed_counter)}
 
     def _load_state(self, sd):
-        self.sq_avg.copy_(sd["sq_avg"])
-        self.terminal_value = float(sd.get("terminal_value", self.terminal_value))
-        self.sims, self.c_puct = int(sd.get("sims", self.sims)), float(sd.get("c_puct", self.c_puct))
+        super()._load_state(sd)
         self.noise_eps, self.noise_alpha = float(sd.get("noise_eps", self.noise_eps)), float(sd.get("noise_alpha", self.noise_alpha))
         self.temp_plies, self.seed_counter = int(sd.get("temp_plies", self.temp_plies)), int(sd.get("seed_counter", self.seed_counter))
-        self.fused = bool(sd.get("fused_search", self.fused)) and self.endgame_table is None
+        self.fused = self.fused and self.endgame_table is None
         if int(sd.get("max_plies", self.max_plies)) != self.max_plies:
             raise ValueError("the checkpoint's games have at most %d plies, this trainer's %d: the update's scratch is sized by it" % (
                 int(sd["max_plies"]), self.max_plies))

@@ -13,7 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .vec_env import _describe, _lookahead_shape, _policy_input, _ptr, _require_gpu, _same_gpu, _stream
+from ._args import _describe, _lookahead_shape, _policy_input, _ptr, _require_gpu, _same_gpu, _stream
 
 
 class EndgameTable:
@@ -107,3 +107,17 @@ class EndgameTable:
         if sd["endgame_layout"] != cls.LAYOUT:
             raise ValueError("%s holds table layout %r, this library reads layout %d: build it again" % (path, sd["endgame_layout"], cls.LAYOUT))
         return cls(sd["board_size"], sd["max_cubes"], sd["max_total"], sd["table"].contiguous())
+
+
+def _accept_table(who, table, board_size, other_size, name="endgame_table", load=None):
+    """The endgame table that a caller was given as its argument `name`: an EndgameTable, or -- where the caller says how it loads
+    one, load(path) -- the path of a saved one.  board_size: what the caller plays (None: any); other_size: its own sentence about a
+    table of another size, the table's size left open twice.  -> the table, else ValueError"""
+    if load is not None and isinstance(table, (str, os.PathLike)):
+        table = load(table)
+    if not isinstance(table, EndgameTable):
+        raise ValueError("%s: %s must be an EndgameTable%s, got %s" % (who, name, "" if load is None else " or the path of a saved one",
+                                                                       type(table).__name__))
+    if board_size is not None and table.board_size != board_size:
+        raise ValueError("%s: %s" % (who, other_size % (table.board_size, table.board_size)))
+    return table

@@ -24,6 +24,7 @@ import ctypes as C
 import torch
 import torch.nn as nn
 
+from ._args import _ptr, _stream
 from .a2c import A2CTrainer, FusedTrainer, all_reduce_gradients, n_step_returns
 
 
@@ -127,7 +128,6 @@ class FusedPPOTrainer(FusedTrainer):
 
     def _launch(self):
         from ._lib import check
-        from .vec_env import _ptr, _stream
         env, lib = self.env, self.lib
         K, total, B = self.n_steps, self.n_steps * env.N, self.batch_size
         cfg, hp = C.byref(env.cfg), C.byref(self.hyper)

@@ -12,7 +12,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import ewn_gym_amd as ea  # noqa: E402
 from ewn_gym_amd._lib import EwnA2cHyper, check  # noqa: E402
-from ewn_gym_amd.vec_env import _ptr, _stream  # noqa: E402
+from ewn_gym_amd._args import _ptr, _stream  # noqa: E402
 from tests.test_gpu_policy import make_model  # noqa: E402
 from ewn_gym_amd.a2c import n_step_returns  # noqa: E402
 

@@ -27,7 +27,7 @@ from ewn_gym_amd._lib import EwnA2cHyper, check  # noqa: E402
 from ewn_gym_amd.a2c import FusedA2CTrainer  # noqa: E402
 from ewn_gym_amd.distill import SearchDistillTrainer  # noqa: E402
 from ewn_gym_amd.tournament import evaluate  # noqa: E402
-from ewn_gym_amd.vec_env import _ptr, _stream  # noqa: E402
+from ewn_gym_amd._args import _ptr, _stream  # noqa: E402
 from tools.predict_policy_time import timed  # noqa: E402
 
 

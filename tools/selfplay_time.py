@@ -28,7 +28,8 @@ import ewn_gym_amd as ea  # noqa: E402
 from ewn_gym_amd.a2c import ActorCritic  # noqa: E402
 from ewn_gym_amd.distill import PuctSelfPlayTrainer  # noqa: E402
 from ewn_gym_amd.tournament import evaluate  # noqa: E402
-from ewn_gym_amd.vec_env import _ptr, _puct_search, _stream  # noqa: E402
+from ewn_gym_amd._args import _ptr, _stream  # noqa: E402
+from ewn_gym_amd.search import _puct_search  # noqa: E402
 from tools.distill_time import make_env  # noqa: E402
 
 
