@@ -436,7 +436,10 @@ EWN_DEV void philox4x32_10_pair(u32 c0, u32 c1, u32 c2, u32 c3, u32 k0, u32 k1, 
     for (int r = 0; r < 10; r++) {
         const u32 k = (r & 1) ? kO : kE, m = (r & 1) ? mO : mE;
         const u32 send = y ^ k;
-        const u32 h = __umulhi(m, x), l = m * x;
+        // both halves of the product from ONE 64-bit multiply (v_mad_u64_u32): it issues at the cost of one v_mul_lo_u32 or
+        // v_mul_hi_u32, not of the two it replaces (tools/valu_probe.hip, profiles/r07/valu_probe.json)
+        const u64 p = (u64)m * x;
+        const u32 h = (u32)(p >> 32), l = (u32)p;
         x = h ^ (u32)__builtin_amdgcn_update_dpp(0, (int)send, 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true);
         y = l;
         if (r & 1) kO += wO; else kE += wE;

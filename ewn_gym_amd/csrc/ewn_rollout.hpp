@@ -478,13 +478,14 @@ __global__ __launch_bounds__(D3_BS, (OPP == 2 ? 2 : 1)) void k_rollout_slots(Rol
     int term = 0, trunc = 0, info = EWN_INFO_NONE, aflag = 0, adir = 0, oflag = 0, odir = 0;
     u32 omove = 0;                                  // OPP 0: the opponent's move as d3_search returns it (bmove)
     bool reply = false;
+    const int klim = live ? c.K : 0;                // steps this lane plays: `pending` below is then one compare, straight into the ballot
 #ifdef EWN_ROLLOUT_STAMPS
     unsigned long long st_acc[6] = { 0, 0, 0, 0, 0, 0 }, st_prev;   // [4] counts the iterations
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_prev) :: "memory");
     const unsigned long long st_begin = st_prev;
 #endif
     while (true) {
-        const bool pending = live && kdone < c.K;
+        const bool pending = kdone < klim;
         if (__builtin_amdgcn_ballot_w64(pending) == 0) break; // this wave's games have all played K steps
         const bool start = pending && phase == 0;
         const bool active = start && !frozen;

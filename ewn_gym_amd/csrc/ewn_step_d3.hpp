@@ -285,7 +285,11 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
     const M one = 1;
 
     // root slots: <= 2 cubes x 3 dirs in the reference's list order (envs/ewn.py:338-375)
-    const u32 rsel = pk_sel<S>(Tb, c.posP, dice), rpp = pk_pair(c.posP, rsel);
+    const u32 rsel_all = pk_sel<S>(Tb, c.posP, dice), rpp_all = pk_pair(c.posP, rsel_all);
+    // PERLANE: the call's own cube is selected FIRST, by shifting the selector and the pair word down by 8 * slotL, so that its fields
+    // are extracted once and "slot 0" below is that cube (a sel entry has 16 bits: the second cube's `larger` flag reads 0 by itself).
+    // The shallow depths search both cubes in their one call: slotL is 0 there.
+    const u32 rsel = PERLANE ? rsel_all >> (8 * slotL) : rsel_all, rpp = PERLANE ? rpp_all >> (8 * slotL) : rpp_all;
     const int rb0 = (int)(rpp & 0xFFu), rb1 = (int)(rpp >> 8);
     const bool have0 = !(rb0 & PK_OFF), have1 = !(rb1 & PK_OFF);
     const int flag0 = (int)(rsel >> 15);
@@ -296,7 +300,7 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
 
     double best = -__builtin_inf(); // alpha = max(alpha, best_val): the running best (root beta stays +inf)
     if constexpr (PERLANE) {
-        *have_second = have1;
+        *have_second = !(rpp_all & ((u32)PK_OFF << 8));
         if (slotL == 0) { bflag = 0; bdir = 0; } else best = best_in;
         if (bmove && slotL != 0) bm = *bmove;
     } else { bflag = 0; bdir = 0; }
@@ -344,24 +348,24 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
         for (int d = 0; d < 3; d++) {
             const u32 kf = Tb->rkf[d][rb];
             rset[i][d] = Tb->rsetT[d][rb];
-            keep[i][d] = kf & 0xFFFFu;    // rank addresses stay below 2^13
+            keep[i][d] = kf;              // its low half is the mask: rank addresses stay below 2^13, so the high half ANDs with zeros
             fixed[i][d] = kf >> 16;
         }
     }
 
     // the six root destinations, read before the loop: inside it the read's whole latency stood in front of every root
     const u32 dq0 = (u32)Tb->nbp[0][rp0] | ((u32)Tb->nbp[1][rp0] << 8) | ((u32)Tb->nbp[2][rp0] << 16);
-    const u32 dq1 = (u32)Tb->nbp[0][rp1] | ((u32)Tb->nbp[1][rp1] << 8) | ((u32)Tb->nbp[2][rp1] << 16);
+    [[maybe_unused]] u32 dq1 = 0;
+    if constexpr (!PERLANE) dq1 = (u32)Tb->nbp[0][rp1] | ((u32)Tb->nbp[1][rp1] << 8) | ((u32)Tb->nbp[2][rp1] << 16);
 
     // a real loop, not unrolled: the body is ~300 instructions and six copies of it (plus the rest of the
     // kernel) do not fit the instruction cache shared by two CUs
     // (the slot-task kernel's three roots ARE unrolled: 24 KB of code still fit, the direction becomes a constant: -1.5 %, 163 -> 152 VGPRs)
     constexpr int ROOT_UNROLL = PERLANE ? 3 : 1;
-    const u32 rmL = slotL == 0 ? rm0 : rm1;
     D3_PRIO_HI();   // once per call, not per root: the priority stays raised until the search returns (see below)
     #pragma unroll ROOT_UNROLL
     for (int r = 0; r < (PERLANE ? 3 : 6); r++) {
-        const int slot = PERLANE ? slotL : (r >= 3 ? 1 : 0), dir = PERLANE ? r : r - 3 * slot;
+        const int slot = PERLANE ? 0 : (r >= 3 ? 1 : 0), dir = PERLANE ? r : r - 3 * slot;   // PERLANE: the call's cube sits in slot 0
         const int rp = slot == 0 ? rp0 : rp1;
         const int dest = (int)(((slot == 0 ? dq0 : dq1) >> (8 * dir)) & 0xFFu);
         const bool valid = (slot == 0 ? have0 : have1) && dest != 255;
@@ -466,7 +470,7 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
         #pragma unroll
         for (int d = 1; d < 6; d++) v = v + ft_val6<S>(Tb, wq[d]);
         v = term ? 10.0 : v;
-        if (valid && v > best) { best = v; bflag = slot == 0 ? flag0 : 0; bdir = dir; if constexpr (PERLANE) bm = rmL | ((u32)dest << 16); }
+        if (valid && v > best) { best = v; bflag = slot == 0 ? flag0 : 0; bdir = dir; if constexpr (PERLANE) bm = rm0 | ((u32)dest << 16); }
     }
     D3_PRIO_LO();
     if constexpr (PERLANE) { if (bmove) *bmove = bm; }

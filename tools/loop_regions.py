@@ -8,8 +8,9 @@ region holding the most instructions.  Every basic block of it is printed with i
 v_mul_hi_u32 / v_mad_*) and DPP counts.  A block is tagged `search` when it lies between the loop's first `s_setprio 2` and its
 last `s_setprio 0` (d3_search's priority raise and drop, ewn_step_d3.hpp), else `step`.  The step blocks are what the env step
 costs outside the opponent's search; blocks a wave takes only rarely (auto-reset, a rejected Lemire draw) are counted there too,
-so the `step` total is an upper bound of what an iteration issues outside the search.  A block with >= 20 32-bit multiplies is
-a Philox-4x32-10 block: the first one in the loop is prime() at step start (noted `prime`), every later one (noted `refill`) is
+so the `step` total is an upper bound of what an iteration issues outside the search.  A block with >= 10 32-bit multiplies is
+a Philox-4x32-10 block (ten rounds of one 64-bit multiply in the pair form, of two in the one-lane form; sources that still issue
+the high and low halves separately have 20 and 40): the first one in the loop is prime() at step start (noted `prime`), every later one (noted `refill`) is
 reached only when a Lemire draw is rejected, with probability <= 6 / 2^32 per draw.  `step_common` is the step total without the
 refills.  These are static counts, not measurements.
 
@@ -102,7 +103,7 @@ def analyse(blocks):
         c["label"] = lab
         c["region"] = "search" if s0 <= i <= s1 else "step"
         c["note"] = ""
-        if c["region"] == "step" and c["mul"] >= 20:    # a Philox-4x32-10 block: 20 multiplies (pair form) or 40
+        if c["region"] == "step" and c["mul"] >= 10:    # a Philox-4x32-10 block: 10 64-bit multiplies (pair form) or 20
             c["note"] = "refill" if seen_philox else "prime"
             seen_philox = True
         rows.append(c)

@@ -82,6 +82,16 @@ def main():
     except Exception:
         head = None
     out = {"source_hash": source_hash(), "git_head_when_summarised": head}
+    # entries of configurations that are not collected again this time ride along, marked with the sources they were measured on
+    tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+    if os.path.exists(tpath):
+        old = json.load(open(tpath))
+        for k, v in old.items():
+            if k in out:
+                continue
+            if isinstance(v, dict):
+                v.setdefault("collected_on_source_hash", old.get("source_hash"))
+            out[k] = v
     mixp = os.path.join(dst, "isa_mix.json")
     probe = os.path.join(dst, "valu_probe.json")
     # (directory, dominant kernel, bench.py's key, env steps per launch of that kernel, lanes, isa_mix kernel substring for its own issue peak)
@@ -162,7 +172,10 @@ def main():
             if "k_rollout_slotsILi5ELi2ELi0ELi1ELb0ELi1E" in kname and "peak_wave_insts_per_s" in kv:  # the headline instance (record-only trajectory)
                 out["valu_issue_peak_per_s"] = kv["peak_wave_insts_per_s"]["hot_loop"]
                 out["valu_issue_peak_source"] = "tools/isa_mix.py hot loop of %s priced with tools/valu_probe.py (valu_probe.json beside it)" % kname
-    json.dump(out, open(os.path.join(ROOT, "profiles", "pmc_traffic.json"), "w"), indent=1)
+    for k in ("valu_issue_peak_per_s", "valu_issue_peak_source"):   # the chip-wide peak goes last, as before
+        if k in out:
+            out[k] = out.pop(k)
+    json.dump(out, open(tpath, "w"), indent=1)
     print(json.dumps(out, indent=1))
     if not os.path.exists(probe):
         print("note: %s missing -- run tools/valu_probe.py on the GPU box and tools/isa_mix.py here" % probe, file=sys.stderr)

@@ -36,7 +36,8 @@ typedef uint32_t u32;
 #define F_v_mov_b32_dpp(r) "v_mov_b32_dpp " r ", " r " quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n"
 #define F_v_lshlrev_b64(r) "v_lshlrev_b64 " r ", 1, " r "\n"
 #define F_v_lshrrev_b64(r) "v_lshrrev_b64 " r ", 1, " r "\n"
-#define F_v_add_f64(r) "v_add_f64 " r ", " r ", %8\n"
+#define F_v_mad_u64_u32(r) "v_mad_u64_u32 " r ", vcc, %8, %8, " r "\n"
+#define F_v_add_f64(r)"v_add_f64 " r ", " r ", %8\n"
 #define F_v_mul_f64(r) "v_mul_f64 " r ", " r ", %8\n"
 #define F_v_max_f64(r) "v_max_f64 " r ", " r ", %8\n"
 #define F_v_cmp_le_f64(r) "v_cmp_le_f64 vcc, " r ", %8\n"
@@ -61,6 +62,7 @@ typedef uint32_t u32;
     X(v_mov_b32_dpp, 32) \
     X(v_lshlrev_b64, 64) \
     X(v_lshrrev_b64, 64) \
+    X(v_mad_u64_u32, 64) \
     X(v_add_f64, -64) \
     X(v_mul_f64, -64) \
     X(v_max_f64, -64) \
