@@ -597,12 +597,24 @@ def selfplay_outcomes(winner, live):
     return z.contiguous(), counts.to(torch.float32).contiguous()
 
 
+NOISE_BLOCK = 16384     # selfplay_noise draws whole blocks of this many consecutive global games
+
+
 def selfplay_noise(M, noise_alpha, key, game_offset, ply, device="cuda"):
-    """selfplay_puct's root noise of one ply: float32 [M, 6] Gamma(noise_alpha) variates (torch._standard_gamma) on a generator seeded
-    from key, game_offset and the ply.  Normalised over the legal edges by the kernel they are Dirichlet(noise_alpha) noise."""
-    gen = torch.Generator(device=device)
-    gen.manual_seed((int(key) * 0x9E3779B97F4A7C15 + int(game_offset) * 0xD1B54A32D192ED03 + int(ply) * 0x2545F4914F6CDD1D) & (2 ** 63 - 1))
-    return torch._standard_gamma(torch.full((int(M), 6), float(noise_alpha), dtype=torch.float32, device=device), generator=gen)
+    """selfplay_puct's root noise of one ply: float32 [M, 6] Gamma(noise_alpha) variates (torch._standard_gamma), row m for the global
+    game g = game_offset + m.  A row depends on key, the ply and g alone: the games are cut into blocks of NOISE_BLOCK consecutive
+    global ids, block j is one [NOISE_BLOCK, 6] draw on a generator seeded from key, j and the ply, and the call returns its rows of
+    the blocks it touches -- so the shards of a run (game_offset + the shard's first lane) get the rows the whole run gets.
+    Normalised over the legal edges by the kernel they are Dirichlet(noise_alpha) noise."""
+    M, first = int(M), int(game_offset)
+    rows = []
+    for j in range(first // NOISE_BLOCK, (first + max(M, 1) - 1) // NOISE_BLOCK + 1):
+        gen = torch.Generator(device=device)
+        gen.manual_seed((int(key) * 0x9E3779B97F4A7C15 + j * 0xD1B54A32D192ED03 + int(ply) * 0x2545F4914F6CDD1D) & (2 ** 63 - 1))
+        block = torch._standard_gamma(torch.full((NOISE_BLOCK, 6), float(noise_alpha), dtype=torch.float32, device=device), generator=gen)
+        lo, hi = max(first, j * NOISE_BLOCK), min(first + M, (j + 1) * NOISE_BLOCK)
+        rows.append(block[lo - j * NOISE_BLOCK:hi - j * NOISE_BLOCK])
+    return rows[0].contiguous() if len(rows) == 1 else torch.cat(rows)
 
 
 def selfplay_puct(boards, dice, params, sims=64, max_plies=None, c_puct=1.5, terminal_value=1.0, noise_eps=0.25, noise_alpha=1.0,
@@ -617,8 +629,9 @@ def selfplay_puct(boards, dice, params, sims=64, max_plies=None, c_puct=1.5, ter
     over the number of moves, AlphaZero's rule of thumb), not a measurement.  endgame_table: predict_puct's, at the leaves.
     fused=True: a ply's search is the one launch of ewn_puct_search, the records are the same bit for bit; not
     together with endgame_table.
-    The noise is torch._standard_gamma on a generator seeded from key, game_offset and the ply, drawn once per ply for all M games
-    and read by each chunk's rows: a call repeats itself bit for bit, whatever the chunk.  Returns a dict: board int8 [T, M, S, S], dice int8
+    The noise is selfplay_noise: torch._standard_gamma keyed by key, the ply and the global game game_offset + m, drawn once per ply
+    for all M games and read by each chunk's rows: a call repeats itself bit for bit, whatever the chunk, and the calls on the shards
+    of M games (game_offset moved to each shard's first game) give the rows of the one call on all of them.  Returns a dict: board int8 [T, M, S, S], dice int8
     [T, M], visits int32 [T, M, 2, 3], value float32 [T, M], action int8 [T, M, 2], live bool [T, M] (T = max_plies; rows past a
     game's end are zero), z and weight float32 [T, M] (selfplay_outcomes), winner int32 [M], plies int32 [M]."""
     who = "selfplay_puct"
