@@ -19,6 +19,15 @@ def _on_device(boards, dice, S, dev, other_size):
     return b.to(dev).to(torch.int8).reshape(-1, S, S).contiguous(), d.to(dev).to(torch.int8).reshape(-1).contiguous()
 
 
+class _PlainPolicyFn:
+    """policy_fn of an agent whose predict_batch needs no step: named before ModelAgent in the bases, it replaces that one's keyed
+    policy_fn"""
+
+    def policy_fn(self):
+        """(board, dice, t) -> actions, the callable tournament.evaluate takes"""
+        return lambda b, d, t: self.predict_batch(b, d)
+
+
 class ModelAgent(PolicyBase):
     def __init__(self, model_or_path, board_size=5, cube_layer=3, deterministic=True, key=0):
         """model_or_path: an a2c.ActorCritic, its flat fp32 parameter vector (ActorCritic.flat_parameters() order), or the path of a
@@ -78,7 +87,7 @@ def _leaf_table(who, table, board_size):
                          load=EndgameTable.load)
 
 
-class ValueSearchAgent(ModelAgent):
+class ValueSearchAgent(_PlainPolicyFn, ModelAgent):
     """The trained actor-critic searching one move ahead with its own value net (ewn_predict_lookahead): one agent move,
     the opponent's best reply under every dice, the critic at the next agent-to-move state -- plain expectiminimax, no pruning.  This
     project's counterpart of the reference's AlphaZeroMinimaxAgent (classical_policies/minimax.py:96-223: expectiminimax whose leaf
@@ -100,12 +109,8 @@ class ValueSearchAgent(ModelAgent):
         return self._ea.predict_lookahead(b, d, self.params, terminal_value=self.terminal_value, return_q=return_q,
                                           cube_layer=self.cube_layer, plies=self.plies, endgame_table=self.endgame_table)
 
-    def policy_fn(self):
-        """(board, dice, t) -> actions, the callable tournament.evaluate takes"""
-        return lambda b, d, t: self.predict_batch(b, d)
 
-
-class PuctAgent(ModelAgent):
+class PuctAgent(_PlainPolicyFn, ModelAgent):
     """The trained actor-critic behind a PUCT search of `sims` simulations (ewn_gym_amd.predict_puct): the policy head
     says where to look, the value head what a leaf is worth, chance nodes take the dice in a fixed stratified order.  This project's
     counterpart of the reference's AlphaZeroMCTSAgent (classical_policies/alpha_zero/MCTS.py), on the network the trainers here
@@ -131,12 +136,8 @@ class PuctAgent(ModelAgent):
                                      return_visits=return_visits, return_q=return_q, return_value=return_value,
                                      cube_layer=self.cube_layer, endgame_table=self.endgame_table, fused=self.fused)
 
-    def policy_fn(self):
-        """(board, dice, t) -> actions, the callable tournament.evaluate takes"""
-        return lambda b, d, t: self.predict_batch(b, d)
 
-
-class EndgameAgent(PolicyBase):
+class EndgameAgent(_PlainPolicyFn, PolicyBase):
     """The exact move wherever an endgame table covers the position, `fallback`'s elsewhere.  table: an
     ewn_gym_amd.EndgameTable or the path of a saved one; fallback: any policy of this package with predict_batch(boards, dice).
     The fallback is asked for ALL rows of a batch and the exact actions are laid over its answer with one torch.where: no row
@@ -168,7 +169,3 @@ class EndgameAgent(PolicyBase):
     def predict(self, obs, **kwargs):
         b, d = obs_arrays(obs)
         return self.predict_batch(b, d)[0].cpu().numpy(), None
-
-    def policy_fn(self):
-        """(board, dice, t) -> actions, the callable tournament.evaluate takes"""
-        return lambda b, d, t: self.predict_batch(b, d)

@@ -31,6 +31,15 @@ def wilson(wins, n, z=1.959963984540054):
     return (max(0.0, c - h), min(1.0, c + h))
 
 
+def _model_size(spec):
+    return getattr(spec["model"], "S", spec.get("board_size", 5))
+
+
+def _torch_policy(model):
+    """the model's argmax in torch (model.act), the per-step policy of a bare "mlp" agent"""
+    return lambda b, d, t: model.act(b, d, deterministic=True)[0]
+
+
 def _policy(spec, cube_layer, key):
     if callable(spec):          # e.g. A2CTrainer.policy_fn(): (board, dice, t) -> int8 [N, 2]
         return spec
@@ -46,19 +55,16 @@ def _policy(spec, cube_layer, key):
                                             cube_layer=cube_layer)[0]
     if kind == "mlp":           # the model's policy through ewn_predict_policy; evaluate() itself plays this kind on its own paths
         from classical_policies.model import ModelAgent
-        model = spec["model"]
-        return ModelAgent(model, board_size=getattr(model, "S", spec.get("board_size", 5)), cube_layer=cube_layer,
+        return ModelAgent(spec["model"], board_size=_model_size(spec), cube_layer=cube_layer,
                           deterministic=spec.get("deterministic", True), key=key).policy_fn()
     if kind == "mlp_lookahead":   # the model's lookahead on its own value net (ewn_predict_lookahead; "plies": 2 the two-move one), ply by ply through ewn_step
         from classical_policies.model import ValueSearchAgent
-        model = spec["model"]
-        return ValueSearchAgent(model, board_size=getattr(model, "S", spec.get("board_size", 5)), cube_layer=cube_layer,
+        return ValueSearchAgent(spec["model"], board_size=_model_size(spec), cube_layer=cube_layer,
                                 terminal_value=spec.get("terminal_value", 1.0), plies=spec.get("plies", 1),
                                 endgame_table=spec.get("endgame_table")).policy_fn()   # a table or its path: exact leaves
     if kind == "mlp_puct":      # the model's PUCT search on both of its heads (predict_puct), ply by ply through ewn_step
         from classical_policies.model import PuctAgent
-        model = spec["model"]
-        return PuctAgent(model, board_size=getattr(model, "S", spec.get("board_size", 5)), cube_layer=cube_layer, sims=spec.get("sims", 64),
+        return PuctAgent(spec["model"], board_size=_model_size(spec), cube_layer=cube_layer, sims=spec.get("sims", 64),
                          c_puct=spec.get("c_puct", 1.5), terminal_value=spec.get("terminal_value", 1.0),
                          endgame_table=spec.get("endgame_table"), fused=spec.get("fused", False)).policy_fn()   # fused: one launch (4r)
     if kind == "endgame":       # the exact move where the endgame table covers the position, the "fallback" spec's policy elsewhere
@@ -75,8 +81,7 @@ class _SpecPolicy:
 
     def __init__(self, spec, cube_layer, key):
         if isinstance(spec, dict) and spec.get("kind") == "mlp":   # evaluate() plays a bare "mlp" agent itself; inside a wrapper it is the per-step policy
-            model = spec["model"]
-            self.fn = lambda b, d, t: model.act(b, d, deterministic=True)[0]
+            self.fn = _torch_policy(spec["model"])
         else:
             self.fn = _policy(spec, cube_layer, key)
         self.t = 0
@@ -93,12 +98,71 @@ def flat_policy_params(model):
     return torch.cat([p.detach().reshape(-1).to(torch.float32) for p in model.parameters()]).contiguous()
 
 
+def _model_on_board(who, model, board_size):
+    """raise unless the model plays board_size; who: how the message starts ("evaluate: the model")"""
+    if getattr(model, "S", board_size) != board_size:
+        raise ValueError("%s plays %dx%d boards, the evaluation is on %dx%d" % (who, model.S, model.S, board_size, board_size))
+
+
 def _totals_result(totals, num, engine):
     score, length = totals["return_sum"], totals["n_steps"]   # un-shaped env: the only non-zero reward of an episode is its last
     wins = int((score > 0).sum().item())
     lo, hi = wilson(wins, num)
     return {"scores": score, "lengths": length, "wins": wins, "episodes": num, "win_rate": wins / num, "engine": engine,
             "ci95": [lo, hi], "avg_score": float(score.mean().item()), "avg_length": float(length.float().mean().item())}
+
+
+# ---------------------------------------------------------------- the evaluation env and the two loops every evaluation ends in
+
+def _eval_env(opponent, num, board_size, cube_layer, rng, seed_offset, key, before_reset=None):
+    """The evaluation env, reset to the seeds seed_offset .. seed_offset + num - 1.  opponent: a classical spec, or None for the env the
+    model-opponent paths build (opponent_policy="random"; the model is not the env's to know).  before_reset(env): what has to come
+    between the two, a refusal or set_opponent_model."""
+    own = {"opponent_policy": "random"} if opponent is None else {
+        "opponent_policy": opponent["kind"], "max_depth": opponent.get("max_depth", 3), "heuristic": opponent.get("heuristic", "hybrid"),
+        "num_simulations": opponent.get("num_simulations", 10), "num_env_copies": opponent.get("num_env_copies", 5)}
+    env = VecEWN(num, board_size=board_size, cube_layer=cube_layer, rng=rng, autoreset=False, philox_key=key ^ 0x5DEECE66D, **own)
+    if before_reset is not None:
+        before_reset(env)
+    env.reset(seeds=torch.arange(seed_offset, seed_offset + num, dtype=torch.int64).to(torch.int32))
+    return env
+
+
+def _play_chunks(env, launch, max_steps, chunk, num, engine):
+    """The engine's loop: launch(t0, totals) enqueues `chunk` steps of every lane from step t0 on and adds to the totals; one host read
+    per chunk stops it once every lane is done."""
+    totals = env.alloc_totals()
+    for t0 in range(0, max_steps, chunk):
+        launch(t0, totals)
+        if bool((env.done != 0).all()):
+            break
+    env.check_rng()
+    return _totals_result(totals, num, engine)
+
+
+def _play_plies(env, policy, max_steps, num, engine):
+    """The per-step loop: one policy evaluation and one step() per ply, one host read per ply."""
+    score = torch.zeros(num, dtype=torch.float64, device=env.device)
+    length = torch.zeros(num, dtype=torch.int32, device=env.device)
+    for t in range(max_steps):
+        alive = env.done == 0
+        if not bool(alive.any()):
+            break
+        _, _, reward, terminated, _, _ = env.step(policy(env.board, env.dice, t))
+        just = alive & (terminated != 0)
+        score = torch.where(just, reward, score)
+        length += alive.to(torch.int32)
+    env.check_rng()
+    return _totals_result({"return_sum": score, "n_steps": length}, num, engine)
+
+
+def _rollout_launch(env, agent, chunk):
+    """env.rollout (ewn_step_k; with a model set ewn_step_k_vs) as _play_chunks' launch where it serves the agent -- RandomAgent or
+    'hybrid' minimax -- else None"""
+    if not (isinstance(agent, dict) and agent["kind"] in ("random", "minimax") and agent.get("heuristic", "hybrid") == "hybrid"
+            and env.supports_rollout(agent["kind"], agent.get("max_depth", 3))):
+        return None
+    return lambda t0, totals: env.rollout(chunk, agent=agent["kind"], agent_max_depth=agent.get("max_depth", 3), totals=totals)
 
 
 def evaluate(agent, opponent, num=1024, board_size=5, cube_layer=3, rng="mt19937", seed_offset=0, key=12345, max_steps=400,
@@ -123,66 +187,29 @@ def evaluate(agent, opponent, num=1024, board_size=5, cube_layer=3, rng="mt19937
     ("engine" in the result says which one ran)."""
     if opponent["kind"] == "mlp":
         return _evaluate_vs_model(agent, opponent, num, board_size, cube_layer, rng, seed_offset, key, max_steps, chunk)
-    env = VecEWN(num, board_size=board_size, cube_layer=cube_layer, opponent_policy=opponent["kind"],
-                 max_depth=opponent.get("max_depth", 3), heuristic=opponent.get("heuristic", "hybrid"),
-                 num_simulations=opponent.get("num_simulations", 10), num_env_copies=opponent.get("num_env_copies", 5),
-                 rng=rng, autoreset=False, philox_key=key ^ 0x5DEECE66D)
-    env.reset(seeds=torch.arange(seed_offset, seed_offset + num, dtype=torch.int64).to(torch.int32))
-    if (use_rollout and isinstance(agent, dict) and agent["kind"] in ("random", "minimax") and agent.get("heuristic", "hybrid") == "hybrid"
-            and env.supports_rollout(agent["kind"], agent.get("max_depth", 3))):
-        totals = env.alloc_totals()
-        for _ in range(0, max_steps, chunk):
-            env.rollout(chunk, agent=agent["kind"], agent_max_depth=agent.get("max_depth", 3), totals=totals)
-            if bool((env.done != 0).all()):
-                break
-        env.check_rng()
-        return _totals_result(totals, num, "ewn_step_k")
+    env = _eval_env(opponent, num, board_size, cube_layer, rng, seed_offset, key)
+    launch = _rollout_launch(env, agent, chunk) if use_rollout else None
+    if launch is not None:
+        return _play_chunks(env, launch, max_steps, chunk, num, "ewn_step_k")
     if use_rollout and isinstance(agent, dict) and agent["kind"] in ("minimax", "mcts") and env.supports_agent_rollout(agent):
         # the MCTS agent, or the minimax agent against MCTS: ewn_step_k_agent, whose MCTS agent draws the playouts the per-step loop's
         # predict_mcts draws at the same step t (step_base + k)
-        totals = env.alloc_totals()
-        for t0 in range(0, max_steps, chunk):
-            env.agent_rollout(chunk, agent, step_base=t0, key=key, totals=totals)
-            if bool((env.done != 0).all()):
-                break
-        env.check_rng()
-        return _totals_result(totals, num, "ewn_step_k_agent")
+        return _play_chunks(env, lambda t0, totals: env.agent_rollout(chunk, agent, step_base=t0, key=key, totals=totals),
+                            max_steps, chunk, num, "ewn_step_k_agent")
     if isinstance(agent, dict) and agent["kind"] == "mlp":
         model = agent["model"]
-        if getattr(model, "S", board_size) != board_size:
-            raise ValueError("evaluate: the model plays %dx%d boards, the evaluation is on %dx%d" % (model.S, model.S, board_size, board_size))
+        _model_on_board("evaluate: the model", model, board_size)
         params = flat_policy_params(model).to(env.device)
         # the engine's call for this opponent (the MCTS opponent's playout stream is keyed by the lane's RNG header, so the chunking
         # changes nothing there either), or None: the per-step loop below
         engine = ("ewn_policy_eval" if env.supports_policy_eval() else
                   "ewn_policy_eval_mcts" if env.supports_policy_eval_mcts() else None)
         if use_rollout and engine is not None and params.numel() == env.policy_param_count():
-            totals = env.alloc_totals()
-            for _ in range(0, max_steps, chunk):
-                env.eval_policy(chunk, params, totals)
-                if bool((env.done != 0).all()):
-                    break
-            env.check_rng()
-            return _totals_result(totals, num, engine)
-        policy = lambda b, d, t: model.act(b, d, deterministic=True)[0]   # noqa: E731
+            return _play_chunks(env, lambda t0, totals: env.eval_policy(chunk, params, totals), max_steps, chunk, num, engine)
+        policy = _torch_policy(model)      # not _policy's ModelAgent (ewn_predict_policy)
     else:
         policy = _policy(agent, cube_layer, key)
-    score = torch.zeros(num, dtype=torch.float64, device=env.device)
-    length = torch.zeros(num, dtype=torch.int32, device=env.device)
-    for t in range(max_steps):
-        alive = env.done == 0
-        if not bool(alive.any()):
-            break
-        actions = policy(env.board, env.dice, t)
-        _, _, reward, terminated, _, _ = env.step(actions)
-        just = alive & (terminated != 0)
-        score = torch.where(just, reward, score)
-        length += alive.to(torch.int32)
-    env.check_rng()
-    wins = int((score > 0).sum().item())
-    lo, hi = wilson(wins, num)
-    return {"scores": score, "lengths": length, "wins": wins, "episodes": num, "win_rate": wins / num, "engine": "ewn_step",
-            "ci95": [lo, hi], "avg_score": float(score.mean().item()), "avg_length": float(length.float().mean().item())}
+    return _play_plies(env, policy, max_steps, num, "ewn_step")
 
 
 def _evaluate_vs_model(agent, opponent, num, board_size, cube_layer, rng, seed_offset, key, max_steps, chunk):
@@ -192,21 +219,15 @@ def _evaluate_vs_model(agent, opponent, num, board_size, cube_layer, rng, seed_o
         raise ValueError("evaluate: a model opponent ({'kind': 'mlp'}) is played by a model agent only (ewn_policy_eval_vs); every other "
                          "agent kind meets it in evaluate_vs_model (ewn_step_k_vs / ewn_step_vs)")
     for side in (agent, opponent):
-        if getattr(side["model"], "S", board_size) != board_size:
-            raise ValueError("evaluate: a model plays %dx%d boards, the evaluation is on %dx%d" % (side["model"].S, side["model"].S, board_size, board_size))
-    env = VecEWN(num, board_size=board_size, cube_layer=cube_layer, opponent_policy="random", rng=rng, autoreset=False,
-                 philox_key=key ^ 0x5DEECE66D)
-    if not env.supports_policy_eval_vs():
-        raise ValueError("evaluate: ewn_policy_eval_vs does not serve %dx%d boards with cube_layer %d" % (board_size, board_size, cube_layer))
-    env.reset(seeds=torch.arange(seed_offset, seed_offset + num, dtype=torch.int64).to(torch.int32))
+        _model_on_board("evaluate: a model", side["model"], board_size)
+
+    def served(env):
+        if not env.supports_policy_eval_vs():
+            raise ValueError("evaluate: ewn_policy_eval_vs does not serve %dx%d boards with cube_layer %d" % (board_size, board_size, cube_layer))
+    env = _eval_env(None, num, board_size, cube_layer, rng, seed_offset, key, before_reset=served)
     params, opp = flat_policy_params(agent["model"]).to(env.device), flat_policy_params(opponent["model"]).to(env.device)
-    totals = env.alloc_totals()
-    for _ in range(0, max_steps, chunk):
-        env.eval_policy(chunk, params, totals, opponent_params=opp)
-        if bool((env.done != 0).all()):
-            break
-    env.check_rng()
-    return _totals_result(totals, num, "ewn_policy_eval_vs")
+    return _play_chunks(env, lambda t0, totals: env.eval_policy(chunk, params, totals, opponent_params=opp),
+                        max_steps, chunk, num, "ewn_policy_eval_vs")
 
 
 def _stand_in_random(env):
@@ -216,22 +237,15 @@ def _stand_in_random(env):
     from .vec_env import legal_actions
     M = 0xFFFFFFFF
 
-    def fmix(h):
+    def fmix(h):            # on a tensor of lanes and on a Python int alike
         h = h ^ (h >> 16)
         h = (h * 0x85EBCA6B) & M
         h = h ^ (h >> 13)
         h = (h * 0xC2B2AE35) & M
         return h ^ (h >> 16)
 
-    def fmix_int(h):
-        h ^= h >> 16
-        h = (h * 0x85EBCA6B) & M
-        h ^= h >> 13
-        h = (h * 0xC2B2AE35) & M
-        return h ^ (h >> 16)
-
     key = int(env.cfg.philox_key)
-    kterm = fmix_int((key & M) ^ 0x41474E54) ^ (((key >> 32) * 0x85EBCA6B) & M)
+    kterm = fmix((key & M) ^ 0x41474E54) ^ (((key >> 32) * 0x85EBCA6B) & M)
     lane = torch.arange(env.N, dtype=torch.int64, device=env.device) + int(env.cfg.lane_offset)
     philox = int(env.cfg.rng_kind) == 1
 
@@ -260,36 +274,26 @@ def evaluate_vs_model(agent, opponent, num=1024, board_size=5, cube_layer=3, rng
     if isinstance(agent, dict) and agent.get("kind") == "mlp":
         return _evaluate_vs_model(agent, opponent, num, board_size, cube_layer, rng, seed_offset, key, max_steps, chunk)
     model = opponent["model"]
-    if getattr(model, "S", board_size) != board_size:
-        raise ValueError("evaluate_vs_model: the model plays %dx%d boards, the evaluation is on %dx%d" % (model.S, model.S, board_size, board_size))
-    env = VecEWN(num, board_size=board_size, cube_layer=cube_layer, opponent_policy="random", rng=rng, autoreset=False,
-                 philox_key=key ^ 0x5DEECE66D)
-    if not env.supports_step_vs():
-        raise ValueError("evaluate_vs_model: ewn_step_vs does not serve %dx%d boards with cube_layer %d" % (board_size, board_size, cube_layer))
-    env.set_opponent_model(flat_policy_params(model).to(env.device), deterministic=deterministic, noise_key=key)
-    env.reset(seeds=torch.arange(seed_offset, seed_offset + num, dtype=torch.int64).to(torch.int32))
-    if (use_rollout and isinstance(agent, dict) and agent["kind"] in ("random", "minimax") and agent.get("heuristic", "hybrid") == "hybrid"
-            and env.supports_rollout(agent["kind"], agent.get("max_depth", 3))):
-        totals = env.alloc_totals()
-        for _ in range(0, max_steps, chunk):
-            env.rollout(chunk, agent=agent["kind"], agent_max_depth=agent.get("max_depth", 3), totals=totals)
-            if bool((env.done != 0).all()):
-                break
-        env.check_rng()
-        return _totals_result(totals, num, "ewn_step_k_vs")
+    _model_on_board("evaluate_vs_model: the model", model, board_size)
+
+    def seat(env):          # the refusal, then the model takes the opponent's seat: both before the reset
+        if not env.supports_step_vs():
+            raise ValueError("evaluate_vs_model: ewn_step_vs does not serve %dx%d boards with cube_layer %d" % (board_size, board_size, cube_layer))
+        env.set_opponent_model(flat_policy_params(model).to(env.device), deterministic=deterministic, noise_key=key)
+    env = _eval_env(None, num, board_size, cube_layer, rng, seed_offset, key, before_reset=seat)
+    launch = _rollout_launch(env, agent, chunk) if use_rollout else None
+    if launch is not None:
+        return _play_chunks(env, launch, max_steps, chunk, num, "ewn_step_k_vs")
     policy = _stand_in_random(env) if isinstance(agent, dict) and agent.get("kind") == "random" else _policy(agent, cube_layer, key)
-    score = torch.zeros(num, dtype=torch.float64, device=env.device)
-    length = torch.zeros(num, dtype=torch.int32, device=env.device)
-    for t in range(max_steps):
-        alive = env.done == 0
-        if not bool(alive.any()):
-            break
-        _, _, reward, terminated, _, _ = env.step(policy(env.board, env.dice, t))
-        just = alive & (terminated != 0)
-        score = torch.where(just, reward, score)
-        length += alive.to(torch.int32)
-    env.check_rng()
-    return _totals_result({"return_sum": score, "n_steps": length}, num, "ewn_step_vs")
+    return _play_plies(env, policy, max_steps, num, "ewn_step_vs")
+
+
+def _row(r):
+    return {k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}
+
+
+def _classical_spec(kind, max_depth, heuristic, num_simulations, num_env_copies):
+    return {"kind": kind, "max_depth": max_depth, "heuristic": heuristic, "num_simulations": num_simulations, "num_env_copies": num_env_copies}
 
 
 def evaluate_agents_vs_model(model, names=("random", "minimax", "mcts"), num=1024, max_depth=5, num_simulations=10, num_env_copies=5,
@@ -297,9 +301,9 @@ def evaluate_agents_vs_model(model, names=("random", "minimax", "mcts"), num=102
     """every listed classical agent against the model as the opponent"""
     table = {}
     for a in names:
-        agent = {"kind": a, "max_depth": max_depth, "heuristic": heuristic, "num_simulations": num_simulations, "num_env_copies": num_env_copies}
+        agent = _classical_spec(a, max_depth, heuristic, num_simulations, num_env_copies)
         r = evaluate_vs_model(agent, {"kind": "mlp", "model": model}, num=num, board_size=board_size, cube_layer=cube_layer, rng=rng)
-        table["%s vs opponent_model" % a] = {k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}
+        table["%s vs opponent_model" % a] = _row(r)
     return table
 
 
@@ -307,13 +311,12 @@ def tournament(names=("random", "minimax", "mcts"), num=1024, max_depth=5, num_s
                board_size=5, cube_layer=3, heuristic="hybrid", rng="mt19937"):
     """eval_pairs.py:10-35: every (agent, opponent) pair, 1024 episodes, depth 5, 10 simulations by default."""
     def spec(n):
-        return {"kind": n, "max_depth": max_depth, "heuristic": heuristic, "num_simulations": num_simulations,
-                "num_env_copies": num_env_copies}
+        return _classical_spec(n, max_depth, heuristic, num_simulations, num_env_copies)
     table = {}
     for a in names:
         for o in names:
             r = evaluate(spec(a), spec(o), num=num, board_size=board_size, cube_layer=cube_layer, rng=rng)
-            table["%s vs %s" % (a, o)] = {k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}
+            table["%s vs %s" % (a, o)] = _row(r)
     return table
 
 
@@ -347,52 +350,28 @@ def evaluate_model(model, names=("random", "minimax"), num=1024, max_depth=5, nu
     fused (with puct): that search as one launch per move (ewn_puct_search): the same moves, so the same rows.
     endgame_leaves (with lookahead and endgame_table): the table is not laid over the agents' moves; beside the lookahead's row
     stands the same lookahead with the table's exact values at the leaves it covers, "lookahead + exact leaves vs ..." """
-    table = {}
-    leaf_table = None
-    if endgame_leaves:
-        if endgame_table is None or not lookahead:
-            raise ValueError("evaluate_model: endgame_leaves goes with lookahead and an endgame_table")
+    if endgame_leaves and (endgame_table is None or not lookahead):
+        raise ValueError("evaluate_model: endgame_leaves goes with lookahead and an endgame_table")
+    if endgame_table is not None:       # loaded once
         from .endgame import EndgameTable
-        leaf_table = endgame_table if isinstance(endgame_table, EndgameTable) else EndgameTable.load(endgame_table)
-    elif endgame_table is not None:
-        return _evaluate_model_endgame(model, names, num, max_depth, num_simulations, num_env_copies, board_size, cube_layer, heuristic,
-                                       rng, lookahead, endgame_table)
-    for o in names:
-        opp = {"kind": o, "max_depth": max_depth, "heuristic": heuristic, "num_simulations": num_simulations, "num_env_copies": num_env_copies}
-        r = evaluate({"kind": "mlp", "model": model}, opp, num=num, board_size=board_size, cube_layer=cube_layer, rng=rng)
-        table["model vs %s" % o] = {k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}
-        if lookahead:
-            plies = 2 if int(lookahead) == 2 else 1
-            r = evaluate({"kind": "mlp_lookahead", "model": model, "plies": plies}, opp, num=num, board_size=board_size, cube_layer=cube_layer,
-                         rng=rng)
-            table[("lookahead(2) vs %s" if plies == 2 else "lookahead vs %s") % o] = {k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}
-            if leaf_table is not None:
-                r = evaluate({"kind": "mlp_lookahead", "model": model, "plies": plies, "endgame_table": leaf_table}, opp, num=num,
-                             board_size=board_size, cube_layer=cube_layer, rng=rng)
-                table[("lookahead(2) + exact leaves vs %s" if plies == 2 else "lookahead + exact leaves vs %s") % o] = {
-                    k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}
-        if puct is not None:
-            r = evaluate({"kind": "mlp_puct", "model": model, "sims": int(puct), "fused": bool(fused)}, opp, num=num, board_size=board_size, cube_layer=cube_layer,
-                         rng=rng)
-            table["puct(%d) vs %s" % (int(puct), o)] = {k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}
-    return table
-
-
-def _evaluate_model_endgame(model, names, num, max_depth, num_simulations, num_env_copies, board_size, cube_layer, heuristic, rng, lookahead,
-                            endgame_table):
-    """evaluate_model with every agent wrapped in the endgame kind; the table is loaded once"""
-    from .endgame import EndgameTable
-    t = endgame_table if isinstance(endgame_table, EndgameTable) else EndgameTable.load(endgame_table)
-    table = {}
-    agents = [("endgame+model vs %s", {"kind": "mlp", "model": model})]
+        endgame_table = endgame_table if isinstance(endgame_table, EndgameTable) else EndgameTable.load(endgame_table)
+    agents = [("model", {"kind": "mlp", "model": model})]       # (the row's label, the agent's spec), in the order of the rows
     if lookahead:
         plies = 2 if int(lookahead) == 2 else 1
-        agents.append(("endgame+lookahead(2) vs %s" if plies == 2 else "endgame+lookahead vs %s", {"kind": "mlp_lookahead", "model": model, "plies": plies}))
+        label = "lookahead(2)" if plies == 2 else "lookahead"
+        agents.append((label, {"kind": "mlp_lookahead", "model": model, "plies": plies}))
+        if endgame_leaves:
+            agents.append((label + " + exact leaves", {"kind": "mlp_lookahead", "model": model, "plies": plies, "endgame_table": endgame_table}))
+    if endgame_table is not None and not endgame_leaves:     # the table laid over every agent's moves; these tables have no PUCT row
+        agents = [("endgame+" + label, {"kind": "endgame", "table": endgame_table, "fallback": spec}) for label, spec in agents]
+    elif puct is not None:
+        agents.append(("puct(%d)" % int(puct), {"kind": "mlp_puct", "model": model, "sims": int(puct), "fused": bool(fused)}))
+    table = {}
     for o in names:
-        opp = {"kind": o, "max_depth": max_depth, "heuristic": heuristic, "num_simulations": num_simulations, "num_env_copies": num_env_copies}
+        opp = _classical_spec(o, max_depth, heuristic, num_simulations, num_env_copies)
         for label, spec in agents:
-            r = evaluate({"kind": "endgame", "table": t, "fallback": spec}, opp, num=num, board_size=board_size, cube_layer=cube_layer, rng=rng)
-            table[label % o] = {k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}
+            r = evaluate(spec, opp, num=num, board_size=board_size, cube_layer=cube_layer, rng=rng)
+            table["%s vs %s" % (label, o)] = _row(r)
     return table
 
 
@@ -451,7 +430,7 @@ def main():
         r = evaluate({"kind": "mlp", "model": load_policy(a.model, a.board_size, a.cube_layer)},
                      {"kind": "mlp", "model": load_policy(a.opponent_model, a.board_size, a.cube_layer)},
                      num=a.num, board_size=a.board_size, cube_layer=a.cube_layer, rng=a.rng)
-        t = {"model vs opponent_model": {k: r[k] for k in ("wins", "episodes", "win_rate", "ci95", "avg_length", "engine")}}
+        t = {"model vs opponent_model": _row(r)}
     elif a.model is not None:
         model = load_policy(a.model, a.board_size, a.cube_layer)
         t = evaluate_model(model, a.agents, a.num, a.max_depth, a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer,
