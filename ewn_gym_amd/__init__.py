@@ -9,8 +9,9 @@ from .search import (lookahead_expand, lookahead_reduce, lookahead_targets, pred
                      predict_puct, puct_advance, puct_begin, puct_result, puct_tree_views, puct_play, selfplay_noise, selfplay_outcomes,
                      selfplay_puct, puct_search)
 from .endgame import EndgameTable  # noqa: F401
+from .games import selfplay_puct_games  # noqa: F401
 
 __all__ = ["VecEWN", "EwnError", "INFO_MESSAGES", "legal_actions", "apply_action", "playout_wins", "evaluate", "predict_minimax", "predict_random",
            "predict_mcts", "predict_policy", "predict_lookahead", "lookahead_expand", "lookahead_reduce", "lookahead_targets", "sup_grad", "EndgameTable",
            "predict_puct", "puct_begin", "puct_advance", "puct_result", "puct_tree_views",
-           "puct_play", "selfplay_noise", "selfplay_outcomes", "selfplay_puct", "puct_search"]
+           "puct_play", "selfplay_noise", "selfplay_outcomes", "selfplay_puct", "puct_search", "selfplay_puct_games"]

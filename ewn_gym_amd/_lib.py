@@ -34,7 +34,8 @@ EXPORTS = ["ewn_abi_version", "ewn_strerror", "ewn_rng_words", "ewn_step_scratch
            "ewn_sup_scratch_bytes", "ewn_sup_grad", "ewn_lookahead_targets",
            "ewn_endgame_table_bytes", "ewn_endgame_build", "ewn_endgame_lookup", "ewn_predict_lookahead_eg",
            "ewn_puct_tree_bytes", "ewn_puct_begin", "ewn_puct_advance", "ewn_puct_result",
-           "ewn_puct_advance_noise", "ewn_puct_play", "ewn_puct_search"]
+           "ewn_puct_advance_noise", "ewn_puct_play", "ewn_puct_search",
+           "ewn_puct_selfplay_scratch_bytes", "ewn_puct_selfplay"]
 AGENT = {"random": 0, "minimax": 1, "sample": 2, "mlp": 3}   # "mlp": the trained policy, through ewn_step_k_policy   # "sample": env.action_space.sample(), all six actions (EWN_AGENT_SAMPLE)
 AGENT_MCTS = 4   # ewn_agent.kind of the MCTS agent (ewn_step_k_agent only; ewn_step_k does not take it)
 
@@ -186,6 +187,9 @@ def load():
         "ewn_puct_advance_noise": (i32, [i32, i32, i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, C.c_float, vp, vp, vp]),
         "ewn_puct_play": (i32, [i32, i32, i32, vp, vp, vp, vp, i32, C.c_uint64, C.c_int64, vp, vp, vp, vp, vp, vp, vp]),
         "ewn_puct_search": (i32, [i32, i32, i32, i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, C.c_float, vp, vp]),
+        "ewn_puct_selfplay_scratch_bytes": (C.c_int64, [i32, i32, i32, i32, i32, i32]),
+        "ewn_puct_selfplay": (i32, [i32, i32, i32, i32, i32, C.c_float, C.c_float, vp, vp, C.c_float, i32, C.c_uint64, C.c_int64, i32, i32,
+                               vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -21,7 +21,7 @@ FILE_FLAGS = {"ewn_policy.hip": ["-fno-slp-vectorize"], "ewn_policy_eval.hip": [
               "ewn_policy_eval_mcts.hip": ["-fno-slp-vectorize"], "ewn_selfplay.hip": ["-fno-slp-vectorize"],
               "ewn_step_vs.hip": ["-fno-slp-vectorize"], "ewn_predict_policy.hip": ["-fno-slp-vectorize"],
               "ewn_predict_lookahead.hip": ["-fno-slp-vectorize"], "ewn_lookahead_stages.hip": ["-fno-slp-vectorize"],
-              "ewn_puct_fused.hip": ["-fno-slp-vectorize"]}
+              "ewn_puct_fused.hip": ["-fno-slp-vectorize"], "ewn_puct_games.hip": ["-fno-slp-vectorize"]}
 
 
 def stale():

@@ -113,10 +113,8 @@ __global__ __launch_bounds__(PU_NT) void k_puct_result(int S, int M, PuResultBuf
     }
 }
 
-// The move of a self-play game off a finished tree (ewn_puct_play): a wave per game, the position played is the tree's
-// root.  The edge is the first winning one, else drawn in proportion to the root's visits while ply < temp_plies (integer
-// arithmetic on a Philox word), else k_puct_result's first maximum; the record row, the board after the move seen from the other
-// side, the next dice (a second Philox word) and the game's state are written.  The budget is read from the first tree's header
+// The move of a self-play game off a finished tree (ewn_puct_play): a wave per game and trip around ewn_puct.hpp's
+// pu_play, the one copy that the whole-game kernel of ewn_puct_games.hip calls as well.  The budget is read from the first tree's header
 template <int S>
 __global__ __launch_bounds__(PU_NT) void k_puct_play(int M, int temp_plies, u32 k0, u32 k1, long long game_offset, PuPlayBuf B)
 {
@@ -124,101 +122,16 @@ __global__ __launch_bounds__(PU_NT) void k_puct_play(int M, int temp_plies, u32 
     __shared__ __attribute__((aligned(16))) int8_t lds[(PU_NT / 64) * PU_WAVE];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     int8_t *base = lds + wave * PU_WAVE;
-    uint8_t *pos = (uint8_t *)(base + PU_O_POS);
-    float *sw = (float *)(base + PU_O_OWN);
-    int *sn = (int *)(base + PU_O_OWN) + 8;
     const int sims = ((const int *)B.tree)[4];
     const bool known = sims >= 0 && sims <= PU_MAX_SIMS && ((const int *)B.tree)[5] == PU_LAYOUT;
     const PuLayout L = pu_layout(S, known ? sims : 0);
+    const PuRecord R = { B.rec_board, B.rec_dice, B.rec_visits, B.rec_value, B.rec_action, B.rec_live };
 
     #pragma unroll 1
     for (int m0 = (int)blockIdx.x * (PU_NT / 64) + wave; m0 < M; m0 += (int)gridDim.x * (PU_NT / 64)) {   // wave-uniform
         const size_t m = (size_t)m0;
-        int *g = B.game + m * 4;
-        const int ply = g[0], over = g[1];
-        const PuTree T = pu_tree((uint8_t *)B.tree, m, L);     // read only
-        bool tree = false, live = false;
-        int kd = 0, nn = 0, PA = 0, PO = 0;
-        float ww = 0.0f;
-        PuEdge E = { 0, 0, 0, 0, false };
-        if (known) {
-            const int count = T.hdr[0], pending = T.hdr[2];
-            tree = T.hdr[4] == sims && T.hdr[5] == PU_LAYOUT && count >= 1 && count <= L.nodes && pending < count;
-        }
-        if (tree && over == 0 && T.hdr[3] == 0) {
-            __builtin_amdgcn_wave_barrier();                   // what was there is read
-            if (la_observation<S, 64>(T.board, lane, base, pos, PA, PO)) {
-                E = pu_edge<S>(base, pos, PA, PO, la_dice((int)T.dice[0]), lane);
-                if (lane < 6) {
-                    kd = T.kind[lane]; nn = T.n[lane]; ww = T.w[lane];
-                    kd = kd == E.kind ? kd : 0;                // an edge the rules do not know is no edge
-                }
-            }
-        }
-        if (lane < 8) { sw[lane] = ww; sn[lane] = nn; }
-        const u32 wins = (u32)__builtin_amdgcn_ballot_w64(kd == 1) & 0x3Fu, searched = (u32)__builtin_amdgcn_ballot_w64(kd == 2) & 0x3Fu;
-        __builtin_amdgcn_wave_barrier();
-        live = (wins | searched) != 0;
-        if (!live) {                                           // over, degenerate, without a move, or no tree: nothing is played
-            if (lane < CELLS && B.rec_board) B.rec_board[m * CELLS + lane] = 0;
-            if (lane < 6 && B.rec_visits) B.rec_visits[m * 6 + lane] = 0;
-            if (lane < 2 && B.rec_action) B.rec_action[m * 2 + lane] = 0;
-            if (lane == 0) {
-                if (B.rec_dice) B.rec_dice[m] = 0;
-                if (B.rec_value) B.rec_value[m] = 0.0f;
-                if (B.rec_live) B.rec_live[m] = 0;
-                if (tree && over == 0) g[1] = 1;               // a game that cannot go on is over, without a winner
-            }
-        } else {
-            u32 o[4];
-            const unsigned long long gid = (unsigned long long)game_offset + (unsigned long long)m;
-            philox4x32_10((u32)ply, (u32)gid, (u32)(gid >> 32), 0x50555350u, k0, k1, o);
-            const int tn = sn[0] + sn[1] + sn[2] + sn[3] + sn[4] + sn[5];
-            int best;
-            if (wins) best = __builtin_ctz(wins);              // a win on the board is played
-            else {
-                u32 ts = 0;                                    // the visits of the searched edges
-                #pragma unroll
-                for (int i = 0; i < 6; i++) ts += ((searched >> i) & 1u) ? (u32)sn[i] : 0u;
-                best = __builtin_ctz(searched);
-                if (ply < temp_plies && ts > 0) {              // in proportion to the visits: the first edge whose running sum passes r
-                    const u32 r = __umulhi(o[0], ts);
-                    u32 run = 0;
-                    bool found = false;
-                    #pragma unroll
-                    for (int i = 0; i < 6; i++) {
-                        run += ((searched >> i) & 1u) ? (u32)sn[i] : 0u;
-                        if (!found && ((searched >> i) & 1u) && run > r) { best = i; found = true; }
-                    }
-                } else {
-                    int nb = sn[best];
-                    #pragma unroll
-                    for (int i = 1; i < 6; i++) if (((searched >> i) & 1u) && sn[i] > nb) { nb = sn[i]; best = i; }
-                }
-            }
-            const int bk = (wins >> best) & 1u ? 1 : 2;
-            const int bsrc = __shfl(E.src, best), bdst = __shfl(E.dst, best), bcube = __shfl(E.cube, best);
-            if (lane < CELLS) {
-                if (B.rec_board) B.rec_board[m * CELLS + lane] = base[lane];
-                const int rc = CELLS - 1 - lane;               // flip(b1)
-                int v = base[rc];
-                v = rc == bsrc ? 0 : v;
-                v = rc == bdst ? bcube : v;
-                B.boards[m * CELLS + lane] = (int8_t)(-v);
-            }
-            if (lane < 6 && B.rec_visits) B.rec_visits[m * 6 + lane] = nn;
-            if (lane == 0) {
-                const float tw = ((((sw[0] + sw[1]) + sw[2]) + sw[3]) + sw[4]) + sw[5];
-                if (B.rec_dice) B.rec_dice[m] = T.dice[0];
-                if (B.rec_value) B.rec_value[m] = tn > 0 ? tw / (float)tn : 0.0f;
-                if (B.rec_action) { B.rec_action[m * 2] = (int8_t)(best / 3); B.rec_action[m * 2 + 1] = (int8_t)(best % 3); }
-                if (B.rec_live) B.rec_live[m] = 1;
-                B.dice[m] = (int8_t)(1 + (int)__umulhi(o[1], 6u));
-                g[0] = ply + 1;
-                if (bk == 1) { g[1] = 1; g[2] = (ply & 1) ? -1 : 1; }
-            }
-        }
-        __builtin_amdgcn_wave_barrier();                       // this trip's LDS is read: the next may overwrite it
+        pu_play<S>(pu_tree((uint8_t *)B.tree, m, L), known, sims, L.nodes, B.boards + m * CELLS, B.dice + m, B.game + m * 4, temp_plies, k0, k1,
+                   (unsigned long long)game_offset + (unsigned long long)m, R, m, lane, base);   // the tree is read only
     }
 }
 

@@ -1,7 +1,8 @@
-// ewn_puct.hpp -- the one copy of the PUCT tree's device code (DESIGN.md 4o, 4q, 4r): the layout, a node's edges, the backup, the
-// root written by begin, the evaluation of a pending node and one simulation's walk.  ewn_puct.hip (the staged kernels: the
-// network's outputs come and the leaf rows go through global memory, a launch per step) and ewn_puct_fused.hip (the whole search in
-// one launch: both come and go through LDS) call the same functions, so the two paths agree byte for byte by construction.
+// ewn_puct.hpp -- the one copy of the PUCT tree's device code (DESIGN.md 4o, 4q, 4r, 4s): the layout, a node's edges, the backup, the
+// root written by begin, the evaluation of a pending node, one simulation's walk and the move of a self-play game (pu_play).
+// ewn_puct.hip (the staged kernels: the network's outputs come and the leaf rows go through global memory, a launch per step),
+// ewn_puct_fused.hip (the whole search in one launch: both come and go through LDS) and ewn_puct_games.hip (whole games in one
+// launch: that search with the move and a game loop round it) call the same functions, so the paths agree byte for byte by construction.
 //
 // A wave per tree.  Per-edge state (N, W, P, kind, child[.][d'], cn[.][d']) of edge a is read and written by lane a alone, in every
 // kernel.  What one lane writes and ANOTHER reads through global memory -- a node's dice and parent triple and the header (lane 0
@@ -10,7 +11,8 @@
 //   staged:  the write and the read are in different launches (boards, dice and parent triples are written one launch before they
 //            are read);
 //   fused:   a tree stays on ONE wave from the fill to the end of the search, and between the write and the read lies a block
-//            barrier (__syncthreads: a workgroup-scope release / acquire), the barriers of the round structure.
+//            barrier (__syncthreads: a workgroup-scope release / acquire), the barriers of the round structure.  Whole games: the
+//            same, with the board, dice and game state that pu_play writes for the next ply's pu_root among the values handed over.
 // Within one call of pu_round nothing is read that another lane wrote in the same call: a board cell is read by the lane that wrote
 // it, the nodes of a backup chain and of a walk were created in earlier rounds, and the node created now is not entered again.
 // The node's board goes to LDS by ewn_lookahead.hpp's la_observation, so that la_find and la_root apply unchanged.
@@ -294,6 +296,109 @@ EWN_DEV void pu_round(const PuTree &T, int sims, float c_puct, float inv_tv, int
         if (lane == 0) leaf_dice[0] = 1;
     }
     __builtin_amdgcn_wave_barrier();                           // this trip's LDS is read: the next may overwrite it
+}
+
+// the record buffers of ewn_puct_play: rows of board [CELLS], dice, visits [6], value, action [2], live; each pointer may be NULL
+struct PuRecord { int8_t *board; int8_t *dice; int *visits; float *value; int8_t *action; int8_t *live; };
+
+// The move of one self-play game off its finished tree, by one wave (ewn_puct_play's definition): the position played
+// is the tree's root.  The edge is the first winning one, else drawn in proportion to the root's visits while ply < temp_plies
+// (integer arithmetic on a Philox word of ply and gid), else k_puct_result's first maximum; the record row, the board after the move
+// seen from the other side (board [CELLS]), the next dice (dice [1], a second Philox word) and the game's state g = {ply, over,
+// winner, 0} are written; the record row is row r of R's buffers.  known: the budget is one a tree can have; T is only read.  Returns whether the game goes on.
+// base: the wave's PU_WAVE bytes of LDS
+template <int S>
+EWN_DEV bool pu_play(const PuTree &T, bool known, int sims, int nodes, int8_t *board, int8_t *dice, int *g, int temp_plies, u32 k0, u32 k1,
+                     unsigned long long gid, const PuRecord &R, size_t r, int lane, int8_t *base)
+{
+    constexpr int CELLS = S * S;
+    uint8_t *pos = (uint8_t *)(base + PU_O_POS);
+    float *sw = (float *)(base + PU_O_OWN);
+    int *sn = (int *)(base + PU_O_OWN) + 8;
+    const int ply = g[0], over = g[1];
+    bool tree = false, live = false, goes_on = false;
+    int kd = 0, nn = 0, PA = 0, PO = 0;
+    float ww = 0.0f;
+    PuEdge E = { 0, 0, 0, 0, false };
+    if (known) {
+        const int count = T.hdr[0], pending = T.hdr[2];
+        tree = T.hdr[4] == sims && T.hdr[5] == PU_LAYOUT && count >= 1 && count <= nodes && pending < count;
+    }
+    if (tree && over == 0 && T.hdr[3] == 0) {
+        __builtin_amdgcn_wave_barrier();                       // what was there is read
+        if (la_observation<S, 64>(T.board, lane, base, pos, PA, PO)) {
+            E = pu_edge<S>(base, pos, PA, PO, la_dice((int)T.dice[0]), lane);
+            if (lane < 6) {
+                kd = T.kind[lane]; nn = T.n[lane]; ww = T.w[lane];
+                kd = kd == E.kind ? kd : 0;                    // an edge the rules do not know is no edge
+            }
+        }
+    }
+    if (lane < 8) { sw[lane] = ww; sn[lane] = nn; }
+    const u32 wins = (u32)__builtin_amdgcn_ballot_w64(kd == 1) & 0x3Fu, searched = (u32)__builtin_amdgcn_ballot_w64(kd == 2) & 0x3Fu;
+    __builtin_amdgcn_wave_barrier();
+    live = (wins | searched) != 0;
+    if (!live) {                                               // over, degenerate, without a move, or no tree: nothing is played
+        if (lane < CELLS && R.board) R.board[r * CELLS + lane] = 0;
+        if (lane < 6 && R.visits) R.visits[r * 6 + lane] = 0;
+        if (lane < 2 && R.action) R.action[r * 2 + lane] = 0;
+        if (lane == 0) {
+            if (R.dice) R.dice[r] = 0;
+            if (R.value) R.value[r] = 0.0f;
+            if (R.live) R.live[r] = 0;
+            if (tree && over == 0) g[1] = 1;                   // a game that cannot go on is over, without a winner
+        }
+    } else {
+        u32 o[4];
+        philox4x32_10((u32)ply, (u32)gid, (u32)(gid >> 32), 0x50555350u, k0, k1, o);
+        const int tn = sn[0] + sn[1] + sn[2] + sn[3] + sn[4] + sn[5];
+        int best;
+        if (wins) best = __builtin_ctz(wins);                  // a win on the board is played
+        else {
+            u32 ts = 0;                                        // the visits of the searched edges
+            #pragma unroll
+            for (int i = 0; i < 6; i++) ts += ((searched >> i) & 1u) ? (u32)sn[i] : 0u;
+            best = __builtin_ctz(searched);
+            if (ply < temp_plies && ts > 0) {                  // in proportion to the visits: the first edge whose running sum passes r
+                const u32 r = __umulhi(o[0], ts);
+                u32 run = 0;
+                bool found = false;
+                #pragma unroll
+                for (int i = 0; i < 6; i++) {
+                    run += ((searched >> i) & 1u) ? (u32)sn[i] : 0u;
+                    if (!found && ((searched >> i) & 1u) && run > r) { best = i; found = true; }
+                }
+            } else {
+                int nb = sn[best];
+                #pragma unroll
+                for (int i = 1; i < 6; i++) if (((searched >> i) & 1u) && sn[i] > nb) { nb = sn[i]; best = i; }
+            }
+        }
+        const int bk = (wins >> best) & 1u ? 1 : 2;
+        const int bsrc = __shfl(E.src, best), bdst = __shfl(E.dst, best), bcube = __shfl(E.cube, best);
+        if (lane < CELLS) {
+            if (R.board) R.board[r * CELLS + lane] = base[lane];
+            const int rc = CELLS - 1 - lane;                   // flip(b1)
+            int v = base[rc];
+            v = rc == bsrc ? 0 : v;
+            v = rc == bdst ? bcube : v;
+            board[lane] = (int8_t)(-v);
+        }
+        if (lane < 6 && R.visits) R.visits[r * 6 + lane] = nn;
+        if (lane == 0) {
+            const float tw = ((((sw[0] + sw[1]) + sw[2]) + sw[3]) + sw[4]) + sw[5];
+            if (R.dice) R.dice[r] = T.dice[0];
+            if (R.value) R.value[r] = tn > 0 ? tw / (float)tn : 0.0f;
+            if (R.action) { R.action[r * 2] = (int8_t)(best / 3); R.action[r * 2 + 1] = (int8_t)(best % 3); }
+            if (R.live) R.live[r] = 1;
+            dice[0] = (int8_t)(1 + (int)__umulhi(o[1], 6u));
+            g[0] = ply + 1;
+            if (bk == 1) { g[1] = 1; g[2] = (ply & 1) ? -1 : 1; }
+        }
+        goes_on = bk != 1;
+    }
+    __builtin_amdgcn_wave_barrier();                           // this trip's LDS is read: the next may overwrite it
+    return goes_on;
 }
 
 // ewn_lookahead_expand's order of refusals: arguments, geometry, the empty batch, pointers; then the values -- all before the launch

@@ -22,6 +22,7 @@ from ._args import _finite, _not_negative, _positive, _ptr, _stream
 from ._lib import check
 from .a2c import FusedTrainer
 from .endgame import EndgameTable, _accept_table
+from .games import selfplay_puct_games
 from .search import (SELFPLAY_MAX_PLIES, _noise_eps, _play_numbers, _puct_numbers, lookahead_targets, predict_lookahead, predict_puct,
                      selfplay_puct, sup_grad)
 from .sharding import all_reduce_counters
@@ -206,7 +207,7 @@ class PuctSelfPlayTrainer(_SupervisedTrainer):
 
     def __init__(self, env, sims=64, c_puct=1.5, terminal_value=1.0, noise_eps=0.25, noise_alpha=1.0, temp_plies=8, max_plies=None,
                  learning_rate=7e-4, pi_coef=1.0, vf_coef=0.5, max_grad_norm=0.5, rms_alpha=0.99, rms_eps=1e-5, seed=None,
-                 endgame_table=None, chunk=1024, fused=False):
+                 endgame_table=None, chunk=1024, fused=False, whole_games=False):
         who = "PuctSelfPlayTrainer"
         _puct_numbers(who, sims, c_puct, terminal_value)
         _noise_eps(who, noise_eps)
@@ -216,8 +217,11 @@ class PuctSelfPlayTrainer(_SupervisedTrainer):
             raise ValueError("%s: max_plies must be a positive integer or None, got %r" % (who, max_plies))
         if fused and endgame_table is not None:
             raise ValueError("%s: fused=True does not take an endgame_table: the exact-leaf substitution is the staged path's" % who)
+        if whole_games and endgame_table is not None:
+            raise ValueError("%s: whole_games=True does not take an endgame_table: the exact-leaf substitution is the staged path's" % who)
         # endgame_table: exact values at the leaves the table covers (4p), nothing else
         # fused: a ply's search as the one launch of ewn_puct_search (4r): the same records bit for bit
+        # whole_games: all games in the one launch of ewn_puct_selfplay (4s), chunk and fused are then not read: the same records again
         super().__init__(who, env, sims=sims, c_puct=c_puct, terminal_value=terminal_value, fused=fused, pi_coef=pi_coef, vf_coef=vf_coef,
                          endgame_table=endgame_table, learning_rate=learning_rate, max_grad_norm=max_grad_norm, rms_alpha=rms_alpha,
                          rms_eps=rms_eps, n_steps=1, seed=seed, use_graph=False, opponent=None, opponent_update_every=100,
@@ -225,7 +229,7 @@ class PuctSelfPlayTrainer(_SupervisedTrainer):
         self.max_plies = SELFPLAY_MAX_PLIES[env.S] if max_plies is None else int(max_plies)
         self._size_scratch(self.max_plies)
         self.noise_eps, self.noise_alpha, self.temp_plies = float(noise_eps), float(noise_alpha), int(temp_plies)
-        self.chunk = int(chunk)
+        self.chunk, self.whole_games = int(chunk), bool(whole_games)
         self.seed_base, self.seed_counter = (0 if seed is None else int(seed)), 0   # the counter: one per update, saved and resumed
         self.records = None                      # the last update's games (selfplay_puct's dict)
         self._games = [0.0, 0.0, 0.0, 0.0]       # live rows, mean plies, share of finished games, the first mover's share of them
@@ -243,10 +247,15 @@ class PuctSelfPlayTrainer(_SupervisedTrainer):
     def _launch(self):
         env = self.env
         board, dice, first = self.fresh_positions()
-        rec = selfplay_puct(board, dice, self.params, sims=self.sims, max_plies=self.max_plies, c_puct=self.c_puct,
-                            terminal_value=self.terminal_value, noise_eps=self.noise_eps, noise_alpha=self.noise_alpha,
-                            temp_plies=self.temp_plies, key=self.noise_key, game_offset=first, chunk=self.chunk,
-                            endgame_table=self.endgame_table, cube_layer=env.L, fused=self.fused)
+        if self.whole_games:
+            rec = selfplay_puct_games(board, dice, self.params, sims=self.sims, max_plies=self.max_plies, c_puct=self.c_puct,
+                                      terminal_value=self.terminal_value, noise_eps=self.noise_eps, noise_alpha=self.noise_alpha,
+                                      temp_plies=self.temp_plies, key=self.noise_key, game_offset=first, cube_layer=env.L)
+        else:
+            rec = selfplay_puct(board, dice, self.params, sims=self.sims, max_plies=self.max_plies, c_puct=self.c_puct,
+                                terminal_value=self.terminal_value, noise_eps=self.noise_eps, noise_alpha=self.noise_alpha,
+                                temp_plies=self.temp_plies, key=self.noise_key, game_offset=first, chunk=self.chunk,
+                                endgame_table=self.endgame_table, cube_layer=env.L, fused=self.fused)
         self.records = rec
         R, S = self.max_plies * env.N, env.S
         b, d = rec["board"].reshape(R, S, S), rec["dice"].reshape(R).clamp(min=1)         # rows past a game's end hold dice 0
@@ -274,13 +283,15 @@ class PuctSelfPlayTrainer(_SupervisedTrainer):
 
     def _state(self):
         return {**super()._state(), "noise_eps": float(self.noise_eps), "noise_alpha": float(self.noise_alpha),
-                "temp_plies": int(self.temp_plies), "max_plies": int(self.max_plies), "seed_counter": int(self.seed_counter)}
+                "temp_plies": int(self.temp_plies), "max_plies": int(self.max_plies), "seed_counter": int(self.seed_counter),
+                "whole_games": bool(self.whole_games)}
 
     def _load_state(self, sd):
         super()._load_state(sd)
         self.noise_eps, self.noise_alpha = float(sd.get("noise_eps", self.noise_eps)), float(sd.get("noise_alpha", self.noise_alpha))
         self.temp_plies, self.seed_counter = int(sd.get("temp_plies", self.temp_plies)), int(sd.get("seed_counter", self.seed_counter))
         self.fused = self.fused and self.endgame_table is None
+        self.whole_games = bool(sd.get("whole_games", self.whole_games)) and self.endgame_table is None
         if int(sd.get("max_plies", self.max_plies)) != self.max_plies:
             raise ValueError("the checkpoint's games have at most %d plies, this trainer's %d: the update's scratch is sized by it" % (
                 int(sd["max_plies"]), self.max_plies))

@@ -597,6 +597,11 @@ def selfplay_outcomes(winner, live):
     return z.contiguous(), counts.to(torch.float32).contiguous()
 
 
+def _game_column(game, i):
+    """column i of game [M, 4] as a dense tensor of its own: stride 1 at M == 1 too, where .contiguous() hands the strided view back"""
+    return torch.empty(game.shape[0], dtype=game.dtype, device=game.device).copy_(game[:, i])
+
+
 NOISE_BLOCK = 16384     # selfplay_noise draws whole blocks of this many consecutive global games
 
 
@@ -672,6 +677,6 @@ def selfplay_puct(boards, dice, params, sims=64, max_plies=None, c_puct=1.5, ter
                 if (t + 1) % int(check_every) == 0 and bool(cg[:, 1].all()):
                     break
     rec["live"] = rec["live"].view(torch.bool)
-    rec["winner"], rec["plies"] = game[:, 2].contiguous(), game[:, 0].contiguous()
+    rec["winner"], rec["plies"] = _game_column(game, 2), _game_column(game, 0)
     rec["z"], rec["weight"] = selfplay_outcomes(rec["winner"], rec["live"])
     return rec

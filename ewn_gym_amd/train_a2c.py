@@ -35,6 +35,9 @@ def _parser():
     ap.add_argument("--fused", action="store_true",
                     help="SEARCH --search puct, SELFPLAY: the PUCT search in one kernel launch (ewn_puct_search, DESIGN.md 4r) instead of the "
                          "staged launches: the same targets bit for bit; not with --endgame_leaves")
+    ap.add_argument("--whole_games", action="store_true",
+                    help="SELFPLAY: all games of an update in one kernel launch that refills a finished game's column with the next game "
+                         "(ewn_puct_selfplay, DESIGN.md 4s): the same records bit for bit; --fused is then not read; not with --endgame_leaves")
     ap.add_argument("--noise_eps", type=float, default=0.25, help="SELFPLAY: the weight of the Dirichlet noise in the root's priors (0: none)")
     ap.add_argument("--noise_alpha", type=float, default=1.0,
                     help="SELFPLAY: the Dirichlet parameter (about 10 / the number of moves, AlphaZero's rule of thumb: a choice, not a measurement)")
@@ -116,6 +119,10 @@ def main():
         raise SystemExit("--fused is read by SEARCH --search puct and by SELFPLAY only")
     if a.fused and a.endgame_leaves:
         raise SystemExit("--fused does not go with --endgame_leaves: the exact-leaf substitution is the staged search's")
+    if a.whole_games and a.algorithm != "SELFPLAY":
+        raise SystemExit("--whole_games is read by SELFPLAY only")
+    if a.whole_games and a.endgame_leaves:
+        raise SystemExit("--whole_games does not go with --endgame_leaves: the exact-leaf substitution is the staged search's")
     if a.endgame_table is not None and a.algorithm not in ("SEARCH", "SELFPLAY"):
         raise SystemExit("--endgame_table is read by SEARCH and SELFPLAY only")
     if a.endgame_leaves and (a.algorithm not in ("SEARCH", "SELFPLAY") or a.endgame_table is None):
@@ -152,7 +159,8 @@ def main():
         from .distill import PuctSelfPlayTrainer
         trainer = PuctSelfPlayTrainer(env, sims=a.sims, c_puct=a.c_puct, terminal_value=a.terminal_value, noise_eps=a.noise_eps,
                                       noise_alpha=a.noise_alpha, temp_plies=a.temp_plies, max_plies=a.max_plies,
-                                      learning_rate=a.learning_rate, seed=mseed, endgame_table=a.endgame_table, fused=a.fused)
+                                      learning_rate=a.learning_rate, seed=mseed, endgame_table=a.endgame_table, fused=a.fused,
+                                      whole_games=a.whole_games)
     elif a.trainer == "fused" or model_opp is not None or (a.trainer == "auto" and env.supports_policy_rollout()):
         trainer = FusedA2CTrainer(env, n_steps=a.n_steps, learning_rate=a.learning_rate, seed=mseed, **okw)
     else:

@@ -648,6 +648,33 @@ int ewn_puct_search(int board_size, int cube_layer, int M, int sims, int rounds,
                     const int8_t *boards, const int8_t *dice, const float *params,
                     const float *root_noise /* [M][6] or NULL */, float noise_eps, void *tree, void *stream);
 
+/* ---- whole self-play games of the PUCT search in one launch, finished columns refilled ----
+ * ewn_puct_selfplay plays M games from boards [M][S*S], dice [M], game [M][4] (ewn_puct_play's {ply, over, winner, 0}) to their end
+ * or to ply max_plies.  Per ply of a game: ewn_puct_search on its position (round 0 with row (ply * M + m) of `noise` when noise
+ * != NULL), then ewn_puct_play with key and game_offset + m into row `ply` of the record buffers -- rows of [max_plies][M]... with
+ * row stride M, each pointer may be NULL as in ewn_puct_play.  boards, dice and game are updated in place.  Every record row
+ * 0 .. max_plies - 1 of every game is written: rows a game does not play (below the ply it enters with, after its end, all rows of
+ * a game that enters over or with ply outside 0 .. max_plies - 1) are zeros.  The records, boards, dice and game equal what
+ * the ply-by-ply sequence leaves, byte for byte; what scratch or the record buffers held before the call does not matter.
+ * A block has `tile` columns (1 .. 32; 0: the library's choice) and there are `blocks` blocks (1 .. 256; 0: the library's choice),
+ * never more than ceil(M / tile); block b of nb owns games b M / nb .. (b + 1) M / nb - 1, and a column whose game has ended takes
+ * the block's next one.  tile and blocks change no byte of the result.  scratch: blocks x tile trees of ewn_puct_tree_bytes(),
+ * 4-byte aligned; ewn_puct_selfplay_scratch_bytes returns that product for the effective values (0 for M == 0; negative: the
+ * refusal for M, the geometry, sims, tile or blocks).
+ * Refusals in ewn_puct_search's order, all before the launch: EWN_EINVAL for M < 0 or M > INT_MAX / 64; EWN_EUNSUPPORTED by
+ * geometry; EWN_OK without a launch for M == 0; EWN_ENULL for a missing params, boards, dice, game or scratch; then EWN_EINVAL for
+ * sims outside 0 .. 4096, a scratch or game that is not 4-byte aligned, a terminal_value that is not finite and positive, a c_puct
+ * that is not finite and non-negative; for max_plies < 1, temp_plies < 0, tile outside 0 .. 32, blocks outside 0 .. 256; and, only
+ * when noise is given, a noise_eps that is not finite or outside [0, 1].
+ * One kernel launch on `stream`, vector stores only, no atomics, no allocation, no synchronisation; all row offsets are 64-bit. */
+int64_t ewn_puct_selfplay_scratch_bytes(int board_size, int cube_layer, int M, int sims, int tile, int blocks);
+int ewn_puct_selfplay(int board_size, int cube_layer, int M, int sims, int max_plies, float c_puct, float terminal_value,
+                      const float *params, const float *noise /* [max_plies][M][6] or NULL */, float noise_eps,
+                      int temp_plies, uint64_t key, int64_t game_offset, int tile, int blocks,
+                      int8_t *boards, int8_t *dice, int32_t *game,
+                      int8_t *rec_board, int8_t *rec_dice, int32_t *rec_visits, float *rec_value, int8_t *rec_action, int8_t *rec_live,
+                      void *scratch, void *stream);
+
 /* ---- the supervised update on M given observations: targets from outside (a search: expert iteration) ----
  * loss = (1/M) sum_m w_m (pi_coef CE_m + vf_coef (V_m - v*_m)^2),  CE_m = -sum_i p_i logsoftmax_head(i)(logits_m)_i, with
  * p = target_pi[m][0..4] (entries 0-1 the flag head, 2-4 the direction head; the caller makes each head's mass 1, or 0 to mask the

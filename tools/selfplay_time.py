@@ -11,6 +11,10 @@ device event between the stages; median (min, max) of `--runs` windows after a w
 Part 3, 5x5: `--updates` updates of PuctSelfPlayTrainer from a fresh network, then over `--episodes` episodes (seeds 0 .. n-1,
 MT19937-compat dice) the wins of its argmax policy and of predict_puct(sims=64) on it against RandomAgent and against minimax(5), with
 Wilson 95 % intervals (DESIGN.md sets 4m's A2C and SEARCH rows beside them: this tool does not train those again).
+With --whole_games only this runs: per board (--boards), batch (--M) and budget (--sims) the recorded positions
+per second of selfplay_puct(fused=True) at chunk 1 024, 4 096 and 16 384 (those not above M, and M itself) and of selfplay_puct_games
+at every --tile (0: the library's choice) and --blocks, all alternated in one process, windows as in part 1.  The first call of every
+case is checked against the first case's records, byte for byte.
 Prints one JSON line per row.  No pass bar: nothing here was measured before."""
 import argparse
 import ctypes as C
@@ -70,6 +74,41 @@ def part1(runs):
         pps = [x[0] for x in r]
         print(json.dumps({"board": S, "M": M, "sims": sims, "positions_per_s_median_min_max": [round(statistics.median(pps)), round(min(pps)), round(max(pps))],
                           "positions_per_call": r[0][1], "seconds_per_call_median": round(statistics.median(x[2] for x in r), 3)}), flush=True)
+
+
+def part_games(runs, boards, batches, budgets, tiles, blocks):
+    for S in boards:
+        torch.manual_seed(9)
+        params = ActorCritic(S, 6).cuda().flat_parameters()
+        for M in batches:
+            b, d = openings(S, M)
+            for sims in budgets:
+                cases = {}
+                for chunk in sorted({min(c, M) for c in (1024, 4096, 16384)}):
+                    cases[("fused", chunk, 0)] = lambda chunk=chunk: ea.selfplay_puct(b, d, params, sims=sims, key=3, fused=True, chunk=chunk)
+                for tile in tiles:
+                    cases[("whole_games", tile, blocks)] = lambda tile=tile: ea.selfplay_puct_games(b, d, params, sims=sims, key=3, tile=tile or None,
+                                                                                                    blocks=blocks or None)
+                first, rates = None, {k: [] for k in cases}
+                for k, fn in cases.items():                           # warm-up, and the records are the same on every path
+                    rec = fn()
+                    first = rec if first is None else first
+                    assert all(torch.equal(rec[name], first[name]) for name in first), k
+                for _ in range(runs):                                 # alternated
+                    for k, fn in cases.items():
+                        s, n = window(fn)
+                        rates[k].append((n / s, n, s))
+                # the whole-games path draws the noise of all max_plies plies up front, the ply loop only the plies it plays
+                T = ea.search.SELFPLAY_MAX_PLIES[S]
+                draw = [window(lambda: {"live": torch.stack([ea.selfplay_noise(M, 1.0, 3, 0, t) for t in range(T)])[0, :, 0] > 0})[0] for _ in range(runs + 1)][1:]
+                print(json.dumps({"board": S, "M": M, "sims": sims, "noise_of_all_%d_plies_seconds_median_min_max" % T:
+                                  [round(statistics.median(draw), 5), round(min(draw), 5), round(max(draw), 5)],
+                                  "longest_game_plies": int(first["plies"].max()), "mean_game_plies": round(float(first["plies"].float().mean()), 2)}), flush=True)
+                for (path, x, y), r in rates.items():
+                    pps = [v[0] for v in r]
+                    print(json.dumps({"board": S, "M": M, "sims": sims, "path": path, **({"chunk": x} if path == "fused" else {"tile": x, "blocks": y}),
+                                      "positions_per_s_median_min_max": [round(statistics.median(pps)), round(min(pps)), round(max(pps))],
+                                      "positions_per_call": r[0][1], "seconds_per_call_median": round(statistics.median(v[2] for v in r), 4)}), flush=True)
 
 
 def part2(runs):
@@ -157,7 +196,15 @@ def main():
     ap.add_argument("--episodes", type=int, default=1024)
     ap.add_argument("--skip_timing", action="store_true")
     ap.add_argument("--skip_learning", action="store_true")
+    ap.add_argument("--whole_games", action="store_true", help="only the comparison of selfplay_puct(fused=True) with selfplay_puct_games")
+    ap.add_argument("--boards", type=int, nargs="+", default=[5, 7])
+    ap.add_argument("--M", type=int, nargs="+", default=[1024, 4096, 16384, 65536])
+    ap.add_argument("--sims", type=int, nargs="+", default=[16, 64])
+    ap.add_argument("--tile", type=int, nargs="+", default=[0, 4, 8, 16, 32], help="--whole_games: columns per block, 0 the library's choice")
+    ap.add_argument("--blocks", type=int, default=256, help="--whole_games: blocks, 0 the library's choice")
     a = ap.parse_args()
+    if a.whole_games:
+        return part_games(a.runs, a.boards, a.M, a.sims, a.tile, a.blocks)
     if not a.skip_timing:
         part1(a.runs)
         part2(a.runs)
