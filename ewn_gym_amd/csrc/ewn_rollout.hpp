@@ -19,6 +19,11 @@
 
 // Diagnostic build only (tools/rollout_stamps.py, -DEWN_ROLLOUT_STAMPS): s_memtime at the phase boundaries of a step, summed over the
 // K steps of a launch per wave and written over the (then meaningless) return_sum buffer.  Never defined in the shipped library.
+// Diagnostic builds only: which levers of the slot-task kernel's derived tables are on (see k_rollout_slots)
+#ifndef EWN_MT_LEVERS
+#define EWN_MT_LEVERS 3
+#endif
+
 #ifdef EWN_ROLLOUT_STAMPS
 #define RSTAMP(i) do { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); st_acc[i] += t_ - st_prev; st_prev = t_; } while (0)
 #else
@@ -229,6 +234,68 @@ EWN_DEV void roll_opponent_half(const FastTab<S> *Tb, RState<S> &s, u32 e, int o
     roll_opponent_move<S>(Tb, s, k, pb, q, dice, r, R, reward, term, info, slot);
 }
 
+// ---- the same pieces on the slot-task kernel's derived tables (ewn_movetab.hpp): m0 / m1 are the fused entries of the two cubes
+// the dice selects (first and second byte of pk_pair(s.posN, e)), read together by the caller; everything else about the agent's
+// move -- legal directions, destination, both real cells -- comes out of them by byte extraction.
+
+template <int S>
+EWN_DEV void roll_stand_in_action(const FastTab<S> *Tb, const MoveEnt &m0, const MoveEnt &m1, u32 e, LaneRng &r, const RollCfg &c, int game, int &aflag, int &adir)
+{
+    const u32 okm = me_legal(m0) | (me_legal(m1) << 3);
+    const int n = __popc(okm);
+    const u32 w = agent_hash(r.seed_mix(), r.draws(), (u32)(c.lane_offset + game), c.key);
+    if (c.agent_sample) {
+        const int a6 = (int)__umulhi(w, 6u);
+        aflag = a6 >= 3 ? 1 : 0;
+        adir = a6 - 3 * aflag;
+    } else if (n > 0) {
+        const int slot = Tb->nth[okm * 8u + __umulhi(w, (u32)n)];
+        aflag = slot < 3 ? (int)(e >> 15) : 0;
+        adir = slot < 3 ? slot : slot - 3;
+    }
+}
+
+// slot_move on REAL cells, no table: the source cell is byte (shp / 8) of w, the destination byte (shq / 8).  With T > 1 a lane
+// extracts only the cell it stores to: one select between the two shifts (loop-invariant where they are constants) and one v_bfe
+template <int T>
+EWN_DEV void slot_move_real(int8_t *slot, int sub, u32 w, int shp, int shq, int v)
+{
+    if constexpr (T == 1) { slot[(w >> shp) & 0xFFu] = 0; slot[(w >> shq) & 0xFFu] = (int8_t)v; }
+    else {
+        const bool dst = sub == 1;
+        if (sub < 2) slot[(w >> (dst ? shq : shp)) & 0xFFu] = (int8_t)(dst ? v : 0);
+    }
+}
+
+template <int S, int T>
+EWN_DEV bool roll_agent_half(RState<S> &s, const MoveEnt &m0, const MoveEnt &m1, u32 e, int aflag, int adir, int &dice, LaneRng &r, double R,
+                             double &reward, int &term, int &trunc, int &info, int8_t *slot, int sub)
+{
+    const bool first = aflag == 1 || ((e >> 8) & 7u) == 6u; // pk_cube's choice between the two
+    const int k = pk_cube(e, aflag == 1);
+    MoveEnt m;
+    m.mv = first ? m0.mv : m1.mv; m.rc = first ? m0.rc : m1.rc;
+    const int q = me_dest(m, adir); // no cube at all: byte 6 -> 255
+    if (q == 255) { reward = -R; term = 1; trunc = 1; info = EWN_INFO_INVALID_PLAYER; return false; }
+    if (slot) slot_move_real<T>(slot, sub, m.rc, 0, 8 + 8 * adir, k + 1); // the agent's cube k is the real +(k + 1)
+    rs_move<S, false>(s, k, q);
+    constexpr RingGeo<S> G{};   // Tb->ri_origin, the ring index of cell (0, 0), is a constant of the ring order
+    if (q == G.ring_of_rm[0] || s.P == 0) { reward = R; term = 1; info = EWN_INFO_WON; return false; }
+    dice = r.randint(1, 7);
+    return true;
+}
+
+// opponent half once its move is known, with the move's real cells: bytes (shp / 8) and (shq / 8) of w
+template <int S, int T>
+EWN_DEV void roll_opponent_move_real(RState<S> &s, int k, int q, u32 w, int shp, int shq, int &dice, LaneRng &r, double R,
+                                     double &reward, int &term, int &info, int8_t *slot, int sub)
+{
+    if (slot) slot_move_real<T>(slot, sub, w, shp, shq, -(k + 1));
+    rs_move<S, true>(s, k, q);
+    if (q == FastTab<S>::CELLS - 1 || s.N == 0) { reward = -R; term = 1; info = EWN_INFO_LOST; }
+    else dice = r.randint(1, 7);
+}
+
 // AGENT 0: RandomAgent (the hash-driven uniform legal pick of ewn_step_out.random_action); 1: ExpectiMinimaxAgent of
 // max_depth 1-4 ('hybrid'); 2: of max_depth 5-6.  OPP as in k_step_d3: 0 minimax max_depth 1-4, 1 RandomAgent, 2 minimax 5-6.
 // H2: the opponent's search runs on the 'two_min_dist' table image (envs/minimax_ewn.py:133-178; a side's index is the sum of its two
@@ -437,12 +504,16 @@ __global__ __launch_bounds__(D3_BS, (OPP == 2 ? 2 : 1)) void k_rollout_slots(Rol
     constexpr int CELLS = S * S, GPB = D3_BS / T;   // games per block
     constexpr int TS = T > 2 ? 2 : T;               // lanes per game the depth-5 search can use
     constexpr int STR = RecGeo<S>::STR;             // LDS bytes per game: the game's board slot, one trajectory record wide
-    __shared__ __attribute__((aligned(16))) int8_t lds_st[GPB * STR + FAST_TAB_BYTES(S) + GPB * 16];
+    // the levers of the derived tables, for A/B builds (-DEWN_MT_LEVERS=n): 1 = the agent half and the max_depth 5 / 6 opponent's move,
+    // 2 = the search entry with the max_depth 1-4 opponent's move.  The library ships both.
+    constexpr bool MT_BND = (EWN_MT_LEVERS & 1) != 0, MT_SRCH = (EWN_MT_LEVERS & 2) != 0;
+    __shared__ __attribute__((aligned(16))) int8_t lds_st[GPB * STR + FAST_TAB_BYTES(S) + GPB * 16 + SlotTabGeo<S>::EXTRA];
     int8_t *lds = lds_st;
     int8_t *tb = lds + GPB * STR;
     tables_to_lds<FAST_TAB_BYTES(S)>(tb, (const int8_t *)B.tables); // LDS-DMA, waited for at the barrier
     const FastTab<S> *Tb = (const FastTab<S> *)tb;
     uint8_t *garr = (uint8_t *)(tb + FAST_TAB_BYTES(S));
+    const SlotTabs<S> D = slot_tabs_at<S>(tb, (int8_t *)garr + GPB * 16); // derived tables (ewn_movetab.hpp), built below
 
     const int g0 = (int)blockIdx.x * GPB, ng = min(GPB, c.N - g0);
     const int gl = threadIdx.x / T, sub = threadIdx.x % T, game = g0 + gl;
@@ -463,6 +534,8 @@ __global__ __launch_bounds__(D3_BS, (OPP == 2 ? 2 : 1)) void k_rollout_slots(Rol
     r.begin_kernel();
     lds_dma_wait();
     __syncthreads();
+    // the image is in LDS: one derived entry per thread, in front of the barrier the loop waits behind anyway
+    for (int e = threadIdx.x; e < 256; e += D3_BS) slot_tabs_build<S>(Tb, D, e);
     RState<S> s;
     d3_decode<S, T>(live ? lds + gl * CELLS : lds, sub, garr + gl * 16, s);
     __syncthreads();                                // every game is in registers: the board area becomes the per-game slots
@@ -492,31 +565,42 @@ __global__ __launch_bounds__(D3_BS, (OPP == 2 ? 2 : 1)) void k_rollout_slots(Rol
         if (start) {
             reward = 0.0; term = frozen ? 1 : 0; trunc = 0; info = EWN_INFO_NONE; reply = false; aflag = 0; adir = 0;
             const u32 esel = pk_sel<S>(Tb, s.posN, dice);
-            roll_stand_in_action<S>(Tb, s, esel, r, c, game, aflag, adir);
+            [[maybe_unused]] MoveEnt m0 = {}, m1 = {};
+            if constexpr (MT_BND) {
+                const u32 pp = pk_pair(s.posN, esel);
+                m0 = me_read(D.mvn, (int)(pp & 0xFFu)); m1 = me_read(D.mvn, (int)((pp >> 8) & 0xFFu)); // the two candidate cubes' entries, together
+                roll_stand_in_action<S>(Tb, m0, m1, esel, r, c, game, aflag, adir);
+            } else roll_stand_in_action<S>(Tb, s, esel, r, c, game, aflag, adir);
             if (active) { // a frozen lane's stream stays where its last step left it
                 if constexpr (RNGK == 0) r.prefetch();
                 r.begin_step();
                 // the game's two lanes share the step's Philox block (the lanes of a game take the same branches)
                 if constexpr (RNGK == 1) { if constexpr (T == 2) r.ps.prime_pair(sub); else r.ps.prime(); }
-                reply = roll_agent_half<S, T>(Tb, s, esel, aflag, adir, dice, r, c.reward, reward, term, trunc, info, slot_m, sub);
+                if constexpr (MT_BND) reply = roll_agent_half<S, T>(s, m0, m1, esel, aflag, adir, dice, r, c.reward, reward, term, trunc, info, slot_m, sub);
+                else reply = roll_agent_half<S, T>(Tb, s, esel, aflag, adir, dice, r, c.reward, reward, term, trunc, info, slot_m, sub);
             }
         }
         RSTAMP(0); // start of an env step: the agent's action, RNG block, agent half
         // one cube's three roots of the opponent's search, run by every lane (lanes without a pending reply compute on a harmless
         // state, so the DPP exchanges inside always see their partners)
         bool second = false;
-        if constexpr (OPP == 0) best = d3_search<S, T, H2, true>(Tb, s, dice, sub, c.depth, oflag, odir, phase, best, &second, &omove);
+        if constexpr (OPP == 0) best = d3_search<S, T, H2, true, MT_SRCH>(Tb, s, dice, sub, c.depth, oflag, odir, phase, best, &second, &omove, &D);
         else best = d5c_search<S, TS, true>(Tb, s, dice, T > 2 ? (sub & 1) : sub, oflag, odir, phase, best, &second);
         RSTAMP(1); // search
         if (pending && phase == 0 && reply && second) phase = 1; // the same env step goes on with the second cube
         else if (pending) {
             phase = 0;
             if (reply) {
-                if constexpr (OPP == 0) { // the search's chosen root is the move
+                if constexpr (OPP == 0 && MT_SRCH) { // the search's chosen root is the move, real cells included
+                    roll_opponent_move_real<S, T>(s, (int)(omove & 7u), (int)((omove >> 8) & 0xFFu), omove, 16, 24, dice, r, c.reward, reward, term, info, slot_m, sub);
+                } else if constexpr (OPP == 0) {
                     roll_opponent_move<S, T>(Tb, s, (int)(omove & 7u), (int)((omove >> 8) & 0xFFu), (int)(omove >> 16), dice, r, c.reward, reward, term, info, slot_m, sub);
                 } else {
                     const int k = pk_cube(pk_sel<S>(Tb, s.posP, dice), oflag == 1), pb = pk_get(s.posP, k);
-                    roll_opponent_move<S, T>(Tb, s, k, pb, Tb->nbp[odir][pb], dice, r, c.reward, reward, term, info, slot_m, sub);
+                    if constexpr (MT_BND) {
+                        const MoveEnt mp = me_read(D.mvp, pb);
+                        roll_opponent_move_real<S, T>(s, k, me_dest(mp, odir), mp.rc, 0, 8 + 8 * odir, dice, r, c.reward, reward, term, info, slot_m, sub);
+                    } else roll_opponent_move<S, T>(Tb, s, k, pb, Tb->nbp[odir][pb], dice, r, c.reward, reward, term, info, slot_m, sub);
                 }
             }
             if (!frozen) {

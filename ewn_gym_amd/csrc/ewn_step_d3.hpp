@@ -16,6 +16,7 @@
 //    T lanes; only sub-lane 0 stores.
 #pragma once
 #include "ewn_fast.hpp"
+#include "ewn_movetab.hpp"
 
 // ---- compile-time ring geometry (same order as build_fast_tables: ascending min(row,col), row-major inside a level)
 template <int S>
@@ -276,10 +277,16 @@ template <int T> EWN_DEV void publish(u32 mine, int i, u32 (&out)[6])
 // cube | its position byte << 8 | destination ring cell << 16 -- what the opponent half would otherwise look up again
 // (set whenever a valid root exists, which it does for every position whose game goes on: only the corner a TOP_LEFT cube wins
 // on has no legal direction)
-template <int S, int T, bool H2 = false, bool PERLANE = false>
+// MT (the slot-task rollout kernel only, with PERLANE): D = the block's derived tables (ewn_movetab.hpp).  The root cube's three
+// destinations and the real cells of its moves are ONE 8-byte read, a replier cube's setup two or three wide reads, and bmove becomes
+// cube | destination ring cell << 8 | REAL source cell << 16 | REAL destination cell << 24: the caller's two byte stores into the
+// game's board slot need no table either.
+template <int S, int T, bool H2 = false, bool PERLANE = false, bool MT = false>
 __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S> &c, int dice, int sub, int depth, int &bflag, int &bdir,
-                                            int slotL = 0, double best_in = 0.0, bool *have_second = nullptr, u32 *bmove = nullptr)
+                                            int slotL = 0, double best_in = 0.0, bool *have_second = nullptr, u32 *bmove = nullptr,
+                                            [[maybe_unused]] const SlotTabs<S> *D = nullptr)
 {
+    static_assert(!MT || PERLANE, "the derived tables serve the per-lane search entry");
     typedef typename MaskOf<S>::type M;
     constexpr int KPT = 6 / T + (6 % T ? 1 : 0); // replier cubes / dice values per lane: k = sub + T*i
     const M one = 1;
@@ -295,8 +302,17 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
     const int flag0 = (int)(rsel >> 15);
     const int rp0 = rb0 & 63, rp1 = rb1 & 63;
     // (cube | position byte << 8) of the two root cubes, for bmove
-    const u32 rm0 = (rsel & 7u) | ((rpp & 0xFFu) << 8), rm1 = ((rsel >> 8) & 7u) | (rpp & 0xFF00u);
+    u32 rm0 = (rsel & 7u) | ((rpp & 0xFFu) << 8), rm1 = ((rsel >> 8) & 7u) | (rpp & 0xFF00u);
     u32 bm = 0;
+    // MT: the call's root cube's fused entry (a position byte that is off the board reads "no legal direction, destinations 255").
+    // rm0 = the entry's destination word with the cube in place of the legal mask: the packed move of direction d is then ONE
+    // byte permute of (real cells, rm0) -- bytes 0 and 1 + d of rm0, bytes 0 and 1 + d of the real cells
+    [[maybe_unused]] MoveEnt me0 = {};
+    if constexpr (MT) {
+        me0 = me_read(D->mvp, rb0);
+        rm0 = (me0.mv & 0xFFFFFF00u) | (rsel & 7u);
+    }
+    #define D3_BM_SEL(d) (0x05040100u + (u32)(d) * 0x01000100u)
 
     double best = -__builtin_inf(); // alpha = max(alpha, best_val): the running best (root beta stays +inf)
     if constexpr (PERLANE) {
@@ -309,11 +325,15 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
         // max_depth 1 and 2 bottom out before the replier moves (classical_policies/minimax.py:19-73: every node, chance nodes
         // included, spends one unit of depth): depth 1 evaluates the position after the root move at the chance node; depth 2
         // at the six min nodes below it, i.e. evaluate()/6 summed six times in dice order.  Every lane of the group does all six roots.
+        [[maybe_unused]] MoveEnt me1 = {}; // MT: the second root cube's entry, made up like the first one's
+        if constexpr (MT) { me1 = me_read(D->mvp, rb1); me1.mv = (me1.mv & 0xFFFFFF00u) | ((rsel >> 8) & 7u); }
         #pragma unroll 1
         for (int r = 0; r < 6; r++) {
             const int slot = r >= 3 ? 1 : 0, dir = r - 3 * slot;
             const int rp = slot == 0 ? rp0 : rp1;
-            const int dest = Tb->nbp[dir][rp];
+            int dest;
+            [[maybe_unused]] const u32 rcw = slot == 0 ? me0.rc : me1.rc, mvw = slot == 0 ? rm0 : me1.mv;
+            if constexpr (MT) dest = (int)((mvw >> (8 + 8 * dir)) & 0xFFu); else dest = Tb->nbp[dir][rp];
             const bool valid = (slot == 0 ? have0 : have1) && dest != 255;
             const M bd = valid ? (one << dest) : (M)0;
             const M P1 = (c.P & ~(one << rp)) | bd;
@@ -325,7 +345,11 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
             #pragma unroll
             for (int d = 0; d < 6; d++) v = v + e6;
             v = term ? 10.0 : (depth == 1 ? e1 : v);
-            if (valid && v > best) { best = v; bflag = slot == 0 ? flag0 : 0; bdir = dir; bm = (slot == 0 ? rm0 : rm1) | ((u32)dest << 16); }
+            if (valid && v > best) {
+                best = v; bflag = slot == 0 ? flag0 : 0; bdir = dir;
+                if constexpr (MT) bm = __builtin_amdgcn_perm(rcw, mvw, D3_BM_SEL(dir));
+                else bm = (slot == 0 ? rm0 : rm1) | ((u32)dest << 16);
+            }
         }
         if constexpr (PERLANE) { *have_second = false; if (bmove) *bmove = bm; } // both cubes were searched in this one call
         return best;
@@ -344,6 +368,21 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
         const int rb = pk_get(c.posN, k < 6 ? k : 6);
         rnk[i] = rb & 63;
         rclr[i] = ~(one << rnk[i]);
+        if constexpr (MT) {
+            // the cube's entry, whole: 16-byte pieces and the tail
+            const ReplyEnt<S> *re = D->rep + rb;
+            u32 kf[3];
+            if constexpr (sizeof(M) == 4) {
+                const uint4 a = *(const uint4 *)re; const uint2 b = *((const uint2 *)re + 2);
+                rset[i][0] = a.x; rset[i][1] = a.y; rset[i][2] = a.z; kf[0] = a.w; kf[1] = b.x; kf[2] = b.y;
+            } else {
+                const uint4 a = *(const uint4 *)re, b = *((const uint4 *)re + 1); const u32 t = *((const u32 *)re + 8);
+                rset[i][0] = ((u64)a.y << 32) | a.x; rset[i][1] = ((u64)a.w << 32) | a.z; rset[i][2] = ((u64)b.y << 32) | b.x;
+                kf[0] = b.z; kf[1] = b.w; kf[2] = t;
+            }
+            #pragma unroll
+            for (int d = 0; d < 3; d++) { keep[i][d] = kf[d]; fixed[i][d] = kf[d] >> 16; }
+        } else {
         #pragma unroll
         for (int d = 0; d < 3; d++) {
             const u32 kf = Tb->rkf[d][rb];
@@ -351,10 +390,13 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
             keep[i][d] = kf;              // its low half is the mask: rank addresses stay below 2^13, so the high half ANDs with zeros
             fixed[i][d] = kf >> 16;
         }
+        }
     }
 
     // the six root destinations, read before the loop: inside it the read's whole latency stood in front of every root
-    const u32 dq0 = (u32)Tb->nbp[0][rp0] | ((u32)Tb->nbp[1][rp0] << 8) | ((u32)Tb->nbp[2][rp0] << 16);
+    u32 dq0;
+    if constexpr (MT) dq0 = me0.mv >> 8;
+    else dq0 = (u32)Tb->nbp[0][rp0] | ((u32)Tb->nbp[1][rp0] << 8) | ((u32)Tb->nbp[2][rp0] << 16);
     [[maybe_unused]] u32 dq1 = 0;
     if constexpr (!PERLANE) dq1 = (u32)Tb->nbp[0][rp1] | ((u32)Tb->nbp[1][rp1] << 8) | ((u32)Tb->nbp[2][rp1] << 16);
 
@@ -368,7 +410,8 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
         const int slot = PERLANE ? 0 : (r >= 3 ? 1 : 0), dir = PERLANE ? r : r - 3 * slot;   // PERLANE: the call's cube sits in slot 0
         const int rp = slot == 0 ? rp0 : rp1;
         const int dest = (int)(((slot == 0 ? dq0 : dq1) >> (8 * dir)) & 0xFFu);
-        const bool valid = (slot == 0 ? have0 : have1) && dest != 255;
+        // (MT: the fused entry of a cube that is off the board holds destinations 255 by itself)
+        const bool valid = MT ? dest != 255 : ((slot == 0 ? have0 : have1) && dest != 255);
         const M bd = valid ? (one << dest) : (M)0;
         const M P1 = (c.P & ~(one << rp)) | bd; // own capture: the bit is already set, the count drops by itself
         const M N1 = c.N & ~bd;
@@ -470,9 +513,14 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
         #pragma unroll
         for (int d = 1; d < 6; d++) v = v + ft_val6<S>(Tb, wq[d]);
         v = term ? 10.0 : v;
-        if (valid && v > best) { best = v; bflag = slot == 0 ? flag0 : 0; bdir = dir; if constexpr (PERLANE) bm = rm0 | ((u32)dest << 16); }
+        if (valid && v > best) {
+            best = v; bflag = slot == 0 ? flag0 : 0; bdir = dir;
+            if constexpr (MT) bm = __builtin_amdgcn_perm(me0.rc, rm0, D3_BM_SEL(dir));
+            else if constexpr (PERLANE) bm = rm0 | ((u32)dest << 16);
+        }
     }
     D3_PRIO_LO();
+    #undef D3_BM_SEL
     if constexpr (PERLANE) { if (bmove) *bmove = bm; }
     return best;
 }
