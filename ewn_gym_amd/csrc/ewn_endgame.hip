@@ -130,6 +130,19 @@ __global__ __launch_bounds__(EG_NT) void k_endgame_level(float *tbl, EgGeo g, Eg
     tbl[g.off[ka][ko] + (long long)ia * (long long)eg_n<S>(ko) + (long long)io] = eg_value<S>(tbl, g, Ma, Mo, pa, po);
 }
 
+// The build's clear.  A kernel and not hipMemsetAsync: captured into a hipGraph, a memset node of value 0 is not replayed faithfully
+// by the ROCm 7.0 runtime (from the second replay on it writes an 8-byte pattern that is not zero; tests/test_gpu_stream_contract.py).
+// A table is 4-byte aligned only: `head` entries (0 .. 3) up to the first 16-byte boundary, n4 groups of four, `tail` entries (0 .. 3).
+#define EG_CLEAR_BLOCKS 2048
+__global__ __launch_bounds__(EG_NT) void k_endgame_clear(float *tbl, int head, long long n4, int tail)
+{
+    const long long id = (long long)blockIdx.x * EG_NT + threadIdx.x, stride = (long long)gridDim.x * EG_NT;
+    float4 *body = (float4 *)(tbl + head);
+    for (long long i = id; i < n4; i += stride) body[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (id < head) tbl[id] = 0.0f;
+    if (id < tail) tbl[head + 4 * n4 + id] = 0.0f;
+}
+
 struct EgLookBuf { const float *tbl; const int8_t *boards; const int8_t *dice; int8_t *actions; float *q; float *value; uint8_t *covered; };
 
 // a lane per observation: the work is a handful of dependent gathers, nothing a wave could share
@@ -202,7 +215,14 @@ static int eg_build(int K, int T, float *table, long long entries, const EgGeo &
     EgLevel L;
     for (int level = 2; level <= 2 * T * (S - 1); level++)       // every level's grid must fit before anything is launched
         if (eg_level(S, K, T, level, L) > 0x7FFFFFFFull) return EWN_EUNSUPPORTED;
-    if (hipMemsetAsync(table, 0, (size_t)entries * sizeof(float), s) != hipSuccess) return EWN_ELAUNCH;
+    {
+        const long long to16 = (long long)(((16 - ((uintptr_t)table & 15)) & 15) / sizeof(float));
+        const long long head = to16 < entries ? to16 : entries, n4 = (entries - head) / 4, tail = entries - head - 4 * n4;
+        const long long need = (n4 + EG_NT - 1) / EG_NT;
+        k_endgame_clear<<<dim3((unsigned)(need < 1 ? 1 : (need < EG_CLEAR_BLOCKS ? need : EG_CLEAR_BLOCKS))), dim3(EG_NT), 0, s>>>(table, (int)head, n4, (int)tail);
+        const int rc = launch_status();
+        if (rc != EWN_OK) return rc;
+    }
     for (int level = 2; level <= 2 * T * (S - 1); level++) {     // Phi >= 2: a live position has a cube a side, neither on its corner
         const unsigned long long wg = eg_level(S, K, T, level, L);
         // A level goes out in launches of at most EG_MAX_GRID workgroups.  The runtime takes a grid of 2^24 workgroups of 256 threads

@@ -341,6 +341,15 @@ __global__ __launch_bounds__(BS) void k_apply_action(Geom g, int M, const int8_t
     if (valid) valid[m] = ok ? 1 : 0;
 }
 
+// wins [M] = 0 before the playout kernels add to it.  A kernel and not hipMemsetAsync: captured into a hipGraph, a memset node of
+// value 0 is not replayed faithfully by the ROCm 7.0 runtime (from the second replay on it writes an 8-byte pattern that is not
+// zero; tests/test_gpu_stream_contract.py), and the header promises that every call can be captured
+__global__ __launch_bounds__(BS) void k_zero_wins(int M, int32_t *wins)
+{
+    const long long m = (long long)blockIdx.x * BS + threadIdx.x;
+    if (m < M) wins[m] = 0;
+}
+
 // MinimaxEnv.simulate, envs/minimax_ewn.py:215-238: one thread per (position, playout); any cube_layer
 template <int NW>
 __global__ __launch_bounds__(BS) void k_playout_wins(Geom g, int M, int n_sims, const int8_t *boards, int first_player, u64 key,
@@ -1184,16 +1193,17 @@ int ewn_playout_wins(int board_size, int cube_layer, int M, const int8_t *boards
     if (M == 0) return EWN_OK;
     if (!wins) return EWN_ENULL;
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(wins, 0, (size_t)M * sizeof(int32_t), s) != hipSuccess) return EWN_ELAUNCH;
-    if (g.CN <= 6 && g.S <= 8) {
-        const int gl = playout_group_log2(n_sims);
-        const long long threads = (long long)M << gl;
-        if (threads > 0x7fffffffll * BS) return EWN_EINVAL;
+    const bool lean = g.CN <= 6 && g.S <= 8;
+    const int gl = playout_group_log2(n_sims);
+    const long long threads = lean ? (long long)M << gl : (long long)M * n_sims;
+    if (threads > 0x7fffffffll * BS) return EWN_EINVAL;          // before the clear: a refusal writes nothing
+    k_zero_wins<<<GRID(M), BS, 0, s>>>(M, wins);
+    rc = launch_status();
+    if (rc) return rc;
+    if (lean) {
         k_playout_wins_lean<<<GRID(threads), BS, 0, s>>>(g, M, n_sims, gl, boards, first_player, key, wins);
         return launch_status();
     }
-    const long long threads = (long long)M * n_sims;
-    if (threads > 0x7fffffffll * BS) return EWN_EINVAL;
     BY_NW(g, (k_playout_wins<NWV><<<GRID(threads), BS, 0, s>>>(g, M, n_sims, boards, first_player, key, wins)));
     return launch_status();
 }

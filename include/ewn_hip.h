@@ -17,11 +17,12 @@
  *  - `stream` is a hipStream_t passed as void* (NULL = the null stream).
  *  - Return value: 0 on success, a negative EWN_E* code otherwise (never throws,
  *    never aborts).  ewn_strerror() maps a code to text.
- *  - No hidden global state beyond five tuning overrides, each read once per
- *    process from the environment and selecting only a launch shape or a kernel
- *    instance: EWN_D3_T, EWN_ROLLOUT_T, EWN_ROLLOUT_SLOTS, EWN_MCTS_GPB and
- *    EWN_EVAL_NT.  A call is thread-safe w.r.t. other calls that do not share
- *    buffers.
+ *  - No hidden global state beyond six tuning overrides read from the
+ *    environment, each selecting only a launch shape or a kernel instance.  Five
+ *    are latched -- read once per process, by the first call that needs them:
+ *    EWN_D3_T, EWN_ROLLOUT_T, EWN_ROLLOUT_SLOTS, EWN_MCTS_GPB and EWN_EVAL_NT.
+ *    The sixth, EWN_PUCT_TILE, is read at every call (see ewn_puct_search).  A
+ *    call is thread-safe w.r.t. other calls that do not share buffers.
  *  - Boards are int8, row-major [lane][row][col], value k>0 = TOP_LEFT cube k,
  *    k<0 = BOTTOM_RIGHT cube |k|, 0 = empty (envs/ewn.py:49-58, 94-107).
  *  - Actions are int8 [lane][2] = {chose_larger in {0,1}, direction in {0,1,2}}

@@ -16,7 +16,7 @@ torch = pytest.importorskip("torch")
 from tests.guarded_alloc import GuardedAllocator  # noqa: E402
 from tests.test_gpu_predict_policy import bits, pool  # noqa: E402
 from tests.test_gpu_puct_fused import planted  # noqa: E402
-from tests.test_gpu_puct_selfplay import ROWS, by_hand, check_rules, reset_positions, same_records, selfplay_trainer  # noqa: E402
+from tests.test_gpu_puct_selfplay import ROWS, by_hand, check_rules, reset_positions, row_shapes, same_records, selfplay_trainer  # noqa: E402
 
 GEOMETRIES = ((None, None), (32, 1), (2, 1), (3, 2), (1, 5))   # (tile, blocks); None: the library's choice
 MAX_PLIES = {5: 80, 7: 128}
@@ -97,9 +97,7 @@ def abi_call(ea, S, b, d, params, sims, T, tile, blocks, key, off, temp_plies=8,
     lib, M = ea._lib.load(), b.shape[0]
     z = (lambda shape, dtype, tag: alloc.zeros(shape, dtype=dtype, tag=tag)) if alloc is not None else (
         lambda shape, dtype, tag: torch.zeros(shape, dtype=dtype, device="cuda"))
-    shapes = dict(board=((S, S), torch.int8), dice=((), torch.int8), visits=((2, 3), torch.int32), value=((), torch.float32),
-                  action=((2,), torch.int8), live=((), torch.int8))
-    rec = {k: z((T, M) + s, dt, "rec_" + k) for k, (s, dt) in shapes.items() if k != skip}
+    rec = {k: z((T, M) + s, dt, "rec_" + k) for k, (s, dt) in row_shapes(S).items() if k != skip}
     nscr = int(lib.ewn_puct_selfplay_scratch_bytes(S, 3, M, sims, tile, blocks))
     assert nscr == lib.ewn_puct_tree_bytes(S, 3, sims) * min(blocks, -(-M // tile)) * tile
     scratch = z((nscr,), torch.uint8, "scratch")

@@ -25,6 +25,14 @@ from tests.test_gpu_puct import F, P_TOL, Model, compare, edges, flip, host_view
 
 NOISE_TOL = P_TOL + 16 * 2.0 ** -24
 ROWS = ("board", "dice", "visits", "value", "action", "live")
+
+
+def row_shapes(S):
+    """a record row's (shape per game, dtype) by name, in the order of ROWS: ewn_puct_play's rec_* arguments"""
+    return dict(board=((S, S), torch.int8), dice=((), torch.int8), visits=((2, 3), torch.int32), value=((), torch.float32),
+                action=((2,), torch.int8), live=((), torch.int8))
+
+
 KEYS = ((0, 0), (0xDEADBEEFCAFEF00D, 7), (5, 2 ** 32 + 3), (2 ** 64 - 1, 2 ** 40 + 1))
 
 
@@ -364,9 +372,7 @@ def by_hand(ea, S, b, d, params, sims, T, key, off, eps=0.25, alpha=1.0, temp_pl
     M = b.shape[0]
     cb, cd = b.clone(), d.clone()
     game = torch.zeros((M, 4), dtype=torch.int32, device="cuda")
-    shapes = dict(board=((S, S), torch.int8), dice=((), torch.int8), visits=((2, 3), torch.int32), value=((), torch.float32),
-                  action=((2,), torch.int8), live=((), torch.int8))
-    rec = {k: torch.zeros((T, M) + s, dtype=dt, device="cuda") for k, (s, dt) in shapes.items()}
+    rec = {k: torch.zeros((T, M) + s, dtype=dt, device="cuda") for k, (s, dt) in row_shapes(S).items()}
     for t in range(T):
         noise = ea.selfplay_noise(M, alpha, key, off, t)
         tree, lb, ld = ea.puct_begin(cb, cd, sims)
