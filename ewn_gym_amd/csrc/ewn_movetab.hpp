@@ -16,6 +16,14 @@
 #pragma once
 #include "ewn_fast.hpp"
 
+// Diagnostic builds only (-DEWN_MT_LEVERS=n): which levers of the slot-task kernel's derived tables are on.  1 and 2: the step boundary
+// and the search entry (k_rollout_slots, ewn_rollout.hpp); 8: the key swap of a game's two lanes in d3_search's MT form
+// (ewn_step_d3.hpp).  The library ships all three.  Bit 4 was the fused level table lv2[ffbh P][ffbh N] (one 16-bit read per leaf in
+// place of the two byte reads of lvl[]): built, measured slower and taken out, profiles/r09/README.md.
+#ifndef EWN_MT_LEVERS
+#define EWN_MT_LEVERS 11
+#endif
+
 struct alignas(8) MoveEnt { u32 mv, rc; };
 template <int S, bool WIDE = (sizeof(typename MaskOf<S>::type) == 8)> struct ReplyEnt;
 template <int S> struct alignas(16) ReplyEnt<S, false> { u32 rset[3]; u32 rkf[3]; u32 pad[2]; };

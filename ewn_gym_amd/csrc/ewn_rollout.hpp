@@ -19,10 +19,7 @@
 
 // Diagnostic build only (tools/rollout_stamps.py, -DEWN_ROLLOUT_STAMPS): s_memtime at the phase boundaries of a step, summed over the
 // K steps of a launch per wave and written over the (then meaningless) return_sum buffer.  Never defined in the shipped library.
-// Diagnostic builds only: which levers of the slot-task kernel's derived tables are on (see k_rollout_slots)
-#ifndef EWN_MT_LEVERS
-#define EWN_MT_LEVERS 3
-#endif
+// (EWN_MT_LEVERS, which levers of the slot-task kernel's derived tables are on in a diagnostic build: ewn_movetab.hpp)
 
 #ifdef EWN_ROLLOUT_STAMPS
 #define RSTAMP(i) do { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); st_acc[i] += t_ - st_prev; st_prev = t_; } while (0)
@@ -505,7 +502,8 @@ __global__ __launch_bounds__(D3_BS, (OPP == 2 ? 2 : 1)) void k_rollout_slots(Rol
     constexpr int TS = T > 2 ? 2 : T;               // lanes per game the depth-5 search can use
     constexpr int STR = RecGeo<S>::STR;             // LDS bytes per game: the game's board slot, one trajectory record wide
     // the levers of the derived tables, for A/B builds (-DEWN_MT_LEVERS=n): 1 = the agent half and the max_depth 5 / 6 opponent's move,
-    // 2 = the search entry with the max_depth 1-4 opponent's move.  The library ships both.
+    // 2 = the search entry with the max_depth 1-4 opponent's move (8 = the key swap inside that search, ewn_step_d3.hpp).  The library
+    // ships all three.
     constexpr bool MT_BND = (EWN_MT_LEVERS & 1) != 0, MT_SRCH = (EWN_MT_LEVERS & 2) != 0;
     __shared__ __attribute__((aligned(16))) int8_t lds_st[GPB * STR + FAST_TAB_BYTES(S) + GPB * 16 + SlotTabGeo<S>::EXTRA];
     int8_t *lds = lds_st;

@@ -280,7 +280,9 @@ template <int T> EWN_DEV void publish(u32 mine, int i, u32 (&out)[6])
 // MT (the slot-task rollout kernel only, with PERLANE): D = the block's derived tables (ewn_movetab.hpp).  The root cube's three
 // destinations and the real cells of its moves are ONE 8-byte read, a replier cube's setup two or three wide reads, and bmove becomes
 // cube | destination ring cell << 8 | REAL source cell << 16 | REAL destination cell << 24: the caller's two byte stores into the
-// game's board slot need no table either.
+// game's board slot need no table either.  With T = 2 the two lanes SWAP their cubes' keys (one lane permute per cube where the
+// other forms broadcast every key to both lanes with two) and each lane runs the nearest-cube carries for its own three dice only;
+// the chosen ranks still travel to both lanes in dice order, as the expectation's sum needs them.
 template <int S, int T, bool H2 = false, bool PERLANE = false, bool MT = false>
 __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S> &c, int dice, int sub, int depth, int &bflag, int &bdir,
                                             int slotL = 0, double best_in = 0.0, bool *have_second = nullptr, u32 *bmove = nullptr,
@@ -290,6 +292,9 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
     typedef typename MaskOf<S>::type M;
     constexpr int KPT = 6 / T + (6 % T ? 1 : 0); // replier cubes / dice values per lane: k = sub + T*i
     const M one = 1;
+    // the search's own lever (A/B builds with -DEWN_MT_LEVERS=n, ewn_movetab.hpp): 8 = the two lanes of a game swap their keys instead
+    // of broadcasting them
+    constexpr bool SWAP = MT && T == 2 && (EWN_MT_LEVERS & 8) != 0;
 
     // root slots: <= 2 cubes x 3 dirs in the reference's list order (envs/ewn.py:338-375)
     const u32 rsel_all = pk_sel<S>(Tb, c.posP, dice), rpp_all = pk_pair(c.posP, rsel_all);
@@ -420,7 +425,8 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
         // Four stages, each issuing ALL its LDS reads before the next one consumes them (sched_barrier keeps the compiler from
         // re-serialising them into one round trip per leaf, which is what the register-pressure-driven schedule does):
         // levels -> ranks -> values of the three prefix minima -> cut.
-        u32 tr[6];
+        [[maybe_unused]] u32 tr[6];
+        [[maybe_unused]] u32 km[KPT];   // SWAP: my cubes' keys
         constexpr int CH = KPT > 3 ? 3 : KPT; // cubes staged together: 9 leaves in flight; more only costs registers
         #pragma unroll
         for (int i0 = 0; i0 < KPT; i0 += CH) {
@@ -480,9 +486,42 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
                 rk = va[ii] <= best ? a[ii][0] : rk;
                 u32 key = rk | (v2[ii] <= best ? D3_CUT : 0x8000u);
                 key = rnk[i] != dest ? key : FAST_KNONE;
-                publish<T>(key, i, tr); // after this every lane holds tr[k] for all six cubes (cube k = j + T*i lives in lane j)
+                if constexpr (SWAP) km[i] = key;
+                else publish<T>(key, i, tr); // after this every lane holds tr[k] for all six cubes (cube k = j + T*i lives in lane j)
             }
         }
+        u32 wq[6];
+        if constexpr (SWAP) {
+            // T = 2: ONE lane swap per cube.  A lane then holds its own three keys (cubes sub, sub + 2, sub + 4) and its partner's three,
+            // and only its own three dice need the carries.  The partner's keys are aligned to the lane's parity, padded with "no such
+            // cube": q[i] = the partner's cube just BELOW my cube i, q[i + 1] the one just above, so that the six cubes read
+            // q0 m0 q1 m1 q2 m2 q3 in ascending order in either lane (lane 0: q0 is the pad, lane 1: q3).
+            u32 pk[3], q[4];
+            #pragma unroll
+            for (int i = 0; i < 3; i++) pk[i] = dpp_u32<DPP_XOR1>(km[i]);
+            q[0] = sub ? pk[0] : FAST_KNONE; q[1] = sub ? pk[1] : pk[0]; q[2] = sub ? pk[2] : pk[1]; q[3] = sub ? FAST_KNONE : pk[2];
+            // nearest on-board cube above (the F of a pair: its copy drops D3_CUT, see below) and below each of my cubes
+            u32 up3[3], dn3[3];
+            u32 cur = q[3] & ~D3_CUT;   // (FAST_KNONE has no D3_CUT to drop)
+            #pragma unroll
+            for (int i = 2; i >= 0; i--) {
+                up3[i] = cur;
+                if (i > 0) { cur = km[i] != FAST_KNONE ? (km[i] & ~D3_CUT) : cur; cur = q[i] != FAST_KNONE ? (q[i] & ~D3_CUT) : cur; }
+            }
+            cur = q[0];
+            #pragma unroll
+            for (int i = 0; i < 3; i++) {
+                dn3[i] = cur;
+                if (i < 2) { cur = km[i] != FAST_KNONE ? km[i] : cur; cur = q[i + 1] != FAST_KNONE ? q[i + 1] : cur; }
+            }
+            // the chosen ranks travel as before: all six in dice order in both lanes, two broadcasts each (a swap would need six
+            // selects on `sub` to put them in order: nine instructions against six)
+            #pragma unroll
+            for (int i = 0; i < 3; i++) {
+                const u32 w = (km[i] != FAST_KNONE ? km[i] : min(up3[i], dn3[i])) & 0x1FFFu;
+                publish<T>(w, i, wq);
+            }
+        } else {
         // which cubes a dice value selects (find_near_cube): carry the nearest on-board cube's key along
         // A key that cuts carries D3_CUT (ranks stay below it, "does not cut" keys above it); the copy that travels as "nearest cube
         // ABOVE" (the F of a pair) drops the flag, which puts a cutting F below everything else: the pair's result is then ONE min.
@@ -498,7 +537,6 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
         // my share of the six chance branches: dice index d = sub + T*i.  Reply order is the larger-neighbour cube F, then
         // the smaller-neighbour cube G (get_legal_actions): the loop stops in F if F cuts (key < 0x8000: the result is F's cut
         // value whatever G is), else in G if G cuts, else it returns the minimum over both -- min(F, G) & 0x7fff in either case.
-        u32 wq[6];
         #pragma unroll
         for (int i = 0; i < KPT; i++) {
             const u32 e = own_of<T>(tr, i, sub), u = own_of<T>(upT, i, sub), dn = own_of<T>(downT, i, sub);
@@ -507,6 +545,7 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
             const u32 w = (e != FAST_KNONE ? e : min(u, dn)) & 0x1FFFu;
             publish<T>(w, i, wq);
         }
+        } // !SWAP
         // expected_val += val / 6 in dice order, minimax.py:72.  The sum starts from its first term: 0.0 + x is x bit for bit unless
         // x is -0.0, and no table holds one (build_fast_tables checks val6[])
         double v = ft_val6<S>(Tb, wq[0]);

@@ -14,6 +14,11 @@ within each 32-lane half; lanes reading the same dword (64-bit read: the same 8 
 address on a bank costs one more LDS cycle.  The model prints, per layout, the mean cycles per half-wave read (1.0 = conflict-free)
 and the extra cycles per wave-level read instruction (two halves) -- the quantity SQ_LDS_BANK_CONFLICT / instruction measures.
 
+--lv2 adds a table the 5x5 search does NOT ship (built and measured slower, profiles/r09/README.md): both levels' share of a leaf's
+rank address in one 16-bit read at lv2[zP][zN], zP / zN = v_ffbh_u32 of the leaf's two ring-space masks (31 - the highest ring
+index, -1 for an empty mask), issued for steered leaves too, in place of the two byte reads of lvl[] (72 bytes on 18 banks: one
+cycle each).  The candidates are row strides in bytes; the figures of profiles/r09 come from here.
+
 Not modelled: the byte-wide reads of the small tables and the six val6[] reads of a root's expectation (they need the cut-off replay).
 """
 import argparse
@@ -49,13 +54,27 @@ def rank_lookup():
     return tab
 
 
+# ring order of the canonical cells (RingGeo, ewn_step_d3.hpp): ascending min(row, col), row-major inside a level
+RING = {}
+for _t in range(S):
+    for _i in range(S):
+        for _j in range(S):
+            if min(_i, _j) == _t:
+                RING[(_i, _j)] = len(RING)
+
+
+def ffbh(cells):
+    """v_ffbh_u32 of a side's ring-space mask"""
+    return 31 - max(RING[c] for c in cells) if cells else -1
+
+
 def side_index(cells):
     """(level, count) index of a side: 8 x the highest level min(i, j) of its cubes + their number; 0 for an empty side"""
     return 8 * max(min(c) for c in cells) + len(cells) if cells else 0
 
 
 def search_tasks(board, dice_opp):
-    """the search tasks of one position (real-space board, agent > 0) as lists of 3 root directions x 2 lanes x 9 (ix, iy, steer)"""
+    """the search tasks of one position (real-space board, agent > 0) as lists of 3 root directions x 2 lanes x 9 (ix, iy, steer, zP, zN)"""
     P, N = {}, {}   # cube number -> canonical cell (board rotated by 180 degrees)
     for i in range(S):
         for j in range(S):
@@ -89,17 +108,17 @@ def search_tasks(board, dice_opp):
                 for ii in range(3):
                     k = sub + 2 * ii + 1
                     for d, (ei, ej) in enumerate(DIRS):
-                        if k not in N:
-                            reads[sub].append((0, 0, 1)); continue           # cube off the board: rank[0]
+                        if k not in N:   # cube off the board: rank[0]; the level read sees the root's masks (less a stale bit)
+                            reads[sub].append((0, 0, 1, ffbh(P1), ffbh(N1))); continue
                         c = N[k]
                         dn_ = (c[0] - ei, c[1] - ej)
                         if dn_[0] < 0 or dn_[1] < 0:
-                            reads[sub].append((0, 0, 1)); continue           # no such reply: rank[0]
-                        if dn_ == (0, 0):
-                            reads[sub].append((0, 1, 1)); continue           # reply onto the origin: rank[1]
+                            reads[sub].append((0, 0, 1, ffbh(P1), ffbh(N1 - {c}))); continue   # no such reply: rank[0]
                         N2 = (N1 - {c}) | {dn_}
                         P2 = P1 - {dn_}
-                        reads[sub].append((side_index(P2), side_index(N2), 0))
+                        if dn_ == (0, 0):
+                            reads[sub].append((0, 1, 1, ffbh(P2), ffbh(N2))); continue           # reply onto the origin: rank[1]
+                        reads[sub].append((side_index(P2), side_index(N2), 0, ffbh(P2), ffbh(N2)))
             task.append(reads)
         tasks.append(task)
     return tasks
@@ -145,6 +164,9 @@ LAYOUTS = collections.OrderedDict((
 ))
 
 
+LV2_ROWS = (68, 76, 128, 132, 140)   # bytes per row of the fused level table: 33 entries need 66
+
+
 def half_cycles(addrs, gran, banks):
     """LDS cycles of one 32-lane half: the largest number of distinct `gran`-byte units on one bank"""
     per = collections.defaultdict(set)
@@ -159,6 +181,7 @@ def main():
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--waves", type=int, default=4000)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--lv2", action="store_true", help="also model the fused level table's read, per candidate row stride")
     a = ap.parse_args()
     rng = np.random.default_rng(a.seed)
     rank = rank_lookup()
@@ -171,17 +194,22 @@ def main():
     print("distinct iy among the un-steered reads: %d; distinct (iy / 2) %% 32 banks: %d" % (len(iys), len({(y // 2) % 32 for y in iys})))
     res = {name: [0, 0] for name in LAYOUTS}
     val = [0, 0]
+    lv2 = {row: [0, 0] for row in LV2_ROWS}
     for _ in range(a.waves):
         wave = [tasks[i] for i in rng.integers(len(tasks), size=32)]
         for r in range(3):
             for ii in range(3):
-                ranks = [[[int(rank[x, y]) for (x, y, _) in wave[g][r][sub][3 * ii:3 * ii + 3]] for sub in range(2)] for g in range(32)]
+                ranks = [[[int(rank[x, y]) for (x, y, _, _, _) in wave[g][r][sub][3 * ii:3 * ii + 3]] for sub in range(2)] for g in range(32)]
                 for d in range(3):
                     for half in range(2):
                         reads = [wave[g][r][sub][3 * ii + d] for g in range(16 * half, 16 * half + 16) for sub in range(2)]
                         for name, f in LAYOUTS.items():
-                            res[name][0] += half_cycles([f(x, y) for (x, y, _) in reads], 4, 32)
+                            res[name][0] += half_cycles([f(x, y) for (x, y, _, _, _) in reads], 4, 32)
                             res[name][1] += 1
+                        if a.lv2:
+                            for row in LV2_ROWS:
+                                lv2[row][0] += half_cycles([(zp + 1) * row + (zn + 1) * 2 for (_, _, _, zp, zn) in reads], 4, 32)
+                                lv2[row][1] += 1
                         # the value read that belongs to this rank read: prefix minimum over directions 0..d
                         va = [8192 + min(ranks[g][sub][:d + 1]) for g in range(16 * half, 16 * half + 16) for sub in range(2)]
                         val[0] += half_cycles(va, 8, 64)
@@ -190,6 +218,9 @@ def main():
     for name, (c, n) in res.items():
         print("%-44s %25.3f  %33.3f" % (name, c / n, 2 * (c / n - 1)))
     print("%-44s %25.3f  %33.3f" % ("val[] read (64-bit, by rank)", val[0] / val[1], 2 * (val[0] / val[1] - 1)))
+    for row, (c, n) in lv2.items():
+        if n:
+            print("%-44s %25.3f  %33.3f" % ("lv2[zP][zN] read, %d-B rows (%d dwords)" % (row, row // 4), c / n, 2 * (c / n - 1)))
 
 
 if __name__ == "__main__":
