@@ -8,6 +8,7 @@ leaf is a network's value exists for the networks trained here: ValueSearchAgent
 lookahead on the actor-critic's own value net, ewn_predict_lookahead) and PuctAgent (a PUCT search on
 both of its heads, ewn_gym_amd.predict_puct: the counterpart of AlphaZeroMCTSAgent), beside ModelAgent.
 EndgameAgent plays the exact move where an endgame table covers the position and a fallback policy elsewhere.
+PlayoutSearchAgent is PuctAgent's tree without a network: uniform priors, random playouts at the leaves (plain MCTS with chance nodes).
 """
 from classical_policies.base import PolicyBase
 from classical_policies.random_policy import RandomAgent
@@ -15,6 +16,7 @@ from classical_policies.minimax import ExpectiMinimaxAgent, AlphaZeroMinimaxAgen
 from classical_policies.mcts import MctsAgent
 from classical_policies.alpha_zero import AlphaZeroAgent
 from classical_policies.model import EndgameAgent, ModelAgent, PuctAgent, ValueSearchAgent
+from classical_policies.playout_search import PlayoutSearchAgent
 
 # the names BASELINE.json's north_star uses
 RandomPolicy = RandomAgent
@@ -22,4 +24,5 @@ MiniMaxPolicy = ExpectiMinimaxAgent
 MCTSPolicy = MctsAgent
 
 __all__ = ["PolicyBase", "RandomAgent", "ExpectiMinimaxAgent", "MctsAgent", "AlphaZeroAgent", "AlphaZeroMinimaxAgent",
-           "RandomPolicy", "MiniMaxPolicy", "MCTSPolicy", "ModelAgent", "ValueSearchAgent", "PuctAgent", "EndgameAgent"]
+           "RandomPolicy", "MiniMaxPolicy", "MCTSPolicy", "ModelAgent", "ValueSearchAgent", "PuctAgent", "EndgameAgent",
+           "PlayoutSearchAgent"]

@@ -53,6 +53,13 @@ def _policy(spec, cube_layer, key):
         return lambda b, d, t: predict_mcts(b, d, spec.get("num_simulations", 10), spec.get("num_env_copies", 5),
                                             key=(key + 0x9E3779B97F4A7C15 * (t + 1)) & 0xFFFFFFFFFFFFFFFF,
                                             cube_layer=cube_layer)[0]
+    if kind == "playout_search":   # the PUCT tree with uniform priors and random playouts at the leaves (predict_playout_search),
+        # ply by ply through ewn_step; keyed like the mcts kind: episode m is observation id m, step t its own key
+        from .playout_search import KEY_PLY, _numbers, predict_playout_search
+        _numbers("playout_search", spec.get("sims", 64), spec.get("playouts", 64), spec.get("c_puct", 1.5), key, 0)   # refused here, not at the first ply
+        return lambda b, d, t: predict_playout_search(b, d, sims=spec.get("sims", 64), playouts=spec.get("playouts", 64),
+                                                      c_puct=spec.get("c_puct", 1.5), key=(key + KEY_PLY * (t + 1)) & 0xFFFFFFFFFFFFFFFF,
+                                                      cube_layer=cube_layer)
     if kind == "mlp":           # the model's policy through ewn_predict_policy; evaluate() itself plays this kind on its own paths
         from classical_policies.model import ModelAgent
         return ModelAgent(spec["model"], board_size=_model_size(spec), cube_layer=cube_layer,
@@ -171,8 +178,9 @@ def evaluate(agent, opponent, num=1024, board_size=5, cube_layer=3, rng="mt19937
     {"kind": "mlp_lookahead", "model": ..., terminal_value=, plies=} (its lookahead on its own value net, ply by ply),
     {"kind": "mlp_puct", "model": ..., sims=, c_puct=, terminal_value=} (its PUCT search on both of its heads, ply by ply),
     {"kind": "endgame", "table": an EndgameTable or its path, "fallback": any of these dicts} (the exact move where the table covers
-    the position, the fallback's elsewhere, ply by ply), or a callable
-    policy (board, dice, t) -> actions.
+    the position, the fallback's elsewhere, ply by ply),
+    {"kind": "playout_search", sims=, playouts=, c_puct=} (the same tree without a network: uniform priors, random playouts at the
+    leaves, ply by ply), or a callable policy (board, dice, t) -> actions.
     agent / opponent: dicts {"kind": "random"|"minimax"|"mcts", max_depth=, heuristic=, num_simulations=, num_env_copies=}.
     Returns per-episode scores (float64 tensor), episode lengths and summary statistics.
     When both sides are engine policies the table-driven kernels cover (RandomAgent, 'hybrid' minimax; cube_layer 3) the whole
@@ -308,13 +316,17 @@ def evaluate_agents_vs_model(model, names=("random", "minimax", "mcts"), num=102
 
 
 def tournament(names=("random", "minimax", "mcts"), num=1024, max_depth=5, num_simulations=10, num_env_copies=5,
-               board_size=5, cube_layer=3, heuristic="hybrid", rng="mt19937"):
-    """eval_pairs.py:10-35: every (agent, opponent) pair, 1024 episodes, depth 5, 10 simulations by default."""
+               board_size=5, cube_layer=3, heuristic="hybrid", rng="mt19937", sims=64, playouts=64, c_puct=1.5):
+    """eval_pairs.py:10-35: every (agent, opponent) pair, 1024 episodes, depth 5, 10 simulations by default.
+    "playout_search" among the names (sims, playouts and c_puct are its own): the tree search on random playouts, an agent only --
+    the env has no such opponent -- so it adds the rows "playout_search vs <every other name>"."""
     def spec(n):
+        if n == "playout_search":
+            return {"kind": n, "sims": sims, "playouts": playouts, "c_puct": c_puct}
         return _classical_spec(n, max_depth, heuristic, num_simulations, num_env_copies)
     table = {}
     for a in names:
-        for o in names:
+        for o in (o for o in names if o != "playout_search"):
             r = evaluate(spec(a), spec(o), num=num, board_size=board_size, cube_layer=cube_layer, rng=rng)
             table["%s vs %s" % (a, o)] = _row(r)
     return table
@@ -378,7 +390,11 @@ def evaluate_model(model, names=("random", "minimax"), num=1024, max_depth=5, nu
 def _parser():
     ap = argparse.ArgumentParser(description="agent-vs-opponent win-rate matrix (counterpart of eval_pairs.py); with --model, a "
                                              "trained policy against each listed opponent (counterpart of eval_A2C.py)")
-    ap.add_argument("--agents", nargs="+", default=["random", "minimax", "mcts"])
+    ap.add_argument("--agents", nargs="+", default=["random", "minimax", "mcts"],
+                    help="random, minimax, mcts; without --model also playout_search (the tree search on random playouts, an agent only)")
+    ap.add_argument("--sims", type=int, default=64, help="playout_search: simulations per move")
+    ap.add_argument("--playouts", type=int, default=64, help="playout_search: random playouts per leaf")
+    ap.add_argument("--c_puct", type=float, default=1.5, help="playout_search: the exploration constant")
     ap.add_argument("--model", default=None, help="checkpoint (best.pt) of any of the trainers: evaluate its deterministic policy")
     ap.add_argument("--opponent_model", default=None, help="a checkpoint that plays the opponent (its argmax): against --model, or "
                                                            "without --model against every agent of --agents")
@@ -423,6 +439,8 @@ def main():
         ap.error("--endgame_table goes with --model and the classical opponents of --agents")
     if a.endgame_leaves and not (a.endgame_table and a.lookahead):
         ap.error("--endgame_leaves goes with --lookahead and --endgame_table")
+    if "playout_search" in a.agents and (a.model is not None or a.opponent_model is not None):
+        ap.error("playout_search among --agents goes without --model and --opponent_model")
     if a.opponent_model is not None and a.model is None:
         t = evaluate_agents_vs_model(load_policy(a.opponent_model, a.board_size, a.cube_layer), a.agents, a.num, a.max_depth,
                                      a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer, a.heuristic, a.rng)
@@ -438,7 +456,7 @@ def main():
                            endgame_leaves=a.endgame_leaves, fused=a.fused)
     else:
         t = tournament(a.agents, a.num, a.max_depth, a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer,
-                       a.heuristic, a.rng)
+                       a.heuristic, a.rng, sims=a.sims, playouts=a.playouts, c_puct=a.c_puct)
     for k, v in t.items():
         print("%-22s win rate %.3f  (95%% CI %.3f-%.3f, %d/%d, %.1f steps/episode)  %s"
               % (k, v["win_rate"], v["ci95"][0], v["ci95"][1], v["wins"], v["episodes"], v["avg_length"], v["engine"]))
