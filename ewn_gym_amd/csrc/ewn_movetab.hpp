@@ -18,10 +18,14 @@
 
 // Diagnostic builds only (-DEWN_MT_LEVERS=n): which levers of the slot-task kernel's derived tables are on.  1 and 2: the step boundary
 // and the search entry (k_rollout_slots, ewn_rollout.hpp); 8: the key swap of a game's two lanes in d3_search's MT form
-// (ewn_step_d3.hpp).  The library ships all three.  Bit 4 was the fused level table lv2[ffbh P][ffbh N] (one 16-bit read per leaf in
-// place of the two byte reads of lvl[]): built, measured slower and taken out, profiles/r09/README.md.
+// (ewn_step_d3.hpp); 32: at two lanes per game the expectation's six val6[] terms are read three per lane and summed once, on the
+// even lane (ewn_step_d3.hpp).  The library ships all four.  Bit 4 was the fused level table lv2[ffbh P][ffbh N] (one 16-bit read
+// per leaf in place of the two byte reads of lvl[]): built, measured slower and taken out, profiles/r09/README.md.  Bit 16 was a
+// fused leaf table leaf[ix][iy] = { val, rank } of 16-byte entries (one ds_read_b128 per leaf in place of the rank read and the
+// value reads a round trip later, 28 KB more LDS per block): built and measured; alone it gained what bit 32 gains, together
+// with bit 32 nothing, and it was taken out, profiles/r10/README.md.
 #ifndef EWN_MT_LEVERS
-#define EWN_MT_LEVERS 11
+#define EWN_MT_LEVERS 43
 #endif
 
 struct alignas(8) MoveEnt { u32 mv, rc; };

@@ -282,7 +282,11 @@ template <int T> EWN_DEV void publish(u32 mine, int i, u32 (&out)[6])
 // cube | destination ring cell << 8 | REAL source cell << 16 | REAL destination cell << 24: the caller's two byte stores into the
 // game's board slot need no table either.  With T = 2 the two lanes SWAP their cubes' keys (one lane permute per cube where the
 // other forms broadcast every key to both lanes with two) and each lane runs the nearest-cube carries for its own three dice only;
-// the chosen ranks still travel to both lanes in dice order, as the expectation's sum needs them.
+// the chosen ranks travel to both lanes in dice order only where the next lever is off.
+// With T = 2 (lever 32 of EWN_MT_LEVERS) the expectation is summed ONCE per game: a lane keeps its own three chosen ranks and reads its
+// own three val6[] terms, the odd lane's three doubles cross to the even lane (six lane permutes), the even lane adds all six in
+// dice order -- the expression it always was -- and the sum returns to the odd lane with two permutes.  The odd lane adds the same
+// six terms in another order; that sum is overwritten before anything reads it.
 template <int S, int T, bool H2 = false, bool PERLANE = false, bool MT = false>
 __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S> &c, int dice, int sub, int depth, int &bflag, int &bdir,
                                             int slotL = 0, double best_in = 0.0, bool *have_second = nullptr, u32 *bmove = nullptr,
@@ -295,6 +299,8 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
     // the search's own lever (A/B builds with -DEWN_MT_LEVERS=n, ewn_movetab.hpp): 8 = the two lanes of a game swap their keys instead
     // of broadcasting them
     constexpr bool SWAP = MT && T == 2 && (EWN_MT_LEVERS & 8) != 0;
+    // 32 = one ordered sum per game (above)
+    constexpr bool SUM1 = MT && T == 2 && (EWN_MT_LEVERS & 32) != 0;
 
     // root slots: <= 2 cubes x 3 dirs in the reference's list order (envs/ewn.py:338-375)
     const u32 rsel_all = pk_sel<S>(Tb, c.posP, dice), rpp_all = pk_pair(c.posP, rsel_all);
@@ -490,7 +496,8 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
                 else publish<T>(key, i, tr); // after this every lane holds tr[k] for all six cubes (cube k = j + T*i lives in lane j)
             }
         }
-        u32 wq[6];
+        [[maybe_unused]] u32 wq[6];
+        [[maybe_unused]] u32 wo[KPT];   // SUM1: the chosen ranks of my own dice
         if constexpr (SWAP) {
             // T = 2: ONE lane swap per cube.  A lane then holds its own three keys (cubes sub, sub + 2, sub + 4) and its partner's three,
             // and only its own three dice need the carries.  The partner's keys are aligned to the lane's parity, padded with "no such
@@ -519,7 +526,7 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
             #pragma unroll
             for (int i = 0; i < 3; i++) {
                 const u32 w = (km[i] != FAST_KNONE ? km[i] : min(up3[i], dn3[i])) & 0x1FFFu;
-                publish<T>(w, i, wq);
+                if constexpr (SUM1) wo[i] = w; else publish<T>(w, i, wq);
             }
         } else {
         // which cubes a dice value selects (find_near_cube): carry the nearest on-board cube's key along
@@ -543,14 +550,28 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
             // the dice cube alone if it is on the board; else F = up, G = down: F's cut value if F cuts (flag dropped: the smallest),
             // else G's if G cuts (flagged: below every key that does not cut), else the smaller minimum; no cube above: down alone
             const u32 w = (e != FAST_KNONE ? e : min(u, dn)) & 0x1FFFu;
-            publish<T>(w, i, wq);
+            if constexpr (SUM1) wo[i] = w; else publish<T>(w, i, wq);
         }
         } // !SWAP
         // expected_val += val / 6 in dice order, minimax.py:72.  The sum starts from its first term: 0.0 + x is x bit for bit unless
         // x is -0.0, and no table holds one (build_fast_tables checks val6[])
-        double v = ft_val6<S>(Tb, wq[0]);
-        #pragma unroll
-        for (int d = 1; d < 6; d++) v = v + ft_val6<S>(Tb, wq[d]);
+        double v;
+        if constexpr (SUM1) {
+            // my three terms (dice sub, sub + 2, sub + 4) and my partner's; on the even lane e0 + o0 + e1 + o1 + e2 + o2 is the sum in
+            // dice order, and both lanes take that one
+            double m6[3], o6[3];
+            #pragma unroll
+            for (int i = 0; i < 3; i++) m6[i] = ft_val6<S>(Tb, wo[i]);
+            #pragma unroll
+            for (int i = 0; i < 3; i++) o6[i] = dpp_f64<DPP_XOR1>(m6[i]);
+            v = m6[0];
+            v = v + o6[0]; v = v + m6[1]; v = v + o6[1]; v = v + m6[2]; v = v + o6[2];
+            v = dpp_f64<Bcast<2, 0>::CTRL>(v);
+        } else {
+            v = ft_val6<S>(Tb, wq[0]);
+            #pragma unroll
+            for (int d = 1; d < 6; d++) v = v + ft_val6<S>(Tb, wq[d]);
+        }
         v = term ? 10.0 : v;
         if (valid && v > best) {
             best = v; bflag = slot == 0 ? flag0 : 0; bdir = dir;

@@ -19,6 +19,13 @@ rank address in one 16-bit read at lv2[zP][zN], zP / zN = v_ffbh_u32 of the leaf
 index, -1 for an empty mask), issued for steered leaves too, in place of the two byte reads of lvl[] (72 bytes on 18 banks: one
 cycle each).  The candidates are row strides in bytes; the figures of profiles/r09 come from here.
 
+--leaf adds the fused leaf table of the 5x5 search (ewn_movetab.hpp): leaf[ix][iy] = {val, rank}, 16 bytes, ONE 128-bit read per leaf in
+place of the rank read and (a third of) the value reads.  A 128-bit read banks by (byte address / 4) % 64 and is served in four
+groups of 16 lanes -- lanes {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same plus 32 -- one cycle per group when no two lanes
+of a group read distinct entries on one bank.  Steered leaves read entry 0 ("no such reply") or entry 1 (a reply onto the origin).
+The candidates are row strides in ENTRIES (39 = the table's own width); printed: cycles per 16-lane group and per wave instruction
+(4.0 = conflict-free, the same LDS-array time as the 16-bit read + the 64-bit read it replaces), profiles/r10/README.md.
+
 Not modelled: the byte-wide reads of the small tables and the six val6[] reads of a root's expectation (they need the cut-off replay).
 """
 import argparse
@@ -167,6 +174,12 @@ LAYOUTS = collections.OrderedDict((
 LV2_ROWS = (68, 76, 128, 132, 140)   # bytes per row of the fused level table: 33 entries need 66
 
 
+LEAF_ROWS = (39, 40, 41, 42, 43, 44, 45, 46, 47, 48, 49, 50)   # entries per row of the fused leaf table: 39 x 39 entries are used
+# the four lane groups of a 128-bit read, as lane numbers inside the wave
+B128_GROUPS = [[l + h for l in g] for h in (0, 32) for g in (list(range(0, 4)) + list(range(12, 16)) + list(range(20, 28)),
+                                                            list(range(4, 12)) + list(range(16, 20)) + list(range(28, 32)))]
+
+
 def half_cycles(addrs, gran, banks):
     """LDS cycles of one 32-lane half: the largest number of distinct `gran`-byte units on one bank"""
     per = collections.defaultdict(set)
@@ -182,6 +195,7 @@ def main():
     ap.add_argument("--waves", type=int, default=4000)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--lv2", action="store_true", help="also model the fused level table's read, per candidate row stride")
+    ap.add_argument("--leaf", action="store_true", help="also model the fused leaf table's 128-bit read, per candidate row stride")
     a = ap.parse_args()
     rng = np.random.default_rng(a.seed)
     rank = rank_lookup()
@@ -195,12 +209,19 @@ def main():
     res = {name: [0, 0] for name in LAYOUTS}
     val = [0, 0]
     lv2 = {row: [0, 0] for row in LV2_ROWS}
+    leaf = {row: [0, 0] for row in LEAF_ROWS}
     for _ in range(a.waves):
         wave = [tasks[i] for i in rng.integers(len(tasks), size=32)]
         for r in range(3):
             for ii in range(3):
                 ranks = [[[int(rank[x, y]) for (x, y, _, _, _) in wave[g][r][sub][3 * ii:3 * ii + 3]] for sub in range(2)] for g in range(32)]
                 for d in range(3):
+                    if a.leaf:   # lane 2 g + sub reads the leaf of task g
+                        for row in LEAF_ROWS:
+                            for grp in B128_GROUPS:
+                                rd = [wave[l // 2][r][l % 2][3 * ii + d] for l in grp]
+                                leaf[row][0] += half_cycles([16 * (x * row + y) for (x, y, _, _, _) in rd], 16, 64)
+                                leaf[row][1] += 1
                     for half in range(2):
                         reads = [wave[g][r][sub][3 * ii + d] for g in range(16 * half, 16 * half + 16) for sub in range(2)]
                         for name, f in LAYOUTS.items():
@@ -221,6 +242,11 @@ def main():
     for row, (c, n) in lv2.items():
         if n:
             print("%-44s %25.3f  %33.3f" % ("lv2[zP][zN] read, %d-B rows (%d dwords)" % (row, row // 4), c / n, 2 * (c / n - 1)))
+    if a.leaf:
+        print("%-44s %s  %s" % ("leaf[][] read, layout", "  cycles per 16-lane group", "      cycles per wave instruction"))
+    for row, (c, n) in leaf.items():
+        if n:
+            print("%-44s %25.3f  %33.3f" % ("leaf[ix][iy] read (128-bit), %d-entry rows" % row, c / n, 4 * c / n))
 
 
 if __name__ == "__main__":
