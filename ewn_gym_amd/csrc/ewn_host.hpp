@@ -158,7 +158,7 @@ static inline int d3_threads_per_game(int n_games)
     // latency only add redundant instructions.
     // Re-measured at the end of round 2 (table-driven setup, one-min pair selection): two lanes per game are now as fast as or faster
     // than four at every lane count below 131 072 (2 048 .. 24 576 games: one-step launch 9.9-10.4 us against 10.1-12.1), so the
-    // four-lanes-per-game instances were dropped from the library (d3_search keeps its T = 4 code: `own_of` / `publish`).
+    // four-lanes-per-game instances were dropped from the library, and later the T = 4 code of d3_search and its helpers with them.
     if (n_games >= 131072) return 1;
     return 2;
 }

@@ -16,17 +16,13 @@
 #pragma once
 #include "ewn_fast.hpp"
 
-// Diagnostic builds only (-DEWN_MT_LEVERS=n): which levers of the slot-task kernel's derived tables are on.  1 and 2: the step boundary
-// and the search entry (k_rollout_slots, ewn_rollout.hpp); 8: the key swap of a game's two lanes in d3_search's MT form
-// (ewn_step_d3.hpp); 32: at two lanes per game the expectation's six val6[] terms are read three per lane and summed once, on the
-// even lane (ewn_step_d3.hpp).  The library ships all four.  Bit 4 was the fused level table lv2[ffbh P][ffbh N] (one 16-bit read
-// per leaf in place of the two byte reads of lvl[]): built, measured slower and taken out, profiles/r09/README.md.  Bit 16 was a
-// fused leaf table leaf[ix][iy] = { val, rank } of 16-byte entries (one ds_read_b128 per leaf in place of the rank read and the
-// value reads a round trip later, 28 KB more LDS per block): built and measured; alone it gained what bit 32 gains, together
-// with bit 32 nothing, and it was taken out, profiles/r10/README.md.
-#ifndef EWN_MT_LEVERS
-#define EWN_MT_LEVERS 43
-#endif
+// Who reads them: the step boundary of k_rollout_slots (ewn_rollout.hpp: the agent half and the max_depth 5 / 6 opponent's move) and
+// the PERLANE form of d3_search (ewn_step_d3.hpp: the search entry with the max_depth 1-4 opponent's move).  Two more derived tables
+// were built and measured behind a lever of the macro that once switched all of this, and dropped: bit 4, a fused level table
+// lv2[ffbh P][ffbh N] (one 16-bit read per leaf in place of the two byte reads of lvl[]), measured slower, profiles/r09/README.md;
+// bit 16, a fused leaf table leaf[ix][iy] = { val, rank } of 16-byte entries (one ds_read_b128 per leaf in place of the rank read
+// and the value reads a round trip later, 28 KB more LDS per block), which alone gained what the one ordered sum per game gains and
+// together with it nothing, profiles/r10/README.md.
 
 struct alignas(8) MoveEnt { u32 mv, rc; };
 template <int S, bool WIDE = (sizeof(typename MaskOf<S>::type) == 8)> struct ReplyEnt;

@@ -19,7 +19,6 @@
 
 // Diagnostic build only (tools/rollout_stamps.py, -DEWN_ROLLOUT_STAMPS): s_memtime at the phase boundaries of a step, summed over the
 // K steps of a launch per wave and written over the (then meaningless) return_sum buffer.  Never defined in the shipped library.
-// (EWN_MT_LEVERS, which levers of the slot-task kernel's derived tables are on in a diagnostic build: ewn_movetab.hpp)
 
 #ifdef EWN_ROLLOUT_STAMPS
 #define RSTAMP(i) do { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); st_acc[i] += t_ - st_prev; st_prev = t_; } while (0)
@@ -159,12 +158,10 @@ EWN_DEV void rec_store(const int8_t *slot, int sub, int dice, int aflag, int adi
 // The stand-in agent's action for the current observation (the agent is the canonical BOTTOM_RIGHT side): RandomAgent.predict -- the
 // same draw ewn_step_out.random_action makes at the end of the previous step -- or, with c.agent_sample, env.action_space.sample():
 // one of the six (flag, direction) pairs, legal or not.  Hash-driven: the dice stream is not touched.
-// e: pk_sel(s.posN, dice), which the agent half reads too
+// e: pk_sel(s.posN, dice), which the agent half reads too; okm: the legal directions of the two cubes it selects (bits 0..2, 3..5)
 template <int S>
-EWN_DEV void roll_stand_in_action(const FastTab<S> *Tb, const RState<S> &s, u32 e, LaneRng &r, const RollCfg &c, int game, int &aflag, int &adir)
+EWN_DEV void roll_stand_in_action(const FastTab<S> *Tb, u32 okm, u32 e, LaneRng &r, const RollCfg &c, int game, int &aflag, int &adir)
 {
-    const u32 pp = pk_pair(s.posN, e);
-    const u32 okm = (u32)Tb->lgn[pp & 0xFFu] | ((u32)Tb->lgn[pp >> 8] << 3);
     const int n = __popc(okm);
     const u32 w = agent_hash(r.seed_mix(), r.draws(), (u32)(c.lane_offset + game), c.key);
     if (c.agent_sample) {
@@ -177,32 +174,33 @@ EWN_DEV void roll_stand_in_action(const FastTab<S> *Tb, const RState<S> &s, u32 
         adir = slot < 3 ? slot : slot - 3;
     }
 }
-
-// A move's two byte stores into the game's LDS slot: the source cell cleared, the destination set to `v`.  With T = 1 one lane stores
-// both, source first (LDS stores of one wave land in program order); with T > 1 lane 0 of the game clears the source and lane 1
-// sets the destination: one table read and one store per lane (the cells differ, so the order does not matter).
-template <int S, int T>
-EWN_DEV void slot_move(const FastTab<S> *Tb, int8_t *slot, int sub, int pb, int q, int v)
+// ... the legal directions read from the image
+template <int S>
+EWN_DEV void roll_stand_in_action(const FastTab<S> *Tb, const RState<S> &s, u32 e, LaneRng &r, const RollCfg &c, int game, int &aflag, int &adir)
 {
-    if constexpr (T == 1) { const int cp = Tb->real_of_ring[pb & 63], cq = Tb->real_of_ring[q & 63]; slot[cp] = 0; slot[cq] = (int8_t)v; }
-    else {
-        const bool dst = sub == 1;
-        if (sub < 2) slot[Tb->real_of_ring[(dst ? q : pb) & 63]] = (int8_t)(dst ? v : 0);
-    }
+    const u32 pp = pk_pair(s.posN, e);
+    roll_stand_in_action<S>(Tb, (u32)Tb->lgn[pp & 0xFFu] | ((u32)Tb->lgn[pp >> 8] << 3), e, r, c, game, aflag, adir);
+}
+
+// A move's two byte stores into the game's LDS slot, by the game's one lane: the source cell cleared, then the destination set to `v`
+// (LDS stores of one wave land in program order)
+template <int S>
+EWN_DEV void slot_move(const FastTab<S> *Tb, int8_t *slot, int pb, int q, int v)
+{
+    const int cp = Tb->real_of_ring[pb & 63], cq = Tb->real_of_ring[q & 63]; slot[cp] = 0; slot[cq] = (int8_t)v;
 }
 
 // agent half of step() (envs/ewn.py:438-458): true if the opponent has to reply (then `dice` is the opponent's roll)
-// e: pk_sel(s.posN, dice); slot: the game's board bytes in LDS, kept current (NULL: the caller encodes the board itself),
-// by the game's T lanes (`sub`: this lane's index among them)
-template <int S, int T = 1>
+// e: pk_sel(s.posN, dice); slot: the game's board bytes in LDS, kept current (NULL: the caller encodes the board itself)
+template <int S>
 EWN_DEV bool roll_agent_half(const FastTab<S> *Tb, RState<S> &s, u32 e, int aflag, int adir, int &dice, LaneRng &r, double R,
-                             double &reward, int &term, int &trunc, int &info, int8_t *slot = nullptr, int sub = 0)
+                             double &reward, int &term, int &trunc, int &info, int8_t *slot = nullptr)
 {
     const int k = pk_cube(e, aflag == 1);
     const int pb = pk_get(s.posN, k);
     const int q = Tb->nbn[adir][pb]; // no cube at all: byte 6 -> 255
     if (q == 255) { reward = -R; term = 1; trunc = 1; info = EWN_INFO_INVALID_PLAYER; return false; }
-    if (slot) slot_move<S, T>(Tb, slot, sub, pb, q, k + 1); // the agent's cube k is the real +(k + 1)
+    if (slot) slot_move<S>(Tb, slot, pb, q, k + 1); // the agent's cube k is the real +(k + 1)
     rs_move<S, false>(s, k, q);
     if (q == Tb->ri_origin || s.P == 0) { reward = R; term = 1; info = EWN_INFO_WON; return false; }
     dice = r.randint(1, 7);
@@ -210,11 +208,11 @@ EWN_DEV bool roll_agent_half(const FastTab<S> *Tb, RState<S> &s, u32 e, int afla
 }
 
 // opponent half (envs/ewn.py:464-486) once its move is known: cube k from ring cell pb (its position byte) to ring cell q
-template <int S, int T = 1>
+template <int S>
 EWN_DEV void roll_opponent_move(const FastTab<S> *Tb, RState<S> &s, int k, int pb, int q, int &dice, LaneRng &r, double R,
-                                double &reward, int &term, int &info, int8_t *slot = nullptr, int sub = 0)
+                                double &reward, int &term, int &info, int8_t *slot = nullptr)
 {
-    if (slot) slot_move<S, T>(Tb, slot, sub, pb, q, -(k + 1));
+    if (slot) slot_move<S>(Tb, slot, pb, q, -(k + 1));
     rs_move<S, true>(s, k, q);
     if (q == FastTab<S>::CELLS - 1 || s.N == 0) { reward = -R; term = 1; info = EWN_INFO_LOST; }
     else dice = r.randint(1, 7);
@@ -238,29 +236,20 @@ EWN_DEV void roll_opponent_half(const FastTab<S> *Tb, RState<S> &s, u32 e, int o
 template <int S>
 EWN_DEV void roll_stand_in_action(const FastTab<S> *Tb, const MoveEnt &m0, const MoveEnt &m1, u32 e, LaneRng &r, const RollCfg &c, int game, int &aflag, int &adir)
 {
-    const u32 okm = me_legal(m0) | (me_legal(m1) << 3);
-    const int n = __popc(okm);
-    const u32 w = agent_hash(r.seed_mix(), r.draws(), (u32)(c.lane_offset + game), c.key);
-    if (c.agent_sample) {
-        const int a6 = (int)__umulhi(w, 6u);
-        aflag = a6 >= 3 ? 1 : 0;
-        adir = a6 - 3 * aflag;
-    } else if (n > 0) {
-        const int slot = Tb->nth[okm * 8u + __umulhi(w, (u32)n)];
-        aflag = slot < 3 ? (int)(e >> 15) : 0;
-        adir = slot < 3 ? slot : slot - 3;
-    }
+    roll_stand_in_action<S>(Tb, me_legal(m0) | (me_legal(m1) << 3), e, r, c, game, aflag, adir);
 }
 
-// slot_move on REAL cells, no table: the source cell is byte (shp / 8) of w, the destination byte (shq / 8).  With T > 1 a lane
-// extracts only the cell it stores to: one select between the two shifts (loop-invariant where they are constants) and one v_bfe
+// slot_move on REAL cells, no table: the source cell is byte (shp / 8) of w, the destination byte (shq / 8).  With T = 2 lane 0 of
+// the game clears the source and lane 1 sets the destination (the cells differ, so the order does not matter): a lane extracts
+// only the cell it stores to, one select between the two shifts (loop-invariant where they are constants) and one v_bfe
 template <int T>
 EWN_DEV void slot_move_real(int8_t *slot, int sub, u32 w, int shp, int shq, int v)
 {
+    static_assert(T == 1 || T == 2, "one or two lanes per game");
     if constexpr (T == 1) { slot[(w >> shp) & 0xFFu] = 0; slot[(w >> shq) & 0xFFu] = (int8_t)v; }
     else {
         const bool dst = sub == 1;
-        if (sub < 2) slot[(w >> (dst ? shq : shp)) & 0xFFu] = (int8_t)(dst ? v : 0);
+        slot[(w >> (dst ? shq : shp)) & 0xFFu] = (int8_t)(dst ? v : 0);
     }
 }
 
@@ -302,7 +291,6 @@ template <int S, int T, int OPP, int RNGK, int AGENT, bool H2 = false, int TRJ =
 __global__ __launch_bounds__(D3_BS, ((OPP == 2 || AGENT == 2) ? 2 : 1)) void k_rollout_d3(RollCfg c, RollBuf B) // the max_depth 5 / 6 search: hold it to 256 registers (two waves per SIMD)
 {
     constexpr int CELLS = S * S, GPB = D3_BS / T; // games per block
-    constexpr int TS = T > 2 ? 2 : T;             // lanes per game the depth-5 search can use
     // LDS: boards | table image(s) | 16 bytes per game of decode scratch.  With the RandomAgent agent (one image) the block is a
     // STATIC array: its address is then a compile-time constant that folds into the offset field of every ds_read, where the
     // dynamic-LDS base is a link-time symbol the compiler adds with one VALU instruction in front of every table read (43 per
@@ -368,7 +356,7 @@ __global__ __launch_bounds__(D3_BS, ((OPP == 2 || AGENT == 2) ? 2 : 1)) void k_r
             // ExpectiMinimaxAgent.predict(canonical observation): the agent's own position IS canonical for it once flipped
             const RState<S> f = rs_flip<S>(Ta, s);
             if constexpr (AGENT == 1) d3_search<S, T>(Ta, f, dice, sub, c.agent_depth, aflag, adir);
-            else d5_dispatch<S, TS>(Ta, f, dice, T > 2 ? (sub & 1) : sub, aflag, adir);
+            else d5_dispatch<S, T>(Ta, f, dice, sub, aflag, adir);
         }
         if (active) { // a frozen lane's stream stays where its last step left it
             if constexpr (RNGK == 0) r.prefetch();
@@ -382,7 +370,7 @@ __global__ __launch_bounds__(D3_BS, ((OPP == 2 || AGENT == 2) ? 2 : 1)) void k_r
         // the opponent's search: run by every lane (lanes without a pending reply compute on a harmless state)
         int oflag = 0, odir = 0;
         if constexpr (OPP == 0) d3_search<S, T, H2>(Tb, s, dice, sub, c.depth, oflag, odir);
-        if constexpr (OPP == 2) d5_dispatch<S, TS, H2>(Tb, s, dice, T > 2 ? (sub & 1) : sub, oflag, odir);
+        if constexpr (OPP == 2) d5_dispatch<S, T, H2>(Tb, s, dice, sub, oflag, odir);
         RSTAMP(2); // search
         if (reply) {
             // opponent half, envs/ewn.py:464-486
@@ -499,12 +487,7 @@ __global__ __launch_bounds__(D3_BS, (OPP == 2 ? 2 : 1)) void k_rollout_slots(Rol
     static_assert(OPP == 0 || OPP == 2, "minimax opponents");
     static_assert(!(H2 && OPP == 2), "'two_min_dist' at max_depth 5 / 6 keeps the reference's loops (d5_search): lock-step kernel only");
     constexpr int CELLS = S * S, GPB = D3_BS / T;   // games per block
-    constexpr int TS = T > 2 ? 2 : T;               // lanes per game the depth-5 search can use
     constexpr int STR = RecGeo<S>::STR;             // LDS bytes per game: the game's board slot, one trajectory record wide
-    // the levers of the derived tables, for A/B builds (-DEWN_MT_LEVERS=n): 1 = the agent half and the max_depth 5 / 6 opponent's move,
-    // 2 = the search entry with the max_depth 1-4 opponent's move (8 = the key swap inside that search, ewn_step_d3.hpp).  The library
-    // ships all three.
-    constexpr bool MT_BND = (EWN_MT_LEVERS & 1) != 0, MT_SRCH = (EWN_MT_LEVERS & 2) != 0;
     __shared__ __attribute__((aligned(16))) int8_t lds_st[GPB * STR + FAST_TAB_BYTES(S) + GPB * 16 + SlotTabGeo<S>::EXTRA];
     int8_t *lds = lds_st;
     int8_t *tb = lds + GPB * STR;
@@ -563,42 +546,35 @@ __global__ __launch_bounds__(D3_BS, (OPP == 2 ? 2 : 1)) void k_rollout_slots(Rol
         if (start) {
             reward = 0.0; term = frozen ? 1 : 0; trunc = 0; info = EWN_INFO_NONE; reply = false; aflag = 0; adir = 0;
             const u32 esel = pk_sel<S>(Tb, s.posN, dice);
-            [[maybe_unused]] MoveEnt m0 = {}, m1 = {};
-            if constexpr (MT_BND) {
-                const u32 pp = pk_pair(s.posN, esel);
-                m0 = me_read(D.mvn, (int)(pp & 0xFFu)); m1 = me_read(D.mvn, (int)((pp >> 8) & 0xFFu)); // the two candidate cubes' entries, together
-                roll_stand_in_action<S>(Tb, m0, m1, esel, r, c, game, aflag, adir);
-            } else roll_stand_in_action<S>(Tb, s, esel, r, c, game, aflag, adir);
+            MoveEnt m0 = {}, m1 = {};   // (declared apart from their reads: written as one initialisation the loop is scheduled differently)
+            const u32 pp = pk_pair(s.posN, esel);
+            m0 = me_read(D.mvn, (int)(pp & 0xFFu)); m1 = me_read(D.mvn, (int)((pp >> 8) & 0xFFu)); // the two candidate cubes' entries, together
+            roll_stand_in_action<S>(Tb, m0, m1, esel, r, c, game, aflag, adir);
             if (active) { // a frozen lane's stream stays where its last step left it
                 if constexpr (RNGK == 0) r.prefetch();
                 r.begin_step();
                 // the game's two lanes share the step's Philox block (the lanes of a game take the same branches)
                 if constexpr (RNGK == 1) { if constexpr (T == 2) r.ps.prime_pair(sub); else r.ps.prime(); }
-                if constexpr (MT_BND) reply = roll_agent_half<S, T>(s, m0, m1, esel, aflag, adir, dice, r, c.reward, reward, term, trunc, info, slot_m, sub);
-                else reply = roll_agent_half<S, T>(Tb, s, esel, aflag, adir, dice, r, c.reward, reward, term, trunc, info, slot_m, sub);
+                reply = roll_agent_half<S, T>(s, m0, m1, esel, aflag, adir, dice, r, c.reward, reward, term, trunc, info, slot_m, sub);
             }
         }
         RSTAMP(0); // start of an env step: the agent's action, RNG block, agent half
         // one cube's three roots of the opponent's search, run by every lane (lanes without a pending reply compute on a harmless
         // state, so the DPP exchanges inside always see their partners)
         bool second = false;
-        if constexpr (OPP == 0) best = d3_search<S, T, H2, true, MT_SRCH>(Tb, s, dice, sub, c.depth, oflag, odir, phase, best, &second, &omove, &D);
-        else best = d5c_search<S, TS, true>(Tb, s, dice, T > 2 ? (sub & 1) : sub, oflag, odir, phase, best, &second);
+        if constexpr (OPP == 0) best = d3_search<S, T, H2, true>(Tb, s, dice, sub, c.depth, oflag, odir, phase, best, &second, &omove, &D);
+        else best = d5c_search<S, T, true>(Tb, s, dice, sub, oflag, odir, phase, best, &second);
         RSTAMP(1); // search
         if (pending && phase == 0 && reply && second) phase = 1; // the same env step goes on with the second cube
         else if (pending) {
             phase = 0;
             if (reply) {
-                if constexpr (OPP == 0 && MT_SRCH) { // the search's chosen root is the move, real cells included
+                if constexpr (OPP == 0) { // the search's chosen root is the move, real cells included
                     roll_opponent_move_real<S, T>(s, (int)(omove & 7u), (int)((omove >> 8) & 0xFFu), omove, 16, 24, dice, r, c.reward, reward, term, info, slot_m, sub);
-                } else if constexpr (OPP == 0) {
-                    roll_opponent_move<S, T>(Tb, s, (int)(omove & 7u), (int)((omove >> 8) & 0xFFu), (int)(omove >> 16), dice, r, c.reward, reward, term, info, slot_m, sub);
                 } else {
                     const int k = pk_cube(pk_sel<S>(Tb, s.posP, dice), oflag == 1), pb = pk_get(s.posP, k);
-                    if constexpr (MT_BND) {
-                        const MoveEnt mp = me_read(D.mvp, pb);
-                        roll_opponent_move_real<S, T>(s, k, me_dest(mp, odir), mp.rc, 0, 8 + 8 * odir, dice, r, c.reward, reward, term, info, slot_m, sub);
-                    } else roll_opponent_move<S, T>(Tb, s, k, pb, Tb->nbp[odir][pb], dice, r, c.reward, reward, term, info, slot_m, sub);
+                    const MoveEnt mp = me_read(D.mvp, pb);
+                    roll_opponent_move_real<S, T>(s, k, me_dest(mp, odir), mp.rc, 0, 8 + 8 * odir, dice, r, c.reward, reward, term, info, slot_m, sub);
                 }
             }
             if (!frozen) {

@@ -8,7 +8,7 @@
 //    the search.  The agent is the canonical BOTTOM_RIGHT side ("replier" geometry), the
 //    opponent the canonical TOP_LEFT side; an action [flag, dir] means the same in both
 //    views (envs/ewn.py:289-296);
-//  * T lanes cooperate on one game (the code is written for T = 1, 2, 4; the library instantiates 1 and 2): each computes a share of the 108 leaves
+//  * T lanes cooperate on one game (T = 1 or 2): each computes a share of the 108 leaves
 //    and of the 36 (root, dice) scans and they swap results with DPP lane permutes inside
 //    the wavefront.  At 65 536 lanes a thread per game is ONE wave per SIMD; T lanes per
 //    game give T waves per SIMD, which is what hides LDS/global latency and doubles the
@@ -34,7 +34,7 @@ struct RingGeo {
 };
 
 // Quad-permute DPP (a VALU operand modifier: no LDS round trip).  The T lanes of a game are T consecutive
-// lanes inside one quad (T <= 4), so "lane j of my group" is a quad_perm broadcast.
+// lanes inside one quad (T <= 2), so "lane j of my group" is a quad_perm broadcast.
 template <int CTRL> EWN_DEV u32 dpp_u32(u32 v) { return (u32)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, true); }
 template <int CTRL> EWN_DEV double dpp_f64(double v)
 {
@@ -44,12 +44,11 @@ template <int CTRL> EWN_DEV double dpp_f64(double v)
 }
 // broadcast from lane J of a group of T lanes
 template <int T, int J> struct Bcast {
-    // T == 4: quad_perm [J,J,J,J]; T == 2: pairs (0,1) and (2,3): [J,J,2+J,2+J]
-    static constexpr int CTRL = T == 4 ? (J | (J << 2) | (J << 4) | (J << 6)) : (J | (J << 2) | ((2 + J) << 4) | ((2 + J) << 6));
+    static_assert(T == 2, "pairs (0,1) and (2,3) of a quad");
+    static constexpr int CTRL = J | (J << 2) | ((2 + J) << 4) | ((2 + J) << 6);   // quad_perm [J,J,2+J,2+J]
 };
-// xor-1 / xor-2 lane swaps inside a quad
+// xor-1 lane swap inside a quad
 #define DPP_XOR1 0xB1 /* quad_perm [1,0,3,2] */
-#define DPP_XOR2 0x4E /* quad_perm [2,3,0,1] */
 
 // A side's six cubes: byte k of a u64 = ring index of cube k (0-based), bit 6 set once the cube is off the board (the low six
 // bits are then stale); bytes 6 and 7 are permanently "off the board", which is what a table answers "no such cube" with.
@@ -239,24 +238,17 @@ EWN_DEV u32 rank_u32(u32 r) { asm("" : "+v"(r)); return r; }
 // element `sub + T * i` of a six-element array held identically by the T lanes of a group, for the lane with index `sub`
 template <int T> EWN_DEV u32 own_of(const u32 (&v)[6], int i, int sub)
 {
+    static_assert(T == 1 || T == 2, "one or two lanes per game");
     if constexpr (T == 1) return v[i];
-    else if constexpr (T == 2) return sub ? v[2 * i + 1] : v[2 * i];
-    else {
-        if (i == 0) { const u32 lo = (sub & 1) ? v[1] : v[0], hi = (sub & 1) ? v[3] : v[2]; return (sub & 2) ? hi : lo; }
-        return (sub & 1) ? v[5] : v[4];   // lanes 2 and 3 have no second dice (6 % 4 = 2): their value is never used
-    }
+    else return sub ? v[2 * i + 1] : v[2 * i];
 }
 
 // every lane of a group of T gets all T lanes' `mine`: out[T * i + j] = lane j's value
 template <int T> EWN_DEV void publish(u32 mine, int i, u32 (&out)[6])
 {
+    static_assert(T == 1 || T == 2, "one or two lanes per game");
     if constexpr (T == 1) out[i] = mine;
-    else if constexpr (T == 2) { out[2 * i] = dpp_u32<Bcast<2, 0>::CTRL>(mine); out[2 * i + 1] = dpp_u32<Bcast<2, 1>::CTRL>(mine); }
-    else {
-        if (i == 0) { out[0] = dpp_u32<Bcast<4, 0>::CTRL>(mine); out[1] = dpp_u32<Bcast<4, 1>::CTRL>(mine);
-                      out[2] = dpp_u32<Bcast<4, 2>::CTRL>(mine); out[3] = dpp_u32<Bcast<4, 3>::CTRL>(mine); }
-        else { out[4] = dpp_u32<Bcast<4, 0>::CTRL>(mine); out[5] = dpp_u32<Bcast<4, 1>::CTRL>(mine); }
-    }
+    else { out[2 * i] = dpp_u32<Bcast<2, 0>::CTRL>(mine); out[2 * i + 1] = dpp_u32<Bcast<2, 1>::CTRL>(mine); }
 }
 
 // Depth-3 search in ring space ('hybrid', 'min_dist' or 'attk' by table image), shared by T lanes (sub = my index in the group).
@@ -273,34 +265,28 @@ template <int T> EWN_DEV void publish(u32 mine, int i, u32 (&out)[6])
 // PERLANE (the slot-task rollout kernel, ewn_rollout.hpp): one call searches the three roots of ONE root cube -- slotL = 0: the
 // first cube of the legal list, 1: the second -- and carries best / bflag / bdir in and out, so that a game whose dice selects a
 // single cube (most do) is finished after one call; returns through `have_second` whether the list has a second cube.
+// It reads D = the block's derived tables (ewn_movetab.hpp): the root cube's three destinations and the real cells of its moves are
+// ONE 8-byte read, a replier cube's setup two or three wide reads.
 // bmove (PERLANE only, may be NULL): the chosen root as the move the caller makes, carried in and out like bflag / bdir:
-// cube | its position byte << 8 | destination ring cell << 16 -- what the opponent half would otherwise look up again
-// (set whenever a valid root exists, which it does for every position whose game goes on: only the corner a TOP_LEFT cube wins
-// on has no legal direction)
-// MT (the slot-task rollout kernel only, with PERLANE): D = the block's derived tables (ewn_movetab.hpp).  The root cube's three
-// destinations and the real cells of its moves are ONE 8-byte read, a replier cube's setup two or three wide reads, and bmove becomes
-// cube | destination ring cell << 8 | REAL source cell << 16 | REAL destination cell << 24: the caller's two byte stores into the
-// game's board slot need no table either.  With T = 2 the two lanes SWAP their cubes' keys (one lane permute per cube where the
-// other forms broadcast every key to both lanes with two) and each lane runs the nearest-cube carries for its own three dice only;
-// the chosen ranks travel to both lanes in dice order only where the next lever is off.
-// With T = 2 (lever 32 of EWN_MT_LEVERS) the expectation is summed ONCE per game: a lane keeps its own three chosen ranks and reads its
-// own three val6[] terms, the odd lane's three doubles cross to the even lane (six lane permutes), the even lane adds all six in
-// dice order -- the expression it always was -- and the sum returns to the odd lane with two permutes.  The odd lane adds the same
-// six terms in another order; that sum is overwritten before anything reads it.
-template <int S, int T, bool H2 = false, bool PERLANE = false, bool MT = false>
+// cube | destination ring cell << 8 | REAL source cell << 16 | REAL destination cell << 24 -- what the opponent half would otherwise
+// look up again, and the caller's two byte stores into the game's board slot need no table either (set whenever a valid root
+// exists, which it does for every position whose game goes on: only the corner a TOP_LEFT cube wins on has no legal direction)
+// PERLANE with T = 2 (PAIR below): the two lanes SWAP their cubes' keys (one lane permute per cube where the other forms broadcast
+// every key to both lanes with two) and each lane runs the nearest-cube carries for its own three dice only.  The expectation is
+// summed ONCE per game: a lane keeps its own three chosen ranks and reads its own three val6[] terms, the odd lane's three doubles
+// cross to the even lane (six lane permutes), the even lane adds all six in dice order -- the expression it always was -- and the
+// sum returns to the odd lane with two permutes.  The odd lane adds the same six terms in another order; that sum is overwritten
+// before anything reads it.
+template <int S, int T, bool H2 = false, bool PERLANE = false>
 __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S> &c, int dice, int sub, int depth, int &bflag, int &bdir,
                                             int slotL = 0, double best_in = 0.0, bool *have_second = nullptr, u32 *bmove = nullptr,
                                             [[maybe_unused]] const SlotTabs<S> *D = nullptr)
 {
-    static_assert(!MT || PERLANE, "the derived tables serve the per-lane search entry");
+    static_assert(T == 1 || T == 2, "the six replier cubes and dice values are split over one or two lanes");
     typedef typename MaskOf<S>::type M;
-    constexpr int KPT = 6 / T + (6 % T ? 1 : 0); // replier cubes / dice values per lane: k = sub + T*i
+    constexpr int KPT = 6 / T; // replier cubes / dice values per lane: k = sub + T*i
     const M one = 1;
-    // the search's own lever (A/B builds with -DEWN_MT_LEVERS=n, ewn_movetab.hpp): 8 = the two lanes of a game swap their keys instead
-    // of broadcasting them
-    constexpr bool SWAP = MT && T == 2 && (EWN_MT_LEVERS & 8) != 0;
-    // 32 = one ordered sum per game (above)
-    constexpr bool SUM1 = MT && T == 2 && (EWN_MT_LEVERS & 32) != 0;
+    constexpr bool PAIR = PERLANE && T == 2;   // the slot-task kernel's two-lane form: keys swapped, one ordered sum per game
 
     // root slots: <= 2 cubes x 3 dirs in the reference's list order (envs/ewn.py:338-375)
     const u32 rsel_all = pk_sel<S>(Tb, c.posP, dice), rpp_all = pk_pair(c.posP, rsel_all);
@@ -312,16 +298,16 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
     const bool have0 = !(rb0 & PK_OFF), have1 = !(rb1 & PK_OFF);
     const int flag0 = (int)(rsel >> 15);
     const int rp0 = rb0 & 63, rp1 = rb1 & 63;
-    // (cube | position byte << 8) of the two root cubes, for bmove
-    u32 rm0 = (rsel & 7u) | ((rpp & 0xFFu) << 8), rm1 = ((rsel >> 8) & 7u) | (rpp & 0xFF00u);
+    [[maybe_unused]] const u32 rc0 = rsel & 7u, rc1 = (rsel >> 8) & 7u;   // the two root cubes, for bmove
     u32 bm = 0;
-    // MT: the call's root cube's fused entry (a position byte that is off the board reads "no legal direction, destinations 255").
+    // PERLANE: the call's root cube's fused entry (a position byte that is off the board reads "no legal direction, destinations 255").
     // rm0 = the entry's destination word with the cube in place of the legal mask: the packed move of direction d is then ONE
     // byte permute of (real cells, rm0) -- bytes 0 and 1 + d of rm0, bytes 0 and 1 + d of the real cells
     [[maybe_unused]] MoveEnt me0 = {};
-    if constexpr (MT) {
+    [[maybe_unused]] u32 rm0 = 0;
+    if constexpr (PERLANE) {
         me0 = me_read(D->mvp, rb0);
-        rm0 = (me0.mv & 0xFFFFFF00u) | (rsel & 7u);
+        rm0 = (me0.mv & 0xFFFFFF00u) | rc0;
     }
     #define D3_BM_SEL(d) (0x05040100u + (u32)(d) * 0x01000100u)
 
@@ -336,15 +322,15 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
         // max_depth 1 and 2 bottom out before the replier moves (classical_policies/minimax.py:19-73: every node, chance nodes
         // included, spends one unit of depth): depth 1 evaluates the position after the root move at the chance node; depth 2
         // at the six min nodes below it, i.e. evaluate()/6 summed six times in dice order.  Every lane of the group does all six roots.
-        [[maybe_unused]] MoveEnt me1 = {}; // MT: the second root cube's entry, made up like the first one's
-        if constexpr (MT) { me1 = me_read(D->mvp, rb1); me1.mv = (me1.mv & 0xFFFFFF00u) | ((rsel >> 8) & 7u); }
+        [[maybe_unused]] MoveEnt me1 = {}; // PERLANE: the second root cube's entry, made up like the first one's
+        if constexpr (PERLANE) { me1 = me_read(D->mvp, rb1); me1.mv = (me1.mv & 0xFFFFFF00u) | rc1; }
         #pragma unroll 1
         for (int r = 0; r < 6; r++) {
             const int slot = r >= 3 ? 1 : 0, dir = r - 3 * slot;
             const int rp = slot == 0 ? rp0 : rp1;
             int dest;
             [[maybe_unused]] const u32 rcw = slot == 0 ? me0.rc : me1.rc, mvw = slot == 0 ? rm0 : me1.mv;
-            if constexpr (MT) dest = (int)((mvw >> (8 + 8 * dir)) & 0xFFu); else dest = Tb->nbp[dir][rp];
+            if constexpr (PERLANE) dest = (int)((mvw >> (8 + 8 * dir)) & 0xFFu); else dest = Tb->nbp[dir][rp];
             const bool valid = (slot == 0 ? have0 : have1) && dest != 255;
             const M bd = valid ? (one << dest) : (M)0;
             const M P1 = (c.P & ~(one << rp)) | bd;
@@ -358,8 +344,7 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
             v = term ? 10.0 : (depth == 1 ? e1 : v);
             if (valid && v > best) {
                 best = v; bflag = slot == 0 ? flag0 : 0; bdir = dir;
-                if constexpr (MT) bm = __builtin_amdgcn_perm(rcw, mvw, D3_BM_SEL(dir));
-                else bm = (slot == 0 ? rm0 : rm1) | ((u32)dest << 16);
+                if constexpr (PERLANE) bm = __builtin_amdgcn_perm(rcw, mvw, D3_BM_SEL(dir));
             }
         }
         if constexpr (PERLANE) { *have_second = false; if (bmove) *bmove = bm; } // both cubes were searched in this one call
@@ -375,11 +360,11 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
     u32 keep[KPT][3], fixed[KPT][3];
     #pragma unroll
     for (int i = 0; i < KPT; i++) {
-        const int k = sub + T * i;          // may be >= 6 for the last slot when 6 % T != 0: byte 6/7 = a cube that is off the board
-        const int rb = pk_get(c.posN, k < 6 ? k : 6);
+        const int k = sub + T * i;
+        const int rb = pk_get(c.posN, k);
         rnk[i] = rb & 63;
         rclr[i] = ~(one << rnk[i]);
-        if constexpr (MT) {
+        if constexpr (PERLANE) {
             // the cube's entry, whole: 16-byte pieces and the tail
             const ReplyEnt<S> *re = D->rep + rb;
             u32 kf[3];
@@ -406,7 +391,7 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
 
     // the six root destinations, read before the loop: inside it the read's whole latency stood in front of every root
     u32 dq0;
-    if constexpr (MT) dq0 = me0.mv >> 8;
+    if constexpr (PERLANE) dq0 = me0.mv >> 8;
     else dq0 = (u32)Tb->nbp[0][rp0] | ((u32)Tb->nbp[1][rp0] << 8) | ((u32)Tb->nbp[2][rp0] << 16);
     [[maybe_unused]] u32 dq1 = 0;
     if constexpr (!PERLANE) dq1 = (u32)Tb->nbp[0][rp1] | ((u32)Tb->nbp[1][rp1] << 8) | ((u32)Tb->nbp[2][rp1] << 16);
@@ -421,8 +406,8 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
         const int slot = PERLANE ? 0 : (r >= 3 ? 1 : 0), dir = PERLANE ? r : r - 3 * slot;   // PERLANE: the call's cube sits in slot 0
         const int rp = slot == 0 ? rp0 : rp1;
         const int dest = (int)(((slot == 0 ? dq0 : dq1) >> (8 * dir)) & 0xFFu);
-        // (MT: the fused entry of a cube that is off the board holds destinations 255 by itself)
-        const bool valid = MT ? dest != 255 : ((slot == 0 ? have0 : have1) && dest != 255);
+        // (PERLANE: the fused entry of a cube that is off the board holds destinations 255 by itself)
+        const bool valid = PERLANE ? dest != 255 : ((slot == 0 ? have0 : have1) && dest != 255);
         const M bd = valid ? (one << dest) : (M)0;
         const M P1 = (c.P & ~(one << rp)) | bd; // own capture: the bit is already set, the count drops by itself
         const M N1 = c.N & ~bd;
@@ -432,8 +417,8 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
         // re-serialising them into one round trip per leaf, which is what the register-pressure-driven schedule does):
         // levels -> ranks -> values of the three prefix minima -> cut.
         [[maybe_unused]] u32 tr[6];
-        [[maybe_unused]] u32 km[KPT];   // SWAP: my cubes' keys
-        constexpr int CH = KPT > 3 ? 3 : KPT; // cubes staged together: 9 leaves in flight; more only costs registers
+        [[maybe_unused]] u32 km[KPT];   // PAIR: my cubes' keys
+        constexpr int CH = 3; // cubes staged together: 9 leaves in flight; more only costs registers
         #pragma unroll
         for (int i0 = 0; i0 < KPT; i0 += CH) {
             M P2[CH][3], N2[CH][3];
@@ -492,13 +477,13 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
                 rk = va[ii] <= best ? a[ii][0] : rk;
                 u32 key = rk | (v2[ii] <= best ? D3_CUT : 0x8000u);
                 key = rnk[i] != dest ? key : FAST_KNONE;
-                if constexpr (SWAP) km[i] = key;
+                if constexpr (PAIR) km[i] = key;
                 else publish<T>(key, i, tr); // after this every lane holds tr[k] for all six cubes (cube k = j + T*i lives in lane j)
             }
         }
         [[maybe_unused]] u32 wq[6];
-        [[maybe_unused]] u32 wo[KPT];   // SUM1: the chosen ranks of my own dice
-        if constexpr (SWAP) {
+        [[maybe_unused]] u32 wo[KPT];   // PAIR: the chosen ranks of my own dice
+        if constexpr (PAIR) {
             // T = 2: ONE lane swap per cube.  A lane then holds its own three keys (cubes sub, sub + 2, sub + 4) and its partner's three,
             // and only its own three dice need the carries.  The partner's keys are aligned to the lane's parity, padded with "no such
             // cube": q[i] = the partner's cube just BELOW my cube i, q[i + 1] the one just above, so that the six cubes read
@@ -521,12 +506,11 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
                 dn3[i] = cur;
                 if (i < 2) { cur = km[i] != FAST_KNONE ? km[i] : cur; cur = q[i + 1] != FAST_KNONE ? q[i + 1] : cur; }
             }
-            // the chosen ranks travel as before: all six in dice order in both lanes, two broadcasts each (a swap would need six
-            // selects on `sub` to put them in order: nine instructions against six)
+            // the chosen ranks of my own three dice stay in this lane
             #pragma unroll
             for (int i = 0; i < 3; i++) {
                 const u32 w = (km[i] != FAST_KNONE ? km[i] : min(up3[i], dn3[i])) & 0x1FFFu;
-                if constexpr (SUM1) wo[i] = w; else publish<T>(w, i, wq);
+                wo[i] = w;
             }
         } else {
         // which cubes a dice value selects (find_near_cube): carry the nearest on-board cube's key along
@@ -550,13 +534,13 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
             // the dice cube alone if it is on the board; else F = up, G = down: F's cut value if F cuts (flag dropped: the smallest),
             // else G's if G cuts (flagged: below every key that does not cut), else the smaller minimum; no cube above: down alone
             const u32 w = (e != FAST_KNONE ? e : min(u, dn)) & 0x1FFFu;
-            if constexpr (SUM1) wo[i] = w; else publish<T>(w, i, wq);
+            publish<T>(w, i, wq);   // the chosen ranks travel to every lane in dice order
         }
-        } // !SWAP
+        } // !PAIR
         // expected_val += val / 6 in dice order, minimax.py:72.  The sum starts from its first term: 0.0 + x is x bit for bit unless
         // x is -0.0, and no table holds one (build_fast_tables checks val6[])
         double v;
-        if constexpr (SUM1) {
+        if constexpr (PAIR) {
             // my three terms (dice sub, sub + 2, sub + 4) and my partner's; on the even lane e0 + o0 + e1 + o1 + e2 + o2 is the sum in
             // dice order, and both lanes take that one
             double m6[3], o6[3];
@@ -575,8 +559,7 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
         v = term ? 10.0 : v;
         if (valid && v > best) {
             best = v; bflag = slot == 0 ? flag0 : 0; bdir = dir;
-            if constexpr (MT) bm = __builtin_amdgcn_perm(me0.rc, rm0, D3_BM_SEL(dir));
-            else if constexpr (PERLANE) bm = rm0 | ((u32)dest << 16);
+            if constexpr (PERLANE) bm = __builtin_amdgcn_perm(me0.rc, rm0, D3_BM_SEL(dir));
         }
     }
     D3_PRIO_LO();
@@ -708,11 +691,11 @@ EWN_DEV void d3_decode(const int8_t *b, int sub, uint8_t *ga, RState<S> &s)
     // bytes 6 and 7 are forced "off the board" whatever a malformed board (|v| > 6) scattered there
     s.posN = ((((u64)x.w << 32) | x.z) >> 8) | PK_PADS;                                      // bytes 9..14 -> 0..5
     s.posP = (((u64)__builtin_bswap32(x.x) << 32) | __builtin_bswap32(x.y)) | PK_PADS;       // bytes 7..2 -> 0..5, 1..0 -> 6..7
-    if constexpr (T >= 2) {
+    static_assert(T == 1 || T == 2, "one round of the lane combine");
+    if constexpr (T == 2) {
         #define D3_OR64(x, ctrl) x |= ((u64)dpp_u32<ctrl>((u32)(x >> 32)) << 32) | dpp_u32<ctrl>((u32)x)
         #define D3_ORM(x, ctrl) do { if constexpr (sizeof(M) == 4) x |= (M)dpp_u32<ctrl>((u32)x); else { u64 t_ = (u64)x; D3_OR64(t_, ctrl); x = (M)t_; } } while (0)
         D3_ORM(P, DPP_XOR1); D3_ORM(N, DPP_XOR1);
-        if constexpr (T == 4) { D3_ORM(P, DPP_XOR2); D3_ORM(N, DPP_XOR2); }
         #undef D3_ORM
         #undef D3_OR64
     }
@@ -911,7 +894,7 @@ __global__ __launch_bounds__(D3_BS, (OPP == 2 ? 2 : 1)) void k_step_d3(D3Cfg c, 
     // so the DPP exchanges inside always see their partners
     int oflag = 0, odir = 0;
     if constexpr (OPP == 0) d3_search<S, T, H2>(Tb, s, dice, sub, c.depth, oflag, odir);
-    if constexpr (OPP == 2) d5_dispatch<S, (T > 2 ? 2 : T), H2>(Tb, s, dice, sub, oflag, odir); // max_depth 5 / 6: its own instances (T = 1, 2), so its registers do not weigh on the others
+    if constexpr (OPP == 2) d5_dispatch<S, T, H2>(Tb, s, dice, sub, oflag, odir); // max_depth 5 / 6: its own instances, so its registers do not weigh on the others
     if (reply) {
         // opponent half, envs/ewn.py:464-486
         const u32 e = pk_sel<S>(Tb, s.posP, dice);
