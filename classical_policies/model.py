@@ -117,12 +117,17 @@ class PuctAgent(_PlainPolicyFn, ModelAgent):
     produce.  Always deterministic: a win on the board, else the most visited move.  sims=0 plays the first legal move unless one wins.
     endgame_table (an ewn_gym_amd.EndgameTable or the path of a saved one): a leaf that the table covers is worth its exact value
     instead of the value head's.  fused=True: the search of a batch is one kernel launch (ewn_puct_search, DESIGN.md
-    4r) instead of 2 sims + 3: the same moves; not together with endgame_table."""
+    4r) instead of 2 sims + 3: the same moves; not together with endgame_table.  leaves=2..32: the search of a batch is the one launch
+    of ewn_puct_search_wide, up to that many leaves per tree and round: fewer rounds, other trees, so not always the
+    moves of leaves=1; not together with endgame_table."""
 
-    def __init__(self, model_or_path, board_size=5, cube_layer=3, sims=64, c_puct=1.5, terminal_value=1.0, endgame_table=None, fused=False):
+    def __init__(self, model_or_path, board_size=5, cube_layer=3, sims=64, c_puct=1.5, terminal_value=1.0, endgame_table=None, fused=False,
+                 leaves=1):
         from ewn_gym_amd.search import _fused_table, _puct_numbers
+        from ewn_gym_amd.wide import _NO_TABLE, _leaves_alone
         self.sims = _puct_numbers("PuctAgent", sims, c_puct, terminal_value)
         _fused_table("PuctAgent", fused, endgame_table)
+        self.leaves = _leaves_alone("PuctAgent", leaves, endgame_table=(endgame_table is not None, _NO_TABLE))
         self.fused = bool(fused)
         self.c_puct, self.terminal_value = float(c_puct), float(terminal_value)
         super().__init__(model_or_path, board_size=board_size, cube_layer=cube_layer, deterministic=True)
@@ -134,7 +139,7 @@ class PuctAgent(_PlainPolicyFn, ModelAgent):
         b, d = self._on_device(boards, dice)
         return self._ea.predict_puct(b, d, self.params, sims=self.sims, c_puct=self.c_puct, terminal_value=self.terminal_value,
                                      return_visits=return_visits, return_q=return_q, return_value=return_value,
-                                     cube_layer=self.cube_layer, endgame_table=self.endgame_table, fused=self.fused)
+                                     cube_layer=self.cube_layer, endgame_table=self.endgame_table, fused=self.fused, leaves=self.leaves)
 
 
 class EndgameAgent(_PlainPolicyFn, PolicyBase):

@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SRC = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".hip")]
 DEPS = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + [os.path.join(HERE, "..", "include", h)
-                                                                    for h in ("ewn_hip.h", "ewn_playout_search.h")]
+                                                                    for h in ("ewn_hip.h", "ewn_playout_search.h", "ewn_puct_wide.h")]
 OUT = os.path.join(HERE, "lib", "libewn_hip.so")
 OBJ = os.path.join(HERE, "lib", "obj")
 # -ffp-contract=off: the fp64 heuristic and expectation sums must round exactly like the
@@ -22,7 +22,8 @@ FILE_FLAGS = {"ewn_policy.hip": ["-fno-slp-vectorize"], "ewn_policy_eval.hip": [
               "ewn_policy_eval_mcts.hip": ["-fno-slp-vectorize"], "ewn_selfplay.hip": ["-fno-slp-vectorize"],
               "ewn_step_vs.hip": ["-fno-slp-vectorize"], "ewn_predict_policy.hip": ["-fno-slp-vectorize"],
               "ewn_predict_lookahead.hip": ["-fno-slp-vectorize"], "ewn_lookahead_stages.hip": ["-fno-slp-vectorize"],
-              "ewn_puct_fused.hip": ["-fno-slp-vectorize"], "ewn_puct_games.hip": ["-fno-slp-vectorize"]}
+              "ewn_puct_fused.hip": ["-fno-slp-vectorize"], "ewn_puct_games.hip": ["-fno-slp-vectorize"],
+              "ewn_puct_wide.hip": ["-fno-slp-vectorize"]}
 
 
 def stale():

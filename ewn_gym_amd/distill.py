@@ -26,6 +26,7 @@ from .games import selfplay_puct_games
 from .search import (SELFPLAY_MAX_PLIES, _noise_eps, _play_numbers, _puct_numbers, lookahead_targets, predict_lookahead, predict_puct,
                      selfplay_puct, sup_grad)
 from .sharding import all_reduce_counters
+from .wide import _NO_TABLE, _NO_WHOLE_GAMES, _leaves_alone
 
 
 def puct_targets(visits, q, value, terminal_value=1.0, one_cube=None):
@@ -55,7 +56,7 @@ class _SupervisedTrainer(FusedTrainer):
     subclass's `_launch` collects its rows and targets and ends in `_update`."""
 
     def __init__(self, who, env, *, sims, c_puct, terminal_value, fused, pi_coef, vf_coef, endgame_table, learning_rate, max_grad_norm,
-                 rms_alpha, rms_eps, **trainer):
+                 rms_alpha, rms_eps, leaves=1, **trainer):
         """who: the subclass, as its errors name it; an endgame_table that is not an EndgameTable is the path of one and is loaded
         onto the env's GPU; trainer: FusedTrainer's arguments after env.  The subclass then calls _size_scratch"""
         self.pi_coef, self.vf_coef = _not_negative(who, "pi_coef", pi_coef), _not_negative(who, "vf_coef", vf_coef)
@@ -67,6 +68,7 @@ class _SupervisedTrainer(FusedTrainer):
         super().__init__(env, **trainer)
         self.sq_avg = torch.zeros_like(self.params)
         self.sims, self.c_puct, self.terminal_value, self.fused = int(sims), float(c_puct), float(terminal_value), bool(fused)
+        self.leaves = int(leaves)          # > 1: the PUCT search as the one launch of ewn_puct_search_wide (4u), other trees than 1
         # the optimiser step is ewn_a2c_apply: of this struct it reads max_grad_norm, learning_rate, rms_alpha, rms_eps, world_size
         self.hyper = _lib.EwnA2cHyper(0.0, float(vf_coef), 0.0, float(max_grad_norm), float(learning_rate), float(rms_alpha), float(rms_eps),
                                       int(self.world))
@@ -96,14 +98,15 @@ class _SupervisedTrainer(FusedTrainer):
 
     def _state(self):
         return {"sq_avg": self.sq_avg, "terminal_value": float(self.terminal_value), "sims": int(self.sims), "c_puct": float(self.c_puct),
-                "fused_search": bool(self.fused)}
+                "fused_search": bool(self.fused), "leaves": int(self.leaves)}
 
     def _load_state(self, sd):
-        """the keys of _state; a subclass then withdraws `fused` where what it was built with does not allow it"""
+        """the keys of _state; a subclass then withdraws `fused` and `leaves` where what it was built with does not allow them"""
         self.sq_avg.copy_(sd["sq_avg"])
         self.terminal_value = float(sd.get("terminal_value", self.terminal_value))
         self.sims, self.c_puct = int(sd.get("sims", self.sims)), float(sd.get("c_puct", self.c_puct))
         self.fused = bool(sd.get("fused_search", self.fused))
+        self.leaves = int(sd.get("leaves", self.leaves))
 
 
 class SearchDistillTrainer(_SupervisedTrainer):
@@ -117,7 +120,8 @@ class SearchDistillTrainer(_SupervisedTrainer):
 
     def __init__(self, env, n_steps=5, learning_rate=7e-4, pi_coef=1.0, vf_coef=0.5, temperature=0.0, plies=1, terminal_value=1.0,
                  max_grad_norm=0.5, rms_alpha=0.99, rms_eps=1e-5, seed=None, opponent=None, opponent_update_every=100,
-                 opponent_deterministic=False, endgame_table=None, search="lookahead", sims=64, c_puct=1.5, endgame_leaves=False, fused=False):
+                 opponent_deterministic=False, endgame_table=None, search="lookahead", sims=64, c_puct=1.5, endgame_leaves=False, fused=False,
+                 leaves=1):
         who = "SearchDistillTrainer"
         if search not in ("lookahead", "puct"):
             raise ValueError("SearchDistillTrainer: search must be 'lookahead' or 'puct', got %r" % (search,))
@@ -133,6 +137,8 @@ class SearchDistillTrainer(_SupervisedTrainer):
             raise ValueError("SearchDistillTrainer: fused=True is the PUCT search in one launch: it needs search='puct'")
         if fused and endgame_leaves:
             raise ValueError("SearchDistillTrainer: fused=True does not take endgame_leaves=True: the exact leaves are the staged path's")
+        leaves = _leaves_alone(who, leaves, **{"search=%r" % (search,): (search != "puct", "it is the PUCT search's (search='puct')"),
+                                               "endgame_leaves=True": (endgame_leaves, _NO_TABLE)})
         if endgame_table is not None and not float(terminal_value) > 0.0:
             raise ValueError("SearchDistillTrainer: with an endgame table terminal_value must be positive (it scales the exact q), "
                              "got %r" % (terminal_value,))
@@ -140,7 +146,7 @@ class SearchDistillTrainer(_SupervisedTrainer):
         # fused: the PUCT search as the one launch of ewn_puct_search (4r): the same targets bit for bit
         super().__init__(who, env, sims=sims, c_puct=c_puct, terminal_value=terminal_value, fused=fused, pi_coef=pi_coef, vf_coef=vf_coef,
                          endgame_table=endgame_table, learning_rate=learning_rate, max_grad_norm=max_grad_norm, rms_alpha=rms_alpha,
-                         rms_eps=rms_eps, n_steps=n_steps, seed=seed, use_graph=False, opponent=opponent,
+                         rms_eps=rms_eps, leaves=leaves, n_steps=n_steps, seed=seed, use_graph=False, opponent=opponent,
                          opponent_update_every=opponent_update_every, opponent_deterministic=opponent_deterministic)
         self._size_scratch(self.n_steps)
         self.endgame_leaves = bool(endgame_leaves)   # the search itself takes the table: exact values at the leaves it covers (4p)
@@ -158,7 +164,7 @@ class SearchDistillTrainer(_SupervisedTrainer):
         if self.search == "puct":
             _, visits, q, value = predict_puct(self._boards, self._dice, self.params, sims=self.sims, c_puct=self.c_puct,
                                                terminal_value=self.terminal_value, return_visits=True, return_q=True, return_value=True,
-                                               cube_layer=env.L, fused=self.fused, **leaves)
+                                               cube_layer=env.L, fused=self.fused, leaves=self.leaves, **leaves)
             target_pi, target_value, weight = puct_targets(visits, q, value, self.terminal_value)
             if self.endgame_table is not None:     # covered rows: the exact q's targets, as the lookahead's rows get them
                 _, covered, q_exact = self.endgame_table.lookup(self._boards, self._dice, return_q=True)
@@ -182,6 +188,7 @@ class SearchDistillTrainer(_SupervisedTrainer):
         self.plies = int(sd.get("plies", self.plies))
         self.search = sd.get("search", self.search)
         self.fused = self.fused and self.search == "puct" and not self.endgame_leaves
+        self.leaves = self.leaves if self.search == "puct" and not self.endgame_leaves else 1
 
 
 def both_flags_one_cube(boards, dice):
@@ -207,7 +214,7 @@ class PuctSelfPlayTrainer(_SupervisedTrainer):
 
     def __init__(self, env, sims=64, c_puct=1.5, terminal_value=1.0, noise_eps=0.25, noise_alpha=1.0, temp_plies=8, max_plies=None,
                  learning_rate=7e-4, pi_coef=1.0, vf_coef=0.5, max_grad_norm=0.5, rms_alpha=0.99, rms_eps=1e-5, seed=None,
-                 endgame_table=None, chunk=1024, fused=False, whole_games=False):
+                 endgame_table=None, chunk=1024, fused=False, whole_games=False, leaves=1):
         who = "PuctSelfPlayTrainer"
         _puct_numbers(who, sims, c_puct, terminal_value)
         _noise_eps(who, noise_eps)
@@ -219,12 +226,14 @@ class PuctSelfPlayTrainer(_SupervisedTrainer):
             raise ValueError("%s: fused=True does not take an endgame_table: the exact-leaf substitution is the staged path's" % who)
         if whole_games and endgame_table is not None:
             raise ValueError("%s: whole_games=True does not take an endgame_table: the exact-leaf substitution is the staged path's" % who)
+        leaves = _leaves_alone(who, leaves, endgame_table=(endgame_table is not None, _NO_TABLE),
+                               **{"whole_games=True": (whole_games, _NO_WHOLE_GAMES)})
         # endgame_table: exact values at the leaves the table covers (4p), nothing else
         # fused: a ply's search as the one launch of ewn_puct_search (4r): the same records bit for bit
         # whole_games: all games in the one launch of ewn_puct_selfplay (4s), chunk and fused are then not read: the same records again
         super().__init__(who, env, sims=sims, c_puct=c_puct, terminal_value=terminal_value, fused=fused, pi_coef=pi_coef, vf_coef=vf_coef,
                          endgame_table=endgame_table, learning_rate=learning_rate, max_grad_norm=max_grad_norm, rms_alpha=rms_alpha,
-                         rms_eps=rms_eps, n_steps=1, seed=seed, use_graph=False, opponent=None, opponent_update_every=100,
+                         rms_eps=rms_eps, leaves=leaves, n_steps=1, seed=seed, use_graph=False, opponent=None, opponent_update_every=100,
                          opponent_deterministic=False, policy_rollout=False)
         self.max_plies = SELFPLAY_MAX_PLIES[env.S] if max_plies is None else int(max_plies)
         self._size_scratch(self.max_plies)
@@ -255,7 +264,7 @@ class PuctSelfPlayTrainer(_SupervisedTrainer):
             rec = selfplay_puct(board, dice, self.params, sims=self.sims, max_plies=self.max_plies, c_puct=self.c_puct,
                                 terminal_value=self.terminal_value, noise_eps=self.noise_eps, noise_alpha=self.noise_alpha,
                                 temp_plies=self.temp_plies, key=self.noise_key, game_offset=first, chunk=self.chunk,
-                                endgame_table=self.endgame_table, cube_layer=env.L, fused=self.fused)
+                                endgame_table=self.endgame_table, cube_layer=env.L, fused=self.fused, leaves=self.leaves)
         self.records = rec
         R, S = self.max_plies * env.N, env.S
         b, d = rec["board"].reshape(R, S, S), rec["dice"].reshape(R).clamp(min=1)         # rows past a game's end hold dice 0
@@ -292,6 +301,7 @@ class PuctSelfPlayTrainer(_SupervisedTrainer):
         self.temp_plies, self.seed_counter = int(sd.get("temp_plies", self.temp_plies)), int(sd.get("seed_counter", self.seed_counter))
         self.fused = self.fused and self.endgame_table is None
         self.whole_games = bool(sd.get("whole_games", self.whole_games)) and self.endgame_table is None
+        self.leaves = self.leaves if self.endgame_table is None and not self.whole_games else 1
         if int(sd.get("max_plies", self.max_plies)) != self.max_plies:
             raise ValueError("the checkpoint's games have at most %d plies, this trainer's %d: the update's scratch is sized by it" % (
                 int(sd["max_plies"]), self.max_plies))

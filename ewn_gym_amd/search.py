@@ -436,12 +436,17 @@ def _puct_scratch(c, nb, S, dev, fused):
             torch.empty(c, dtype=torch.float32, device=dev))
 
 
-def _search_setup(lib, S, L, M, sims, chunk, c_puct, terminal_value, dev, fused):
+def _search_setup(lib, S, L, M, sims, chunk, c_puct, terminal_value, dev, fused, leaves=1):
     """what predict_puct and selfplay_puct search M observations on: (the observations of a chunk, its _puct_scratch, allocated once per
-    call, c_puct and terminal_value as the kernels take them)"""
+    call, c_puct and terminal_value as the kernels take them).  leaves > 1 (the wide launch): the tree alone, and the
+    launch's marks behind it"""
     c = max(1, min(int(chunk), M))
     nb = int(lib.ewn_puct_tree_bytes(S, L, sims))
-    return c, _puct_scratch(c, nb, S, dev, fused), C.c_float(float(c_puct)), C.c_float(float(terminal_value))
+    scratch = _puct_scratch(c, nb, S, dev, fused or leaves > 1)
+    if leaves > 1:
+        from .wide import _wide_scratch
+        scratch += (_wide_scratch(lib, S, L, c, sims, dev),)
+    return c, scratch, C.c_float(float(c_puct)), C.c_float(float(terminal_value))
 
 
 def puct_search(boards, dice, params, sims, c_puct=1.5, terminal_value=1.0, root_noise=None, noise_eps=0.25, rounds=None, cube_layer=3,
@@ -472,11 +477,16 @@ def puct_search(boards, dice, params, sims, c_puct=1.5, terminal_value=1.0, root
     return out
 
 
-def _puct_search(lib, S, L, n, sims, b, d, params, cp, tv, table, scratch, st, noise=None, eps=0.0, fused=False):
+def _puct_search(lib, S, L, n, sims, b, d, params, cp, tv, table, scratch, st, noise=None, eps=0.0, fused=False, leaves=1):
     """predict_puct's and selfplay_puct's search of n observations on the caller's scratch: begin, then sims + 1 rounds of
     ewn_predict_policy and advance.  noise (float32 [n, 6]): the first round, which evaluates the roots, is the noise instance's.
-    fused: the one launch of ewn_puct_search instead -- the same bytes in the tree; of the scratch only the tree is used"""
-    tree, lb, ld, la, lg, lv = scratch
+    fused: the one launch of ewn_puct_search instead -- the same bytes in the tree; of the scratch only the tree is used.
+    leaves > 1: the one launch of ewn_puct_search_wide, whatever fused says -- another tree, in fewer rounds"""
+    tree, lb, ld, la, lg, lv = scratch[:6]
+    if leaves > 1:
+        from .wide import _launch
+        _launch(lib, S, L, n, sims, leaves, cp, tv, b, d, params, noise, eps, 0, 0, tree, scratch[6], st)
+        return
     if fused:
         check(lib.ewn_puct_search(S, L, n, sims, -1, cp, tv, _ptr(b), _ptr(d), _ptr(params), _ptr(noise), C.c_float(eps), _ptr(tree), st),
               "ewn_puct_search")
@@ -496,7 +506,7 @@ def _puct_search(lib, S, L, n, sims, b, d, params, cp, tv, table, scratch, st, n
 
 
 def predict_puct(boards, dice, params, sims=64, c_puct=1.5, terminal_value=1.0, return_visits=False, return_q=False, return_value=False,
-                 cube_layer=3, chunk=1024, endgame_table=None, fused=False):
+                 cube_layer=3, chunk=1024, endgame_table=None, fused=False, leaves=1):
     """What the trained actor-critic plays after a PUCT search of `sims` simulations on its own two heads: the policy
     head says where to look, the value head what a leaf is worth, a move that wins on the board is worth +1 and is played; the
     opponent's and the agent's later dice are chance nodes sampled in a fixed stratified order, so the search is deterministic.
@@ -508,11 +518,16 @@ def predict_puct(boards, dice, params, sims=64, c_puct=1.5, terminal_value=1.0, 
     endgame_table (an EndgameTable of the boards' size on the same GPU): a pending leaf that the table covers is worth
     terminal_value * max_a q_exact(leaf board, leaf dice) instead of the value head's output; the logits are the policy head's.
     fused=True: each chunk's search is the one launch of ewn_puct_search -- the same trees byte for byte, so the same
-    results bit for bit, and no leaf-row scratch; not together with endgame_table (the exact leaves stay on the staged path)."""
+    results bit for bit, and no leaf-row scratch; not together with endgame_table (the exact leaves stay on the staged path).
+    leaves: 1 is all of the above; 2..32: each chunk's search is the one launch of ewn_puct_search_wide, which collects
+    up to that many leaves per tree and round under a virtual loss -- about sims / leaves rounds, another tree and so other
+    results than leaves=1, whatever fused says; not together with endgame_table."""
     who = "predict_puct"
     lib = _lib.load()
     sims = _puct_numbers(who, sims, c_puct, terminal_value)
     _fused_table(who, fused, endgame_table)
+    from .wide import _NO_TABLE, _leaves_alone
+    leaves = _leaves_alone(who, leaves, endgame_table=(endgame_table is not None, _NO_TABLE))
     _at_least_one(who, "chunk", chunk)
     M, S, L, dev, t = _network_inputs(who, boards, dice, params, cube_layer, table=endgame_table)
     _same_gpu(who, dev, "params", t.items())
@@ -521,14 +536,14 @@ def predict_puct(boards, dice, params, sims=64, c_puct=1.5, terminal_value=1.0, 
     visits = torch.zeros((M, 2, 3), dtype=torch.int32, device=dev) if return_visits else None
     q = torch.zeros((M, 2, 3), dtype=torch.float32, device=dev) if return_q else None
     val = torch.zeros(M, dtype=torch.float32, device=dev) if return_value else None
-    c, scratch, cp, tv = _search_setup(lib, S, L, M, sims, chunk, c_puct, terminal_value, dev, fused)
+    c, scratch, cp, tv = _search_setup(lib, S, L, M, sims, chunk, c_puct, terminal_value, dev, fused, leaves)
     tree = scratch[0]
     with torch.cuda.device(dev):
         st = _stream()
         for i in range(0, M, c):
             n = min(c, M - i)
             sl = slice(i, i + n)
-            _puct_search(lib, S, L, n, sims, b[sl], d[sl], params, cp, tv, endgame_table, scratch, st, fused=fused)
+            _puct_search(lib, S, L, n, sims, b[sl], d[sl], params, cp, tv, endgame_table, scratch, st, fused=fused, leaves=leaves)
             check(lib.ewn_puct_result(S, L, n, _ptr(tree), _ptr(acts[sl]), _ptr(None if visits is None else visits[sl]),
                                       _ptr(None if q is None else q[sl]), _ptr(None if val is None else val[sl]), st), "ewn_puct_result")
     return _outputs(acts, visits, q, val)
@@ -623,7 +638,8 @@ def selfplay_noise(M, noise_alpha, key, game_offset, ply, device="cuda"):
 
 
 def selfplay_puct(boards, dice, params, sims=64, max_plies=None, c_puct=1.5, terminal_value=1.0, noise_eps=0.25, noise_alpha=1.0,
-                  temp_plies=8, key=0, game_offset=0, chunk=1024, check_every=8, endgame_table=None, cube_layer=3, fused=False):
+                  temp_plies=8, key=0, game_offset=0, chunk=1024, check_every=8, endgame_table=None, cube_layer=3, fused=False,
+                  leaves=1):
     """M games of the PUCT search against itself, from the given positions to the end: per ply puct_begin, sims + 1
     rounds of ewn_predict_policy and advance -- the first with Dirichlet(noise_alpha) noise of weight noise_eps on the root's priors
     (ewn_puct_advance_noise) -- then ewn_puct_play into row t: the move is drawn in proportion to the visits for the first
@@ -633,7 +649,8 @@ def selfplay_puct(boards, dice, params, sims=64, max_plies=None, c_puct=1.5, ter
     summed distance to its corner by at least one, so a game lasts at most 69 / 117 plies.  noise_alpha = 1.0 is a choice (about 10
     over the number of moves, AlphaZero's rule of thumb), not a measurement.  endgame_table: predict_puct's, at the leaves.
     fused=True: a ply's search is the one launch of ewn_puct_search, the records are the same bit for bit; not
-    together with endgame_table.
+    together with endgame_table.  leaves: 1 is all of the above; 2..32: a ply's search is the one launch of
+    ewn_puct_search_wide with that ply's noise rows -- other trees, so other games; not together with endgame_table.
     The noise is selfplay_noise: torch._standard_gamma keyed by key, the ply and the global game game_offset + m, drawn once per ply
     for all M games and read by each chunk's rows: a call repeats itself bit for bit, whatever the chunk, and the calls on the shards
     of M games (game_offset moved to each shard's first game) give the rows of the one call on all of them.  Returns a dict: board int8 [T, M, S, S], dice int8
@@ -643,6 +660,8 @@ def selfplay_puct(boards, dice, params, sims=64, max_plies=None, c_puct=1.5, ter
     lib = _lib.load()
     sims = _puct_numbers(who, sims, c_puct, terminal_value)
     _fused_table(who, fused, endgame_table)
+    from .wide import _NO_TABLE, _leaves_alone
+    leaves = _leaves_alone(who, leaves, endgame_table=(endgame_table is not None, _NO_TABLE))
     eps = _noise_eps(who, noise_eps)
     temp_plies, key, game_offset = _play_numbers(who, temp_plies, key, game_offset)
     _positive(who, "noise_alpha", noise_alpha)
@@ -657,7 +676,7 @@ def selfplay_puct(boards, dice, params, sims=64, max_plies=None, c_puct=1.5, ter
     b, d, table = inputs["boards"], inputs["dice"], endgame_table
     rec = {name: torch.zeros((T, M) + shape(S), dtype=dt, device=dev) for name, dt, shape in _PLAY_ROWS}
     game = torch.zeros((M, 4), dtype=torch.int32, device=dev)
-    c, scratch, cp, tv = _search_setup(lib, S, L, M, sims, chunk, c_puct, terminal_value, dev, fused)
+    c, scratch, cp, tv = _search_setup(lib, S, L, M, sims, chunk, c_puct, terminal_value, dev, fused, leaves)
     with torch.cuda.device(dev):
         st = _stream()
         drawn = []
@@ -670,7 +689,7 @@ def selfplay_puct(boards, dice, params, sims=64, max_plies=None, c_puct=1.5, ter
                     if t == len(drawn):                        # a ply's noise is drawn once, for all M games: later chunks read their rows
                         drawn.append(selfplay_noise(M, noise_alpha, key, game_offset, t, dev))
                     noise = drawn[t][i:i + n]
-                _puct_search(lib, S, L, n, sims, cb, cd, params, cp, tv, table, scratch, st, noise, eps, fused)
+                _puct_search(lib, S, L, n, sims, cb, cd, params, cp, tv, table, scratch, st, noise, eps, fused, leaves)
                 check(lib.ewn_puct_play(S, L, n, _ptr(scratch[0]), _ptr(cb), _ptr(cd), _ptr(cg), temp_plies, C.c_uint64(key),
                                         C.c_int64(game_offset + i), *[_ptr(rec[name][t, i:i + n]) for name, _, _ in _PLAY_ROWS], st),
                       "ewn_puct_play")

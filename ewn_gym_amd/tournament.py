@@ -73,7 +73,8 @@ def _policy(spec, cube_layer, key):
         from classical_policies.model import PuctAgent
         return PuctAgent(spec["model"], board_size=_model_size(spec), cube_layer=cube_layer, sims=spec.get("sims", 64),
                          c_puct=spec.get("c_puct", 1.5), terminal_value=spec.get("terminal_value", 1.0),
-                         endgame_table=spec.get("endgame_table"), fused=spec.get("fused", False)).policy_fn()   # fused: one launch (4r)
+                         endgame_table=spec.get("endgame_table"), fused=spec.get("fused", False),   # fused: one launch (4r)
+                         leaves=spec.get("leaves", 1)).policy_fn()                                  # leaves > 1: the wide launch (4u)
     if kind == "endgame":       # the exact move where the endgame table covers the position, the "fallback" spec's policy elsewhere
         from classical_policies.model import EndgameAgent
         if "table" not in spec or "fallback" not in spec:
@@ -354,12 +355,14 @@ def load_policy(path, board_size=5, cube_layer=3, device="cuda"):
 
 def evaluate_model(model, names=("random", "minimax"), num=1024, max_depth=5, num_simulations=10, num_env_copies=5, board_size=5,
                    cube_layer=3, heuristic="hybrid", rng="mt19937", lookahead=False, endgame_table=None, puct=None,
-                   endgame_leaves=False, fused=False):
+                   endgame_leaves=False, fused=False, leaves=1):
     """eval_A2C.py's loop: the model's deterministic policy against every listed opponent; lookahead (1 / True, or 2): and, beside
     each, its lookahead policy of that many moves ({"kind": "mlp_lookahead", "plies": ...}) on the same episodes.  endgame_table (an
     EndgameTable or its path): every agent plays the exact move where the table covers the position ({"kind": "endgame"}, ply by ply).
     puct (a number of simulations): and its PUCT search of that budget ({"kind": "mlp_puct", "sims": ...}), rows "puct(SIMS) vs ..."
     fused (with puct): that search as one launch per move (ewn_puct_search): the same moves, so the same rows.
+    leaves (with puct; 2..32): that search with up to so many leaves per tree and round (ewn_puct_search_wide): fewer
+    rounds per move, other trees, so other rows.
     endgame_leaves (with lookahead and endgame_table): the table is not laid over the agents' moves; beside the lookahead's row
     stands the same lookahead with the table's exact values at the leaves it covers, "lookahead + exact leaves vs ..." """
     if endgame_leaves and (endgame_table is None or not lookahead):
@@ -377,7 +380,7 @@ def evaluate_model(model, names=("random", "minimax"), num=1024, max_depth=5, nu
     if endgame_table is not None and not endgame_leaves:     # the table laid over every agent's moves; these tables have no PUCT row
         agents = [("endgame+" + label, {"kind": "endgame", "table": endgame_table, "fallback": spec}) for label, spec in agents]
     elif puct is not None:
-        agents.append(("puct(%d)" % int(puct), {"kind": "mlp_puct", "model": model, "sims": int(puct), "fused": bool(fused)}))
+        agents.append(("puct(%d)" % int(puct), {"kind": "mlp_puct", "model": model, "sims": int(puct), "fused": bool(fused), "leaves": leaves}))
     table = {}
     for o in names:
         opp = _classical_spec(o, max_depth, heuristic, num_simulations, num_env_copies)
@@ -407,6 +410,9 @@ def _parser():
     ap.add_argument("--fused", action="store_true",
                     help="with --puct: the search of a move in one kernel launch (ewn_puct_search) instead of the staged launches; the "
                          "same moves")
+    ap.add_argument("--leaves", type=int, default=1, metavar="N",
+                    help="with --puct: up to N leaves per tree and round in one kernel launch per move (ewn_puct_search_wide): about "
+                         "SIMS / N rounds instead of SIMS + 1; another tree than N = 1, so not always the same moves")
     ap.add_argument("--endgame_table", default=None,
                     help="with --model: a saved EndgameTable; the model (and its --lookahead) plays the exact move wherever the table "
                          "covers the position")
@@ -435,6 +441,8 @@ def main():
         ap.error("--puct takes 0..4096 simulations")
     if a.fused and a.puct is None:
         ap.error("--fused goes with --puct")
+    if a.leaves != 1 and (a.puct is None or not 1 <= a.leaves <= 32):
+        ap.error("--leaves goes with --puct and takes 1..32")
     if a.endgame_table and (a.model is None or a.opponent_model is not None):
         ap.error("--endgame_table goes with --model and the classical opponents of --agents")
     if a.endgame_leaves and not (a.endgame_table and a.lookahead):
@@ -453,7 +461,7 @@ def main():
         model = load_policy(a.model, a.board_size, a.cube_layer)
         t = evaluate_model(model, a.agents, a.num, a.max_depth, a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer,
                            a.heuristic, a.rng, lookahead=a.lookahead or False, endgame_table=a.endgame_table, puct=a.puct,
-                           endgame_leaves=a.endgame_leaves, fused=a.fused)
+                           endgame_leaves=a.endgame_leaves, fused=a.fused, leaves=a.leaves)
     else:
         t = tournament(a.agents, a.num, a.max_depth, a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer,
                        a.heuristic, a.rng, sims=a.sims, playouts=a.playouts, c_puct=a.c_puct)

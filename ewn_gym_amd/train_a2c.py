@@ -35,6 +35,10 @@ def _parser():
     ap.add_argument("--fused", action="store_true",
                     help="SEARCH --search puct, SELFPLAY: the PUCT search in one kernel launch (ewn_puct_search, DESIGN.md 4r) instead of the "
                          "staged launches: the same targets bit for bit; not with --endgame_leaves")
+    ap.add_argument("--leaves", type=int, default=1, metavar="N",
+                    help="SEARCH --search puct, SELFPLAY: up to N leaves per tree and round in one kernel launch per search "
+                         "(ewn_puct_search_wide, DESIGN.md 4u): about sims / N rounds instead of sims + 1, other trees than N = 1; not with "
+                         "--endgame_leaves or --whole_games")
     ap.add_argument("--whole_games", action="store_true",
                     help="SELFPLAY: all games of an update in one kernel launch that refills a finished game's column with the next game "
                          "(ewn_puct_selfplay, DESIGN.md 4s): the same records bit for bit; --fused is then not read; not with --endgame_leaves")
@@ -119,6 +123,12 @@ def main():
         raise SystemExit("--fused is read by SEARCH --search puct and by SELFPLAY only")
     if a.fused and a.endgame_leaves:
         raise SystemExit("--fused does not go with --endgame_leaves: the exact-leaf substitution is the staged search's")
+    if a.leaves != 1 and not (a.algorithm == "SELFPLAY" or (a.algorithm == "SEARCH" and a.search == "puct")):
+        raise SystemExit("--leaves is read by SEARCH --search puct and by SELFPLAY only")
+    if not 1 <= a.leaves <= 32:
+        raise SystemExit("--leaves takes 1..32")
+    if a.leaves != 1 and (a.endgame_leaves or a.whole_games):
+        raise SystemExit("--leaves %d does not go with --endgame_leaves or --whole_games: both evaluate one leaf per tree and round" % a.leaves)
     if a.whole_games and a.algorithm != "SELFPLAY":
         raise SystemExit("--whole_games is read by SELFPLAY only")
     if a.whole_games and a.endgame_leaves:
@@ -154,13 +164,13 @@ def main():
         from .distill import SearchDistillTrainer
         trainer = SearchDistillTrainer(env, n_steps=a.n_steps, learning_rate=a.learning_rate, temperature=a.temperature, plies=a.plies,
                                        terminal_value=a.terminal_value, seed=mseed, endgame_table=a.endgame_table, search=a.search,
-                                       sims=a.sims, c_puct=a.c_puct, endgame_leaves=a.endgame_leaves, fused=a.fused, **okw)
+                                       sims=a.sims, c_puct=a.c_puct, endgame_leaves=a.endgame_leaves, fused=a.fused, leaves=a.leaves, **okw)
     elif a.algorithm == "SELFPLAY":
         from .distill import PuctSelfPlayTrainer
         trainer = PuctSelfPlayTrainer(env, sims=a.sims, c_puct=a.c_puct, terminal_value=a.terminal_value, noise_eps=a.noise_eps,
                                       noise_alpha=a.noise_alpha, temp_plies=a.temp_plies, max_plies=a.max_plies,
                                       learning_rate=a.learning_rate, seed=mseed, endgame_table=a.endgame_table, fused=a.fused,
-                                      whole_games=a.whole_games)
+                                      whole_games=a.whole_games, leaves=a.leaves)
     elif a.trainer == "fused" or model_opp is not None or (a.trainer == "auto" and env.supports_policy_rollout()):
         trainer = FusedA2CTrainer(env, n_steps=a.n_steps, learning_rate=a.learning_rate, seed=mseed, **okw)
     else:
