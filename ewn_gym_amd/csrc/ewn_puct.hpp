@@ -27,6 +27,7 @@
 #define PU_O_POS 64
 #define PU_O_OWN 80
 #define PU_WAVE (PU_O_OWN + 16 * 4)
+#define PU_SUM_MIN 0x1p-60f   // pu_evaluate: below this sum of the legal softmax products the priors are formed relative to the legal edges
 
 // One tree, sections of structure-of-arrays inside one 4-byte aligned buffer; `nodes` = sims + 1.  Offsets in bytes:
 //   hdr    int32 [8]            node count | simulations begun | pending node (-1: none) | degenerate | sims | PU_LAYOUT | 0 | 0
@@ -133,7 +134,15 @@ EWN_DEV void pu_root(const PuTree &T, const int8_t *row, const int8_t *dice, int
 struct PuNoise { const float *row; float eps, keep; };
 
 // The evaluation of the pending node: priors from the five logits at lg (softmax over the flags times softmax over the directions,
-// normalised over the legal edges), kind, then the backup of v = *vp * inv_tv clamped to [-1, 1].  NOISE: when the node is the root,
+// normalised over the legal edges), kind, then the backup of v = *vp * inv_tv clamped to [-1, 1].  Both softmaxes are taken relative
+// to the maximum of ALL their entries, so a network that puts its mass on illegal moves leaves the legal products, and their sum,
+// in the denormals or at zero.  Where the sum is below PU_SUM_MIN (wave-uniform: every lane reads the same six words) the same
+// priors are formed again relative to the legal edges alone: b the first legal edge of the largest logit sum, e_a = expf of the
+// DIFFERENCES (l_f[a] - l_f[b]) + (l_r[a] - l_r[b]) (the direction term alone where both flags name one cube), P_a = e_a / sum e.
+// e_b is 1, so that sum lies in [1, 6]; the differences are taken before anything is added, so an offset common to all logits
+// cancels exactly.  At and above PU_SUM_MIN the arithmetic is the product's, bit for bit as it always was: an edge whose product has
+// left the normal numbers (below 2^-126) has a prior below 2^-126 / PU_SUM_MIN = 2^-66, far inside the priors' tolerance of 2^-19
+// (DESIGN.md 4o).  Finite logits and a value that is not a NaN are the contract.  NOISE: when the node is the root,
 // its priors are mixed with the caller's weights, normalised over the legal edges, before the backup and before the first
 // simulation selects on them.  lg and vp may lie in global memory or in LDS
 template <int S, bool NOISE>
@@ -156,10 +165,31 @@ EWN_DEV void pu_evaluate(const PuTree &T, int pending, const float *lg, const fl
         const float r0 = expf(l2 - mr), r1 = expf(l3 - mr), r2 = expf(l4 - mr), sr = (r0 + r1) + r2;
         const int f = lane >= 3, r = lane - 3 * f;
         const float pf = (f ? f1 : f0) / sf, pr = (r == 0 ? r0 : r == 1 ? r1 : r2) / sr;
-        const float raw = E.kind == 0 ? 0.0f : E.one ? pr : pf * pr;
+        float raw = E.kind == 0 ? 0.0f : E.one ? pr : pf * pr;
         if (lane < 8) sc[lane] = raw;
         __builtin_amdgcn_wave_barrier();
-        const float sum = ((((sc[0] + sc[1]) + sc[2]) + sc[3]) + sc[4]) + sc[5];
+        float sum = ((((sc[0] + sc[1]) + sc[2]) + sc[3]) + sc[4]) + sc[5];
+        if (!(sum >= PU_SUM_MIN)) {                            // the legal products ran out of fp32: relative to the legal edges
+            const u32 legal = (u32)__builtin_amdgcn_ballot_w64(E.kind != 0) & 0x3Fu;
+            int b = -1;
+            float tb = 0.0f;
+            #pragma unroll
+            for (int i = 0; i < 6; i++) {
+                const float tf = i >= 3 ? l1 - mf : l0 - mf, tr = (i % 3 == 0 ? l2 : i % 3 == 1 ? l3 : l4) - mr;
+                const float ti = E.one ? tr : tf + tr;
+                if (((legal >> i) & 1u) && (b < 0 || ti > tb)) { b = i; tb = ti; }
+            }
+            if (b >= 0) {
+                const float lfb = b >= 3 ? l1 : l0, lrb = b % 3 == 0 ? l2 : b % 3 == 1 ? l3 : l4;
+                const float lf = f ? l1 : l0, lr = r == 0 ? l2 : r == 1 ? l3 : l4;
+                const float df = lf - lfb, dr = lr - lrb;
+                raw = E.kind == 0 ? 0.0f : expf(E.one ? dr : df + dr);
+                __builtin_amdgcn_wave_barrier();               // the products are read
+                if (lane < 8) sc[lane] = raw;
+                __builtin_amdgcn_wave_barrier();
+                sum = ((((sc[0] + sc[1]) + sc[2]) + sc[3]) + sc[4]) + sc[5];
+            }
+        }
         if constexpr (NOISE) {
             float prior = E.kind == 0 ? 0.0f : raw / sum;
             if (pending == 0) {
