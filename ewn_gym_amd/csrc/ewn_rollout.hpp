@@ -488,13 +488,15 @@ __global__ __launch_bounds__(D3_BS, (OPP == 2 ? 2 : 1)) void k_rollout_slots(Rol
     static_assert(!(H2 && OPP == 2), "'two_min_dist' at max_depth 5 / 6 keeps the reference's loops (d5_search): lock-step kernel only");
     constexpr int CELLS = S * S, GPB = D3_BS / T;   // games per block
     constexpr int STR = RecGeo<S>::STR;             // LDS bytes per game: the game's board slot, one trajectory record wide
-    __shared__ __attribute__((aligned(16))) int8_t lds_st[GPB * STR + FAST_TAB_BYTES(S) + GPB * 16 + SlotTabGeo<S>::EXTRA];
+    // the max_depth 1-4 search on a (level, count) image of 5x5 / 6x6 finds its two reply exceptions in the tables (ewn_movetab.hpp)
+    constexpr bool PH = OPP == 0 && !H2 && slot_phantom<S>;
+    __shared__ __attribute__((aligned(16))) int8_t lds_st[GPB * STR + FAST_TAB_BYTES(S) + GPB * 16 + SlotTabGeo<S, PH>::EXTRA];
     int8_t *lds = lds_st;
     int8_t *tb = lds + GPB * STR;
     tables_to_lds<FAST_TAB_BYTES(S)>(tb, (const int8_t *)B.tables); // LDS-DMA, waited for at the barrier
     const FastTab<S> *Tb = (const FastTab<S> *)tb;
     uint8_t *garr = (uint8_t *)(tb + FAST_TAB_BYTES(S));
-    const SlotTabs<S> D = slot_tabs_at<S>(tb, (int8_t *)garr + GPB * 16); // derived tables (ewn_movetab.hpp), built below
+    const SlotTabs<S, PH> D = slot_tabs_at<S, PH>(tb, (int8_t *)garr + GPB * 16); // derived tables (ewn_movetab.hpp), built below
 
     const int g0 = (int)blockIdx.x * GPB, ng = min(GPB, c.N - g0);
     const int gl = threadIdx.x / T, sub = threadIdx.x % T, game = g0 + gl;
@@ -516,7 +518,7 @@ __global__ __launch_bounds__(D3_BS, (OPP == 2 ? 2 : 1)) void k_rollout_slots(Rol
     lds_dma_wait();
     __syncthreads();
     // the image is in LDS: one derived entry per thread, in front of the barrier the loop waits behind anyway
-    for (int e = threadIdx.x; e < 256; e += D3_BS) slot_tabs_build<S>(Tb, D, e);
+    for (int e = threadIdx.x; e < 256; e += D3_BS) slot_tabs_build<S, PH>(Tb, D, e);
     RState<S> s;
     d3_decode<S, T>(live ? lds + gl * CELLS : lds, sub, garr + gl * 16, s);
     __syncthreads();                                // every game is in registers: the board area becomes the per-game slots
@@ -562,7 +564,7 @@ __global__ __launch_bounds__(D3_BS, (OPP == 2 ? 2 : 1)) void k_rollout_slots(Rol
         // one cube's three roots of the opponent's search, run by every lane (lanes without a pending reply compute on a harmless
         // state, so the DPP exchanges inside always see their partners)
         bool second = false;
-        if constexpr (OPP == 0) best = d3_search<S, T, H2, true>(Tb, s, dice, sub, c.depth, oflag, odir, phase, best, &second, &omove, &D);
+        if constexpr (OPP == 0) best = d3_search<S, T, H2, true, PH>(Tb, s, dice, sub, c.depth, oflag, odir, phase, best, &second, &omove, &D);
         else best = d5c_search<S, T, true>(Tb, s, dice, sub, oflag, odir, phase, best, &second);
         RSTAMP(1); // search
         if (pending && phase == 0 && reply && second) phase = 1; // the same env step goes on with the second cube

@@ -277,12 +277,17 @@ template <int T> EWN_DEV void publish(u32 mine, int i, u32 (&out)[6])
 // cross to the even lane (six lane permutes), the even lane adds all six in dice order -- the expression it always was -- and the
 // sum returns to the odd lane with two permutes.  The odd lane adds the same six terms in another order; that sum is overwritten
 // before anything reads it.
-template <int S, int T, bool H2 = false, bool PERLANE = false>
+// PH (PERLANE on 5x5 and 6x6, (level, count) images): D holds the phantom form of the reply entries and Tb is the block's copy of
+// the image with the two spare levels filled in (ewn_movetab.hpp).  A reply that does not exist and a reply onto the origin are then
+// ordinary leaves -- their mask has a cell of level 7 / 6, whose columns of rank[] hold "no such reply" / -10 in every row -- and
+// the leaf's rank address is ft_addr(ix, iy) alone: no keep / fixed, no v_and_or per leaf.
+template <int S, int T, bool H2 = false, bool PERLANE = false, bool PH = false>
 __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S> &c, int dice, int sub, int depth, int &bflag, int &bdir,
                                             int slotL = 0, double best_in = 0.0, bool *have_second = nullptr, u32 *bmove = nullptr,
-                                            [[maybe_unused]] const SlotTabs<S> *D = nullptr)
+                                            [[maybe_unused]] const SlotTabs<S, PH> *D = nullptr)
 {
     static_assert(T == 1 || T == 2, "the six replier cubes and dice values are split over one or two lanes");
+    static_assert(!PH || (PERLANE && !H2 && slot_phantom<S>), "phantom cells: the slot-task form on 5x5 and 6x6, (level, count) images");
     typedef typename MaskOf<S>::type M;
     constexpr int KPT = 6 / T; // replier cubes / dice values per lane: k = sub + T*i
     const M one = 1;
@@ -357,14 +362,28 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
     // per reply, root-invariant: byte address of the rank = (address & keep) | fixed.  An illegal reply reads rank[0] ("no such
     // reply", +inf), a reply onto the origin rank[1] (-10, envs/minimax_ewn.py:45-47).  The exceptions steer the ADDRESS instead
     // of selecting the loaded value: a select on a loaded value makes the compiler branch around the LDS reads.
-    u32 keep[KPT][3], fixed[KPT][3];
+    // (PH: neither; both exceptions are cells of rset, see above)
+    [[maybe_unused]] u32 keep[KPT][3], fixed[KPT][3];
     #pragma unroll
     for (int i = 0; i < KPT; i++) {
         const int k = sub + T * i;
         const int rb = pk_get(c.posN, k);
         rnk[i] = rb & 63;
         rclr[i] = ~(one << rnk[i]);
-        if constexpr (PERLANE) {
+        if constexpr (PH) {
+            // the cube's entry: its three masks.  The read goes through a volatile LDS-address-space pointer: written as a plain
+            // uint4 load the unused last word makes the compiler narrow it to two reads (profiles/r10/README.md)
+            typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+            typedef __attribute__((address_space(3))) const volatile u32x4 lds_u4;
+            lds_u4 *re = (lds_u4 *)(D->rep + rb);
+            if constexpr (sizeof(M) == 4) {
+                const u32x4 a = re[0];
+                rset[i][0] = a.x; rset[i][1] = a.y; rset[i][2] = a.z;
+            } else {
+                const u32x4 a = re[0], b = re[1];
+                rset[i][0] = ((u64)a.y << 32) | a.x; rset[i][1] = ((u64)a.w << 32) | a.z; rset[i][2] = ((u64)b.y << 32) | b.x;
+            }
+        } else if constexpr (PERLANE) {
             // the cube's entry, whole: 16-byte pieces and the tail
             const ReplyEnt<S> *re = D->rep + rb;
             u32 kf[3];
@@ -444,7 +463,8 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
                 #pragma unroll
                 for (int d = 0; d < 3; d++) {
                     const u32 ix = H2 ? lp[ii][d] : lp[ii][d] + (u32)popc_m(P2[ii][d]), iy = H2 ? ln[ii][d] : ln[ii][d] + (u32)popc_m(N2[ii][d]);
-                    a[ii][d] = rank_u32(ft_rank8<S>(Tb, (ft_addr(ix, iy) & keep[i0 + ii][d]) | fixed[i0 + ii][d]));
+                    if constexpr (PH) a[ii][d] = rank_u32(ft_rank8<S>(Tb, ft_addr(ix, iy)));
+                    else a[ii][d] = rank_u32(ft_rank8<S>(Tb, (ft_addr(ix, iy) & keep[i0 + ii][d]) | fixed[i0 + ii][d]));
                 }
             }
             D3_SEARCH_FENCE();
@@ -469,7 +489,8 @@ __device__ __forceinline__ double d3_search(const FastTab<S> *Tb, const RState<S
                 // The cube's key: D3_CUT | its cut value if it cuts, else 0x8000 | its minimum -- two selects for the rank (independent,
                 // last one wins: written as a nested conditional the compiler branches on it), one select between the two flags, one OR.
                 // A cube that is off the board needs nothing here: its position byte has no legal reply (rkf = 0 for bytes 64..127),
-                // so all three addresses were steered to rank[0], its minima are FAST_NONE8 with value +inf, which no `best`
+                // so all three addresses were steered to rank[0] (PH: all three masks of bytes 64..127 hold the "no such reply"
+                // cell, so all three leaves landed in its columns), its minima are FAST_NONE8 with value +inf, which no `best`
                 // reaches, and the key comes out as 0x8000 | FAST_NONE8 = FAST_KNONE by itself.  Only the cube this root has just
                 // captured (root-dependent) reads garbage leaves above: its key is forced to "no such cube".
                 u32 rk = p2[ii];
