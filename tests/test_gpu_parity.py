@@ -597,8 +597,9 @@ def test_mt19937_windows_at_scale(ea):
 
 
 def test_g12_maximum_board_size(ea, golden):
-    """8x8 (the largest supported board) against vectors produced by the reference itself: heuristics, depth 1-3 searches
-    (depth 3 'hybrid' through the table-driven kernel), trajectories vs Random and vs minimax(3)."""
+    """8x8 (the largest board with table images; 9x9 .. 11x11: G18, tests/test_gpu_golden_deep.py) against vectors produced by the
+    reference itself: heuristics, depth 1-3 searches (depth 3 'hybrid' through the table-driven kernel), trajectories vs Random and
+    vs minimax(3)."""
     g = golden("g12_maxboard.json")
     S, L = g["S"], g["L"]
     boards = np.array([r["board"] for r in g["eval"]], np.int8).reshape(-1, S, S)

@@ -159,8 +159,9 @@ def test_g9_flat_monte_carlo_statistics(golden):
 
 
 def test_g12_maximum_board_size(golden):
-    """8x8, the largest board this build supports: heuristics, depth 1-3 search results and full trajectories produced by the
-    reference (oracle/gen_golden_maxboard.py)."""
+    """8x8, the largest board the table-driven kernels serve (9x9 .. 11x11 run on the generic ones: G18,
+    tests/test_oracle_golden_deep.py): heuristics, depth 1-3 search results and full trajectories produced by the reference
+    (oracle/gen_golden_maxboard.py)."""
     g = golden("g12_maxboard.json")
     S, L = g["S"], g["L"]
     boards = np.array([r["board"] for r in g["eval"]], np.int8).reshape(-1, S, S)
