@@ -38,6 +38,7 @@ EXPORTS = ["ewn_abi_version", "ewn_strerror", "ewn_rng_words", "ewn_step_scratch
            "ewn_puct_selfplay_scratch_bytes", "ewn_puct_selfplay"]
 EXPORTS_PLAYOUT_SEARCH = ["ewn_playout_search"]   # include/ewn_playout_search.h: declared in a header of its own
 EXPORTS_PUCT_WIDE = ["ewn_puct_search_wide_scratch_bytes", "ewn_puct_search_wide"]   # include/ewn_puct_wide.h
+EXPORTS_PLAYOUT_SEARCH_EG = ["ewn_playout_search_eg"]   # include/ewn_playout_search_eg.h
 AGENT = {"random": 0, "minimax": 1, "sample": 2, "mlp": 3}   # "mlp": the trained policy, through ewn_step_k_policy   # "sample": env.action_space.sample(), all six actions (EWN_AGENT_SAMPLE)
 AGENT_MCTS = 4   # ewn_agent.kind of the MCTS agent (ewn_step_k_agent only; ewn_step_k does not take it)
 
@@ -193,6 +194,7 @@ def load():
         "ewn_puct_selfplay": (i32, [i32, i32, i32, i32, i32, C.c_float, C.c_float, vp, vp, C.c_float, i32, C.c_uint64, C.c_int64, i32, i32,
                                vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "ewn_playout_search": (i32, [i32, i32, i32, i32, i32, i32, C.c_float, u64, u32, i32, vp, vp, vp, vp]),
+        "ewn_playout_search_eg": (i32, [i32, i32, i32, i32, i32, i32, C.c_float, u64, u32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
         "ewn_puct_search_wide_scratch_bytes": (C.c_int64, [i32, i32, i32, i32]),
         "ewn_puct_search_wide": (i32, [i32, i32, i32, i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, C.c_float, i32, i32, vp, vp, vp]),
     }

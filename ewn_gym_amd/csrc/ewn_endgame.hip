@@ -21,29 +21,6 @@
 #define EG_MAX_BLOCKS 9      // (ka, ko) blocks of a table: K <= 3
 #define EG_MAX_GRID (1u << 22)   // workgroups per launch: a launch's grid is 32 bits of THREADS (2^24 workgroups of EG_NT), see eg_build
 
-// G of the agent's cube `cube` (in Ma) in direction r; -inf where the move leaves the board.  Every index it forms is inside the table:
-// a move never adds a cube and never empties the mover's side, so 1 <= popcounts <= K, their sum <= T, and each side index < n_k.
-template <int S>
-EWN_DEV float eg_move(const float *tbl, const EgGeo &g, int Ma, int Mo, u64 pa, u64 po, int cube, int r)
-{
-    constexpr int C = S * S;
-    const int src = eg_cell(pa, cube), x = src / S, y = src % S;
-    if (!((r == 1 || y < S - 1) && (r == 0 || x < S - 1))) return -__builtin_inff();
-    const int dst = src + (r == 0 ? 1 : r == 1 ? S : S + 1);
-    int Ma1 = Ma, Mo1 = Mo;
-    #pragma unroll
-    for (int k = 1; k <= 6; k++) {
-        if (((Ma >> k) & 1) && eg_cell(pa, k) == dst) Ma1 &= ~(1 << k);
-        if (((Mo >> k) & 1) && eg_cell(po, k) == dst) Mo1 &= ~(1 << k);
-    }
-    if (dst == C - 1 || Mo1 == 0) return 1.0f;
-    const int sh = 8 * (cube - 1);
-    const u64 pa1 = (pa & ~(0xFFull << sh)) | ((u64)dst << sh);
-    const int ka1 = __builtin_popcount((unsigned)Mo1), ko1 = __builtin_popcount((unsigned)Ma1);   // of flip(b1): the sides swap
-    const long long idx = g.off[ka1][ko1] + (long long)eg_side<S>(Mo1, po, true) * (long long)eg_n<S>(ko1) + (long long)eg_side<S>(Ma1, pa1, true);
-    return -tbl[idx];
-}
-
 // E from the best move of each cube: m_d = max(best[cube of flag 0], best[cube of flag 1]); max is exact, so this is the definition's
 // maximum over (f, r) bit for bit
 template <int S>
@@ -153,19 +130,9 @@ __global__ __launch_bounds__(EG_NT) void k_endgame_lookup(int M, EgGeo g, EgLook
     const long long m = (long long)blockIdx.x * EG_NT + threadIdx.x;
     if (m >= M) return;
     const int8_t *b = B.boards + m * C;
-    int Ma = 0, Mo = 0, na = 0, no = 0;
-    u64 pa = 0, po = 0;
-    bool ok = true;
-    #pragma unroll 1
-    for (int c = 0; c < C; c++) {
-        const int v = b[c];
-        if (v == 0) continue;
-        const int k = v > 0 ? v : -v;
-        if (k > 6) { ok = false; continue; }
-        if (v > 0) { ok = ok && !((Ma >> k) & 1) && c != C - 1; Ma |= 1 << k; na++; pa |= (u64)c << (8 * (k - 1)); }
-        else       { ok = ok && !((Mo >> k) & 1) && c != 0;     Mo |= 1 << k; no++; po |= (u64)c << (8 * (k - 1)); }
-    }
-    ok = ok && na >= 1 && no >= 1 && na <= g.K && no <= g.K && na + no <= g.T;   // a cube number twice on a side: not a position
+    int Ma, Mo, na, no;
+    u64 pa, po;
+    const bool ok = eg_position<S>(b, g.K, g.T, Ma, Mo, na, no, pa, po);
     const int d = la_dice((int)B.dice[m]);
     const float ninf = -__builtin_inff();
     float q[6] = {ninf, ninf, ninf, ninf, ninf, ninf}, val = 0.0f;

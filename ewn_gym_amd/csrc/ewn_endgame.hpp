@@ -1,5 +1,6 @@
 // ewn_endgame.hpp -- the one copy of how an endgame table (layout version 1, ewn_endgame.hip's header comment) is indexed, for the
-// units that read one: ewn_endgame.hip (the build and the lookup) and ewn_predict_lookahead.hip (covered leaves).
+// units that read one: ewn_endgame.hip (the build and the lookup), ewn_predict_lookahead.hip (covered leaves) and
+// ewn_playout_search.hip (covered leaves of the playout tree search).
 #pragma once
 #include "ewn_lookahead.hpp"
 
@@ -98,6 +99,64 @@ EWN_DEV u32 eg_side_of(u32 rank, int M, u64 pos, bool turned)
     return v;
 }
 template <int S> EWN_DEV u32 eg_side(int M, u64 pos, bool turned) { return eg_side_of<S>(EG_MASKS.rank[(M >> 1) & 63], M, pos, turned); }
+
+// A board row of C cells (global memory or LDS) as a table position, and whether the (S, K, T) table covers it: cell values within
+// -6 .. 6, no cube number twice on a side (that is not a position), no agent cube on C - 1, no opposing cube on 0, 1 .. K cubes a
+// side and at most T in all.  The one copy of the test: k_endgame_lookup's `covered` and the searches that value covered leaves
+// (k_playout_search<S, true>) call it, so they agree on every board, malformed ones included.  Ma, Mo, pa, po: the sides as
+// registers (above); na, no: the cubes counted, a repeated number counted twice
+template <int S>
+EWN_DEV bool eg_position(const int8_t *b, int K, int T, int &Ma, int &Mo, int &na, int &no, u64 &pa, u64 &po)
+{
+    constexpr int C = S * S;
+    Ma = 0; Mo = 0; na = 0; no = 0; pa = 0; po = 0;
+    bool ok = true;
+    #pragma unroll 1
+    for (int x = 0; x < S; x++) {
+        int v[S];                                                  // a board row at a time: S independent loads, so the latency of
+        #pragma unroll                                             // the memory (LDS or global) is paid once a row and not once a cell
+        for (int y = 0; y < S; y++) v[y] = b[x * S + y];
+        #pragma unroll
+        for (int y = 0; y < S; y++) {
+            const int c = x * S + y, k = v[y] > 0 ? v[y] : -v[y];
+            if (k == 0) continue;
+            if (k > 6) { ok = false; continue; }
+            // the two sides by selects, not by two branches over one body: the compiler merges such branches into one that indexes
+            // the sides' registers as an array in scratch memory
+            const bool own = v[y] > 0;
+            const int bit = 1 << k;
+            const u64 at = (u64)c << (8 * (k - 1));
+            ok = ok && !((own ? Ma : Mo) & bit) && c != (own ? C - 1 : 0);
+            Ma |= own ? bit : 0; Mo |= own ? 0 : bit;
+            na += own ? 1 : 0; no += own ? 0 : 1;
+            pa |= own ? at : 0ull; po |= own ? 0ull : at;
+        }
+    }
+    return ok && na >= 1 && no >= 1 && na <= K && no <= K && na + no <= T;
+}
+
+// G of the agent's cube `cube` (in Ma) in direction r; -inf where the move leaves the board.  Every index it forms is inside the table:
+// a move never adds a cube and never empties the mover's side, so 1 <= popcounts <= K, their sum <= T, and each side index < n_k.
+template <int S>
+EWN_DEV float eg_move(const float *tbl, const EgGeo &g, int Ma, int Mo, u64 pa, u64 po, int cube, int r)
+{
+    constexpr int C = S * S;
+    const int src = eg_cell(pa, cube), x = src / S, y = src % S;
+    if (!((r == 1 || y < S - 1) && (r == 0 || x < S - 1))) return -__builtin_inff();
+    const int dst = src + (r == 0 ? 1 : r == 1 ? S : S + 1);
+    int Ma1 = Ma, Mo1 = Mo;
+    #pragma unroll
+    for (int k = 1; k <= 6; k++) {
+        if (((Ma >> k) & 1) && eg_cell(pa, k) == dst) Ma1 &= ~(1 << k);
+        if (((Mo >> k) & 1) && eg_cell(po, k) == dst) Mo1 &= ~(1 << k);
+    }
+    if (dst == C - 1 || Mo1 == 0) return 1.0f;
+    const int sh = 8 * (cube - 1);
+    const u64 pa1 = (pa & ~(0xFFull << sh)) | ((u64)dst << sh);
+    const int ka1 = __builtin_popcount((unsigned)Mo1), ko1 = __builtin_popcount((unsigned)Ma1);   // of flip(b1): the sides swap
+    const long long idx = g.off[ka1][ko1] + (long long)eg_side<S>(Mo1, po, true) * (long long)eg_n<S>(ko1) + (long long)eg_side<S>(Ma1, pa1, true);
+    return -tbl[idx];
+}
 
 // ---------------------------------------------------------------- host
 static inline bool eg_params_ok(int S, int K, int T) { return S >= 3 && S <= 11 && K >= 1 && K <= 3 && T >= 2 && T <= 2 * K; }

@@ -18,9 +18,28 @@
 // between two rounds (and between the fill and the root) lies __syncthreads.  Every index read from the tree is range-checked by
 // pu_round; what `tree` held before the call cannot matter, because every byte is written before any is read.  No atomics on
 // global memory: the playouts' `next` counter and pstate_load's four words are LDS atomics of the wave's own.
+//
+// The second instance, k_playout_search<S, true> (C ABI: ewn_playout_search_eg, include/ewn_playout_search_eg.h): a
+// pending leaf that an endgame table covers takes its exact value from the table and runs no playouts.  Byte for byte the sequence
+// above with EndgameTable.lookup(leaf rows, leaf dice) before each round's playouts: where the lookup says covered, the value is
+// its q at the action it returns, the first maximum of the six under a strict >; elsewhere the playouts' share, under the same key
+// and row index as without a table.
+//   per round, pending >= 0 (wave-uniform): a ballot counts the row's cubes; with more than max_total the row is not covered
+//              (the lookup's test counts the same cells) and is played out.  Else every lane scans the wave's leaf row in LDS
+//              (eg_position, the lookup's own coverage test: broadcast reads, the same registers on all 64 lanes).  Covered:
+//              lanes 0 .. 5 each gather one eg_move for (f, r) = (lane / 3, lane % 3) -- six independent loads, one memory round
+//              trip -- the six go round the wave by shuffles, every lane folds them in action order, lane 0 writes the value
+//              into LDS, a wave barrier.  Not covered: the playout branch above, unchanged.
+// Every rule above holds for it as it stands: the grid and trip structure, a wave without a tree reaching every barrier, the block
+// barrier between the fill and the root and between two rounds, the tree on one wave, pu_round's range checks, every byte written
+// before any is read.  The table is only read, with indices that eg_move's argument keeps inside it (the coverage test comes first,
+// a move never adds a cube); it must be complete before the launch in stream order.  The geometry (EgGeo) travels by value among the
+// kernel's arguments.  leaf_counts (may be NULL): {rounds a table valued, rounds playouts valued} per tree, two wave-uniform
+// counters in registers that lane 0 stores once after the round loop, a plain vector store.
 #include "ewn_puct.hpp"
 #include "ewn_playout.hpp"
-#include "../../include/ewn_playout_search.h"
+#include "ewn_endgame.hpp"
+#include "../../include/ewn_playout_search_eg.h"
 
 #define PS_NT 256            // threads per block: four waves, one tree each per trip
 #define PS_NW (PS_NT / 64)
@@ -38,10 +57,14 @@ static_assert(PS_WAVE % 16 == 0 && PS_O_LEAF % 16 == 0 && PS_O_GW % 16 == 0, "ev
 
 struct PsBuf { const int8_t *boards; const int8_t *dice; uint8_t *tree; };
 
+// the table instance's own arguments; the plain instance carries an empty struct
+template <bool EG> struct PsEg {};
+template <> struct PsEg<true> { const float *tbl; int *counts; EgGeo g; };
+
 // rounds: R of the contract, 0 .. sims + 1; n: playouts per leaf, 1 .. 4096; k0, k1: the key's halves
-template <int S>
+template <int S, bool EG = false>
 __global__ __launch_bounds__(PS_NT) void k_playout_search(int M, int sims, int rounds, int n, float c_puct, u32 k0, u32 k1, u32 obs_id0,
-                                                          PuLayout L, PsBuf B)
+                                                          PuLayout L, PsBuf B, PsEg<EG> E)
 {
     constexpr int CELLS = S * S;
     __shared__ PlayTab tab;
@@ -77,12 +100,34 @@ __global__ __launch_bounds__(PS_NT) void k_playout_search(int M, int sims, int r
         }
         __syncthreads();                                       // the table is built; the fill is done before the root goes over it
         if (has) pu_root<S>(T, B.boards + m * CELLS, B.dice + m, sims, leaf, ldice, lane, base);
+        int by_table = 0, by_playouts = 0;                     // EG: the rounds of this tree that either valued (wave-uniform)
         #pragma unroll 1
         for (int rnd = 0; rnd < rounds; rnd++) {
             __syncthreads();                                   // the tree's words are handed over
             if (has) {
                 const int pending = __builtin_amdgcn_readfirstlane(T.hdr[2]);
-                if (pending >= 0) {                            // wave-uniform: the leaf in the wave's row is a position to play out
+                bool covered = false;                          // wave-uniform: every lane scans the same row
+                if constexpr (EG) {
+                    // more cubes on the row than a table position has: not covered whatever else (eg_position counts every cell that
+                    // is not empty, or refuses the row for a value outside -6 .. 6), and the scan is skipped
+                    const int cubes = pending >= 0 ? __builtin_popcountll(__builtin_amdgcn_ballot_w64(lane < CELLS && leaf[lane < CELLS ? lane : 0] != 0)) : 0;
+                    if (pending >= 0 && cubes <= E.g.T) {
+                        int Ma, Mo, na, no;
+                        u64 pa, po;
+                        covered = __builtin_amdgcn_readfirstlane((int)eg_position<S>(leaf, E.g.K, E.g.T, Ma, Mo, na, no, pa, po)) != 0;
+                        if (covered) {
+                            float q = -__builtin_inff();
+                            if (lane < 6) q = eg_move<S>(E.tbl, E.g, Ma, Mo, pa, po, la_find(lane / 3, la_dice((int)ldice[0]), Ma), lane % 3);
+                            float qb = __shfl(q, 0, 64);           // k_endgame_lookup's fold: the first maximum, -0.0 == +0.0
+                            #pragma unroll
+                            for (int i = 1; i < 6; i++) { const float qi = __shfl(q, i, 64); if (qi > qb) qb = qi; }
+                            if (lane == 0) val[0] = qb;
+                            __builtin_amdgcn_wave_barrier();
+                        }
+                    }
+                    by_table += covered ? 1 : 0; by_playouts += pending >= 0 && !covered ? 1 : 0;
+                }
+                if (pending >= 0 && !covered) {                // wave-uniform: the leaf in the wave's row is a position to play out
                     if (lane == 0) *next = 64;                 // the same wave reads it: its LDS operations execute in order
                     const PState b0 = pstate_load(g, leaf, lane, 64, gw);
                     const u32 word = PlayoutRng::obs_word(obs_id0 + (u32)m0, 0x53494D55u, key + (u64)rnd * 0x9E3779B97F4A7C15ull);
@@ -95,6 +140,9 @@ __global__ __launch_bounds__(PS_NT) void k_playout_search(int M, int sims, int r
                 pu_round<S, false>(T, sims, c_puct, 1.0f, L.nodes, lg, val, Z, leaf, ldice, lane, base);
             }
         }
+        if constexpr (EG) {
+            if (has && E.counts && lane == 0) { E.counts[2 * m] = by_table; E.counts[2 * m + 1] = by_playouts; }
+        }
     }
 }
 
@@ -103,7 +151,16 @@ static int ps_launch(int M, int sims, int rounds, int n, float c_puct, uint64_t 
 {
     const PuLayout L = pu_layout(S, sims);
     return pol_launch_kernel(k_playout_search<S>, blocks, PS_NT, 0, 64 * 1024, POL_LDS_MAX, s, M, sims, rounds, n, c_puct, (u32)key,
-                             (u32)(key >> 32), (u32)obs_id0, L, b);
+                             (u32)(key >> 32), (u32)obs_id0, L, b, PsEg<false>{});
+}
+
+template <int S>
+static int ps_launch_eg(int M, int sims, int rounds, int n, float c_puct, uint64_t key, uint32_t obs_id0, unsigned blocks, const PsBuf &b,
+                        const PsEg<true> &e, hipStream_t s)
+{
+    const PuLayout L = pu_layout(S, sims);
+    return pol_launch_kernel(k_playout_search<S, true>, blocks, PS_NT, 0, 64 * 1024, POL_LDS_MAX, s, M, sims, rounds, n, c_puct, (u32)key,
+                             (u32)(key >> 32), (u32)obs_id0, L, b, e);
 }
 
 // ewn_puct_search's order of refusals with this entry's own values last, all before the launch
@@ -124,4 +181,30 @@ int ewn_playout_search(int board_size, int cube_layer, int M, int sims, int roun
     hipStream_t s = (hipStream_t)stream;
     return board_size == 5 ? ps_launch<5>(M, sims, R, playouts, c_puct, key, obs_id0, grid, b, s)
                            : ps_launch<7>(M, sims, R, playouts, c_puct, key, obs_id0, grid, b, s);
+}
+
+// ewn_playout_search's refusals in its order, the table's after the entry's own values
+int ewn_playout_search_eg(int board_size, int cube_layer, int M, int sims, int rounds, int playouts, float c_puct, uint64_t key,
+                          uint32_t obs_id0, int blocks, int max_cubes, int max_total, const float *table,
+                          const int8_t *boards, const int8_t *dice, void *tree, int32_t *leaf_counts, void *stream)
+{
+    const int rc = pu_refuse(board_size, cube_layer, M);
+    if (rc != EWN_OK || M == 0) return rc;
+    if (!table || !boards || !dice || !tree) return EWN_ENULL;
+    if (sims < 0 || sims > PU_MAX_SIMS) return EWN_EINVAL;
+    if ((uintptr_t)tree & 3) return EWN_EINVAL;
+    if (playouts < 1 || playouts > EWN_PLAYOUT_SEARCH_MAX_PLAYOUTS) return EWN_EINVAL;
+    if (!std::isfinite(c_puct) || c_puct < 0.0f) return EWN_EINVAL;
+    if (blocks < 0 || blocks > EWN_PLAYOUT_SEARCH_MAX_BLOCKS) return EWN_EINVAL;
+    if (!eg_params_ok(board_size, max_cubes, max_total)) return EWN_EINVAL;
+    if (((uintptr_t)table & 3) || ((uintptr_t)leaf_counts & 3)) return EWN_EINVAL;
+    const int R = rounds < 0 || rounds > sims + 1 ? sims + 1 : rounds;
+    const unsigned grid = blocks > 0 ? (unsigned)blocks : la_blocks(M, PS_NW, EWN_PLAYOUT_SEARCH_MAX_BLOCKS);
+    PsBuf b = { boards, dice, (uint8_t *)tree };
+    PsEg<true> e;
+    e.tbl = table; e.counts = leaf_counts;
+    eg_geo(board_size, max_cubes, max_total, e.g);
+    hipStream_t s = (hipStream_t)stream;
+    return board_size == 5 ? ps_launch_eg<5>(M, sims, R, playouts, c_puct, key, obs_id0, grid, b, e, s)
+                           : ps_launch_eg<7>(M, sims, R, playouts, c_puct, key, obs_id0, grid, b, e, s);
 }

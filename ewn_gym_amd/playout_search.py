@@ -60,19 +60,29 @@ def playout_search(boards, dice, sims, playouts=64, c_puct=1.5, key=0, obs_id0=0
     who = "playout_search"
     lib = _lib.load()
     sims, playouts, key, obs_id0 = _numbers(who, sims, playouts, c_puct, key, obs_id0)
+    rounds, blocks = _rounds_and_blocks(who, rounds, blocks, sims)
+    M, S, dev, b, d = _observations(who, boards, dice, cube_layer)
+    L = int(cube_layer)
+    out = _trees(who, lib, out, M, S, L, sims, dev)
+    with torch.cuda.device(dev):
+        _launch(lib, S, L, M, sims, rounds, playouts, C.c_float(float(c_puct)), key, obs_id0, blocks, b, d, out, _stream())
+    return out
+
+
+def _rounds_and_blocks(who, rounds, blocks, sims):
+    """rounds= and blocks= of a whole search as the entry takes them: -1 for all rounds, 0 for the library's grid"""
     if rounds is not None and not (isinstance(rounds, (int, np.integer)) and int(rounds) >= 0):
         raise ValueError("%s: rounds must be None or an integer that is not negative, got %r" % (who, rounds))
     if blocks is not None and not (isinstance(blocks, (int, np.integer)) and 1 <= int(blocks) <= PLAYOUT_SEARCH_MAX_BLOCKS):
         raise ValueError("%s: blocks must be None or an integer in 1..%d, got %r" % (who, PLAYOUT_SEARCH_MAX_BLOCKS, blocks))
-    M, S, dev, b, d = _observations(who, boards, dice, cube_layer)
-    L = int(cube_layer)
+    return -1 if rounds is None else min(int(rounds), sims + 1), 0 if blocks is None else int(blocks)
+
+
+def _trees(who, lib, out, M, S, L, sims, dev):
+    """out= of a whole search: a fresh buffer of M trees, or the caller's, checked"""
     if out is None:
-        out = torch.empty((M, int(lib.ewn_puct_tree_bytes(S, L, sims))), dtype=torch.uint8, device=dev)
-    else:
-        _holds_trees(who, "out", out, _puct_tree(who, out, S, sims, L)[0], M, dev)
-    with torch.cuda.device(dev):
-        _launch(lib, S, L, M, sims, -1 if rounds is None else min(int(rounds), sims + 1), playouts, C.c_float(float(c_puct)), key, obs_id0,
-                0 if blocks is None else int(blocks), b, d, out, _stream())
+        return torch.empty((M, int(lib.ewn_puct_tree_bytes(S, L, sims))), dtype=torch.uint8, device=dev)
+    _holds_trees(who, "out", out, _puct_tree(who, out, S, sims, L)[0], M, dev)
     return out
 
 

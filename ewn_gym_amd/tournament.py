@@ -57,6 +57,13 @@ def _policy(spec, cube_layer, key):
         # ply by ply through ewn_step; keyed like the mcts kind: episode m is observation id m, step t its own key
         from .playout_search import KEY_PLY, _numbers, predict_playout_search
         _numbers("playout_search", spec.get("sims", 64), spec.get("playouts", 64), spec.get("c_puct", 1.5), key, 0)   # refused here, not at the first ply
+        if spec.get("endgame_table") is not None:   # a table or its path (loaded once): exact values at the leaves it covers
+            from .endgame import EndgameTable, _accept_table
+            from .playout_exact import predict_playout_search_exact
+            table = _accept_table("playout_search", spec["endgame_table"], None, None, load=EndgameTable.load)
+            return lambda b, d, t: predict_playout_search_exact(b, d, table, sims=spec.get("sims", 64), playouts=spec.get("playouts", 64),
+                                                                c_puct=spec.get("c_puct", 1.5), key=(key + KEY_PLY * (t + 1)) & 0xFFFFFFFFFFFFFFFF,
+                                                                cube_layer=cube_layer)
         return lambda b, d, t: predict_playout_search(b, d, sims=spec.get("sims", 64), playouts=spec.get("playouts", 64),
                                                       c_puct=spec.get("c_puct", 1.5), key=(key + KEY_PLY * (t + 1)) & 0xFFFFFFFFFFFFFFFF,
                                                       cube_layer=cube_layer)
@@ -180,7 +187,7 @@ def evaluate(agent, opponent, num=1024, board_size=5, cube_layer=3, rng="mt19937
     {"kind": "mlp_puct", "model": ..., sims=, c_puct=, terminal_value=} (its PUCT search on both of its heads, ply by ply),
     {"kind": "endgame", "table": an EndgameTable or its path, "fallback": any of these dicts} (the exact move where the table covers
     the position, the fallback's elsewhere, ply by ply),
-    {"kind": "playout_search", sims=, playouts=, c_puct=} (the same tree without a network: uniform priors, random playouts at the
+    {"kind": "playout_search", sims=, playouts=, c_puct=, endgame_table=} (the same tree without a network: uniform priors, random playouts at the
     leaves, ply by ply), or a callable policy (board, dice, t) -> actions.
     agent / opponent: dicts {"kind": "random"|"minimax"|"mcts", max_depth=, heuristic=, num_simulations=, num_env_copies=}.
     Returns per-episode scores (float64 tensor), episode lengths and summary statistics.
@@ -317,13 +324,19 @@ def evaluate_agents_vs_model(model, names=("random", "minimax", "mcts"), num=102
 
 
 def tournament(names=("random", "minimax", "mcts"), num=1024, max_depth=5, num_simulations=10, num_env_copies=5,
-               board_size=5, cube_layer=3, heuristic="hybrid", rng="mt19937", sims=64, playouts=64, c_puct=1.5):
+               board_size=5, cube_layer=3, heuristic="hybrid", rng="mt19937", sims=64, playouts=64, c_puct=1.5, playout_table=None):
     """eval_pairs.py:10-35: every (agent, opponent) pair, 1024 episodes, depth 5, 10 simulations by default.
     "playout_search" among the names (sims, playouts and c_puct are its own): the tree search on random playouts, an agent only --
-    the env has no such opponent -- so it adds the rows "playout_search vs <every other name>"."""
+    the env has no such opponent -- so it adds the rows "playout_search vs <every other name>".  playout_table: an EndgameTable or
+    the path of a saved one (loaded once) whose exact values that search takes at the leaves it covers."""
+    if playout_table is not None:
+        from .endgame import EndgameTable, _accept_table
+        playout_table = _accept_table("tournament", playout_table, board_size, "playout_table is for %%dx%%d boards, the tournament plays %dx%d" % (
+            board_size, board_size), name="playout_table", load=EndgameTable.load)
+
     def spec(n):
         if n == "playout_search":
-            return {"kind": n, "sims": sims, "playouts": playouts, "c_puct": c_puct}
+            return {"kind": n, "sims": sims, "playouts": playouts, "c_puct": c_puct, "endgame_table": playout_table}
         return _classical_spec(n, max_depth, heuristic, num_simulations, num_env_copies)
     table = {}
     for a in names:
@@ -398,6 +411,8 @@ def _parser():
     ap.add_argument("--sims", type=int, default=64, help="playout_search: simulations per move")
     ap.add_argument("--playouts", type=int, default=64, help="playout_search: random playouts per leaf")
     ap.add_argument("--c_puct", type=float, default=1.5, help="playout_search: the exploration constant")
+    ap.add_argument("--playout_table", default=None, metavar="PATH",
+                    help="playout_search: a saved EndgameTable; the leaves it covers are worth their exact value and run no playouts")
     ap.add_argument("--model", default=None, help="checkpoint (best.pt) of any of the trainers: evaluate its deterministic policy")
     ap.add_argument("--opponent_model", default=None, help="a checkpoint that plays the opponent (its argmax): against --model, or "
                                                            "without --model against every agent of --agents")
@@ -449,6 +464,8 @@ def main():
         ap.error("--endgame_leaves goes with --lookahead and --endgame_table")
     if "playout_search" in a.agents and (a.model is not None or a.opponent_model is not None):
         ap.error("playout_search among --agents goes without --model and --opponent_model")
+    if a.playout_table and "playout_search" not in a.agents:
+        ap.error("--playout_table goes with playout_search among --agents")
     if a.opponent_model is not None and a.model is None:
         t = evaluate_agents_vs_model(load_policy(a.opponent_model, a.board_size, a.cube_layer), a.agents, a.num, a.max_depth,
                                      a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer, a.heuristic, a.rng)
@@ -464,7 +481,7 @@ def main():
                            endgame_leaves=a.endgame_leaves, fused=a.fused, leaves=a.leaves)
     else:
         t = tournament(a.agents, a.num, a.max_depth, a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer,
-                       a.heuristic, a.rng, sims=a.sims, playouts=a.playouts, c_puct=a.c_puct)
+                       a.heuristic, a.rng, sims=a.sims, playouts=a.playouts, c_puct=a.c_puct, playout_table=a.playout_table)
     for k, v in t.items():
         print("%-22s win rate %.3f  (95%% CI %.3f-%.3f, %d/%d, %.1f steps/episode)  %s"
               % (k, v["win_rate"], v["ci95"][0], v["ci95"][1], v["wins"], v["episodes"], v["avg_length"], v["engine"]))
