@@ -78,13 +78,14 @@ class ModelAgent(PolicyBase):
         return lambda b, d, t: self.predict_batch(b, d, key=(self.key + 0x9E3779B97F4A7C15 * (t + 1)) & 0xFFFFFFFFFFFFFFFF)
 
 
-def _leaf_table(who, table, board_size):
-    """endgame_table= of a searching agent: None, an EndgameTable, or the path of a saved one (loaded once), for the agent's boards"""
+def _leaf_table(who, table, board_size, name="endgame_table"):
+    """endgame_table= (or `name`=) of a searching agent: None, an EndgameTable, or the path of a saved one (loaded once), for the
+    agent's boards"""
     from ewn_gym_amd.endgame import EndgameTable, _accept_table
     if table is None:
         return None
     return _accept_table(who, table, board_size, "the table is for %%dx%%d boards, the agent plays %dx%d" % (board_size, board_size),
-                         load=EndgameTable.load)
+                         name=name, load=EndgameTable.load)
 
 
 class ValueSearchAgent(_PlainPolicyFn, ModelAgent):
@@ -119,19 +120,23 @@ class PuctAgent(_PlainPolicyFn, ModelAgent):
     instead of the value head's.  fused=True: the search of a batch is one kernel launch (ewn_puct_search, DESIGN.md
     4r) instead of 2 sims + 3: the same moves; not together with endgame_table.  leaves=2..32: the search of a batch is the one launch
     of ewn_puct_search_wide, up to that many leaves per tree and round: fewer rounds, other trees, so not always the
-    moves of leaves=1; not together with endgame_table."""
+    moves of leaves=1; not together with endgame_table.  leaf_table (a table or the path of a saved one, loaded once): endgame_table's
+    exact leaves with the search of a batch in the one launch of ewn_puct_search_eg; fused is not read; not together
+    with endgame_table or leaves > 1."""
 
     def __init__(self, model_or_path, board_size=5, cube_layer=3, sims=64, c_puct=1.5, terminal_value=1.0, endgame_table=None, fused=False,
-                 leaves=1):
-        from ewn_gym_amd.search import _fused_table, _puct_numbers
+                 leaves=1, leaf_table=None):
+        from ewn_gym_amd.search import _fused_table, _leaf_table_alone, _puct_numbers
         from ewn_gym_amd.wide import _NO_TABLE, _leaves_alone
         self.sims = _puct_numbers("PuctAgent", sims, c_puct, terminal_value)
         _fused_table("PuctAgent", fused, endgame_table)
         self.leaves = _leaves_alone("PuctAgent", leaves, endgame_table=(endgame_table is not None, _NO_TABLE))
+        _leaf_table_alone("PuctAgent", leaf_table, endgame_table, self.leaves)
         self.fused = bool(fused)
         self.c_puct, self.terminal_value = float(c_puct), float(terminal_value)
         super().__init__(model_or_path, board_size=board_size, cube_layer=cube_layer, deterministic=True)
         self.endgame_table = _leaf_table("PuctAgent", endgame_table, board_size)
+        self.leaf_table = _leaf_table("PuctAgent", leaf_table, board_size, name="leaf_table")
 
     def predict_batch(self, boards, dice, return_visits=False, return_q=False, return_value=False):
         """boards (M,S,S), dice (M,) device or host arrays -> int8 (M,2) device tensor (and the int32 (M,2,3) root visits, the float32
@@ -139,7 +144,8 @@ class PuctAgent(_PlainPolicyFn, ModelAgent):
         b, d = self._on_device(boards, dice)
         return self._ea.predict_puct(b, d, self.params, sims=self.sims, c_puct=self.c_puct, terminal_value=self.terminal_value,
                                      return_visits=return_visits, return_q=return_q, return_value=return_value,
-                                     cube_layer=self.cube_layer, endgame_table=self.endgame_table, fused=self.fused, leaves=self.leaves)
+                                     cube_layer=self.cube_layer, endgame_table=self.endgame_table, fused=self.fused, leaves=self.leaves,
+                                     leaf_table=self.leaf_table)
 
 
 class EndgameAgent(_PlainPolicyFn, PolicyBase):

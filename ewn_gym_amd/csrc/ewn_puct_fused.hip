@@ -22,7 +22,33 @@
 // release and acquire, on one CU and one vector cache.  Per-edge words stay lane-a-only, a board cell is read by the lane that
 // wrote it.  Every index read from the tree is range-checked as in the staged kernels; what `tree` held before the call cannot
 // matter, because every byte is written before any is read.  No atomics.
+//
+// The table instances, k_puct_search<S, NOISE, true> (C ABI: ewn_puct_search_eg, include/ewn_puct_exact.h): a pending
+// leaf that an endgame table covers takes its exact value from the table in place of the value head's output; the logits stay the
+// policy head's.  Byte for byte the sequence above with EndgameTable.lookup(leaf rows, leaf dice) between ewn_predict_policy and
+// ewn_puct_advance: where the lookup says covered, the value handed on is fl(terminal_value * q) at the action the lookup returns,
+// the first maximum of the six under a strict > (pu_evaluate then forms fl(that * inv_tv), so the kernel carries terminal_value
+// as well as inv_tv); elsewhere the value head's.
+//   per round, between the two barriers: while wave 0 and wave 1 run the networks, waves 2 .. 7 look the tile's columns up,
+//              column k on wave 2 + k % 6 -- a ballot counts the slot's cubes (more than max_total: not covered, the lookup's test
+//              counts the same cells); else every lane scans the slot (eg_position, the lookup's own coverage test, on the CELLS
+//              bytes at the slot's start: broadcast reads); covered: lanes 0 .. 5 gather one eg_move each for (f, r) = (lane / 3,
+//              lane % 3) with the cube from la_find / la_dice, the six go round the wave by shuffles and are folded in action
+//              order; lane 0 writes (exact, covered) of column k into an LDS array of the instance's own, apart from `value`,
+//              which wave 1 writes in the same phase.  After the barrier the tree's wave hands pu_round the exact value's address
+//              in place of the value head's.  A column without a pending leaf is a zero board: no cube, not covered.
+// Every rule above holds for these instances as it stands: the block barriers and their places; a tree -- its bytes in global
+// memory -- stays on one wave from the fill to the end (a looking-up wave reads the column's slot and dice in LDS, written before
+// the round's first barrier, and the table, and touches no tree); the hand-over rule of ewn_puct.hpp; pu_round's range checks;
+// every byte written before any is read; no atomics, vector stores only.  EgGeo travels by value among the kernel's arguments.  The
+// table is only read, with indices that eg_move's own argument keeps inside it: the coverage test comes first, and a move never
+// adds a cube.  It must be complete before the launch in stream order.  leaf_counts (may be NULL): per tree {rounds the table
+// valued, rounds the value head valued}, kept as wave-uniform registers (16 bits per tree of the wave, at most sims + 1 = 4097
+// each) and stored once by lane 0 after the round loop.  LDS grows by 256 bytes; the plain instances' LDS, registers and
+// instructions are what they were.
 #include "ewn_puct.hpp"
+#include "ewn_endgame.hpp"
+#include "../../include/ewn_puct_exact.h"
 
 #define PUF_NT 512           // threads per block: eight waves (two per SIMD, up to 256 VGPRs each)
 #define PUF_NW (PUF_NT / 64)
@@ -45,9 +71,17 @@ template <int S> struct PufGeo {
 
 struct PufBuf { const int8_t *boards; const int8_t *dice; const float *params; const float *noise; float eps, keep; uint8_t *tree; };
 
+// the table instances' own arguments; the plain instances carry an empty struct.  Their LDS, behind the plain instances': exact [32]
+// floats | covered [32] words
+template <bool EG> struct PufEg {};
+template <> struct PufEg<true> { const float *tbl; int *counts; float tv; EgGeo g; };
+#define PUF_EG_LDS (2 * PUF_TILE * 4)
+#define PUF_NLOOK (PUF_NW - 2)   // the waves that look columns up while waves 0 and 1 run the networks
+
 // tile: the trees per tile, 1 .. PUF_TILE (block-uniform); rounds: R of the contract, 0 .. sims + 1
-template <int S, bool NOISE>
-__global__ __launch_bounds__(PUF_NT, 1) void k_puct_search(int M, int sims, int rounds, int tile, float c_puct, float inv_tv, PuLayout L, PufBuf B)
+template <int S, bool NOISE, bool EG = false>
+__global__ __launch_bounds__(PUF_NT, 1) void k_puct_search(int M, int sims, int rounds, int tile, float c_puct, float inv_tv, PuLayout L, PufBuf B,
+                                                           PufEg<EG> E)
 {
     using P = PufGeo<S>;
     using Q3 = Mlp3Geo<S>;
@@ -82,6 +116,7 @@ __global__ __launch_bounds__(PUF_NT, 1) void k_puct_search(int M, int sims, int 
             const size_t m = (size_t)(first + k);
             pu_root<S>(pu_tree(B.tree, m, L), B.boards + m * CELLS, B.dice + m, sims, slots + k * STR, sdice + k, lane, base);
         }
+        unsigned long long by_table = 0, by_value = 0;        // EG: 16 bits per tree of this wave, tree k in field k / PUF_NW (wave-uniform)
         #pragma unroll 1
         for (int rnd = 0; rnd < rounds; rnd++) {
             __syncthreads();                                   // the leaves are in the slots, the trees' words are handed over
@@ -102,14 +137,66 @@ __global__ __launch_bounds__(PUF_NT, 1) void k_puct_search(int M, int sims, int 
                     if (h == 0) sval[j] = vo[0];
                 }
             }
+            if constexpr (EG) {
+                // ---- the lookups, under the networks: column k by wave 2 + k % PUF_NLOOK, all 64 lanes on the one slot
+                float *sex = (float *)(lds + P::lds_bytes());
+                int *scov = (int *)(sex + PUF_TILE);
+                const int w2 = __builtin_amdgcn_readfirstlane(wave) - 2;
+                if (w2 >= 0) {                                 // wave-uniform
+                    #pragma unroll 1
+                    for (int k = w2; k < nt; k += PUF_NLOOK) {
+                        const int8_t *leaf = slots + k * STR;
+                        // more cubes on the row than a table position has: not covered whatever else (eg_position counts every cell
+                        // that is not empty, or refuses the row for a value outside -6 .. 6), and the scan is skipped
+                        const int cubes = __builtin_popcountll(__builtin_amdgcn_ballot_w64(lane < CELLS && leaf[lane < CELLS ? lane : 0] != 0));
+                        bool covered = false;                  // wave-uniform: every lane scans the same row
+                        float exact = 0.0f;
+                        if (cubes <= E.g.T) {
+                            int Ma, Mo, na, no;
+                            u64 pa, po;
+                            covered = __builtin_amdgcn_readfirstlane((int)eg_position<S>(leaf, E.g.K, E.g.T, Ma, Mo, na, no, pa, po)) != 0;
+                            if (covered) {
+                                float q = -__builtin_inff();
+                                if (lane < 6) q = eg_move<S>(E.tbl, E.g, Ma, Mo, pa, po, la_find(lane / 3, la_dice((int)sdice[k]), Ma), lane % 3);
+                                float qb = __shfl(q, 0, 64);   // k_endgame_lookup's fold: the first maximum, -0.0 == +0.0
+                                #pragma unroll
+                                for (int i = 1; i < 6; i++) { const float qi = __shfl(q, i, 64); if (qi > qb) qb = qi; }
+                                exact = E.tv * qb;             // one rounding; pu_evaluate forms fl(exact * inv_tv)
+                            }
+                        }
+                        if (lane == 0) { sex[k] = exact; scov[k] = covered ? 1 : 0; }
+                    }
+                }
+            }
             __syncthreads();                                   // logits and value are there; the slots are read
             #pragma unroll 1
             for (int k = wave; k < nt; k += PUF_NW) {
                 const size_t m = (size_t)(first + k);
                 PuNoise Z = { nullptr, 0.0f, 0.0f };
                 if constexpr (NOISE) Z = PuNoise{ B.noise + m * 6, B.eps, B.keep };
+                const PuTree T = pu_tree(B.tree, m, L);
+                const float *vp = sval + k;
+                if constexpr (EG) {                            // a covered column holds a position, so its tree has a pending leaf
+                    const float *sex = (const float *)(lds + P::lds_bytes());
+                    const bool covered = __builtin_amdgcn_readfirstlane(((const int *)(sex + PUF_TILE))[k]) != 0;
+                    const bool pending = __builtin_amdgcn_readfirstlane(T.hdr[2]) >= 0;
+                    const int sh = 16 * (__builtin_amdgcn_readfirstlane(k) / PUF_NW);
+                    by_table += (unsigned long long)(covered ? 1 : 0) << sh;
+                    by_value += (unsigned long long)(pending && !covered ? 1 : 0) << sh;
+                    if (covered) vp = sex + k;
+                }
                 // the noise instance is round 0's alone: on later rounds the pending node is never the root, and pu_evaluate asks
-                pu_round<S, NOISE>(pu_tree(B.tree, m, L), sims, c_puct, inv_tv, L.nodes, slg + k * 8, sval + k, Z, slots + k * STR, sdice + k, lane, base);
+                pu_round<S, NOISE>(T, sims, c_puct, inv_tv, L.nodes, slg + k * 8, vp, Z, slots + k * STR, sdice + k, lane, base);
+            }
+        }
+        if constexpr (EG) {
+            if (E.counts && lane == 0) {
+                #pragma unroll 1
+                for (int k = wave; k < nt; k += PUF_NW) {
+                    const int sh = 16 * (k / PUF_NW);
+                    E.counts[2 * (size_t)(first + k)] = (int)((by_table >> sh) & 0xFFFFull);
+                    E.counts[2 * (size_t)(first + k) + 1] = (int)((by_value >> sh) & 0xFFFFull);
+                }
             }
         }
     }
@@ -122,7 +209,18 @@ static int puf_launch(int M, int sims, int rounds, int tile, float c_puct, float
     static_assert(lds <= POL_LDS_MAX, "both weight images + the tile's slots, outputs and the waves' own must fit the CU's LDS");
     const PuLayout L = pu_layout(S, sims);
     return pol_launch_kernel(k_puct_search<S, NOISE>, la_blocks(M, tile, PUF_MAX_BLOCKS), PUF_NT, lds, 64 * 1024, POL_LDS_MAX, s, M, sims, rounds, tile,
-                             c_puct, inv_tv, L, b);
+                             c_puct, inv_tv, L, b, PufEg<false>{});
+}
+
+template <int S, bool NOISE>
+static int puf_launch_eg(int M, int sims, int rounds, int tile, unsigned blocks, float c_puct, float inv_tv, const PufBuf &b, const PufEg<true> &e,
+                         hipStream_t s)
+{
+    constexpr size_t lds = PufGeo<S>::lds_bytes() + PUF_EG_LDS;
+    static_assert(lds <= POL_LDS_MAX, "the plain instance's LDS and the columns' exact values and flags must fit the CU's LDS");
+    const PuLayout L = pu_layout(S, sims);
+    return pol_launch_kernel(k_puct_search<S, NOISE, true>, blocks, PUF_NT, lds, 64 * 1024, POL_LDS_MAX, s, M, sims, rounds, tile, c_puct, inv_tv, L,
+                             b, e);
 }
 
 // Trees per tile.  The networks cost a round the same whatever the tile holds, and a wave walks its trees one after the other, so
@@ -156,4 +254,39 @@ int ewn_puct_search(int board_size, int cube_layer, int M, int sims, int rounds,
     if (root_noise)
         return board_size == 5 ? puf_launch<5, true>(M, sims, R, tile, c_puct, inv_tv, b, s) : puf_launch<7, true>(M, sims, R, tile, c_puct, inv_tv, b, s);
     return board_size == 5 ? puf_launch<5, false>(M, sims, R, tile, c_puct, inv_tv, b, s) : puf_launch<7, false>(M, sims, R, tile, c_puct, inv_tv, b, s);
+}
+
+// ewn_puct_search's refusals in its order, the table among the pointers; then tile and blocks, the table's values, the alignments.
+// No environment variable is read: tile and blocks are arguments, 0 the library's choice
+int ewn_puct_search_eg(int board_size, int cube_layer, int M, int sims, int rounds, float c_puct, float terminal_value, const int8_t *boards,
+                       const int8_t *dice, const float *params, const float *root_noise, float noise_eps, int tile, int blocks, int max_cubes,
+                       int max_total, const float *table, void *tree, int32_t *leaf_counts, void *stream)
+{
+    const int rc = pu_refuse(board_size, cube_layer, M);
+    if (rc != EWN_OK || M == 0) return rc;
+    if (!boards || !dice || !params || !tree || !table) return EWN_ENULL;
+    if (sims < 0 || sims > PU_MAX_SIMS || ((uintptr_t)tree & 3)) return EWN_EINVAL;
+    if (!std::isfinite(terminal_value) || !(terminal_value > 0.0f) || !std::isfinite(c_puct) || c_puct < 0.0f) return EWN_EINVAL;
+    if (root_noise && !(noise_eps >= 0.0f && noise_eps <= 1.0f)) return EWN_EINVAL;   // NaN is refused here as well
+    if (tile < 0 || tile > PUF_TILE || blocks < 0 || blocks > EWN_PUCT_EXACT_MAX_BLOCKS) return EWN_EINVAL;
+    if (!eg_params_ok(board_size, max_cubes, max_total)) return EWN_EINVAL;
+    if (((uintptr_t)table & 3) || ((uintptr_t)leaf_counts & 3)) return EWN_EINVAL;
+    const int R = rounds < 0 || rounds > sims + 1 ? sims + 1 : rounds;
+    if (tile == 0) {                                           // as small as still gives every CU at most one tile
+        tile = (M - 1) / PUF_MAX_BLOCKS + 1;
+        tile = tile < PUF_TILE ? tile : PUF_TILE;
+    }
+    const unsigned need = la_blocks(M, tile, PUF_MAX_BLOCKS);
+    const unsigned nb = blocks == 0 || (unsigned)blocks > need ? need : (unsigned)blocks;
+    PufBuf b = { boards, dice, params, root_noise, root_noise ? noise_eps : 0.0f, root_noise ? 1.0f - noise_eps : 1.0f, (uint8_t *)tree };
+    PufEg<true> e;
+    e.tbl = table; e.counts = leaf_counts; e.tv = terminal_value;
+    eg_geo(board_size, max_cubes, max_total, e.g);
+    const float inv_tv = 1.0f / terminal_value;
+    hipStream_t s = (hipStream_t)stream;
+    if (root_noise)
+        return board_size == 5 ? puf_launch_eg<5, true>(M, sims, R, tile, nb, c_puct, inv_tv, b, e, s)
+                               : puf_launch_eg<7, true>(M, sims, R, tile, nb, c_puct, inv_tv, b, e, s);
+    return board_size == 5 ? puf_launch_eg<5, false>(M, sims, R, tile, nb, c_puct, inv_tv, b, e, s)
+                           : puf_launch_eg<7, false>(M, sims, R, tile, nb, c_puct, inv_tv, b, e, s);
 }

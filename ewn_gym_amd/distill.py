@@ -23,8 +23,8 @@ from ._lib import check
 from .a2c import FusedTrainer
 from .endgame import EndgameTable, _accept_table
 from .games import selfplay_puct_games
-from .search import (SELFPLAY_MAX_PLIES, _noise_eps, _play_numbers, _puct_numbers, lookahead_targets, predict_lookahead, predict_puct,
-                     selfplay_puct, sup_grad)
+from .search import (SELFPLAY_MAX_PLIES, _leaf_table_alone, _noise_eps, _play_numbers, _puct_numbers, lookahead_targets, predict_lookahead,
+                     predict_puct, selfplay_puct, sup_grad)
 from .sharding import all_reduce_counters
 from .wide import _NO_TABLE, _NO_WHOLE_GAMES, _leaves_alone
 
@@ -214,7 +214,7 @@ class PuctSelfPlayTrainer(_SupervisedTrainer):
 
     def __init__(self, env, sims=64, c_puct=1.5, terminal_value=1.0, noise_eps=0.25, noise_alpha=1.0, temp_plies=8, max_plies=None,
                  learning_rate=7e-4, pi_coef=1.0, vf_coef=0.5, max_grad_norm=0.5, rms_alpha=0.99, rms_eps=1e-5, seed=None,
-                 endgame_table=None, chunk=1024, fused=False, whole_games=False, leaves=1):
+                 endgame_table=None, chunk=1024, fused=False, whole_games=False, leaves=1, leaf_table=None):
         who = "PuctSelfPlayTrainer"
         _puct_numbers(who, sims, c_puct, terminal_value)
         _noise_eps(who, noise_eps)
@@ -228,6 +228,9 @@ class PuctSelfPlayTrainer(_SupervisedTrainer):
             raise ValueError("%s: whole_games=True does not take an endgame_table: the exact-leaf substitution is the staged path's" % who)
         leaves = _leaves_alone(who, leaves, endgame_table=(endgame_table is not None, _NO_TABLE),
                                **{"whole_games=True": (whole_games, _NO_WHOLE_GAMES)})
+        _leaf_table_alone(who, leaf_table, endgame_table, leaves, whole_games)
+        # leaf_table (a table or its path): endgame_table's exact leaves with a ply's search in the one launch of ewn_puct_search_eg (4w);
+        # fused is then not read
         # endgame_table: exact values at the leaves the table covers (4p), nothing else
         # fused: a ply's search as the one launch of ewn_puct_search (4r): the same records bit for bit
         # whole_games: all games in the one launch of ewn_puct_selfplay (4s), chunk and fused are then not read: the same records again
@@ -235,6 +238,10 @@ class PuctSelfPlayTrainer(_SupervisedTrainer):
                          endgame_table=endgame_table, learning_rate=learning_rate, max_grad_norm=max_grad_norm, rms_alpha=rms_alpha,
                          rms_eps=rms_eps, leaves=leaves, n_steps=1, seed=seed, use_graph=False, opponent=None, opponent_update_every=100,
                          opponent_deterministic=False, policy_rollout=False)
+        if leaf_table is not None:
+            leaf_table = _accept_table(who, leaf_table, env.S, "the leaf table is for %%dx%%d boards, the env plays %dx%d" % (env.S, env.S),
+                                       name="leaf_table", load=lambda path: EndgameTable.load(path, device=env.board.device))
+        self.leaf_table = leaf_table
         self.max_plies = SELFPLAY_MAX_PLIES[env.S] if max_plies is None else int(max_plies)
         self._size_scratch(self.max_plies)
         self.noise_eps, self.noise_alpha, self.temp_plies = float(noise_eps), float(noise_alpha), int(temp_plies)
@@ -264,7 +271,8 @@ class PuctSelfPlayTrainer(_SupervisedTrainer):
             rec = selfplay_puct(board, dice, self.params, sims=self.sims, max_plies=self.max_plies, c_puct=self.c_puct,
                                 terminal_value=self.terminal_value, noise_eps=self.noise_eps, noise_alpha=self.noise_alpha,
                                 temp_plies=self.temp_plies, key=self.noise_key, game_offset=first, chunk=self.chunk,
-                                endgame_table=self.endgame_table, cube_layer=env.L, fused=self.fused, leaves=self.leaves)
+                                endgame_table=self.endgame_table, cube_layer=env.L, fused=self.fused, leaves=self.leaves,
+                                leaf_table=self.leaf_table)
         self.records = rec
         R, S = self.max_plies * env.N, env.S
         b, d = rec["board"].reshape(R, S, S), rec["dice"].reshape(R).clamp(min=1)         # rows past a game's end hold dice 0
@@ -293,15 +301,15 @@ class PuctSelfPlayTrainer(_SupervisedTrainer):
     def _state(self):
         return {**super()._state(), "noise_eps": float(self.noise_eps), "noise_alpha": float(self.noise_alpha),
                 "temp_plies": int(self.temp_plies), "max_plies": int(self.max_plies), "seed_counter": int(self.seed_counter),
-                "whole_games": bool(self.whole_games)}
+                "whole_games": bool(self.whole_games), "leaf_table_used": self.leaf_table is not None}   # that one was used, not its bytes
 
     def _load_state(self, sd):
         super()._load_state(sd)
         self.noise_eps, self.noise_alpha = float(sd.get("noise_eps", self.noise_eps)), float(sd.get("noise_alpha", self.noise_alpha))
         self.temp_plies, self.seed_counter = int(sd.get("temp_plies", self.temp_plies)), int(sd.get("seed_counter", self.seed_counter))
         self.fused = self.fused and self.endgame_table is None
-        self.whole_games = bool(sd.get("whole_games", self.whole_games)) and self.endgame_table is None
-        self.leaves = self.leaves if self.endgame_table is None and not self.whole_games else 1
+        self.whole_games = bool(sd.get("whole_games", self.whole_games)) and self.endgame_table is None and self.leaf_table is None
+        self.leaves = self.leaves if self.endgame_table is None and self.leaf_table is None and not self.whole_games else 1
         if int(sd.get("max_plies", self.max_plies)) != self.max_plies:
             raise ValueError("the checkpoint's games have at most %d plies, this trainer's %d: the update's scratch is sized by it" % (
                 int(sd["max_plies"]), self.max_plies))

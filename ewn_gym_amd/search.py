@@ -27,15 +27,15 @@ _PLAY_ROWS = (("board", torch.int8, lambda S: (S, S)), ("dice", torch.int8, lamb
               ("value", torch.float32, lambda S: ()), ("action", torch.int8, lambda S: (2,)), ("live", torch.int8, lambda S: ()))
 
 
-def _network_inputs(who, boards, dice, params, cube_layer, more=(), optional=(), table=None):
+def _network_inputs(who, boards, dice, params, cube_layer, more=(), optional=(), table=None, table_name="endgame_table"):
     """The opening of a call on the network, up to the device check, which is the caller's _same_gpu(who, dev, "params", t.items()):
     boards [S, S] or [M, S, S], dice [M], params as predict_policy takes them; more and optional = [(name, x, dtype, shape of (M, P))],
     further inputs in the order they are checked, an optional one may be None; table: an EndgameTable for the boards' size or None
-    (EndgameTable.lookup's texts)
+    (EndgameTable.lookup's texts), the caller's keyword table_name
     -> (M, S, cube_layer, the device of params, {name: checked tensor or None}: params, boards, dice, more, optional, "the table")"""
     M, S, P = _lookahead_shape(who, boards, cube_layer)
     if table is not None:
-        _accept_table(who, table, S, "boards of shape %s, the table is for %%dx%%d" % [M, S, S])
+        _accept_table(who, table, S, "boards of shape %s, the table is for %%dx%%d" % [M, S, S], name=table_name)
     dev = _policy_params(who, params, P, S)
     t = {"params": params}
     for name, x, dtype, shape in (("boards", boards, torch.int8, lambda M, P: (M, S, S)), ("dice", dice, torch.int8, lambda M, P: (M,))) + more:
@@ -426,6 +426,21 @@ def _fused_table(who, fused, endgame_table):
         raise ValueError("%s: fused=True does not take an endgame_table: the exact-leaf substitution is the staged path's (fused=False)" % who)
 
 
+def _leaf_table_alone(who, leaf_table, endgame_table=None, leaves=1, whole_games=False):
+    """the users' keyword: leaf_table is the one launch of ewn_puct_search_eg, which is neither the staged path's
+    substitution, nor the wide launch, nor whole games -> whether there is one"""
+    if leaf_table is None:
+        return False
+    if endgame_table is not None:
+        raise ValueError("%s: leaf_table does not go with endgame_table: both put exact values at the covered leaves, leaf_table in one "
+                         "launch (ewn_puct_search_eg), endgame_table on the staged path" % who)
+    if leaves > 1:
+        raise ValueError("%s: leaf_table does not go with leaves=%d: ewn_puct_search_wide takes no table (leaves=1)" % (who, leaves))
+    if whole_games:
+        raise ValueError("%s: leaf_table does not go with whole_games=True: ewn_puct_selfplay takes no table" % who)
+    return True
+
+
 def _puct_scratch(c, nb, S, dev, fused):
     """a search's scratch for c observations: (tree, leaf boards, leaf dice, leaf actions, logits, value); fused: the tree alone"""
     tree = torch.empty((c, nb), dtype=torch.uint8, device=dev)
@@ -461,28 +476,45 @@ def puct_search(boards, dice, params, sims, c_puct=1.5, terminal_value=1.0, root
     lib = _lib.load()
     sims = _puct_numbers(who, sims, c_puct, terminal_value)
     eps = 0.0 if root_noise is None else _noise_eps(who, noise_eps)
-    if rounds is not None and not (isinstance(rounds, (int, np.integer)) and int(rounds) >= 0):
-        raise ValueError("%s: rounds must be None or an integer that is not negative, got %r" % (who, rounds))
+    rounds = _rounds(who, rounds, sims)
     M, S, L, dev, t = _network_inputs(who, boards, dice, params, cube_layer, optional=(
         ("root_noise", root_noise, torch.float32, lambda M, P: (M, 6)),))
     _same_gpu(who, dev, "params", t.items())
-    if out is None:
-        out = torch.empty((M, int(lib.ewn_puct_tree_bytes(S, L, sims))), dtype=torch.uint8, device=dev)
-    else:
-        _holds_trees(who, "out", out, _puct_tree(who, out, S, sims, cube_layer)[0], M, dev)
+    out = _search_out(who, lib, out, M, S, L, sims, dev)
     with torch.cuda.device(dev):
-        check(lib.ewn_puct_search(S, L, M, sims, -1 if rounds is None else min(int(rounds), sims + 1), C.c_float(float(c_puct)),
+        check(lib.ewn_puct_search(S, L, M, sims, rounds, C.c_float(float(c_puct)),
                                   C.c_float(float(terminal_value)), _ptr(t["boards"]), _ptr(t["dice"]), _ptr(params), _ptr(t["root_noise"]),
                                   C.c_float(eps), _ptr(out), _stream()), "ewn_puct_search")
     return out
 
 
-def _puct_search(lib, S, L, n, sims, b, d, params, cp, tv, table, scratch, st, noise=None, eps=0.0, fused=False, leaves=1):
+def _rounds(who, rounds, sims):
+    """rounds= of a whole search as the entries take it: -1 for all sims + 1"""
+    if rounds is not None and not (isinstance(rounds, (int, np.integer)) and int(rounds) >= 0):
+        raise ValueError("%s: rounds must be None or an integer that is not negative, got %r" % (who, rounds))
+    return -1 if rounds is None else min(int(rounds), sims + 1)
+
+
+def _search_out(who, lib, out, M, S, L, sims, dev):
+    """out= of a whole search: None -> new trees; else the checked contiguous, 4-byte aligned uint8 tensor [M, tree_bytes] on dev"""
+    if out is None:
+        return torch.empty((M, int(lib.ewn_puct_tree_bytes(S, L, sims))), dtype=torch.uint8, device=dev)
+    _holds_trees(who, "out", out, _puct_tree(who, out, S, sims, L)[0], M, dev)
+    return out
+
+
+def _puct_search(lib, S, L, n, sims, b, d, params, cp, tv, table, scratch, st, noise=None, eps=0.0, fused=False, leaves=1, exact=False):
     """predict_puct's and selfplay_puct's search of n observations on the caller's scratch: begin, then sims + 1 rounds of
     ewn_predict_policy and advance.  noise (float32 [n, 6]): the first round, which evaluates the roots, is the noise instance's.
     fused: the one launch of ewn_puct_search instead -- the same bytes in the tree; of the scratch only the tree is used.
-    leaves > 1: the one launch of ewn_puct_search_wide, whatever fused says -- another tree, in fewer rounds"""
+    leaves > 1: the one launch of ewn_puct_search_wide, whatever fused says -- another tree, in fewer rounds.
+    exact: `table` goes to the one launch of ewn_puct_search_eg, whatever fused says -- the staged search with the
+    table, but for the sign of a zero"""
     tree, lb, ld, la, lg, lv = scratch[:6]
+    if exact:
+        from .puct_exact import _launch
+        _launch(lib, S, L, n, sims, -1, cp, tv, b, d, params, noise, eps, 0, 0, table, tree, None, st)
+        return
     if leaves > 1:
         from .wide import _launch
         _launch(lib, S, L, n, sims, leaves, cp, tv, b, d, params, noise, eps, 0, 0, tree, scratch[6], st)
@@ -506,7 +538,7 @@ def _puct_search(lib, S, L, n, sims, b, d, params, cp, tv, table, scratch, st, n
 
 
 def predict_puct(boards, dice, params, sims=64, c_puct=1.5, terminal_value=1.0, return_visits=False, return_q=False, return_value=False,
-                 cube_layer=3, chunk=1024, endgame_table=None, fused=False, leaves=1):
+                 cube_layer=3, chunk=1024, endgame_table=None, fused=False, leaves=1, leaf_table=None):
     """What the trained actor-critic plays after a PUCT search of `sims` simulations on its own two heads: the policy
     head says where to look, the value head what a leaf is worth, a move that wins on the board is worth +1 and is played; the
     opponent's and the agent's later dice are chance nodes sampled in a fixed stratified order, so the search is deterministic.
@@ -521,29 +553,35 @@ def predict_puct(boards, dice, params, sims=64, c_puct=1.5, terminal_value=1.0, 
     results bit for bit, and no leaf-row scratch; not together with endgame_table (the exact leaves stay on the staged path).
     leaves: 1 is all of the above; 2..32: each chunk's search is the one launch of ewn_puct_search_wide, which collects
     up to that many leaves per tree and round under a virtual loss -- about sims / leaves rounds, another tree and so other
-    results than leaves=1, whatever fused says; not together with endgame_table."""
+    results than leaves=1, whatever fused says; not together with endgame_table.
+    leaf_table (an EndgameTable of the boards' size on the same GPU): endgame_table's exact leaves with each chunk's
+    search in the one launch of ewn_puct_search_eg and no leaf-row scratch -- the staged search's results in every value (a zero may
+    differ in its sign); fused is not read; not together with endgame_table or leaves > 1."""
     who = "predict_puct"
     lib = _lib.load()
     sims = _puct_numbers(who, sims, c_puct, terminal_value)
     _fused_table(who, fused, endgame_table)
     from .wide import _NO_TABLE, _leaves_alone
     leaves = _leaves_alone(who, leaves, endgame_table=(endgame_table is not None, _NO_TABLE))
+    exact = _leaf_table_alone(who, leaf_table, endgame_table, leaves)
     _at_least_one(who, "chunk", chunk)
-    M, S, L, dev, t = _network_inputs(who, boards, dice, params, cube_layer, table=endgame_table)
+    M, S, L, dev, t = _network_inputs(who, boards, dice, params, cube_layer, table=leaf_table if exact else endgame_table,
+                                      table_name="leaf_table" if exact else "endgame_table")
     _same_gpu(who, dev, "params", t.items())
     b, d = t["boards"], t["dice"]
     acts = torch.zeros((M, 2), dtype=torch.int8, device=dev)
     visits = torch.zeros((M, 2, 3), dtype=torch.int32, device=dev) if return_visits else None
     q = torch.zeros((M, 2, 3), dtype=torch.float32, device=dev) if return_q else None
     val = torch.zeros(M, dtype=torch.float32, device=dev) if return_value else None
-    c, scratch, cp, tv = _search_setup(lib, S, L, M, sims, chunk, c_puct, terminal_value, dev, fused, leaves)
+    c, scratch, cp, tv = _search_setup(lib, S, L, M, sims, chunk, c_puct, terminal_value, dev, fused or exact, leaves)
     tree = scratch[0]
     with torch.cuda.device(dev):
         st = _stream()
         for i in range(0, M, c):
             n = min(c, M - i)
             sl = slice(i, i + n)
-            _puct_search(lib, S, L, n, sims, b[sl], d[sl], params, cp, tv, endgame_table, scratch, st, fused=fused, leaves=leaves)
+            _puct_search(lib, S, L, n, sims, b[sl], d[sl], params, cp, tv, leaf_table if exact else endgame_table, scratch, st, fused=fused,
+                         leaves=leaves, exact=exact)
             check(lib.ewn_puct_result(S, L, n, _ptr(tree), _ptr(acts[sl]), _ptr(None if visits is None else visits[sl]),
                                       _ptr(None if q is None else q[sl]), _ptr(None if val is None else val[sl]), st), "ewn_puct_result")
     return _outputs(acts, visits, q, val)
@@ -639,7 +677,7 @@ def selfplay_noise(M, noise_alpha, key, game_offset, ply, device="cuda"):
 
 def selfplay_puct(boards, dice, params, sims=64, max_plies=None, c_puct=1.5, terminal_value=1.0, noise_eps=0.25, noise_alpha=1.0,
                   temp_plies=8, key=0, game_offset=0, chunk=1024, check_every=8, endgame_table=None, cube_layer=3, fused=False,
-                  leaves=1):
+                  leaves=1, leaf_table=None):
     """M games of the PUCT search against itself, from the given positions to the end: per ply puct_begin, sims + 1
     rounds of ewn_predict_policy and advance -- the first with Dirichlet(noise_alpha) noise of weight noise_eps on the root's priors
     (ewn_puct_advance_noise) -- then ewn_puct_play into row t: the move is drawn in proportion to the visits for the first
@@ -651,6 +689,8 @@ def selfplay_puct(boards, dice, params, sims=64, max_plies=None, c_puct=1.5, ter
     fused=True: a ply's search is the one launch of ewn_puct_search, the records are the same bit for bit; not
     together with endgame_table.  leaves: 1 is all of the above; 2..32: a ply's search is the one launch of
     ewn_puct_search_wide with that ply's noise rows -- other trees, so other games; not together with endgame_table.
+    leaf_table: predict_puct's -- endgame_table's exact leaves with a ply's search in the one launch of
+    ewn_puct_search_eg; fused is not read; not together with endgame_table or leaves > 1.
     The noise is selfplay_noise: torch._standard_gamma keyed by key, the ply and the global game game_offset + m, drawn once per ply
     for all M games and read by each chunk's rows: a call repeats itself bit for bit, whatever the chunk, and the calls on the shards
     of M games (game_offset moved to each shard's first game) give the rows of the one call on all of them.  Returns a dict: board int8 [T, M, S, S], dice int8
@@ -662,21 +702,23 @@ def selfplay_puct(boards, dice, params, sims=64, max_plies=None, c_puct=1.5, ter
     _fused_table(who, fused, endgame_table)
     from .wide import _NO_TABLE, _leaves_alone
     leaves = _leaves_alone(who, leaves, endgame_table=(endgame_table is not None, _NO_TABLE))
+    exact = _leaf_table_alone(who, leaf_table, endgame_table, leaves)
     eps = _noise_eps(who, noise_eps)
     temp_plies, key, game_offset = _play_numbers(who, temp_plies, key, game_offset)
     _positive(who, "noise_alpha", noise_alpha)
     if int(chunk) < 1 or int(check_every) < 1:
         raise ValueError("%s: chunk and check_every must be at least 1, got %r and %r" % (who, chunk, check_every))
-    M, S, L, dev, inputs = _network_inputs(who, boards, dice, params, cube_layer, table=endgame_table)
+    M, S, L, dev, inputs = _network_inputs(who, boards, dice, params, cube_layer, table=leaf_table if exact else endgame_table,
+                                           table_name="leaf_table" if exact else "endgame_table")
     T = SELFPLAY_MAX_PLIES[S] if max_plies is None else max_plies
     if not (isinstance(T, (int, np.integer)) and int(T) >= 1):
         raise ValueError("%s: max_plies must be a positive integer or None, got %r" % (who, max_plies))
     T = int(T)
     _same_gpu(who, dev, "params", inputs.items())
-    b, d, table = inputs["boards"], inputs["dice"], endgame_table
+    b, d, table = inputs["boards"], inputs["dice"], leaf_table if exact else endgame_table
     rec = {name: torch.zeros((T, M) + shape(S), dtype=dt, device=dev) for name, dt, shape in _PLAY_ROWS}
     game = torch.zeros((M, 4), dtype=torch.int32, device=dev)
-    c, scratch, cp, tv = _search_setup(lib, S, L, M, sims, chunk, c_puct, terminal_value, dev, fused, leaves)
+    c, scratch, cp, tv = _search_setup(lib, S, L, M, sims, chunk, c_puct, terminal_value, dev, fused or exact, leaves)
     with torch.cuda.device(dev):
         st = _stream()
         drawn = []
@@ -689,7 +731,7 @@ def selfplay_puct(boards, dice, params, sims=64, max_plies=None, c_puct=1.5, ter
                     if t == len(drawn):                        # a ply's noise is drawn once, for all M games: later chunks read their rows
                         drawn.append(selfplay_noise(M, noise_alpha, key, game_offset, t, dev))
                     noise = drawn[t][i:i + n]
-                _puct_search(lib, S, L, n, sims, cb, cd, params, cp, tv, table, scratch, st, noise, eps, fused, leaves)
+                _puct_search(lib, S, L, n, sims, cb, cd, params, cp, tv, table, scratch, st, noise, eps, fused, leaves, exact)
                 check(lib.ewn_puct_play(S, L, n, _ptr(scratch[0]), _ptr(cb), _ptr(cd), _ptr(cg), temp_plies, C.c_uint64(key),
                                         C.c_int64(game_offset + i), *[_ptr(rec[name][t, i:i + n]) for name, _, _ in _PLAY_ROWS], st),
                       "ewn_puct_play")

@@ -81,7 +81,8 @@ def _policy(spec, cube_layer, key):
         return PuctAgent(spec["model"], board_size=_model_size(spec), cube_layer=cube_layer, sims=spec.get("sims", 64),
                          c_puct=spec.get("c_puct", 1.5), terminal_value=spec.get("terminal_value", 1.0),
                          endgame_table=spec.get("endgame_table"), fused=spec.get("fused", False),   # fused: one launch (4r)
-                         leaves=spec.get("leaves", 1)).policy_fn()                                  # leaves > 1: the wide launch (4u)
+                         leaves=spec.get("leaves", 1),                                              # leaves > 1: the wide launch (4u)
+                         leaf_table=spec.get("leaf_table")).policy_fn()                             # exact leaves in one launch (4w)
     if kind == "endgame":       # the exact move where the endgame table covers the position, the "fallback" spec's policy elsewhere
         from classical_policies.model import EndgameAgent
         if "table" not in spec or "fallback" not in spec:
@@ -184,7 +185,7 @@ def evaluate(agent, opponent, num=1024, board_size=5, cube_layer=3, rng="mt19937
              use_rollout=True, chunk=16):
     """agent: a dict like the opponent's, {"kind": "mlp", "model": a2c.ActorCritic} (its deterministic policy),
     {"kind": "mlp_lookahead", "model": ..., terminal_value=, plies=} (its lookahead on its own value net, ply by ply),
-    {"kind": "mlp_puct", "model": ..., sims=, c_puct=, terminal_value=} (its PUCT search on both of its heads, ply by ply),
+    {"kind": "mlp_puct", "model": ..., sims=, c_puct=, terminal_value=, leaf_table=} (its PUCT search on both of its heads, ply by ply),
     {"kind": "endgame", "table": an EndgameTable or its path, "fallback": any of these dicts} (the exact move where the table covers
     the position, the fallback's elsewhere, ply by ply),
     {"kind": "playout_search", sims=, playouts=, c_puct=, endgame_table=} (the same tree without a network: uniform priors, random playouts at the
@@ -368,7 +369,7 @@ def load_policy(path, board_size=5, cube_layer=3, device="cuda"):
 
 def evaluate_model(model, names=("random", "minimax"), num=1024, max_depth=5, num_simulations=10, num_env_copies=5, board_size=5,
                    cube_layer=3, heuristic="hybrid", rng="mt19937", lookahead=False, endgame_table=None, puct=None,
-                   endgame_leaves=False, fused=False, leaves=1):
+                   endgame_leaves=False, fused=False, leaves=1, puct_table=None):
     """eval_A2C.py's loop: the model's deterministic policy against every listed opponent; lookahead (1 / True, or 2): and, beside
     each, its lookahead policy of that many moves ({"kind": "mlp_lookahead", "plies": ...}) on the same episodes.  endgame_table (an
     EndgameTable or its path): every agent plays the exact move where the table covers the position ({"kind": "endgame"}, ply by ply).
@@ -376,10 +377,21 @@ def evaluate_model(model, names=("random", "minimax"), num=1024, max_depth=5, nu
     fused (with puct): that search as one launch per move (ewn_puct_search): the same moves, so the same rows.
     leaves (with puct; 2..32): that search with up to so many leaves per tree and round (ewn_puct_search_wide): fewer
     rounds per move, other trees, so other rows.
+    puct_table (with puct, leaves 1 and no endgame_table; an EndgameTable or its path): beside each puct row, the same search with the
+    table's exact values at the leaves it covers, one launch per move (ewn_puct_search_eg), "puct(SIMS) + exact leaves vs ..."
     endgame_leaves (with lookahead and endgame_table): the table is not laid over the agents' moves; beside the lookahead's row
     stands the same lookahead with the table's exact values at the leaves it covers, "lookahead + exact leaves vs ..." """
     if endgame_leaves and (endgame_table is None or not lookahead):
         raise ValueError("evaluate_model: endgame_leaves goes with lookahead and an endgame_table")
+    if puct_table is not None:
+        if puct is None or endgame_table is not None:
+            raise ValueError("evaluate_model: puct_table goes with puct and without endgame_table")
+        from .endgame import EndgameTable, _accept_table
+        from .search import _leaf_table_alone
+        from .wide import _leaves
+        _leaf_table_alone("evaluate_model", puct_table, None, _leaves("evaluate_model", leaves))
+        puct_table = _accept_table("evaluate_model", puct_table, board_size, "the table is for %%dx%%d boards, the evaluation is on %dx%d" % (
+            board_size, board_size), name="puct_table", load=EndgameTable.load)       # loaded once
     if endgame_table is not None:       # loaded once
         from .endgame import EndgameTable
         endgame_table = endgame_table if isinstance(endgame_table, EndgameTable) else EndgameTable.load(endgame_table)
@@ -394,6 +406,8 @@ def evaluate_model(model, names=("random", "minimax"), num=1024, max_depth=5, nu
         agents = [("endgame+" + label, {"kind": "endgame", "table": endgame_table, "fallback": spec}) for label, spec in agents]
     elif puct is not None:
         agents.append(("puct(%d)" % int(puct), {"kind": "mlp_puct", "model": model, "sims": int(puct), "fused": bool(fused), "leaves": leaves}))
+        if puct_table is not None:
+            agents.append(("puct(%d) + exact leaves" % int(puct), {"kind": "mlp_puct", "model": model, "sims": int(puct), "leaf_table": puct_table}))
     table = {}
     for o in names:
         opp = _classical_spec(o, max_depth, heuristic, num_simulations, num_env_copies)
@@ -428,6 +442,10 @@ def _parser():
     ap.add_argument("--leaves", type=int, default=1, metavar="N",
                     help="with --puct: up to N leaves per tree and round in one kernel launch per move (ewn_puct_search_wide): about "
                          "SIMS / N rounds instead of SIMS + 1; another tree than N = 1, so not always the same moves")
+    ap.add_argument("--puct_table", default=None, metavar="PATH",
+                    help="with --puct (and --leaves 1): a saved EndgameTable; beside each puct row, the same search with the table's "
+                         "exact values at the leaves it covers, one launch per move (ewn_puct_search_eg), rows \"puct(SIMS) + exact "
+                         "leaves vs ...\"")
     ap.add_argument("--endgame_table", default=None,
                     help="with --model: a saved EndgameTable; the model (and its --lookahead) plays the exact move wherever the table "
                          "covers the position")
@@ -458,6 +476,8 @@ def main():
         ap.error("--fused goes with --puct")
     if a.leaves != 1 and (a.puct is None or not 1 <= a.leaves <= 32):
         ap.error("--leaves goes with --puct and takes 1..32")
+    if a.puct_table and (a.puct is None or a.leaves != 1):
+        ap.error("--puct_table goes with --puct and --leaves 1")
     if a.endgame_table and (a.model is None or a.opponent_model is not None):
         ap.error("--endgame_table goes with --model and the classical opponents of --agents")
     if a.endgame_leaves and not (a.endgame_table and a.lookahead):
@@ -478,7 +498,7 @@ def main():
         model = load_policy(a.model, a.board_size, a.cube_layer)
         t = evaluate_model(model, a.agents, a.num, a.max_depth, a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer,
                            a.heuristic, a.rng, lookahead=a.lookahead or False, endgame_table=a.endgame_table, puct=a.puct,
-                           endgame_leaves=a.endgame_leaves, fused=a.fused, leaves=a.leaves)
+                           endgame_leaves=a.endgame_leaves, fused=a.fused, leaves=a.leaves, puct_table=a.puct_table)
     else:
         t = tournament(a.agents, a.num, a.max_depth, a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer,
                        a.heuristic, a.rng, sims=a.sims, playouts=a.playouts, c_puct=a.c_puct, playout_table=a.playout_table)

@@ -57,6 +57,10 @@ def _parser():
                     help="SEARCH: a saved EndgameTable; the search's q is replaced by the exact one wherever the table covers the position")
     ap.add_argument("--endgame_leaves", action="store_true",
                     help="SEARCH with --endgame_table: the search also values every leaf that the table covers by the table (DESIGN.md 4p)")
+    ap.add_argument("--puct_table", default=None, metavar="PATH",
+                    help="SELFPLAY: a saved EndgameTable; a leaf of the search that it covers is worth its exact value, a ply's search "
+                         "stays one kernel launch (ewn_puct_search_eg, DESIGN.md 4w); --fused is then not read; not with --endgame_table, "
+                         "--leaves above 1 or --whole_games")
     ap.add_argument("--batch_size", "-b", type=int, default=None,
                     help="PPO: minibatch size in samples of the n_steps x lanes rollout buffer (default: a quarter of it; train.py:178-183)")
     ap.add_argument("--n_epochs", type=int, default=10, help="PPO: passes over the rollout buffer per update (SB3 default)")
@@ -133,6 +137,11 @@ def main():
         raise SystemExit("--whole_games is read by SELFPLAY only")
     if a.whole_games and a.endgame_leaves:
         raise SystemExit("--whole_games does not go with --endgame_leaves: the exact-leaf substitution is the staged search's")
+    if a.puct_table is not None and a.algorithm != "SELFPLAY":
+        raise SystemExit("--puct_table is read by SELFPLAY only")
+    if a.puct_table is not None and (a.endgame_table is not None or a.leaves != 1 or a.whole_games):
+        raise SystemExit("--puct_table does not go with --endgame_table, --leaves above 1 or --whole_games: it is the one launch of the "
+                         "search with exact leaves")
     if a.endgame_table is not None and a.algorithm not in ("SEARCH", "SELFPLAY"):
         raise SystemExit("--endgame_table is read by SEARCH and SELFPLAY only")
     if a.endgame_leaves and (a.algorithm not in ("SEARCH", "SELFPLAY") or a.endgame_table is None):
@@ -170,7 +179,7 @@ def main():
         trainer = PuctSelfPlayTrainer(env, sims=a.sims, c_puct=a.c_puct, terminal_value=a.terminal_value, noise_eps=a.noise_eps,
                                       noise_alpha=a.noise_alpha, temp_plies=a.temp_plies, max_plies=a.max_plies,
                                       learning_rate=a.learning_rate, seed=mseed, endgame_table=a.endgame_table, fused=a.fused,
-                                      whole_games=a.whole_games, leaves=a.leaves)
+                                      whole_games=a.whole_games, leaves=a.leaves, leaf_table=a.puct_table)
     elif a.trainer == "fused" or model_opp is not None or (a.trainer == "auto" and env.supports_policy_rollout()):
         trainer = FusedA2CTrainer(env, n_steps=a.n_steps, learning_rate=a.learning_rate, seed=mseed, **okw)
     else:

@@ -38,6 +38,15 @@ _NO_TABLE = "the exact-leaf substitution is the staged path's (leaves=1, fused=F
 _NO_WHOLE_GAMES = "ewn_puct_selfplay evaluates one leaf per tree and round (leaves=1)"
 
 
+def _tile_and_blocks(who, tile, blocks, most, leaves, max_blocks):
+    """tile= and blocks= of a search on 32-column tiles as the entries take them: 0 for the library's choice"""
+    if tile is not None and not (isinstance(tile, (int, np.integer)) and 1 <= int(tile) <= most):
+        raise ValueError("%s: tile must be None or an integer in 1..%d (32 columns, %d a tree), got %r" % (who, most, leaves, tile))
+    if blocks is not None and not (isinstance(blocks, (int, np.integer)) and 1 <= int(blocks) <= max_blocks):
+        raise ValueError("%s: blocks must be None or an integer in 1..%d, got %r" % (who, max_blocks, blocks))
+    return 0 if tile is None else int(tile), 0 if blocks is None else int(blocks)
+
+
 def _wide_scratch(lib, S, L, n, sims, dev):
     """the marks of a wide search of n observations: what it holds does not matter"""
     return torch.empty(int(check(lib.ewn_puct_search_wide_scratch_bytes(S, L, n, sims), "ewn_puct_search_wide_scratch_bytes")),
@@ -65,11 +74,7 @@ def puct_search_wide(boards, dice, params, sims, leaves, c_puct=1.5, terminal_va
     sims = _puct_numbers(who, sims, c_puct, terminal_value)
     leaves = _leaves(who, leaves)
     eps = 0.0 if root_noise is None else _noise_eps(who, noise_eps)
-    most = PUCT_WIDE_MAX_LEAVES // leaves
-    if tile is not None and not (isinstance(tile, (int, np.integer)) and 1 <= int(tile) <= most):
-        raise ValueError("%s: tile must be None or an integer in 1..%d (32 columns, %d a tree), got %r" % (who, most, leaves, tile))
-    if blocks is not None and not (isinstance(blocks, (int, np.integer)) and 1 <= int(blocks) <= PUCT_WIDE_MAX_BLOCKS):
-        raise ValueError("%s: blocks must be None or an integer in 1..%d, got %r" % (who, PUCT_WIDE_MAX_BLOCKS, blocks))
+    tile, blocks = _tile_and_blocks(who, tile, blocks, PUCT_WIDE_MAX_LEAVES // leaves, leaves, PUCT_WIDE_MAX_BLOCKS)
     M, S, L, dev, t = _network_inputs(who, boards, dice, params, cube_layer, optional=(
         ("root_noise", root_noise, torch.float32, lambda M, P: (M, 6)),))
     _same_gpu(who, dev, "params", t.items())
@@ -79,6 +84,5 @@ def puct_search_wide(boards, dice, params, sims, leaves, c_puct=1.5, terminal_va
         _holds_trees(who, "out", out, _puct_tree(who, out, S, sims, cube_layer)[0], M, dev)
     with torch.cuda.device(dev):
         _launch(lib, S, L, M, sims, leaves, C.c_float(float(c_puct)), C.c_float(float(terminal_value)), t["boards"], t["dice"], params,
-                t["root_noise"], eps, 0 if tile is None else int(tile), 0 if blocks is None else int(blocks), out,
-                _wide_scratch(lib, S, L, M, sims, dev), _stream())
+                t["root_noise"], eps, tile, blocks, out, _wide_scratch(lib, S, L, M, sims, dev), _stream())
     return out
