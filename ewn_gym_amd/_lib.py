@@ -40,6 +40,7 @@ EXPORTS_PLAYOUT_SEARCH = ["ewn_playout_search"]   # include/ewn_playout_search.h
 EXPORTS_PUCT_WIDE = ["ewn_puct_search_wide_scratch_bytes", "ewn_puct_search_wide"]   # include/ewn_puct_wide.h
 EXPORTS_PLAYOUT_SEARCH_EG = ["ewn_playout_search_eg"]   # include/ewn_playout_search_eg.h
 EXPORTS_PUCT_EXACT = ["ewn_puct_search_eg"]   # include/ewn_puct_exact.h
+EXPORTS_PUCT_GAMES_EXACT = ["ewn_puct_selfplay_eg"]   # include/ewn_puct_games_exact.h
 AGENT = {"random": 0, "minimax": 1, "sample": 2, "mlp": 3}   # "mlp": the trained policy, through ewn_step_k_policy   # "sample": env.action_space.sample(), all six actions (EWN_AGENT_SAMPLE)
 AGENT_MCTS = 4   # ewn_agent.kind of the MCTS agent (ewn_step_k_agent only; ewn_step_k does not take it)
 
@@ -200,6 +201,8 @@ def load():
         "ewn_puct_search_wide": (i32, [i32, i32, i32, i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, C.c_float, i32, i32, vp, vp, vp]),
         "ewn_puct_search_eg": (i32, [i32, i32, i32, i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, C.c_float, i32, i32, i32, i32, vp, vp, vp,
                                 vp]),
+        "ewn_puct_selfplay_eg": (i32, [i32, i32, i32, i32, i32, C.c_float, C.c_float, vp, vp, C.c_float, i32, C.c_uint64, C.c_int64, i32, i32,
+                                  vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

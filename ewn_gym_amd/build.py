@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 SRC = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".hip")]
 DEPS = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + [os.path.join(HERE, "..", "include", h)
                                                                     for h in ("ewn_hip.h", "ewn_playout_search.h", "ewn_playout_search_eg.h",
-                                                                              "ewn_puct_wide.h", "ewn_puct_exact.h")]
+                                                                              "ewn_puct_wide.h", "ewn_puct_exact.h", "ewn_puct_games_exact.h")]
 OUT = os.path.join(HERE, "lib", "libewn_hip.so")
 OBJ = os.path.join(HERE, "lib", "obj")
 # -ffp-contract=off: the fp64 heuristic and expectation sums must round exactly like the

@@ -1,7 +1,7 @@
 // ewn_endgame.hpp -- the one copy of how an endgame table (layout version 1, ewn_endgame.hip's header comment) is indexed, for the
 // units that read one: ewn_endgame.hip (the build and the lookup), ewn_predict_lookahead.hip (covered leaves),
-// ewn_playout_search.hip (covered leaves of the playout tree search) and ewn_puct_fused.hip (covered leaves of the
-// one-launch PUCT search).
+// ewn_playout_search.hip (covered leaves of the playout tree search), ewn_puct_fused.hip (covered leaves of the
+// one-launch PUCT search) and ewn_puct_games.hip (the same leaves in whole self-play games).
 #pragma once
 #include "ewn_lookahead.hpp"
 

@@ -31,7 +31,33 @@
 //     any is read, and every record row 0 .. max_plies - 1 of every game is written (rows below the ply a game enters with: zeros).
 //   Independence from the layout.  Which column or block plays a game changes no bit of its records: a column's network outputs
 //     depend on that column alone, and a game's record on its inputs, key, game_offset + m and its noise rows only.
+//
+// The table instances, k_puct_selfplay<S, NOISE, true> (C ABI: ewn_puct_selfplay_eg, include/ewn_puct_games_exact.h): a
+// ply's search is k_puct_search<S, NOISE, true>'s (ewn_puct_fused.hip), so a game's records are, byte for byte, what
+// selfplay_puct(leaf_table=)'s ply loop leaves: per ply ewn_puct_search_eg and ewn_puct_play.  A pending leaf that the table covers is
+// worth fl(terminal_value * q) at the first maximum of the six q under a strict >, in place of the value head's output.
+//   search, between a round's two barriers: while wave 0 and wave 1 run the networks, waves 2 .. 7 look the block's columns up, column
+//            k on wave 2 + k % 6, exactly as k_puct_search's table instances do: the ballot on the slot's non-empty cells against
+//            max_total, eg_position, six eg_move on lanes 0 .. 5 with la_find / la_dice, the fold in action order, one rounding;
+//            lane 0 writes (exact, covered) of column k into LDS words of the instance's own behind PugGeo<S>'s regions.  After the
+//            barrier the tree's wave hands pu_round the exact value's address in place of the value head's where covered.  A column
+//            without a game, and a tree without a pending leaf, shows a zero board: no cube, not covered.
+//   leaf_counts (may be NULL): per game {rounds the table valued, rounds the value head valued}, summed over the plies played here.
+//            Two 32-bit LDS words per column behind the exact values (a game can pass 65 535), zeroed by wave 0 when the column
+//            takes a game, added to by lane 0 of the tree's wave every round, and stored by that lane when the column gives its game
+//            up; a game that is not played gets two zeros from wave 0 on the zero-rows path.  A column's words are written and read
+//            by one lane, but for wave 0's zeros, which a block barrier separates from the rounds.
+// Every rule above holds for these instances as it stands: the phases are block-uniform and the barriers stand where they stood; a
+// column stays on one wave for the whole launch (a looking-up wave reads the column's slot and dice in LDS, written before the
+// round's first barrier, and the table, and touches no tree); the hand-over rule; pu_round's and pu_play's range checks; every byte
+// of a tree and of every record row, and every element of leaf_counts, written before it is read; no atomics, vector stores only,
+// plain C++.  The table is only read, with indices that eg_move's own arguments keep inside it: the coverage test comes first, and a
+// move never adds a cube.  The instance's own arguments (the table, leaf_counts, terminal_value, EgGeo by value) travel in a struct
+// at the END of the kernel's arguments, empty in the plain instances, whose LDS, registers and instructions are what they were; the
+// larger LDS size has its own static_assert against POL_LDS_MAX.
 #include "ewn_puct.hpp"
+#include "ewn_endgame.hpp"
+#include "../../include/ewn_puct_games_exact.h"
 
 #define PUG_NT 512           // threads per block: eight waves (two per SIMD, up to 256 VGPRs each)
 #define PUG_NW (PUG_NT / 64)
@@ -61,6 +87,13 @@ struct PugBuf {
     PuRecord rec; uint8_t *scratch;                            // rec: rows [max_plies][M], row ply * M + m is game m's ply
 };
 
+// the table instances' own arguments; the plain instances carry an empty struct.  Their LDS, behind the plain instances': exact [32]
+// floats | covered [32] words | the columns' leaf counts [32][2] words
+template <bool EG> struct PugEg {};
+template <> struct PugEg<true> { const float *tbl; int *counts; float tv; EgGeo g; };
+#define PUG_EG_LDS (4 * PUG_TILE * 4)
+#define PUG_NLOOK (PUG_NW - 2)   // the waves that look columns up while waves 0 and 1 run the networks
+
 // zeros into rows t0 .. t1 - 1 of game m, by one wave
 template <int CELLS>
 EWN_DEV void pug_zero_rows(const PuRecord &R, int M, int m, int t0, int t1, int lane)
@@ -80,9 +113,9 @@ EWN_DEV void pug_zero_rows(const PuRecord &R, int M, int m, int t0, int t1, int 
 }
 
 // tile: the columns of a block, 1 .. PUG_TILE; the grid's blocks share the M games (M >= 1, gridDim.x <= ceil(M / tile))
-template <int S, bool NOISE>
+template <int S, bool NOISE, bool EG = false>
 __global__ __launch_bounds__(PUG_NT, 1) void k_puct_selfplay(int M, int sims, int max_plies, int tile, int temp_plies, float c_puct, float inv_tv,
-                                                             u32 k0, u32 k1, long long game_offset, PuLayout L, PugBuf B)
+                                                             u32 k0, u32 k1, long long game_offset, PuLayout L, PugBuf B, PugEg<EG> E)
 {
     using P = PugGeo<S>;
     using Q3 = Mlp3Geo<S>;
@@ -120,11 +153,18 @@ __global__ __launch_bounds__(PUG_NT, 1) void k_puct_selfplay(int M, int sims, in
                     const int ply = __builtin_amdgcn_readfirstlane(g[0]), over = __builtin_amdgcn_readfirstlane(g[1]);
                     if (over != 0 || ply < 0 || ply >= max_plies) {   // not played: its rows are zeros
                         pug_zero_rows<CELLS>(B.rec, M, cand, 0, max_plies, lane);
+                        if constexpr (EG) {                    // ... and so are its counts
+                            if (E.counts && lane < 2) E.counts[2 * (size_t)cand + lane] = 0;
+                        }
                         continue;
                     }
                     pug_zero_rows<CELLS>(B.rec, M, cand, 0, ply, lane);
                     m = cand;
                     if (lane == 0) { sgame[k] = cand; sply[k] = ply; }
+                    if constexpr (EG) {                        // the column's counts start with its game
+                        int *scnt = (int *)(lds + P::lds_bytes()) + 2 * PUG_TILE;
+                        if (lane == 0) { scnt[2 * k] = 0; scnt[2 * k + 1] = 0; }
+                    }
                 }
                 held |= m >= 0;
             }
@@ -167,6 +207,37 @@ __global__ __launch_bounds__(PUG_NT, 1) void k_puct_selfplay(int M, int sims, in
                     if (h == 0) sval[j] = vo[0];
                 }
             }
+            if constexpr (EG) {
+                // ---- the lookups, under the networks: column k by wave 2 + k % PUG_NLOOK, all 64 lanes on the one slot (k_puct_search's)
+                float *sex = (float *)(lds + P::lds_bytes());
+                int *scov = (int *)(sex + PUG_TILE);
+                const int w2 = __builtin_amdgcn_readfirstlane(wave) - 2;
+                if (w2 >= 0) {                                 // wave-uniform
+                    #pragma unroll 1
+                    for (int k = w2; k < tile; k += PUG_NLOOK) {
+                        const int8_t *leaf = slots + k * STR;
+                        // more cubes on the row than a table position has: not covered whatever else (eg_position counts every cell
+                        // that is not empty, or refuses the row for a value outside -6 .. 6), and the scan is skipped
+                        const int cubes = __builtin_popcountll(__builtin_amdgcn_ballot_w64(lane < CELLS && leaf[lane < CELLS ? lane : 0] != 0));
+                        bool covered = false;                  // wave-uniform: every lane scans the same row
+                        float exact = 0.0f;
+                        if (cubes <= E.g.T) {
+                            int Ma, Mo, na, no;
+                            u64 pa, po;
+                            covered = __builtin_amdgcn_readfirstlane((int)eg_position<S>(leaf, E.g.K, E.g.T, Ma, Mo, na, no, pa, po)) != 0;
+                            if (covered) {
+                                float q = -__builtin_inff();
+                                if (lane < 6) q = eg_move<S>(E.tbl, E.g, Ma, Mo, pa, po, la_find(lane / 3, la_dice((int)sdice[k]), Ma), lane % 3);
+                                float qb = __shfl(q, 0, 64);   // k_endgame_lookup's fold: the first maximum, -0.0 == +0.0
+                                #pragma unroll
+                                for (int i = 1; i < 6; i++) { const float qi = __shfl(q, i, 64); if (qi > qb) qb = qi; }
+                                exact = E.tv * qb;             // one rounding; pu_evaluate forms fl(exact * inv_tv)
+                            }
+                        }
+                        if (lane == 0) { sex[k] = exact; scov[k] = covered ? 1 : 0; }
+                    }
+                }
+            }
             __syncthreads();                                   // logits and value are there; the slots are read
             #pragma unroll 1
             for (int k = wave; k < tile; k += PUG_NW) {
@@ -174,9 +245,18 @@ __global__ __launch_bounds__(PUG_NT, 1) void k_puct_selfplay(int M, int sims, in
                 if (m0 < 0) continue;                          // a column without a game: its slot stays a zero board with dice 1
                 PuNoise Z = { nullptr, 0.0f, 0.0f };
                 if constexpr (NOISE) Z = PuNoise{ B.noise + ((size_t)__builtin_amdgcn_readfirstlane(sply[k]) * (size_t)M + (size_t)m0) * 6, B.eps, B.keep };
+                const PuTree T = pu_tree(B.scratch, tree0 + (size_t)k, L);
+                const float *vp = sval + k;
+                if constexpr (EG) {                            // a covered column holds a position, so its tree has a pending leaf
+                    const float *sex = (const float *)(lds + P::lds_bytes());
+                    int *scnt = (int *)(lds + P::lds_bytes()) + 2 * PUG_TILE;
+                    const bool covered = __builtin_amdgcn_readfirstlane(((const int *)(sex + PUG_TILE))[k]) != 0;
+                    const bool pending = __builtin_amdgcn_readfirstlane(T.hdr[2]) >= 0;
+                    if (lane == 0) { scnt[2 * k] += covered ? 1 : 0; scnt[2 * k + 1] += pending && !covered ? 1 : 0; }
+                    if (covered) vp = sex + k;
+                }
                 // the noise instance is round 0's alone: on later rounds the pending node is never the root, and pu_evaluate asks
-                pu_round<S, NOISE>(pu_tree(B.scratch, tree0 + (size_t)k, L), sims, c_puct, inv_tv, L.nodes, slg + k * 8, sval + k, Z, slots + k * STR,
-                                   sdice + k, lane, base);
+                pu_round<S, NOISE>(T, sims, c_puct, inv_tv, L.nodes, slg + k * 8, vp, Z, slots + k * STR, sdice + k, lane, base);
             }
         }
         __syncthreads();                                       // ---- play: the last round's header and root are handed over
@@ -194,6 +274,10 @@ __global__ __launch_bounds__(PUG_NT, 1) void k_puct_selfplay(int M, int sims, in
             } else {                                           // over, or cut at max_plies: the remaining rows, and the column is free
                 pug_zero_rows<CELLS>(B.rec, M, m0, ply + 1, max_plies, lane);
                 if (lane == 0) sgame[k] = -1;
+                if constexpr (EG) {                            // the game's counts: the lane that added to them stores them
+                    const int *scnt = (const int *)(lds + P::lds_bytes()) + 2 * PUG_TILE;
+                    if (E.counts && lane == 0) { E.counts[2 * m] = scnt[2 * k]; E.counts[2 * m + 1] = scnt[2 * k + 1]; }
+                }
             }
         }
     }
@@ -205,7 +289,18 @@ static int pug_launch(int M, int sims, int max_plies, int tile, int blocks, int 
 {
     const PuLayout L = pu_layout(S, sims);
     return pol_launch_kernel(k_puct_selfplay<S, NOISE>, (unsigned)blocks, PUG_NT, PugGeo<S>::lds_bytes(), 64 * 1024, POL_LDS_MAX, s, M, sims, max_plies,
-                             tile, temp_plies, c_puct, inv_tv, (u32)key, (u32)(key >> 32), (long long)game_offset, L, b);
+                             tile, temp_plies, c_puct, inv_tv, (u32)key, (u32)(key >> 32), (long long)game_offset, L, b, PugEg<false>{});
+}
+
+template <int S, bool NOISE>
+static int pug_launch_eg(int M, int sims, int max_plies, int tile, int blocks, int temp_plies, float c_puct, float inv_tv, uint64_t key,
+                         int64_t game_offset, const PugBuf &b, const PugEg<true> &e, hipStream_t s)
+{
+    constexpr size_t lds = PugGeo<S>::lds_bytes() + PUG_EG_LDS;
+    static_assert(PugGeo<S>::lds_bytes() % 4 == 0 && lds <= POL_LDS_MAX, "the plain instance's LDS and the columns' exact values, flags and counts must fit the CU's LDS");
+    const PuLayout L = pu_layout(S, sims);
+    return pol_launch_kernel(k_puct_selfplay<S, NOISE, true>, (unsigned)blocks, PUG_NT, lds, 64 * 1024, POL_LDS_MAX, s, M, sims, max_plies, tile,
+                             temp_plies, c_puct, inv_tv, (u32)key, (u32)(key >> 32), (long long)game_offset, L, b, e);
 }
 
 // The library's choice where tile or blocks is 0 (DESIGN.md 4s has the measurements): every CU gets a block, and the columns are as
@@ -233,18 +328,31 @@ int64_t ewn_puct_selfplay_scratch_bytes(int board_size, int cube_layer, int M, i
     return pu_layout(board_size, sims).bytes * (long long)tile * (long long)blocks;
 }
 
+// ewn_puct_search's order of refusals up to tile and blocks, for both entries; pointers: every pointer that must be given is.
+// empty: M == 0, which is EWN_OK before anything else is looked at
+static int pug_refuse(int board_size, int cube_layer, int M, int sims, int max_plies, float c_puct, float terminal_value, bool pointers,
+                      const void *scratch, const void *game, int temp_plies, int tile, int blocks, bool &empty)
+{
+    const int rc = pu_refuse(board_size, cube_layer, M);
+    empty = rc == EWN_OK && M == 0;
+    if (rc != EWN_OK || empty) return rc;
+    if (!pointers) return EWN_ENULL;
+    if (sims < 0 || sims > PU_MAX_SIMS || ((uintptr_t)scratch & 3) || ((uintptr_t)game & 3)) return EWN_EINVAL;
+    if (!std::isfinite(terminal_value) || !(terminal_value > 0.0f) || !std::isfinite(c_puct) || c_puct < 0.0f) return EWN_EINVAL;
+    if (max_plies < 1 || temp_plies < 0 || tile < 0 || tile > PUG_TILE || blocks < 0 || blocks > PUG_MAX_BLOCKS) return EWN_EINVAL;
+    return EWN_OK;
+}
+
 // ewn_puct_search's order of refusals, all before the launch; noise_eps is looked at only when noise is given
 int ewn_puct_selfplay(int board_size, int cube_layer, int M, int sims, int max_plies, float c_puct, float terminal_value, const float *params,
                       const float *noise, float noise_eps, int temp_plies, uint64_t key, int64_t game_offset, int tile, int blocks,
                       int8_t *boards, int8_t *dice, int32_t *game, int8_t *rec_board, int8_t *rec_dice, int32_t *rec_visits, float *rec_value,
                       int8_t *rec_action, int8_t *rec_live, void *scratch, void *stream)
 {
-    const int rc = pu_refuse(board_size, cube_layer, M);
-    if (rc != EWN_OK || M == 0) return rc;
-    if (!params || !boards || !dice || !game || !scratch) return EWN_ENULL;
-    if (sims < 0 || sims > PU_MAX_SIMS || ((uintptr_t)scratch & 3) || ((uintptr_t)game & 3)) return EWN_EINVAL;
-    if (!std::isfinite(terminal_value) || !(terminal_value > 0.0f) || !std::isfinite(c_puct) || c_puct < 0.0f) return EWN_EINVAL;
-    if (max_plies < 1 || temp_plies < 0 || tile < 0 || tile > PUG_TILE || blocks < 0 || blocks > PUG_MAX_BLOCKS) return EWN_EINVAL;
+    bool empty;
+    const int rc = pug_refuse(board_size, cube_layer, M, sims, max_plies, c_puct, terminal_value, params && boards && dice && game && scratch,
+                              scratch, game, temp_plies, tile, blocks, empty);
+    if (rc != EWN_OK || empty) return rc;
     if (noise && !(noise_eps >= 0.0f && noise_eps <= 1.0f)) return EWN_EINVAL;   // NaN is refused here as well
     pug_geometry(M, tile, blocks);
     PugBuf b = { params, noise, noise ? noise_eps : 0.0f, noise ? 1.0f - noise_eps : 1.0f, boards, dice, (int *)game,
@@ -256,4 +364,34 @@ int ewn_puct_selfplay(int board_size, int cube_layer, int M, int sims, int max_p
                                : pug_launch<7, true>(M, sims, max_plies, tile, blocks, temp_plies, c_puct, inv_tv, key, game_offset, b, s);
     return board_size == 5 ? pug_launch<5, false>(M, sims, max_plies, tile, blocks, temp_plies, c_puct, inv_tv, key, game_offset, b, s)
                            : pug_launch<7, false>(M, sims, max_plies, tile, blocks, temp_plies, c_puct, inv_tv, key, game_offset, b, s);
+}
+
+// ewn_puct_selfplay's refusals in its order, the table among the pointers; then the table's values, the alignments; noise_eps last and
+// only when noise is given.  The scratch is ewn_puct_selfplay_scratch_bytes': the same trees under the same geometry rule
+int ewn_puct_selfplay_eg(int board_size, int cube_layer, int M, int sims, int max_plies, float c_puct, float terminal_value, const float *params,
+                         const float *noise, float noise_eps, int temp_plies, uint64_t key, int64_t game_offset, int tile, int blocks,
+                         int8_t *boards, int8_t *dice, int32_t *game, int8_t *rec_board, int8_t *rec_dice, int32_t *rec_visits, float *rec_value,
+                         int8_t *rec_action, int8_t *rec_live, void *scratch, int max_cubes, int max_total, const float *table,
+                         int32_t *leaf_counts, void *stream)
+{
+    bool empty;
+    const int rc = pug_refuse(board_size, cube_layer, M, sims, max_plies, c_puct, terminal_value,
+                              params && boards && dice && game && scratch && table, scratch, game, temp_plies, tile, blocks, empty);
+    if (rc != EWN_OK || empty) return rc;
+    if (!eg_params_ok(board_size, max_cubes, max_total)) return EWN_EINVAL;
+    if (((uintptr_t)table & 3) || ((uintptr_t)leaf_counts & 3)) return EWN_EINVAL;
+    if (noise && !(noise_eps >= 0.0f && noise_eps <= 1.0f)) return EWN_EINVAL;   // NaN is refused here as well
+    pug_geometry(M, tile, blocks);
+    PugBuf b = { params, noise, noise ? noise_eps : 0.0f, noise ? 1.0f - noise_eps : 1.0f, boards, dice, (int *)game,
+                 PuRecord{ rec_board, rec_dice, (int *)rec_visits, rec_value, rec_action, rec_live }, (uint8_t *)scratch };
+    PugEg<true> e;
+    e.tbl = table; e.counts = (int *)leaf_counts; e.tv = terminal_value;
+    eg_geo(board_size, max_cubes, max_total, e.g);
+    const float inv_tv = 1.0f / terminal_value;
+    hipStream_t s = (hipStream_t)stream;
+    if (noise)
+        return board_size == 5 ? pug_launch_eg<5, true>(M, sims, max_plies, tile, blocks, temp_plies, c_puct, inv_tv, key, game_offset, b, e, s)
+                               : pug_launch_eg<7, true>(M, sims, max_plies, tile, blocks, temp_plies, c_puct, inv_tv, key, game_offset, b, e, s);
+    return board_size == 5 ? pug_launch_eg<5, false>(M, sims, max_plies, tile, blocks, temp_plies, c_puct, inv_tv, key, game_offset, b, e, s)
+                           : pug_launch_eg<7, false>(M, sims, max_plies, tile, blocks, temp_plies, c_puct, inv_tv, key, game_offset, b, e, s);
 }

@@ -23,6 +23,7 @@ from ._lib import check
 from .a2c import FusedTrainer
 from .endgame import EndgameTable, _accept_table
 from .games import selfplay_puct_games
+from .games_exact import _games_table_alone, selfplay_puct_games_exact
 from .search import (SELFPLAY_MAX_PLIES, _leaf_table_alone, _noise_eps, _play_numbers, _puct_numbers, lookahead_targets, predict_lookahead,
                      predict_puct, selfplay_puct, sup_grad)
 from .sharding import all_reduce_counters
@@ -214,7 +215,7 @@ class PuctSelfPlayTrainer(_SupervisedTrainer):
 
     def __init__(self, env, sims=64, c_puct=1.5, terminal_value=1.0, noise_eps=0.25, noise_alpha=1.0, temp_plies=8, max_plies=None,
                  learning_rate=7e-4, pi_coef=1.0, vf_coef=0.5, max_grad_norm=0.5, rms_alpha=0.99, rms_eps=1e-5, seed=None,
-                 endgame_table=None, chunk=1024, fused=False, whole_games=False, leaves=1, leaf_table=None):
+                 endgame_table=None, chunk=1024, fused=False, whole_games=False, leaves=1, games_table=None, leaf_table=None):
         who = "PuctSelfPlayTrainer"
         _puct_numbers(who, sims, c_puct, terminal_value)
         _noise_eps(who, noise_eps)
@@ -222,6 +223,7 @@ class PuctSelfPlayTrainer(_SupervisedTrainer):
         _positive(who, "noise_alpha", noise_alpha)
         if max_plies is not None and not (isinstance(max_plies, int) and max_plies >= 1):
             raise ValueError("%s: max_plies must be a positive integer or None, got %r" % (who, max_plies))
+        _games_table_alone(who, games_table, endgame_table, leaf_table, leaves)
         if fused and endgame_table is not None:
             raise ValueError("%s: fused=True does not take an endgame_table: the exact-leaf substitution is the staged path's" % who)
         if whole_games and endgame_table is not None:
@@ -234,6 +236,8 @@ class PuctSelfPlayTrainer(_SupervisedTrainer):
         # endgame_table: exact values at the leaves the table covers (4p), nothing else
         # fused: a ply's search as the one launch of ewn_puct_search (4r): the same records bit for bit
         # whole_games: all games in the one launch of ewn_puct_selfplay (4s), chunk and fused are then not read: the same records again
+        # games_table (a table or its path): leaf_table's records from the one launch of ewn_puct_selfplay_eg (4x); chunk, fused and
+        # whole_games are then not read
         super().__init__(who, env, sims=sims, c_puct=c_puct, terminal_value=terminal_value, fused=fused, pi_coef=pi_coef, vf_coef=vf_coef,
                          endgame_table=endgame_table, learning_rate=learning_rate, max_grad_norm=max_grad_norm, rms_alpha=rms_alpha,
                          rms_eps=rms_eps, leaves=leaves, n_steps=1, seed=seed, use_graph=False, opponent=None, opponent_update_every=100,
@@ -242,6 +246,10 @@ class PuctSelfPlayTrainer(_SupervisedTrainer):
             leaf_table = _accept_table(who, leaf_table, env.S, "the leaf table is for %%dx%%d boards, the env plays %dx%d" % (env.S, env.S),
                                        name="leaf_table", load=lambda path: EndgameTable.load(path, device=env.board.device))
         self.leaf_table = leaf_table
+        if games_table is not None:
+            games_table = _accept_table(who, games_table, env.S, "the games table is for %%dx%%d boards, the env plays %dx%d" % (env.S, env.S),
+                                        name="games_table", load=lambda path: EndgameTable.load(path, device=env.board.device))
+        self.games_table = games_table
         self.max_plies = SELFPLAY_MAX_PLIES[env.S] if max_plies is None else int(max_plies)
         self._size_scratch(self.max_plies)
         self.noise_eps, self.noise_alpha, self.temp_plies = float(noise_eps), float(noise_alpha), int(temp_plies)
@@ -263,7 +271,12 @@ class PuctSelfPlayTrainer(_SupervisedTrainer):
     def _launch(self):
         env = self.env
         board, dice, first = self.fresh_positions()
-        if self.whole_games:
+        if self.games_table is not None:
+            rec = selfplay_puct_games_exact(board, dice, self.params, self.games_table, sims=self.sims, max_plies=self.max_plies,
+                                            c_puct=self.c_puct, terminal_value=self.terminal_value, noise_eps=self.noise_eps,
+                                            noise_alpha=self.noise_alpha, temp_plies=self.temp_plies, key=self.noise_key, game_offset=first,
+                                            cube_layer=env.L)
+        elif self.whole_games:
             rec = selfplay_puct_games(board, dice, self.params, sims=self.sims, max_plies=self.max_plies, c_puct=self.c_puct,
                                       terminal_value=self.terminal_value, noise_eps=self.noise_eps, noise_alpha=self.noise_alpha,
                                       temp_plies=self.temp_plies, key=self.noise_key, game_offset=first, cube_layer=env.L)
@@ -301,7 +314,8 @@ class PuctSelfPlayTrainer(_SupervisedTrainer):
     def _state(self):
         return {**super()._state(), "noise_eps": float(self.noise_eps), "noise_alpha": float(self.noise_alpha),
                 "temp_plies": int(self.temp_plies), "max_plies": int(self.max_plies), "seed_counter": int(self.seed_counter),
-                "whole_games": bool(self.whole_games), "leaf_table_used": self.leaf_table is not None}   # that one was used, not its bytes
+                "whole_games": bool(self.whole_games), "leaf_table_used": self.leaf_table is not None,   # that one was used, not its bytes
+                "games_table_used": self.games_table is not None}
 
     def _load_state(self, sd):
         super()._load_state(sd)

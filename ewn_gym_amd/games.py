@@ -12,6 +12,7 @@ import torch
 from . import _lib
 from ._lib import check
 from ._args import _positive, _ptr, _same_gpu, _stream
+from .endgame import _accept_table
 from .search import (_PLAY_ROWS, SELFPLAY_MAX_PLIES, _game_column, _network_inputs, _noise_eps, _play_numbers, _puct_numbers, selfplay_noise,
                      selfplay_outcomes)
 
@@ -43,29 +44,49 @@ def selfplay_puct_games(boards, dice, params, sims=64, max_plies=None, c_puct=1.
     action int8 [T, M, 2], live bool [T, M], z and weight float32 [T, M], winner int32 [M], plies int32 [M]."""
     who = "selfplay_puct_games"
     lib = _lib.load()
+    a = _games_arguments(who, boards, dice, params, sims, max_plies, c_puct, terminal_value, noise_eps, noise_alpha, temp_plies, key,
+                         game_offset, cube_layer, tile, blocks)
+    return _play_games(lib, a, params, lambda *front: check(lib.ewn_puct_selfplay(*front, _stream()), "ewn_puct_selfplay"))
+
+
+def _games_arguments(who, boards, dice, params, sims, max_plies, c_puct, terminal_value, noise_eps, noise_alpha, temp_plies, key, game_offset,
+                     cube_layer, tile, blocks, table=None, table_name="endgame_table", table_required=False):
+    """The checks of a call that plays whole games in one launch, in selfplay_puct's order and texts: the numbers, then the tensors
+    (table: an EndgameTable for the boards' size, the caller's keyword table_name; None: no table, unless table_required), max_plies,
+    the devices -> a dict of the checked values, as _play_games takes it"""
     sims = _puct_numbers(who, sims, c_puct, terminal_value)
     eps = _noise_eps(who, noise_eps)
     temp_plies, key, game_offset = _play_numbers(who, temp_plies, key, game_offset)
     _positive(who, "noise_alpha", noise_alpha)
     tile, blocks = _geometry(who, "tile", tile, PUCT_GAMES_TILE), _geometry(who, "blocks", blocks, PUCT_GAMES_MAX_BLOCKS)
-    M, S, L, dev, inputs = _network_inputs(who, boards, dice, params, cube_layer)
+    if table_required and table is None:                       # _network_inputs takes None for "no table"
+        _accept_table(who, table, None, None, name=table_name)
+    M, S, L, dev, inputs = _network_inputs(who, boards, dice, params, cube_layer, table=table, table_name=table_name)
     T = SELFPLAY_MAX_PLIES[S] if max_plies is None else max_plies
     if not (isinstance(T, (int, np.integer)) and int(T) >= 1):
         raise ValueError("%s: max_plies must be a positive integer or None, got %r" % (who, max_plies))
-    T = int(T)
     _same_gpu(who, dev, "params", inputs.items())
-    b, d = inputs["boards"].clone(), inputs["dice"].clone()    # played on in place
+    return dict(sims=sims, eps=eps, temp_plies=temp_plies, key=key, game_offset=game_offset, noise_alpha=noise_alpha, tile=tile, blocks=blocks,
+                M=M, S=S, L=L, dev=dev, inputs=inputs, T=int(T), c_puct=float(c_puct), terminal_value=float(terminal_value))
+
+
+def _play_games(lib, a, params, launch):
+    """The buffers of a call that plays whole games in one launch, the launch and the records.  a: _games_arguments' dict;
+    launch(*front): the entry's call and its check, front = ewn_puct_selfplay's arguments up to the scratch -- what a further entry
+    takes goes behind them.  Nothing is launched for M == 0 -> selfplay_puct's dict"""
+    M, S, L, T, dev, sims = a["M"], a["S"], a["L"], a["T"], a["dev"], a["sims"]
+    b, d = a["inputs"]["boards"].clone(), a["inputs"]["dice"].clone()    # played on in place
     rec = {name: torch.empty((T, M) + shape(S), dtype=dt, device=dev) for name, dt, shape in _PLAY_ROWS}   # every row is written
     game = torch.zeros((M, 4), dtype=torch.int32, device=dev)
     if M > 0:
-        noise = torch.stack([selfplay_noise(M, noise_alpha, key, game_offset, t, dev) for t in range(T)]) if eps > 0.0 else None
-        scratch = torch.empty(int(check(lib.ewn_puct_selfplay_scratch_bytes(S, L, M, sims, tile, blocks), "ewn_puct_selfplay_scratch_bytes")),
-                              dtype=torch.uint8, device=dev)
+        noise = (torch.stack([selfplay_noise(M, a["noise_alpha"], a["key"], a["game_offset"], t, dev) for t in range(T)])
+                 if a["eps"] > 0.0 else None)
+        scratch = torch.empty(int(check(lib.ewn_puct_selfplay_scratch_bytes(S, L, M, sims, a["tile"], a["blocks"]),
+                                        "ewn_puct_selfplay_scratch_bytes")), dtype=torch.uint8, device=dev)
         with torch.cuda.device(dev):
-            check(lib.ewn_puct_selfplay(S, L, M, sims, T, C.c_float(float(c_puct)), C.c_float(float(terminal_value)), _ptr(params), _ptr(noise),
-                                        C.c_float(eps), temp_plies, C.c_uint64(key), C.c_int64(game_offset), tile, blocks, _ptr(b), _ptr(d),
-                                        _ptr(game), *[_ptr(rec[name]) for name, _, _ in _PLAY_ROWS], _ptr(scratch), _stream()),
-                  "ewn_puct_selfplay")
+            launch(S, L, M, sims, T, C.c_float(a["c_puct"]), C.c_float(a["terminal_value"]), _ptr(params), _ptr(noise), C.c_float(a["eps"]),
+                   a["temp_plies"], C.c_uint64(a["key"]), C.c_int64(a["game_offset"]), a["tile"], a["blocks"], _ptr(b), _ptr(d), _ptr(game),
+                   *[_ptr(rec[name]) for name, _, _ in _PLAY_ROWS], _ptr(scratch))
     rec["live"] = rec["live"].view(torch.bool)
     rec["winner"], rec["plies"] = _game_column(game, 2), _game_column(game, 0)
     rec["z"], rec["weight"] = selfplay_outcomes(rec["winner"], rec["live"])

@@ -61,6 +61,10 @@ def _parser():
                     help="SELFPLAY: a saved EndgameTable; a leaf of the search that it covers is worth its exact value, a ply's search "
                          "stays one kernel launch (ewn_puct_search_eg, DESIGN.md 4w); --fused is then not read; not with --endgame_table, "
                          "--leaves above 1 or --whole_games")
+    ap.add_argument("--games_table", default=None, metavar="PATH",
+                    help="SELFPLAY: a saved EndgameTable; --puct_table's games with all of them in one kernel launch, finished columns "
+                         "refilled (ewn_puct_selfplay_eg, DESIGN.md 4x); --fused and --whole_games are then not read; not with "
+                         "--endgame_table, --puct_table or --leaves above 1")
     ap.add_argument("--batch_size", "-b", type=int, default=None,
                     help="PPO: minibatch size in samples of the n_steps x lanes rollout buffer (default: a quarter of it; train.py:178-183)")
     ap.add_argument("--n_epochs", type=int, default=10, help="PPO: passes over the rollout buffer per update (SB3 default)")
@@ -142,6 +146,11 @@ def main():
     if a.puct_table is not None and (a.endgame_table is not None or a.leaves != 1 or a.whole_games):
         raise SystemExit("--puct_table does not go with --endgame_table, --leaves above 1 or --whole_games: it is the one launch of the "
                          "search with exact leaves")
+    if a.games_table is not None and a.algorithm != "SELFPLAY":
+        raise SystemExit("--games_table is read by SELFPLAY only")
+    if a.games_table is not None and (a.endgame_table is not None or a.puct_table is not None or a.leaves != 1):
+        raise SystemExit("--games_table does not go with --endgame_table, --puct_table or --leaves above 1: it is the one launch of whole "
+                         "games with exact leaves")
     if a.endgame_table is not None and a.algorithm not in ("SEARCH", "SELFPLAY"):
         raise SystemExit("--endgame_table is read by SEARCH and SELFPLAY only")
     if a.endgame_leaves and (a.algorithm not in ("SEARCH", "SELFPLAY") or a.endgame_table is None):
@@ -179,7 +188,8 @@ def main():
         trainer = PuctSelfPlayTrainer(env, sims=a.sims, c_puct=a.c_puct, terminal_value=a.terminal_value, noise_eps=a.noise_eps,
                                       noise_alpha=a.noise_alpha, temp_plies=a.temp_plies, max_plies=a.max_plies,
                                       learning_rate=a.learning_rate, seed=mseed, endgame_table=a.endgame_table, fused=a.fused,
-                                      whole_games=a.whole_games, leaves=a.leaves, leaf_table=a.puct_table)
+                                      whole_games=a.whole_games, leaves=a.leaves, leaf_table=a.puct_table,
+                                      games_table=a.games_table)
     elif a.trainer == "fused" or model_opp is not None or (a.trainer == "auto" and env.supports_policy_rollout()):
         trainer = FusedA2CTrainer(env, n_steps=a.n_steps, learning_rate=a.learning_rate, seed=mseed, **okw)
     else:
