@@ -406,12 +406,23 @@ __device__ double search(const Geom &g, const GState<NW> &s, int dice, double al
 
 // ---------------------------------------------------------------- RNG
 
-EWN_DEV void philox4x32_10(u32 c0, u32 c1, u32 c2, u32 c3, u32 k0, u32 k1, u32 (&out)[4])
+// the high word of a 32 x 32 bit product, for code the host compiles too (the draw-ahead of a step's dice and the generic stream
+// it is checked against, tests/step_dice_host.hip); on the device it is __umulhi itself
+__host__ EWN_DEV u32 umulhi32(u32 a, u32 b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __umulhi(a, b);
+#else
+    return (u32)(((u64)a * b) >> 32);
+#endif
+}
+
+__host__ EWN_DEV void philox4x32_10(u32 c0, u32 c1, u32 c2, u32 c3, u32 k0, u32 k1, u32 (&out)[4])
 {
     #pragma unroll
     for (int r = 0; r < 10; r++) {
-        const u32 h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const u32 h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        const u32 h0 = umulhi32(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const u32 h1 = umulhi32(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
         const u32 n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
         c0 = n0; c1 = l1; c2 = n2; c3 = l0;
         k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
@@ -457,9 +468,9 @@ struct PhiloxStream {
     u32 c1, c2, c3, k0, k1, n;
     u32 b0, b1, b2, b3;
     u32 have; // block index + 1 currently cached (0 = none)
-    EWN_DEV void init(u32 c1_, u32 c2_, u32 c3_, u64 key, u32 n_) { c1 = c1_; c2 = c2_; c3 = c3_; k0 = (u32)key; k1 = (u32)(key >> 32); n = n_; have = 0; b0 = b1 = b2 = b3 = 0; }
+    __host__ EWN_DEV void init(u32 c1_, u32 c2_, u32 c3_, u64 key, u32 n_) { c1 = c1_; c2 = c2_; c3 = c3_; k0 = (u32)key; k1 = (u32)(key >> 32); n = n_; have = 0; b0 = b1 = b2 = b3 = 0; }
     // compute the block the next draw comes from now (e.g. while a load is in flight); next() will find it cached
-    EWN_DEV void prime()
+    __host__ EWN_DEV void prime()
     {
         const u32 b = n >> 2;
         if (have != b + 1) { u32 o[4]; philox4x32_10(b, c1, c2, c3, k0, k1, o); b0 = o[0]; b1 = o[1]; b2 = o[2]; b3 = o[3]; have = b + 1; }
@@ -470,7 +481,7 @@ struct PhiloxStream {
         const u32 b = n >> 2;
         if (have != b + 1) { u32 o[4]; philox4x32_10_pair(b, c1, c2, c3, k0, k1, sub, o); b0 = o[0]; b1 = o[1]; b2 = o[2]; b3 = o[3]; have = b + 1; }
     }
-    EWN_DEV u32 next()
+    __host__ EWN_DEV u32 next()
     {
         const u32 b = n >> 2;
         if (have != b + 1) { u32 o[4]; philox4x32_10(b, c1, c2, c3, k0, k1, o); b0 = o[0]; b1 = o[1]; b2 = o[2]; b3 = o[3]; have = b + 1; }
@@ -481,7 +492,7 @@ struct PhiloxStream {
     }
 };
 
-EWN_DEV u32 mt_temper(u32 y)
+__host__ EWN_DEV u32 mt_temper(u32 y)
 {
     y ^= (y >> 11);
     y ^= (y << 7) & 0x9d2c5680u;
@@ -490,7 +501,7 @@ EWN_DEV u32 mt_temper(u32 y)
     return y;
 }
 
-EWN_DEV u32 mt_twist(u32 a, u32 b)
+__host__ EWN_DEV u32 mt_twist(u32 a, u32 b)
 {
     const u32 y = (a & 0x80000000u) | (b & 0x7fffffffu);
     return (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
@@ -518,7 +529,7 @@ EWN_DEV void mt_fill_window(u32 seed, int W, u32 *win)
 // Output n of the same stream for W <= n < 454, memory-free (rare path: an episode
 // that consumes more draws than the window holds).  For 227 <= n < 454 the word
 // x[n+397] is itself a first-generation output of the recurrence.
-EWN_DEV u32 mt_output_closed(u32 seed, u32 n)
+__host__ EWN_DEV u32 mt_output_closed(u32 seed, u32 n)
 {
     const u32 j = n >= 227u ? n - 227u : 0u;
     u32 s = seed, sn = 0, sn1 = 0, sj = 0, sj1 = 0, sj397 = 0, sn397 = 0;
@@ -627,7 +638,7 @@ struct LaneRng {
         if (kind == 0 && n + 8u <= W) { p0 = win[n]; p1 = win[n + 1]; p2 = win[n + 2]; p3 = win[n + 3]; p4 = win[n + 4]; p5 = win[n + 5]; p6 = win[n + 6]; p7 = win[n + 7]; }
         else pre_base = 0xFFFFFFF0u; // nothing cached
     }
-    EWN_DEV void load(int kind_, uint4 h, const u32 *win_, u32 W_, u64 key)
+    __host__ EWN_DEV void load(int kind_, uint4 h, const u32 *win_, u32 W_, u64 key)
     {
         kind = kind_; seed = h.x; n = h.y; next_seed = h.z; flags = h.w; W = W_; win = win_;
         p0 = p1 = p2 = p3 = p4 = p5 = p6 = p7 = 0; pre_base = 0xFFFFFFF0u; pre_lim = 8u; q0 = q1 = q2 = q3 = 0; q_valid = false;
@@ -637,9 +648,9 @@ struct LaneRng {
     // 32-bit: inherent for the MT kind).  The Philox kind counts the wraps in the header's 4th word and feeds it to the counter
     // (c2) and to every hash keyed by the episode, so a lane's dice streams do not repeat before 2^64 / stride episodes.
     EWN_DEV u32 seed_mix() const { return kind == 1 ? seed ^ (flags * 0x9E3779B9u) : seed; }
-    EWN_DEV uint4 header() const { return make_uint4(seed, kind == 1 ? ps.n : n, next_seed, flags); }
+    __host__ EWN_DEV uint4 header() const { return make_uint4(seed, kind == 1 ? ps.n : n, next_seed, flags); }
     EWN_DEV u32 draws() const { return kind == 1 ? ps.n : n; }
-    EWN_DEV u32 next()
+    __host__ EWN_DEV u32 next()
     {
         if (kind == 1) return ps.next();
         u32 v;
@@ -703,14 +714,14 @@ struct LaneRng {
         load(kind, make_uint4(s2, 0u, s2 + stride, f), rng_win_ptr(rng, N, W, lane, kind == 0 ? RNGF_CUR(f) : 0u), W, key);
         prefetch();
     }
-    EWN_DEV void begin_step() { if (kind == 1) ps.n = (ps.n + 3u) & ~3u; }
+    __host__ EWN_DEV void begin_step() { if (kind == 1) ps.n = (ps.n + 3u) & ~3u; }
     EWN_DEV int first_dice(int cube_num)
     {
         if (kind != 1) return randint(1, cube_num + 1);      // roll_dice, envs/ewn.py:90-91
         const u32 w = fmix32(seed_mix() ^ fmix32(ps.k0 ^ 0x454E5631u) ^ (ps.k1 * 0x9E3779B1u));
         return 1 + (int)__umulhi(w, (u32)cube_num);           // bias <= cube_num / 2^32
     }
-    EWN_DEV int lemire(u32 range)
+    __host__ EWN_DEV int lemire(u32 range)
     {
         if (range <= 1u) return 0;
         u64 m = (u64)next() * range;
@@ -721,7 +732,7 @@ struct LaneRng {
         }
         return (int)(m >> 32);
     }
-    EWN_DEV int randint(int lo, int hi)
+    __host__ EWN_DEV int randint(int lo, int hi)
     {
         if (kind == 1) return lo + lemire((u32)(hi - lo));
         const u32 rng = (u32)(hi - lo - 1);
@@ -732,5 +743,31 @@ struct LaneRng {
         int guard = 0;
         do { v = next() & mask; } while (v > rng && ++guard < 4096);
         return lo + (int)(v > rng ? 0u : v);
+    }
+    // Philox kind, once per step, right behind begin_step() and prime() / prime_pair(): the two randint(1, 7) a step can make -- the
+    // opponent's dice after the agent half, the next dice after the opponent's move -- out of the block in registers, each with the
+    // stream position behind it.  The caller sets ps.n to n1 / n2 where it used to draw; a step that ends early leaves ps.n alone.
+    // Both words are multiplied unconditionally (the lanes of a wave run together).  Unless both low halves pass Lemire's test
+    // outright (probability 1 - 12 / 2^32) ONE cold block makes the two draws on a copy of the stream exactly as randint does, so a
+    // rejected first draw shifts the second and a rejection in a block's last word goes on into the next block.  There the two key
+    // words pass through VGPRs: the round keys of the inlined Philox copies are then VALU results of the cold block, not twenty
+    // scalars hoisted out of the caller's loop.  The block is used up: the next prime() computes without a test.
+    struct StepDice { int d1, d2; u32 n1, n2; };
+    __host__ EWN_DEV StepDice step_dice()
+    {
+        const u64 m1 = (u64)ps.b0 * 6u, m2 = (u64)ps.b1 * 6u;
+        StepDice o;
+        o.d1 = 1 + (int)(m1 >> 32); o.n1 = ps.n + 1u;
+        o.d2 = 1 + (int)(m2 >> 32); o.n2 = ps.n + 2u;
+        if (__builtin_expect((u32)m1 < 6u || (u32)m2 < 6u, 0)) {
+            LaneRng t = *this;
+#if defined(__HIP_DEVICE_COMPILE__)
+            asm volatile("" : "+v"(t.ps.k0), "+v"(t.ps.k1));
+#endif
+            o.d1 = t.randint(1, 7); o.n1 = t.ps.n;
+            o.d2 = t.randint(1, 7); o.n2 = t.ps.n;
+        }
+        ps.have = 0;
+        return o;
     }
 };

@@ -253,9 +253,10 @@ EWN_DEV void slot_move_real(int8_t *slot, int sub, u32 w, int shp, int shq, int 
     }
 }
 
+// sd: the step's dice drawn ahead (LaneRng::step_dice, Philox kind), or NULL: draw from the stream here (MT19937 kind)
 template <int S, int T>
-EWN_DEV bool roll_agent_half(RState<S> &s, const MoveEnt &m0, const MoveEnt &m1, u32 e, int aflag, int adir, int &dice, LaneRng &r, double R,
-                             double &reward, int &term, int &trunc, int &info, int8_t *slot, int sub)
+EWN_DEV bool roll_agent_half(RState<S> &s, const MoveEnt &m0, const MoveEnt &m1, u32 e, int aflag, int adir, int &dice, LaneRng &r,
+                             const LaneRng::StepDice *sd, double R, double &reward, int &term, int &trunc, int &info, int8_t *slot, int sub)
 {
     const bool first = aflag == 1 || ((e >> 8) & 7u) == 6u; // pk_cube's choice between the two
     const int k = pk_cube(e, aflag == 1);
@@ -267,18 +268,20 @@ EWN_DEV bool roll_agent_half(RState<S> &s, const MoveEnt &m0, const MoveEnt &m1,
     rs_move<S, false>(s, k, q);
     constexpr RingGeo<S> G{};   // Tb->ri_origin, the ring index of cell (0, 0), is a constant of the ring order
     if (q == G.ring_of_rm[0] || s.P == 0) { reward = R; term = 1; info = EWN_INFO_WON; return false; }
-    dice = r.randint(1, 7);
+    if (sd) { dice = sd->d1; r.ps.n = sd->n1; }
+    else dice = r.randint(1, 7);
     return true;
 }
 
 // opponent half once its move is known, with the move's real cells: bytes (shp / 8) and (shq / 8) of w
 template <int S, int T>
-EWN_DEV void roll_opponent_move_real(RState<S> &s, int k, int q, u32 w, int shp, int shq, int &dice, LaneRng &r, double R,
-                                     double &reward, int &term, int &info, int8_t *slot, int sub)
+EWN_DEV void roll_opponent_move_real(RState<S> &s, int k, int q, u32 w, int shp, int shq, int &dice, LaneRng &r,
+                                     const LaneRng::StepDice *sd, double R, double &reward, int &term, int &info, int8_t *slot, int sub)
 {
     if (slot) slot_move_real<T>(slot, sub, w, shp, shq, -(k + 1));
     rs_move<S, true>(s, k, q);
     if (q == FastTab<S>::CELLS - 1 || s.N == 0) { reward = -R; term = 1; info = EWN_INFO_LOST; }
+    else if (sd) { dice = sd->d2; r.ps.n = sd->n2; }
     else dice = r.randint(1, 7);
 }
 
@@ -534,6 +537,9 @@ __global__ __launch_bounds__(D3_BS, (OPP == 2 ? 2 : 1)) void k_rollout_slots(Rol
     int term = 0, trunc = 0, info = EWN_INFO_NONE, aflag = 0, adir = 0, oflag = 0, odir = 0;
     u32 omove = 0;                                  // OPP 0: the opponent's move as d3_search returns it (bmove)
     bool reply = false;
+    // Philox kind: both dice of the step in flight, drawn once from the step's primed block (the second one waits for the search)
+    LaneRng::StepDice sdv; sdv.d1 = sdv.d2 = 1; sdv.n1 = sdv.n2 = 0;
+    const LaneRng::StepDice *sd = RNGK == 1 ? &sdv : nullptr;
     const int klim = live ? c.K : 0;                // steps this lane plays: `pending` below is then one compare, straight into the ballot
 #ifdef EWN_ROLLOUT_STAMPS
     unsigned long long st_acc[6] = { 0, 0, 0, 0, 0, 0 }, st_prev;   // [4] counts the iterations
@@ -556,8 +562,8 @@ __global__ __launch_bounds__(D3_BS, (OPP == 2 ? 2 : 1)) void k_rollout_slots(Rol
                 if constexpr (RNGK == 0) r.prefetch();
                 r.begin_step();
                 // the game's two lanes share the step's Philox block (the lanes of a game take the same branches)
-                if constexpr (RNGK == 1) { if constexpr (T == 2) r.ps.prime_pair(sub); else r.ps.prime(); }
-                reply = roll_agent_half<S, T>(s, m0, m1, esel, aflag, adir, dice, r, c.reward, reward, term, trunc, info, slot_m, sub);
+                if constexpr (RNGK == 1) { if constexpr (T == 2) r.ps.prime_pair(sub); else r.ps.prime(); sdv = r.step_dice(); }
+                reply = roll_agent_half<S, T>(s, m0, m1, esel, aflag, adir, dice, r, sd, c.reward, reward, term, trunc, info, slot_m, sub);
             }
         }
         RSTAMP(0); // start of an env step: the agent's action, RNG block, agent half
@@ -572,11 +578,11 @@ __global__ __launch_bounds__(D3_BS, (OPP == 2 ? 2 : 1)) void k_rollout_slots(Rol
             phase = 0;
             if (reply) {
                 if constexpr (OPP == 0) { // the search's chosen root is the move, real cells included
-                    roll_opponent_move_real<S, T>(s, (int)(omove & 7u), (int)((omove >> 8) & 0xFFu), omove, 16, 24, dice, r, c.reward, reward, term, info, slot_m, sub);
+                    roll_opponent_move_real<S, T>(s, (int)(omove & 7u), (int)((omove >> 8) & 0xFFu), omove, 16, 24, dice, r, sd, c.reward, reward, term, info, slot_m, sub);
                 } else {
                     const int k = pk_cube(pk_sel<S>(Tb, s.posP, dice), oflag == 1), pb = pk_get(s.posP, k);
                     const MoveEnt mp = me_read(D.mvp, pb);
-                    roll_opponent_move_real<S, T>(s, k, me_dest(mp, odir), mp.rc, 0, 8 + 8 * odir, dice, r, c.reward, reward, term, info, slot_m, sub);
+                    roll_opponent_move_real<S, T>(s, k, me_dest(mp, odir), mp.rc, 0, 8 + 8 * odir, dice, r, sd, c.reward, reward, term, info, slot_m, sub);
                 }
             }
             if (!frozen) {

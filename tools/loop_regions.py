@@ -8,8 +8,9 @@ region holding the most instructions.  Every basic block of it is printed with i
 v_mul_hi_u32 / v_mad_*) and DPP counts.  A block is tagged `search` when it lies between the loop's first `s_setprio 2` and its
 last `s_setprio 0` (d3_search's priority raise and drop, ewn_step_d3.hpp), else `step`.  The step blocks are what the env step
 costs outside the opponent's search; blocks a wave takes only rarely (auto-reset, a rejected Lemire draw) are counted there too,
-so the `step` total is an upper bound of what an iteration issues outside the search.  A block with >= 10 32-bit multiplies is
-a Philox-4x32-10 block (ten rounds of one 64-bit multiply in the pair form, of two in the one-lane form; sources that still issue
+so the `step` total is an upper bound of what an iteration issues outside the search.  Blocks laid out behind the loop's latch that
+jump back into it (a branch marked unlikely, e.g. the one cold block of LaneRng::step_dice) are tagged `cold` and totalled apart.
+A block with >= 10 32-bit multiplies is a Philox-4x32-10 block (ten rounds of one 64-bit multiply in the pair form, of two in the one-lane form; sources that still issue
 the high and low halves separately have 20 and 40): the first one in the loop is prime() at step start (noted `prime`), every later one (noted `refill`) is
 reached only when a Lemire draw is rejected, with probability <= 6 / 2^32 per draw.  `step_common` is the step total without the
 refills.  These are static counts, not measurements.
@@ -71,25 +72,33 @@ def counts(insts):
 
 
 def step_loop(blocks):
-    """(first, last) block index of the largest backward-branch region"""
+    """(first, last, hot_last) block index: the largest backward-branch region, widened by every backward-branch region that
+    overlaps it.  Out-of-line blocks that the compiler lays out behind the loop's latch and that jump back into the loop (a branch
+    marked unlikely) are such an overlapping region: hot_last is the latch, the last block of the region that starts first, and
+    the blocks behind it are the loop's cold tail.  Without such blocks hot_last == last."""
     where = {lab: i for i, (lab, _) in enumerate(blocks)}
     size = [len(b[1]) for b in blocks]
-    best = None
+    regions = []
     for i, (_, insts) in enumerate(blocks):
         for op, text in insts:
             if op.startswith("s_cbranch") or op == "s_branch":
                 tgt = text.split()[-1]
                 if tgt in where and where[tgt] <= i:
-                    n = sum(size[where[tgt]:i + 1])
-                    if best is None or n > best[0]:
-                        best = (n, where[tgt], i)
-    if best is None:
+                    regions.append((sum(size[where[tgt]:i + 1]), where[tgt], i))
+    if not regions:
         raise SystemExit("no loop in this kernel")
-    return best[1], best[2]
+    _, lo, hi = max(regions)
+    grown = True
+    while grown:
+        grown = False
+        for _, a, b in regions:
+            if a <= hi and b >= lo and (a < lo or b > hi):
+                lo, hi, grown = min(lo, a), max(hi, b), True
+    return lo, hi, max(b for _, a, b in regions if a == lo)
 
 
 def analyse(blocks):
-    lo, hi = step_loop(blocks)
+    lo, hi, hot = step_loop(blocks)
     loop = blocks[lo:hi + 1]
     # the search: from the block of the first priority raise to the block of the last priority drop
     raise_at = [i for i, (_, ins) in enumerate(loop) if any(t.startswith("s_setprio 2") for _, t in ins)]
@@ -101,14 +110,16 @@ def analyse(blocks):
     for i, (lab, ins) in enumerate(loop):
         c = counts(ins)
         c["label"] = lab
-        c["region"] = "search" if s0 <= i <= s1 else "step"
+        c["region"] = "search" if s0 <= i <= s1 else "cold" if lo + i > hot else "step"
         c["note"] = ""
+        if c["region"] == "cold" and c["mul"] >= 10:
+            c["note"] = "refill"
         if c["region"] == "step" and c["mul"] >= 10:    # a Philox-4x32-10 block: 10 64-bit multiplies (pair form) or 20
             c["note"] = "refill" if seen_philox else "prime"
             seen_philox = True
         rows.append(c)
     keys = ("valu", "lds", "mul", "dpp", "salu", "vmem", "all")
-    tot = {reg: {k: sum(r[k] for r in rows if r["region"] == reg) for k in keys} for reg in ("search", "step")}
+    tot = {reg: {k: sum(r[k] for r in rows if r["region"] == reg) for k in keys} for reg in ("search", "step", "cold")}
     tot["step_common"] = {k: sum(r[k] for r in rows if r["region"] == "step" and r["note"] != "refill") for k in keys}
     return rows, tot
 
@@ -132,7 +143,7 @@ def main():
     print(fmt % ("block", "region", "valu", "lds", "mul", "dpp", "salu", "vmem", ""))
     for r in rows:
         print(fmt % (r["label"], r["region"], r["valu"], r["lds"], r["mul"], r["dpp"], r["salu"], r["vmem"], r["note"]))
-    for reg in ("search", "step", "step_common"):
+    for reg in ("search", "step", "step_common", "cold"):
         t = tot[reg]
         print(fmt % ("total", reg, t["valu"], t["lds"], t["mul"], t["dpp"], t["salu"], t["vmem"], ""))
     if a.json:
