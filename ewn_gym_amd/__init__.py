@@ -15,10 +15,11 @@ from .wide import puct_search_wide  # noqa: F401
 from .playout_exact import playout_search_exact, predict_playout_search_exact  # noqa: F401
 from .puct_exact import puct_search_exact  # noqa: F401
 from .games_exact import selfplay_puct_games_exact  # noqa: F401
+from .arena import arena_puct, arena_puct_games  # noqa: F401
 
 __all__ = ["VecEWN", "EwnError", "INFO_MESSAGES", "legal_actions", "apply_action", "playout_wins", "evaluate", "predict_minimax", "predict_random",
            "predict_mcts", "predict_policy", "predict_lookahead", "lookahead_expand", "lookahead_reduce", "lookahead_targets", "sup_grad", "EndgameTable",
            "predict_puct", "puct_begin", "puct_advance", "puct_result", "puct_tree_views",
            "puct_play", "selfplay_noise", "selfplay_outcomes", "selfplay_puct", "puct_search", "selfplay_puct_games",
            "playout_search", "predict_playout_search", "puct_search_wide", "playout_search_exact", "predict_playout_search_exact",
-           "puct_search_exact", "selfplay_puct_games_exact"]
+           "puct_search_exact", "selfplay_puct_games_exact", "arena_puct", "arena_puct_games"]

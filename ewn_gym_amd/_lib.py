@@ -41,6 +41,7 @@ EXPORTS_PUCT_WIDE = ["ewn_puct_search_wide_scratch_bytes", "ewn_puct_search_wide
 EXPORTS_PLAYOUT_SEARCH_EG = ["ewn_playout_search_eg"]   # include/ewn_playout_search_eg.h
 EXPORTS_PUCT_EXACT = ["ewn_puct_search_eg"]   # include/ewn_puct_exact.h
 EXPORTS_PUCT_GAMES_EXACT = ["ewn_puct_selfplay_eg"]   # include/ewn_puct_games_exact.h
+EXPORTS_PUCT_ARENA = ["ewn_puct_arena_scratch_bytes", "ewn_puct_arena"]   # include/ewn_puct_arena.h
 AGENT = {"random": 0, "minimax": 1, "sample": 2, "mlp": 3}   # "mlp": the trained policy, through ewn_step_k_policy   # "sample": env.action_space.sample(), all six actions (EWN_AGENT_SAMPLE)
 AGENT_MCTS = 4   # ewn_agent.kind of the MCTS agent (ewn_step_k_agent only; ewn_step_k does not take it)
 
@@ -203,6 +204,9 @@ def load():
                                 vp]),
         "ewn_puct_selfplay_eg": (i32, [i32, i32, i32, i32, i32, C.c_float, C.c_float, vp, vp, C.c_float, i32, C.c_uint64, C.c_int64, i32, i32,
                                   vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]),
+        "ewn_puct_arena_scratch_bytes": (C.c_int64, [i32, i32, i32, i32, i32, i32]),
+        "ewn_puct_arena": (i32, [i32, i32, i32, i32, i32, C.c_float, C.c_float, vp, vp, vp, C.c_float, i32, C.c_uint64, C.c_int64, i32, i32,
+                            vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

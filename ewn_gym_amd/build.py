@@ -11,7 +11,8 @@ CSRC = os.path.join(HERE, "csrc")
 SRC = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".hip")]
 DEPS = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + [os.path.join(HERE, "..", "include", h)
                                                                     for h in ("ewn_hip.h", "ewn_playout_search.h", "ewn_playout_search_eg.h",
-                                                                              "ewn_puct_wide.h", "ewn_puct_exact.h", "ewn_puct_games_exact.h")]
+                                                                              "ewn_puct_wide.h", "ewn_puct_exact.h", "ewn_puct_games_exact.h",
+                                                                              "ewn_puct_arena.h")]
 OUT = os.path.join(HERE, "lib", "libewn_hip.so")
 OBJ = os.path.join(HERE, "lib", "obj")
 # -ffp-contract=off: the fp64 heuristic and expectation sums must round exactly like the
@@ -25,6 +26,14 @@ FILE_FLAGS = {"ewn_policy.hip": ["-fno-slp-vectorize"], "ewn_policy_eval.hip": [
               "ewn_predict_lookahead.hip": ["-fno-slp-vectorize"], "ewn_lookahead_stages.hip": ["-fno-slp-vectorize"],
               "ewn_puct_fused.hip": ["-fno-slp-vectorize"], "ewn_puct_games.hip": ["-fno-slp-vectorize"],
               "ewn_puct_wide.hip": ["-fno-slp-vectorize"]}
+# the arena's unit runs the same matrix code and takes the same flag, so that its network outputs are the staged path's bits.  It stands
+# beside FILE_FLAGS, whose eleven entries tests/test_puct_games_exact_cpu.py counts; unit_flags() is what a unit is compiled with
+ARENA_FILE_FLAGS = {"ewn_puct_arena.hip": ["-fno-slp-vectorize"]}
+
+
+def unit_flags(name):
+    """the per-unit flags of csrc/<name>"""
+    return FILE_FLAGS.get(name, []) + ARENA_FILE_FLAGS.get(name, [])
 
 
 def stale():
@@ -43,7 +52,7 @@ def build(force=False, verbose=False):
     jobs = []
     for src in SRC:
         obj = os.path.join(OBJ, os.path.basename(src)[:-4] + ".o")
-        cmd = [hipcc] + FLAGS + FILE_FLAGS.get(os.path.basename(src), []) + extra + ["-c", "-o", obj, src]
+        cmd = [hipcc] + FLAGS + unit_flags(os.path.basename(src)) + extra + ["-c", "-o", obj, src]
         if verbose:
             print(" ".join(cmd), flush=True)
         jobs.append((subprocess.Popen(cmd), obj, cmd))

@@ -50,10 +50,11 @@ def selfplay_puct_games(boards, dice, params, sims=64, max_plies=None, c_puct=1.
 
 
 def _games_arguments(who, boards, dice, params, sims, max_plies, c_puct, terminal_value, noise_eps, noise_alpha, temp_plies, key, game_offset,
-                     cube_layer, tile, blocks, table=None, table_name="endgame_table", table_required=False):
+                     cube_layer, tile, blocks, table=None, table_name="endgame_table", table_required=False, more=(), optional=()):
     """The checks of a call that plays whole games in one launch, in selfplay_puct's order and texts: the numbers, then the tensors
-    (table: an EndgameTable for the boards' size, the caller's keyword table_name; None: no table, unless table_required), max_plies,
-    the devices -> a dict of the checked values, as _play_games takes it"""
+    (table: an EndgameTable for the boards' size, the caller's keyword table_name; None: no table, unless table_required; more and
+    optional: a further entry's inputs, as _network_inputs takes them), max_plies, the devices -> a dict of the checked values, as
+    _play_games takes it"""
     sims = _puct_numbers(who, sims, c_puct, terminal_value)
     eps = _noise_eps(who, noise_eps)
     temp_plies, key, game_offset = _play_numbers(who, temp_plies, key, game_offset)
@@ -61,7 +62,7 @@ def _games_arguments(who, boards, dice, params, sims, max_plies, c_puct, termina
     tile, blocks = _geometry(who, "tile", tile, PUCT_GAMES_TILE), _geometry(who, "blocks", blocks, PUCT_GAMES_MAX_BLOCKS)
     if table_required and table is None:                       # _network_inputs takes None for "no table"
         _accept_table(who, table, None, None, name=table_name)
-    M, S, L, dev, inputs = _network_inputs(who, boards, dice, params, cube_layer, table=table, table_name=table_name)
+    M, S, L, dev, inputs = _network_inputs(who, boards, dice, params, cube_layer, more, optional, table=table, table_name=table_name)
     T = SELFPLAY_MAX_PLIES[S] if max_plies is None else max_plies
     if not (isinstance(T, (int, np.integer)) and int(T) >= 1):
         raise ValueError("%s: max_plies must be a positive integer or None, got %r" % (who, max_plies))

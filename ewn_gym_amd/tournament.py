@@ -417,6 +417,35 @@ def evaluate_model(model, names=("random", "minimax"), num=1024, max_depth=5, nu
     return table
 
 
+def arena(model_a, model_b, num=1024, sims=64, board_size=5, cube_layer=3, seed_offset=0, key=12345, max_plies=None, c_puct=1.5,
+          terminal_value=1.0, whole_games=True):
+    """Two networks' PUCT searches of `sims` simulations against each other, whole games in one launch (arena_puct_games,
+    ewn_puct_arena): what tells whether checkpoint A is stronger than checkpoint B at the strength both are used at.
+    Game m starts from the reset position and dice of seed seed_offset + m // 2, and first[m] = m & 1: every start position is
+    played twice, once with each network moving first.  No root noise, the most visited move; the dice of game m are those of the
+    global game 2 * seed_offset + m under `key`.  whole_games=False plays the same games through arena_puct, ply by ply
+    (ewn_puct_search): the same results.  Returns wins_a, wins_b, undecided (cut at max_plies), episodes, A's win_rate with the
+    Wilson ci95, avg_length (plies), the two halves a_first and b_first, each {wins_a, episodes}, and the engine."""
+    from .arena import arena_puct, arena_puct_games
+    for model in (model_a, model_b):
+        _model_on_board("arena: a model", model, board_size)
+    env = _eval_env(None, (num + 1) // 2, board_size, cube_layer, "mt19937", seed_offset, key)
+    boards = env.board.repeat_interleave(2, 0)[:num].contiguous()
+    dice = env.dice.repeat_interleave(2, 0)[:num].contiguous()
+    first = (torch.arange(num, device=env.device) & 1).to(torch.int8)
+    pa, pb = flat_policy_params(model_a).to(env.device), flat_policy_params(model_b).to(env.device)
+    play = arena_puct_games if whole_games else arena_puct
+    rec = play(boards, dice, pa, pb, first, sims=sims, max_plies=max_plies, c_puct=c_puct, terminal_value=terminal_value, key=key,
+               game_offset=2 * seed_offset, cube_layer=cube_layer)
+    res, a_moves_first = rec["result_a"], rec["first"] == 0
+    wins_a, wins_b = int((res > 0).sum().item()), int((res < 0).sum().item())
+    lo, hi = wilson(wins_a, num)
+    half = lambda sel: {"wins_a": int(((res > 0) & sel).sum().item()), "episodes": int(sel.sum().item())}   # noqa: E731
+    return {"wins_a": wins_a, "wins_b": wins_b, "undecided": num - wins_a - wins_b, "episodes": num, "win_rate": wins_a / num if num else 0.0,
+            "ci95": [lo, hi], "avg_length": float(rec["plies"].float().mean().item()) if num else 0.0, "a_first": half(a_moves_first),
+            "b_first": half(~a_moves_first), "engine": "ewn_puct_arena" if whole_games else "ewn_puct_search"}
+
+
 def _parser():
     ap = argparse.ArgumentParser(description="agent-vs-opponent win-rate matrix (counterpart of eval_pairs.py); with --model, a "
                                              "trained policy against each listed opponent (counterpart of eval_A2C.py)")
@@ -424,7 +453,7 @@ def _parser():
                     help="random, minimax, mcts; without --model also playout_search (the tree search on random playouts, an agent only)")
     ap.add_argument("--sims", type=int, default=64, help="playout_search: simulations per move")
     ap.add_argument("--playouts", type=int, default=64, help="playout_search: random playouts per leaf")
-    ap.add_argument("--c_puct", type=float, default=1.5, help="playout_search: the exploration constant")
+    ap.add_argument("--c_puct", type=float, default=1.5, help="playout_search and --arena: the exploration constant")
     ap.add_argument("--playout_table", default=None, metavar="PATH",
                     help="playout_search: a saved EndgameTable; the leaves it covers are worth their exact value and run no playouts")
     ap.add_argument("--model", default=None, help="checkpoint (best.pt) of any of the trainers: evaluate its deterministic policy")
@@ -436,6 +465,11 @@ def _parser():
     ap.add_argument("--puct", default=None, type=int, metavar="SIMS",
                     help="with --model: beside the raw policy, its PUCT search of SIMS simulations (predict_puct) against the same "
                          "opponents, rows \"puct(SIMS) vs ...\"")
+    ap.add_argument("--arena", default=None, type=int, metavar="SIMS",
+                    help="with --model and --opponent_model: the two checkpoints' PUCT searches of SIMS simulations against each other, "
+                         "whole games in one kernel launch (ewn_puct_arena), every start position once with each moving first, row "
+                         "\"arena(SIMS): model vs opponent_model\"; it reads --num, --c_puct, --board_size and --cube_layer, and no "
+                         "other flag (no --agents, no classical opponent's settings, no --rng: the dice are the search's own)")
     ap.add_argument("--fused", action="store_true",
                     help="with --puct: the search of a move in one kernel launch (ewn_puct_search) instead of the staged launches; the "
                          "same moves")
@@ -466,6 +500,14 @@ def _parser():
 def main():
     ap = _parser()
     a = ap.parse_args()
+    if a.arena is not None:
+        if a.model is None or a.opponent_model is None:
+            ap.error("--arena goes with --model and --opponent_model: it plays the two checkpoints' searches against each other")
+        if (a.puct is not None or a.lookahead or a.fused or a.leaves != 1 or a.puct_table or a.endgame_table or a.endgame_leaves
+                or a.playout_table):
+            ap.error("--arena does not go with --puct, --lookahead, --fused, --leaves or the table flags")
+        if not 0 <= a.arena <= 4096:
+            ap.error("--arena takes 0..4096 simulations")
     if a.lookahead and (a.model is None or a.opponent_model is not None):
         ap.error("--lookahead goes with --model and the classical opponents of --agents")
     if a.puct is not None and (a.model is None or a.opponent_model is not None or a.endgame_table):
@@ -486,7 +528,11 @@ def main():
         ap.error("playout_search among --agents goes without --model and --opponent_model")
     if a.playout_table and "playout_search" not in a.agents:
         ap.error("--playout_table goes with playout_search among --agents")
-    if a.opponent_model is not None and a.model is None:
+    if a.arena is not None:
+        r = arena(load_policy(a.model, a.board_size, a.cube_layer), load_policy(a.opponent_model, a.board_size, a.cube_layer), num=a.num,
+                  sims=a.arena, board_size=a.board_size, cube_layer=a.cube_layer, c_puct=a.c_puct)
+        t = {"arena(%d): model vs opponent_model" % a.arena: dict(r, wins=r["wins_a"])}
+    elif a.opponent_model is not None and a.model is None:
         t = evaluate_agents_vs_model(load_policy(a.opponent_model, a.board_size, a.cube_layer), a.agents, a.num, a.max_depth,
                                      a.num_simulations, a.num_env_copies, a.board_size, a.cube_layer, a.heuristic, a.rng)
     elif a.opponent_model is not None:
